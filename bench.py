@@ -26,6 +26,13 @@ barriers, the max-over-ranks clock and the hand-over of the communicator id need
     python bench.py --gpus N              # no launcher: bench.py starts its N ranks itself (self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --dump-outputs DIR    # also write the last timed step's results to DIR/*.npy
+
+--dump-outputs DIR: after the timed steps, the answer of the LAST timed step -- what a caller of the headline search receives --
+goes to DIR/distances.npy (float32, [nq][k]) and DIR/ids.npy (the int64 row ids as float64, exact below 2^53); N > 1: rank 0's
+merged answer.  Above 64 MB in all, a fixed seeded sample of the queries' rows is written instead, their indices in
+DIR/sampled_rows.npy.  Every input is generated from fixed seeds, so two builds run with the same arguments can be compared
+output for output.
 
 The N > 1 line proves what it measured: `rccl_ranks` / `collectives_per_search` from the library's own counters
 (cvtmi_comm_info), `identical_to_oracle_sample` (every rank scans ITS shard with the CPU oracle for a few queries, rank 0 merges
@@ -102,7 +109,29 @@ def parse_args():
     ap.add_argument("--tune", default="", help="development: cvtmi_set_tuning pairs, name=value,name=value")
     ap.add_argument("--secondary", type=int, default=1,
                     help="N = 1: also measure rotation / encode / SQ8 / flat searches / config 5 (0 = skip)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's distances and ids to DIR/*.npy (at most 64 MB: a seeded sample of rows above)")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """the last timed step's (distances [nq][k] fp32, ids [nq][k] int64) -> path/distances.npy (float32), path/ids.npy (float64);
+    above DUMP_MAX_BYTES a fixed seeded sample of rows (queries), their indices in path/sampled_rows.npy"""
+    d, i = (t.cpu().numpy() for t in out)
+    nq, k = d.shape
+    rows = None
+    if nq * k * (4 + 8) > DUMP_MAX_BYTES:
+        keep = max(1, (DUMP_MAX_BYTES - 4096) // (k * (4 + 8) + 8))   # the row indices and the .npy headers count too
+        rows = np.sort(np.random.default_rng(0x5EED).choice(nq, size=keep, replace=False))
+        d, i = d[rows], i[rows]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "distances.npy"), np.ascontiguousarray(d, dtype=np.float32))
+    np.save(os.path.join(path, "ids.npy"), np.ascontiguousarray(i, dtype=np.float64))
+    if rows is not None:
+        np.save(os.path.join(path, "sampled_rows.npy"), rows.astype(np.float64))
 
 
 class Ctx:
@@ -471,6 +500,8 @@ def headline_n1(ctx, q):
     ctx.barrier(); idx.last_scan()  # drop the warm-up launches from the kernel-time statistics
     elapsed, out = ctx.timed(lambda: fn(q), args.steps, 0)
     scan = idx.last_scan()  # mean HIP-event duration of the scan kernel over the timed steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     traffic, traffic_src = _pmc_traffic(args, nq, k, M)
     name = "SIFT-1M" if args.rows == 1_000_000 else "%d synthetic rows" % args.rows
     roof = scan_roofline(scan, traffic)
@@ -565,6 +596,8 @@ def headline_multi(ctx, q):
         return {"metric": "queries/sec, OPQ-ADC top-%d over 128-d SIFT-1B-shaped rows, row-sharded x%d" % (k, world), "value": None,
                 "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "higher_is_better": True,
                 "scaling": "strong", "error": res["error"]} if ctx.rank == 0 else None
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, ctx.last_out)
     extra = {}
     # The N = 1 point of THIS curve, measured in THIS run: rank 0 alone, every row on its one GPU, the same queries, no collective --
     # so the line carries its own speed-up (the N = 1 line's headline is BASELINE configs[1], another workload).  The others wait.

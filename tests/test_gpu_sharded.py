@@ -1,10 +1,12 @@
 """GPU: the row-sharded search INSIDE the library (cvtmi_comm_*, cvtmi_opq_search_sharded*, csrc/shard.hip).
 
 * world 1 through real RCCL ("comm_force_rccl"): ncclGetUniqueId / ncclCommInitRank / ncclAllGather are bound and run.
-* world 2, 3 and 8 (BASELINE configs[3]'s rank count, shards of 0 and 1 rows included) as separate processes sharing this
-  box's one GPU: RCCL refuses two ranks on one device, so the ranks exchange through the caller-supplied transport (gloo,
-  staged through the host) -- the slot layout, the zero-copy local search into the slot and topk_merge_kernel<true> are
-  exactly what the RCCL transport feeds.  `bench.py --gpus 8 --backend host` runs the configs[3] bench path at 8 ranks.
+* world 2, 3 and 5 (shards of 0 and 1 rows included) as separate processes sharing this box's one GPU: RCCL refuses two
+  ranks on one device, so the ranks exchange through the caller-supplied transport (gloo, staged through the host) -- the
+  slot layout, the zero-copy local search into the slot and topk_merge_kernel<true> are exactly what the RCCL transport
+  feeds.  `bench.py --gpus 5 --backend host` runs the configs[3] bench path at 5 ranks.
+  Five ranks is the most one GPU takes here: with this test process they are six processes holding the device, and a
+  shared GPU is not opened by more than six processes at once (configs[3]'s own 8 ranks run one per GPU).
 Results must equal a single handle holding every row, and the oracle, bit for bit (ids and distance bits)."""
 import os
 import socket
@@ -25,7 +27,7 @@ def _case(seed, n, nq, D=128, M=16, K=256, dup=0):
     books = (rng.normal(size=(M, K, D // M)) * 0.1).astype(np.float32)
     codes = rng.integers(0, K, size=(n, M), dtype=np.uint8)
     if dup and n > 4:  # exact duplicates on both sides of every shard boundary: ties across ranks
-        for w in (2, 3, 8):
+        for w in (2, 3, 5):
             for r in range(1, w):
                 b = (n // w) * r + min(r, n % w)
                 lo, hi = max(0, b - dup), min(n, b + dup)
@@ -104,7 +106,7 @@ def _free_port():
 
 
 @pytest.mark.parametrize("world,n,nq", [(2, 200_000, 64), (3, 100_001, 33), (3, 2, 5), (2, 300, 9),
-                                        (8, 200_003, 40), (8, 9, 5), (8, 5, 3)])   # 8 ranks: shards of 25 000, of 2 / 1 and of 1 / 0 rows
+                                        (5, 200_003, 40), (5, 9, 5), (5, 3, 3)])   # 5 ranks: shards of 40 000, of 2 / 1 and of 1 / 0 rows
 def test_multi_rank_one_gpu_matches_single_handle(world, n, nq, tmp_path, orc):
     import torch
     import cvt_amd
@@ -332,15 +334,16 @@ def test_bench_gpus2_self_launch_host_transport():
     assert "error" not in line
 
 
-def test_bench_gpus8_configs3_shape_on_one_gpu():
-    """BASELINE configs[3] at its own rank count before an 8-GPU node runs it -- `bench.py --gpus 8` over the host
-    transport on this one GPU: 2^26 SIFT-shaped rows in 8 row shards (8 M rows = 128 MB of codes each), ONE all-gather of per-shard
+def test_bench_gpus5_configs3_shape_on_one_gpu():
+    """the BASELINE configs[3] bench path at several ranks before a multi-GPU node runs it -- `bench.py --gpus 5`
+    over the host transport on this one GPU (five ranks: the most one GPU takes, see the module docstring): 5 x 2^23 SIFT-shaped
+    rows in 5 row shards (8 M rows = 128 MB of codes each, the shard of configs[3]'s 8-rank shape), ONE all-gather of per-shard
     top-k per search, every rank's merged list equal to the oracle sample and to one handle holding all the rows.
     (Reference shape of the exchange: retrieval/vlindex/lib/FLANN/mpi/index.h:196-226.)"""
-    line = _bench_line(["--backend", "host"], timeout=1500, gpus=8, large_rows=1 << 26)
-    _check_evidence(line, gpus=8)
+    line = _bench_line(["--backend", "host"], timeout=1500, gpus=5, large_rows=5 << 23)
+    _check_evidence(line, gpus=5)
     assert "error" not in line
-    assert line["config"]["rows"] == 1 << 26 and line["config"]["rows_per_gpu"] == 1 << 23
+    assert line["config"]["rows"] == 5 << 23 and line["config"]["rows_per_gpu"] == 1 << 23
 
 
 def test_bench_gpus2_without_second_gpu_still_prints_a_line():
