@@ -552,6 +552,13 @@ class FlatIndex:
         _check(lib().cvtmi_flat_last_search(self.h, C.byref(f), C.byref(m)))
         return f.value, m.value
 
+    def last_redo(self):
+        """queries of the last search that the exact kernels answered because the fp32 / uint8 threshold filter or the fp32 stream
+        flagged them; -1 when not counted (set_tuning("flat_count_redo", 1) turns counting on; other paths flag nothing: 0)"""
+        r = C.c_int64(0)
+        _check(lib().cvtmi_flat_last_redo(self.h, C.byref(r)))
+        return r.value
+
 
 class HnswIndex:
     """cvtmi_hnsw_*: batched search over a graph file written by the reference's HierarchicalNSW::saveIndex."""

@@ -134,6 +134,7 @@ struct FlatScratch {
     DevBuf s_part_d, s_part_id, s_gthr, s_stage;
     DevBuf f_stats, f_thr, f_marg, f_cnt, f_cand, f_sd, f_si, f_sd2, f_si2, f_seld, f_seli;   // matrix-core filter pipelines
     DevBuf fs_redo, fs_scratch;                                                                // fp32 stream
+    DevBuf redo_count;                                                                         // "flat_count_redo": the count of the flags
     DevBuf io_q, io_d, io_i;                                                                   // staging of the host-pointer entry
     PinBuf io_pin;                  // small calls: [queries | distances | labels] in page-locked memory the kernels write into
     hipStream_t own = nullptr;      // stream of the host-pointer entry (created on first use)
@@ -143,7 +144,7 @@ struct FlatScratch {
     void release_all()
     {
         for (DevBuf *b : { &s_part_d, &s_part_id, &s_gthr, &s_stage, &f_stats, &f_thr, &f_marg, &f_cnt, &f_cand, &f_sd, &f_si, &f_sd2,
-                           &f_si2, &f_seld, &f_seli, &fs_redo, &fs_scratch, &io_q, &io_d, &io_i })
+                           &f_si2, &f_seld, &f_seli, &fs_redo, &fs_scratch, &redo_count, &io_q, &io_d, &io_i })
             b->release();
         io_pin.release();
         if (own) (void)hipStreamDestroy(own);
@@ -178,6 +179,7 @@ struct cvtmi_flat_s {
     bool f_nonfinite = false;   // a row holds inf / NaN: the filter is not used
     std::atomic<int> f_last_filtered{0};    // how the last search was answered (0 exact, 1 filter pipeline, 2 fp32 stream, 3 fp32 threshold filter)
     std::atomic<long long> f_last_worst{0};  // its largest candidate list
+    std::atomic<long long> f_last_redo{-1};  // queries of the last search the exact kernels answered under a redo flag (-1: not counted)
     // fp32 stream (flat_f32_stream.hip): per-row score bias, statistics of the rows ([0] max |x|^2, [1] non-finite rows)
     DevBuf fs_bias, fs_stats;
     int64_t fs_stats_n = -1;    // index size the host copy of the statistics belongs to
@@ -362,6 +364,7 @@ static std::atomic<int> g_scanh_key{0};  // bumped when a planner setting of adc
 static std::atomic<int> g_inject_failure{-1};  // cvtmi_set_tuning("comm_inject_failure", r): the local search of rank r of a sharded search fails (tests)
 static std::atomic<int> g_flat_variant{0};  // cvtmi_set_tuning("flat_variant"): 0 = choose, 1 = exact kernels only, 2 = matrix-core filter wherever it applies
 static std::atomic<int> g_flat_f32_stream{1};  // cvtmi_set_tuning("flat_f32_stream"): 0 = off, 1 = choose, 2 = wherever it applies
+static std::atomic<int> g_flat_count_redo{0};  // cvtmi_set_tuning("flat_count_redo"): 1 = count the redo flags of each search (a copy back and a wait per search)
 
 static int sharded_local_failure(cvtmi_comm_t c)
 {
@@ -478,6 +481,11 @@ int cvtmi_set_tuning(const char *name, int64_t value)
         return CVTMI_OK;
     }
     if (!strcmp(name, "flat_f32_dbg")) { set_flat_f32_dbg((int)value); return CVTMI_OK; }
+    if (!strcmp(name, "flat_count_redo")) {
+        if (value < 0 || value > 1) return fail(CVTMI_EINVAL, "cvtmi_set_tuning: flat_count_redo must be 0 or 1");
+        g_flat_count_redo = (int)value;
+        return CVTMI_OK;
+    }
     if (!strcmp(name, "flat_f32_tfilter")) { set_flat_f32_tfilter((int)value); return CVTMI_OK; }
     if (!strcmp(name, "flat_f32_tfilter_min")) { set_flat_f32_tfilter_min((int)value); return CVTMI_OK; }
     if (!strcmp(name, "flat_f32_tfilter_one")) { set_flat_f32_tfilter_one((int)value); return CVTMI_OK; }
@@ -1855,6 +1863,20 @@ static int flat_search_rows(cvtmi_flat_t h, FlatScratch &S, int64_t n_rows, cons
     return CVTMI_OK;
 }
 
+// "flat_count_redo" 1: how many of a search's nq queries the threshold filters / the fp32 stream flagged for the exact kernels
+// (h->f_last_redo, cvtmi_flat_last_redo).  Off by default: the count is copied back and waited for
+static int flat_count_redo(cvtmi_flat_t h, FlatScratch &S, const uint32_t *flags, int64_t nq, hipStream_t st)
+{
+    if (!g_flat_count_redo.load()) return CVTMI_OK;
+    CVTMI_TRY(S.redo_count.reserve(sizeof(uint32_t)));
+    CVTMI_TRY(launch_count_nonzero(flags, nq, S.redo_count.as<uint32_t>(), st));
+    uint32_t c = 0;
+    CVTMI_HIP(hipMemcpyAsync(&c, S.redo_count.p, sizeof(c), hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(hipStreamSynchronize(st));
+    h->f_last_redo = (long long)c;
+    return CVTMI_OK;
+}
+
 // fp32 search as a stream over the rows (flat_f32_stream.hip).  *done = false: not applicable, the other paths answer
 static int flat_search_streamed(cvtmi_flat_t h, FlatScratch &S, const float *q, int64_t nq, int k, float *dist, int64_t *rows, hipStream_t st, bool *done,
                                 int *how = nullptr)
@@ -1871,6 +1893,7 @@ static int flat_search_streamed(cvtmi_flat_t h, FlatScratch &S, const float *q, 
         CVTMI_TRY(S.fs_redo.reserve((size_t)nq * 2 * sizeof(uint32_t)));
         CVTMI_TRY(launch_flat_f32_tfilter(h->metric, D, h->data.as<float>(), (h->f_rows.p && h->f_rows_n == n) ? h->f_rows.as<float>() : nullptr, h->f_pack.p, h->f_istats.as<uint32_t>(), h->fs_bias.as<float>(), h->fs_stats.as<uint32_t>(), n, q, nq, k,
                                           S.fs_scratch.p, dist, rows, S.fs_redo.as<uint32_t>(), st));
+        CVTMI_TRY(flat_count_redo(h, S, S.fs_redo.as<uint32_t>(), nq, st));
         CVTMI_TRY(flat_search_rows(h, S, n, q, nq, k, dist, rows, st, INT64_MAX, S.fs_redo.as<uint32_t>()));
         *done = true;
         if (how) *how = 3;
@@ -1896,6 +1919,7 @@ static int flat_search_streamed(cvtmi_flat_t h, FlatScratch &S, const float *q, 
                                          (h->f_rows.p && h->f_rows_n == n) ? h->f_rows.as<float>() : nullptr));
     }
     // queries the bound does not cover / whose lists ran over: the exact kernels, predicated on the flags (they exit at once otherwise)
+    CVTMI_TRY(flat_count_redo(h, S, S.fs_redo.as<uint32_t>(), nq, st));
     CVTMI_TRY(flat_search_rows(h, S, n, q, nq, k, dist, rows, st, INT64_MAX, S.fs_redo.as<uint32_t>()));
     *done = true;
     return CVTMI_OK;
@@ -2026,6 +2050,7 @@ static int flat_search_bigk_u8(cvtmi_flat_t h, FlatScratch &S, const uint8_t *q,
     CVTMI_TRY(S.fs_redo.reserve((size_t)(nq + 1) * sizeof(uint32_t)));
     uint32_t *flags = S.fs_redo.as<uint32_t>();
     CVTMI_TRY(launch_flat_u8_tfilter(D, h->f_pack.p, h->norms.as<int32_t>(), n, q, nq, k, S.fs_scratch.p, dist, rows, flags, st));
+    CVTMI_TRY(flat_count_redo(h, S, flags + 1, nq, st));
     CVTMI_TRY(flat_search_rows(h, S, n, q, nq, k, dist, rows, st, INT64_MAX, flags + 1));
     h->f_last_worst = 0;
     *done = true;
@@ -2189,6 +2214,7 @@ static int flat_search_leased(cvtmi_flat_t h, FlatScratch &S, const void *q, int
     bool done = false;
     long long worst0 = 0;
     h->f_last_worst = worst0;
+    h->f_last_redo = g_flat_count_redo.load() ? 0 : -1;   // (the routes with redo flags overwrite it)
     int how = 0;
     const FlatRoute r = flat_route(h, q, nq, k, tun);
     if (r.stream || r.tfilter) {
@@ -2299,6 +2325,13 @@ int cvtmi_flat_last_search(cvtmi_flat_t h, int *filtered, int64_t *max_candidate
     if (!h) return fail(CVTMI_EINVAL, "cvtmi_flat_last_search: null handle");
     if (filtered) *filtered = h->f_last_filtered;
     if (max_candidates) *max_candidates = h->f_last_worst;
+    return CVTMI_OK;
+}
+
+int cvtmi_flat_last_redo(cvtmi_flat_t h, int64_t *redone)
+{
+    if (!h || !redone) return fail(CVTMI_EINVAL, "cvtmi_flat_last_redo: null argument");
+    *redone = h->f_last_redo;
     return CVTMI_OK;
 }
 

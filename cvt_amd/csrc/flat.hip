@@ -1334,6 +1334,25 @@ int launch_offset_labels(int64_t *ids, int64_t count, int64_t base, hipStream_t 
     return CVTMI_OK;
 }
 
+// *out = the non-zero words of flags[0 .. count) (one workgroup: the redo flags of one search)
+__global__ __launch_bounds__(kBlock) void count_nonzero_kernel(const uint32_t *flags, int64_t count, uint32_t *out)
+{
+    __shared__ uint32_t total;
+    if (threadIdx.x == 0) total = 0u;
+    __syncthreads();
+    uint32_t c = 0u;
+    for (int64_t i = threadIdx.x; i < count; i += kBlock) c += flags[i] != 0u ? 1u : 0u;
+    if (c) atomicAdd(&total, c);
+    __syncthreads();
+    if (threadIdx.x == 0) *out = total;
+}
+int launch_count_nonzero(const uint32_t *flags, int64_t count, uint32_t *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(count_nonzero_kernel, dim3(1), dim3(kBlock), 0, st, flags, count, out);
+    CVTMI_HIP(hipGetLastError());
+    return CVTMI_OK;
+}
+
 constexpr int STREAM_SLICES = 64;
 // selection after flat_u8_mstream_kernel (flat_mfma.hip): wave minima wmin[nq][G], tile minima tmin[tiles][nqp] -> part [nq][slices][k] -> merge
 int launch_flat_u8_mstream_finish(int D, const uint8_t *data, int64_t n, const uint8_t *q, int64_t nq, int k, const int32_t *wmin, int G,

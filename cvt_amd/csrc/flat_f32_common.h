@@ -108,11 +108,14 @@ template <int NK>
 __device__ __forceinline__ uint32_t fs_wave_select(const uint32_t (&key)[NK], int k, int kmax)
 {
     uint32_t hi = 0, lo = 0xffffffffu;
+    int present = 0;
 #pragma unroll
     for (int j = 0; j < NK; ++j) {
         hi = key[j] > hi ? key[j] : hi;
         lo = (key[j] < lo && key[j] != 0u) ? key[j] : lo;
+        present += __popcll(__ballot(key[j] != 0u));
     }
+    if (present < k) return 0u;   // (below: the common prefix and the all-equal answer are reached by every present key -- k of them)
     hi = fs_wave_max_u32(hi);
     lo = fs_wave_min_u32(lo);
     if (hi <= lo) return hi;   // all present keys equal (or none present: 0)
@@ -136,9 +139,9 @@ __device__ __forceinline__ float fs_qlow(const float *q, int D)
 {
     float s_ = 0.0f;
     for (int e0 = 8 * (threadIdx.x & 63); e0 < D; e0 += 512) {
-        float v[8];
+        float v[8];   // (zeros beyond D: a width of 8 m + 4 ends half-way through its last piece)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = q[e0 + e];
+        for (int e = 0; e < 8; ++e) v[e] = e0 + e < D ? q[e0 + e] : 0.0f;
         bf16x8 h, l;
         fs_split(v, h, l);
 #pragma unroll

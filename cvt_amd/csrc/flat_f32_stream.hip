@@ -27,6 +27,9 @@
 // position bits 2^-18 |T| = 64 uQ: <= 556 uQ (940 uQ at D = 256) on a key; the reference's own sum ~200 uQ (400 uQ) in T units.
 // Two rows are ordered the same way by their keys and by the reference whenever the keys differ by more than
 // 2 x (556 + 200) uQ = 1512 uQ (D <= 128) / 2 x (940 + 400) = 2680 uQ (D = 256); margin = 2^-13 Q = 2048 uQ, 2^-12 Q for D > 128.
+// (Against flat_f32_tfilter.hip's per-width accounting -- 3 D + 1 accumulated terms, 384 uQ of split terms, D / 2 uQ behind b_x, the
+// reference's (D / 4 + 10) uQ, 64 uQ of position bits: 2 x 939 = 1878 uQ at 128-d, 2 x 1419 = 2838 uQ at 256-d; the packed form's one
+// product, 2 x (1.75 D + 75) uQ + 2 W_q -- both margins hold at every width the stream takes.)
 #include <algorithm>
 #include <type_traits>
 

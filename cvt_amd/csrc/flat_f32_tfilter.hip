@@ -31,16 +31,23 @@
 //
 // Bound (u = 2^-24, Q = |q|^2 + max |x|^2 >= 2 |x||q|, |T| <= Q): bf16 keeps 8 significant bits and rounds to nearest even,
 // |v - v1| <= e |v| with e = 2^-8 (half a unit in the last place, relative to the smallest v of a binade), |v - v1 - v2| <= e^2 |v|.
-// Accumulation of m terms whose partial sums stay below Q / 2 in magnitude: 2u per term, m u Q.  Reference sum ~200 uQ in T units.
-//   NPROD 3: omitted x2.q2 <= e^2 |x||q| = 128 uQ, the two split residuals 256 uQ, 3 D + 1 terms 385 uQ, b_x 8 uQ: 777 uQ;
-//            margin 2^-13 Q = 2048 uQ >= 2 (777 + 200).
-//   NPROD 2: x.q - (x1 + x2).q1 = (x - x1 - x2).q + (x1 + x2).(q - q1) <= 128 uQ + (1 + e^2) max |x| |q - q1| =: 128 uQ + W_q, 2 D + 1 terms
-//            257 uQ, b_x 8 uQ.  W_q is evaluated per query (ft_qlow: the residues of the query's own rounding, Cauchy-Schwarz against
-//            the longest row) instead of its worst case e |x||q| = 32 768 uQ -- a query's residues add up to a third of that:
-//            margin 2^-13 Q + 2 W_q >= 2 (393 uQ + W_q + 200 uQ).
-//   NPROD 1: x.q - x1.q1 = (x - x1).q + x1.(q - q1) <= e (2 + e) |x||q| <= 65 664 uQ, D + 1 terms 129 uQ, b_x 8 uQ: 65 801 uQ;
-//            margin 2^-7 Q + 2^-11 Q = 139 264 uQ >= 2 (65 801 + 200).
+// A row r of the true k best and the k rows that reach theta: one of those, s, is no nearer than r in the reference's arithmetic, so
+// score(r) >= score(s) - 2 (E_mma + E_ref) >= theta - 2 (E_mma + E_ref): the margin is twice the error of a score plus the reference's.
+// Every term below grows with the width D (the products the kernel issues, the sums behind b_x and behind the reference's distance):
+//   accumulation: NPROD D + 1 terms (b_x the first), each rounded once to nearest with its partial sum below Q in magnitude: (NPROD D + 1) uQ
+//                 (zero-padded K steps add exact zeros);
+//   b_x (L2): -|x|^2 / 2 from a D-term fp32 sum (flat_f32_bias_kernel): D / 2 uQ;
+//   the reference (dist_f32.h, 4 or 8 lanes): IP (D / 4 + 4) u |x||q| <= (D / 8 + 2) uQ; L2 (D / L + L + 2) u |q - x|^2 with
+//                 |q - x|^2 <= 2 Q, in T units half of it: <= (D / 4 + 10) uQ either way (the rounding of 1 - sum: below, per theta);
+//   NPROD 3: omitted x2.q2 <= e^2 |x||q| = 128 uQ, the two split residuals 256 uQ;
+//   NPROD 2: x.q - (x1 + x2).q1 = (x - x1 - x2).q + (x1 + x2).(q - q1) <= 128 uQ + (1 + e^2) max |x| |q - q1| =: 128 uQ + W_q, W_q
+//            evaluated per query (fs_qlow: the residues of the query's own rounding, Cauchy-Schwarz against the longest row) instead of
+//            its worst case e |x||q| = 32 768 uQ -- a query's residues add up to a third of that;
+//   NPROD 1: x.q - x1.q1 = (x - x1).q + x1.(q - q1) <= max |x - x1| |q| + (1 + e) max |x| |q - q1| =: W_q, per query as well.
+// E = NPROD D + 1 + [L2] D / 2 + D / 4 + 10 + (384 | 128 | 0) uQ; margin = max(2^-13 Q, 2 E uQ) + 2 W_q (ft_fixed_margin, ft_margin):
+// 2^-13 Q = 2048 uQ up to 128-d with three products, 256-d with two, 512-d with one; 2 E = 3 606 uQ at 1024-d, 7 190 uQ at 2048-d (L2).
 #include <algorithm>
+#include <bitset>
 #include <cmath>
 #include <atomic>
 #include <vector>
@@ -338,19 +345,19 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4,
     }
 }
 
-// margin of a query: Qb = (|q|^2 + max |x|^2) 1.001; w = what the omitted low terms can add up to for THIS query, by Cauchy-Schwarz
-// against the longest row / the row with the largest rounding residue (ft_theta_kernel): the worst case e |x||q| per omitted term
-// is two to three times larger than a query's own residues
+// margin of a query: Qb = (|q|^2 + max |x|^2) 1.001; fixed = the width's share per unit of Qb (ft_fixed_margin); w = what the omitted
+// low terms can add up to for THIS query, by Cauchy-Schwarz against the longest row / the row with the largest rounding residue
+// (ft_theta_kernel): the worst case e |x||q| per omitted term is two to three times larger than a query's own residues
 template <bool IP>
-__device__ __forceinline__ float ft_margin(float Qb, float w, float theta)
+__device__ __forceinline__ float ft_margin(float Qb, float fixed, float w, float theta)
 {
-    float m = Qb * 0x1p-13f + 2.0f * w;
+    float m = Qb * fixed + 2.0f * w;
     if (IP) m += (2.0f + fabsf(theta)) * 0x1p-20f;   // the rounding of 1 - sum in the reference
     return m;
 }
 // one wave per query: theta = the k-th largest of its sample maxima, thr = theta - margin (NaN + redo when the bound does not hold)
 template <bool IP, int NK>
-__global__ __launch_bounds__(256) void ft_theta_kernel(const uint32_t *__restrict__ smax, const float *__restrict__ Q, int nq, int D, int k, int nprod,
+__global__ __launch_bounds__(256) void ft_theta_kernel(const uint32_t *__restrict__ smax, const float *__restrict__ Q, int nq, int D, int k, int nprod, float fixed,
                                                        const uint32_t *__restrict__ stats, const uint32_t *__restrict__ pstats, float loosen, float *__restrict__ thr, float *__restrict__ qbnd,
                                                        uint32_t *__restrict__ redo, uint32_t *__restrict__ cnt)
 {
@@ -370,7 +377,7 @@ __global__ __launch_bounds__(256) void ft_theta_kernel(const uint32_t *__restric
         const uint32_t sel = fs_wave_select(key, k, k + k / 4 + 8);
         if (sel != 0u) {   // at least k slots hold a row
             const float theta = key_f32(sel);
-            cut = theta - ft_margin<IP>(Qb, xq2, theta) - loosen * Qb;   // (loosen: test hook, "flat_f32_dbg" 32 -- lists run over, second attempts happen)
+            cut = theta - ft_margin<IP>(Qb, fixed, xq2, theta) - loosen * Qb;   // (loosen: test hook, "flat_f32_dbg" 32 -- lists run over, second attempts happen)
         }
     }
     if (lane == 0) {
@@ -489,7 +496,7 @@ __global__ __launch_bounds__(256) void ft_finish_kernel(const float *__restrict_
                                                         float *__restrict__ thr, const float *__restrict__ qbnd, uint32_t *__restrict__ cnt,
                                                         const uint2 *__restrict__ cand, float *__restrict__ out_d, int64_t *__restrict__ out_i,
                                                         uint32_t *__restrict__ redo, uint32_t *__restrict__ rcount, uint32_t *__restrict__ rlist, int rcap, int second, int nqb,
-                                                        uint32_t *__restrict__ bcount, uint32_t *__restrict__ blist, int rowmajor)
+                                                        uint32_t *__restrict__ bcount, uint32_t *__restrict__ blist, int rowmajor, float fixed)
 {
     __shared__ unsigned long long sel[FT_KEEP];
     __shared__ __attribute__((aligned(16))) float q_s[FT_DMAX];
@@ -582,7 +589,11 @@ __global__ __launch_bounds__(256) void ft_finish_kernel(const float *__restrict_
         __syncthreads();
     }
     const float theta = key_f32(prefix);
-    const float cut2 = theta - ft_margin<IP>(qbnd[q], qbnd[nqb + q], theta);
+    const float cut2 = theta - ft_margin<IP>(qbnd[q], fixed, qbnd[nqb + q], theta);
+    if (!over && cut2 < cut) {   // (workgroup-uniform) rows in [cut2, cut) were never listed: theta did not come from k rows
+        if (tid == 0) redo[q] = 1u;
+        return;
+    }
     if (over) {   // (workgroup-uniform)
         if (tid == 0) {
             const uint32_t pos = cut2 > cut ? atomicAdd(rcount, 1u) : 0xffffffffu;
@@ -670,7 +681,8 @@ template <bool IP, int LANES>
 __global__ __launch_bounds__(1024) void ft_finish_big_kernel(const float *__restrict__ X, int64_t n, int D, const float *__restrict__ Q, int k,
                                                              const float *__restrict__ thr, const float *__restrict__ qbnd, const uint32_t *__restrict__ cnt,
                                                              const uint2 *__restrict__ cand, float *__restrict__ out_d, int64_t *__restrict__ out_i,
-                                                             uint32_t *__restrict__ redo, int nqb, int cstride, int only2, const uint32_t *__restrict__ bcount, const uint32_t *__restrict__ blist, int rowmajor)
+                                                             uint32_t *__restrict__ redo, int nqb, int cstride, int only2, const uint32_t *__restrict__ bcount, const uint32_t *__restrict__ blist, int rowmajor,
+                                                             float fixed)
 {
     // only2: the second chance of the queries ft_finish_kernel marked 2 (their lists are whole, their margin band holds more than FT_KEEP rows):
     // cstride = that kernel's list stride; the mark becomes 0 (answered here) or 1 (the exact kernels)
@@ -750,7 +762,12 @@ __global__ __launch_bounds__(1024) void ft_finish_big_kernel(const float *__rest
         __syncthreads();
     }
     const float theta = key_f32(prefix);
-    const uint32_t cut2_key = f32_key(theta - ft_margin<IP>(qbnd[q], qbnd[nqb + q], theta));
+    const float cut2 = theta - ft_margin<IP>(qbnd[q], fixed, qbnd[nqb + q], theta);
+    if (cut2 < cut) {   // (workgroup-uniform) rows in [cut2, cut) were never listed
+        if (tid == 0) redo[q] = 1u;
+        return;
+    }
+    const uint32_t cut2_key = f32_key(cut2);
     for (uint32_t i = tid; i < nc; i += NTH) {
         if (fb_keys[i] >= cut2_key) {
             const int pos = atomicAdd(&m2_s, 1);
@@ -806,6 +823,12 @@ static int ft_sample_div(int k, int64_t n, int D)
     const double want = std::sqrt(1280.0 * ((double)n * D * 4e-9) / (double)k);
     return std::max(3, std::min(32, (int)(want + 0.5)));   // (3, not 5, since the sample pass keeps its maxima in registers: 1 M x 128-d, k = 100 0.419 -> 0.403 ms)
 }
+// the fixed term of the margin per unit of Q (header, "Bound"): max(2^-13, 2 E u), E the width's error terms in units of uQ
+static float ft_fixed_margin(bool ip, int D, int nprod)
+{
+    const double e = (double)nprod * D + 1.0 + (ip ? 0.0 : D / 2.0) + D / 4.0 + 10.0 + (nprod == 3 ? 384.0 : (nprod == 2 ? 128.0 : 0.0));
+    return (float)std::max(0x1p-13, 2.0 * e * 0x1p-24);
+}
 static std::atomic<int> g_ft_bigk{1};      // "flat_f32_tfilter_bigk": 1 = k = 129 .. 2048 through the pipeline (4096 sample maxima, lists of 32 768, ft_finish_big_kernel), 0 = exact kernels
 static std::atomic<int> g_ft_wide_band{1};   // "flat_f32_tfilter_wide_band": 1 = queries with more than FT_KEEP rows inside the margin band get a second finish (ft_finish_big_kernel), 0 = the exact kernels
 static std::atomic<int> g_ft_retry{0};     // "flat_f32_tfilter_retry": 1 = a second filter pass for the queries whose candidate lists ran over, 0 (default) = the exact kernels at once
@@ -846,6 +869,87 @@ static int ft_auto_min(int D, int k)
     if (flat_f32_stream_qmax(D) == 0) return (D <= 512 || k <= 32) ? 1 : 16;
     return D >= 96 ? std::max(65, flat_f32_stream_private_max(D) + 1) : 65;
 }
+// products a width can multiply (two / three need both terms of a row tile in registers)
+static int ft_products(int D, int want)
+{
+    const int nch = flat_f32_tfilter_nch(D), most = nch <= 8 ? 3 : (nch <= 16 ? 2 : 1);
+    return want < most ? want : most;
+}
+// row tiles per group of the kernel ft_launch_any picks (the table below)
+static int ft_rt(int nch, int nprod)
+{
+    if (nprod == 1) return nch <= 4 ? 4 : (nch <= 10 ? 3 : (nch <= 16 ? 2 : 1));
+    if (nch == 2) return 4;
+    if (nch == 4) return 3;
+    if (nch <= 8) return 2;
+    return 1;
+}
+// (k > 384: as many products as the width has -- the narrower margin keeps the rows that need exact distances near k: at k = 2048 one
+//  product put more than FT_KEEP_BIG rows inside the band and every query went to the exact kernels)
+//  (1000 queries, one / three products: k = 129 1.28 / 1.73 ms, 256 1.53 / 2.05, 1000 3.17 / 2.42, 2048 42 / 3.25)
+//  End of round 6 (the exact finish reads a row-major copy now, so rows inside a wide band cost less; tools/f32_products_by_k.py,
+//  profiles/r06_f32_products_by_k.txt, one / three products, ms per 1000 queries): 1 M x 128-d k = 512 1.13 / 1.35, 768 1.38 / 1.42, 1024 1.62 / 1.52,
+//  1536 26.9 / 1.68; 4 M: 768 2.16 / 3.67, 1024 2.47 / 3.87, 1536 6.4 / 4.1; 10 M: 768 4.1 / 8.5, 1536 5.5 / 9.0, 2048 31.9 / 9.5; 2 M x 256-d: 768 2.7 / 3.3,
+//  1024 3.50 / 3.56, 1536 258 / 4.1 -- three products cost in proportion to the rows, one product's band overflows somewhere past k = 1024: one up to 768
+static int ft_nprod(int D, int64_t nq, int k)
+{
+    const int mode = g_ft_on.load();
+    return ft_products(D, mode == 4 ? (k > 768 ? 3 : (nq <= g_ft_one_max.load() ? 1 : 2)) : mode);
+}
+// queries a workgroup holds
+static int ft_qcap(int nch, int nprod)
+{
+    const int nt = nprod == 3 ? 2 : 1;
+    return std::min(32 * FT_NBMAX, (int)((size_t)(160 * 1024 - 32 * FT_NBMAX * 8 - FT_SLACK) / ((size_t)nch * nt * 1024)) * 32);
+}
+static int ft_chunks(int64_t m, int qcap)
+{
+    int chunks = 1;
+    while (chunks < 32 && (m + chunks - 1) / chunks > qcap) chunks *= 2;
+    return chunks;
+}
+// the sample: about an eighth of the groups (at least ~65 536 rows), a whole number per wave of a chunk
+static int64_t ft_n_sample(int D, int64_t n, int k, int nprod, int chunks)
+{
+    const int nch = flat_f32_tfilter_nch(D), rt = ft_rt(nch, nprod), nw = nch > 32 ? 4 : FT_WAVES;
+    const bool big = k > 128;
+    const int64_t all_groups = ((n + 31) / 32 + rt - 1) / rt, streams = (int64_t)(FT_GRID / chunks) * nw;
+    // (k > 128: a third of the rows -- the k-th largest of 4096 maxima needs many more rows than k behind it)
+    const int64_t want = std::max<int64_t>(all_groups / (big ? std::min(3, ft_sample_div(k, n, D)) : ft_sample_div(k, n, D)), std::min<int64_t>(all_groups, (2048 + rt - 1) / rt));
+    return std::min<int64_t>(all_groups, std::max<int64_t>(1, (want + streams / 2) / streams) * streams);
+}
+// sample slots a pass of m of the nq queries fills (the slot map of flat_f32_tfilter_kernel's MAX mode: two per wave and group, up to
+// sub_slots groups a wave), less one for a last tile whose second half may hold no row
+static int64_t ft_filled_slots(int D, int64_t n, int64_t nq, int64_t m, int k)
+{
+    const int nch = flat_f32_tfilter_nch(D), nprod = ft_nprod(D, nq, k), nw = nch > 32 ? 4 : FT_WAVES;
+    const int chunks = ft_chunks(m, ft_qcap(nch, nprod)), nslots = k > 128 ? FT_SLOTS_BIG : FT_SLOTS;
+    const int64_t n_sample = ft_n_sample(D, n, k, nprod, chunks);
+    const int slices = FT_GRID / chunks;
+    const int64_t stride = (int64_t)slices * nw;   // waves of a chunk; wave (sl, w) takes groups sl + slices w + stride i
+    const int wave_slots = slices * nw * 2, sub = wave_slots >= nslots ? 1 : nslots / wave_slots;
+    int64_t filled = 0;
+    if (wave_slots <= nslots) {   // every wave's slots are its own: two per group, up to sub groups
+        const int64_t base = n_sample / stride, r = n_sample % stride;
+        filled = 2 * (r * std::min<int64_t>(base + 1, sub) + (stride - r) * std::min<int64_t>(base, sub));
+    } else if (n_sample >= stride) {   // every wave has a group; waves share slots
+        filled = nslots;
+    } else {   // (small tables) the waves that have a group, their slot pairs counted once
+        std::bitset<FT_SLOTS_BIG> used;
+        for (int w = 0; w < nw; ++w)
+            for (int sl = 0; sl < slices && sl + (int64_t)slices * w < n_sample; ++sl) used.set((size_t)((sl * nw + w) & (nslots / 2 - 1)));
+        filled = 2 * (int64_t)used.count();
+    }
+    return std::max<int64_t>(0, filled - 1);
+}
+// theta is the k-th largest of the filled slots: 1.25 k of them wanted (as flat_u8_tfilter_applies) -- below that the k-th is a thin
+// and noisy bound, and with fewer than k a query could only go to the exact kernels (32-d, k > 768: the whole table is the sample below
+// ~260 K rows, two slots per 128 rows).  Both the first pass (the most chunks) and a shorter last one are checked
+static bool ft_sample_fills(int D, int64_t n, int64_t nq, int k)
+{
+    const int64_t pass = k > 128 ? FT_PASS_BIG : FT_PASS, first = std::min<int64_t>(nq, pass), last = nq - (nq - 1) / pass * pass;
+    return 4 * ft_filled_slots(D, n, nq, first, k) >= 5 * (int64_t)k && (last == first || 4 * ft_filled_slots(D, n, nq, last, k) >= 5 * (int64_t)k);
+}
 bool flat_f32_tfilter_applies(int metric, int D, int64_t n, int64_t nq, int k)
 {
     return g_ft_on.load() && (metric == CVTMI_METRIC_IP || metric == CVTMI_METRIC_L2F) && flat_f32_tfilter_width(D) &&
@@ -857,7 +961,7 @@ bool flat_f32_tfilter_applies(int metric, int D, int64_t n, int64_t nq, int k)
            (n >= g_ft_min_rows.load() || (k > 128 && n >= std::max<int64_t>(65536, 48 * (int64_t)k) && (D <= 512 || nq >= 16)) ||
             (k <= 128 && n >= std::min<int64_t>(65536, g_ft_min_rows.load()) && flat_f32_stream_qmax(D) == 0 && (D <= 512 || k <= 32 || nq >= 129))) && n < 0xffffffe0LL &&
            k >= 1 && k <= CVTMI_K_MAX && g_ft_bigk.load() + (k <= 128) > 0 &&   // (k > 128: the stream kernels do not take it -- every batch size comes here)
-           (k > 128 || nq >= (g_ft_min_nq.load() > 0 ? g_ft_min_nq.load() : ft_auto_min(D, k)));
+           (k > 128 || nq >= (g_ft_min_nq.load() > 0 ? g_ft_min_nq.load() : ft_auto_min(D, k))) && nq >= 1 && ft_sample_fills(D, n, nq, k);
 }
 // records a wave region holds: three times what 1 M SIFT-like rows gave per wave at k = 100, scaled with k beyond 128
 static uint32_t ft_rec_cap(int64_t m, int k)
@@ -886,21 +990,6 @@ static int ft_launch(bool maxmode, const FtArgs &a, size_t lds, hipStream_t st)
     }
     CVTMI_HIP(hipGetLastError());
     return CVTMI_OK;
-}
-// products a width can multiply (two / three need both terms of a row tile in registers)
-static int ft_products(int D, int want)
-{
-    const int nch = flat_f32_tfilter_nch(D), most = nch <= 8 ? 3 : (nch <= 16 ? 2 : 1);
-    return want < most ? want : most;
-}
-// row tiles per group of the kernel ft_launch_any picks (the table below)
-static int ft_rt(int nch, int nprod)
-{
-    if (nprod == 1) return nch <= 4 ? 4 : (nch <= 10 ? 3 : (nch <= 16 ? 2 : 1));
-    if (nch == 2) return 4;
-    if (nch == 4) return 3;
-    if (nch <= 8) return 2;
-    return 1;
 }
 static int ft_launch_any(int D, int nprod, bool maxmode, const FtArgs &a, size_t lds, hipStream_t st)
 {
@@ -940,26 +1029,18 @@ int launch_flat_f32_tfilter(int metric, int D, const float *X, const float *Xrow
     if (!flat_f32_tfilter_applies(metric, D, n, nq, k)) return fail(CVTMI_EINVAL, "flat_f32_tfilter: D=%d nq=%lld", D, (long long)nq);
     const float *Xe = Xrows ? Xrows : X;   // what the finish kernels gather exact distances from: the row-major copy when the handle keeps one
     const int rm = Xrows ? 1 : 0;
-    const int mode = g_ft_on.load();
-    // (k > 384: as many products as the width has -- the narrower margin keeps the rows that need exact distances near k: at k = 2048 one
-    //  product put more than FT_KEEP_BIG rows inside the band and every query went to the exact kernels)
-    //  (1000 queries, one / three products: k = 129 1.28 / 1.73 ms, 256 1.53 / 2.05, 1000 3.17 / 2.42, 2048 42 / 3.25)
-    //  End of round 6 (the exact finish reads a row-major copy now, so rows inside a wide band cost less; tools/f32_products_by_k.py,
-    //  profiles/r06_f32_products_by_k.txt, one / three products, ms per 1000 queries): 1 M x 128-d k = 512 1.13 / 1.35, 768 1.38 / 1.42, 1024 1.62 / 1.52,
-    //  1536 26.9 / 1.68; 4 M: 768 2.16 / 3.67, 1024 2.47 / 3.87, 1536 6.4 / 4.1; 10 M: 768 4.1 / 8.5, 1536 5.5 / 9.0, 2048 31.9 / 9.5; 2 M x 256-d: 768 2.7 / 3.3,
-    //  1024 3.50 / 3.56, 1536 258 / 4.1 -- three products cost in proportion to the rows, one product's band overflows somewhere past k = 1024: one up to 768
-    const int nprod = ft_products(D, mode == 4 ? (k > 768 ? 3 : (nq <= g_ft_one_max.load() ? 1 : 2)) : mode);
+    const int nprod = ft_nprod(D, nq, k);
     const int nt = nprod == 3 ? 2 : 1;
     const int nch = flat_f32_tfilter_nch(D);
-    const int qcap = std::min(32 * FT_NBMAX, (int)((size_t)(160 * 1024 - 32 * FT_NBMAX * 8 - FT_SLACK) / ((size_t)nch * nt * 1024)) * 32);   // queries a workgroup holds
+    const int qcap = ft_qcap(nch, nprod);   // queries a workgroup holds
+    const float fixed = ft_fixed_margin(metric == CVTMI_METRIC_IP, D, nprod);
     const int64_t n_tiles = (n + 31) / 32;
     const bool big = k > 128;
     const int pass = big ? FT_PASS_BIG : FT_PASS, nslots = big ? FT_SLOTS_BIG : FT_SLOTS;
     const uint32_t fcap = big ? FT_CAP_BIG : FT_CAP;
     for (int64_t a0 = 0; a0 < nq; a0 += pass) {
         const int64_t m = std::min<int64_t>(nq - a0, pass);
-        int chunks = 1;
-        while (chunks < 32 && (m + chunks - 1) / chunks > qcap) chunks *= 2;
+        const int chunks = ft_chunks(m, qcap);
         const int qper = (int)(((m + chunks - 1) / chunks + 31) / 32 * 32);
         const int nw = nch > 32 ? 4 : FT_WAVES;   // waves per workgroup of the filter kernel
         const uint32_t cap = ft_rec_cap(m, k) * (uint32_t)(FT_WAVES / nw);   // (the record area is the same: fewer, larger regions)
@@ -980,22 +1061,16 @@ int launch_flat_f32_tfilter(int metric, int D, const float *X, const float *Xrow
         a.smax = smax; a.nslots = nslots; a.thr = thr; a.rec = rec; a.wcnt = wcnt; a.cap = cap; a.qlist = nullptr; a.qcount = nullptr; a.dbg = get_flat_f32_dbg();
         const size_t lds = (size_t)(qper / 32) * nch * nt * 1024 + FT_SLACK + (size_t)qper * 2 * sizeof(float);
         a.t1 = n_tiles;
-        {   // the sample: about an eighth of the groups (at least ~65 536 rows), a whole number per wave of a chunk
-            const int rt = ft_rt(nch, nprod);
-            const int64_t all_groups = (n_tiles + rt - 1) / rt, streams = (int64_t)(FT_GRID / chunks) * nw;
-            // (k > 128: a third of the rows -- the k-th largest of 4096 maxima needs many more rows than k behind it)
-            const int64_t want = std::max<int64_t>(all_groups / (big ? std::min(3, ft_sample_div(k, n, D)) : ft_sample_div(k, n, D)), std::min<int64_t>(all_groups, (2048 + rt - 1) / rt));
-            a.n_sample = std::min<int64_t>(all_groups, std::max<int64_t>(1, (want + streams / 2) / streams) * streams);
-        }
+        a.n_sample = ft_n_sample(D, n, k, nprod, chunks);
         CVTMI_TRY(ft_launch_any(D, nprod, true, a, lds, st));
         const unsigned tg = (unsigned)((m + 3) / 4);
         const float loosen = (a.dbg & 32) ? 0.02f : 0.0f;
         if (metric == CVTMI_METRIC_IP) {
-            if (big) hipLaunchKernelGGL((ft_theta_kernel<true, FT_SLOTS_BIG / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
-            else hipLaunchKernelGGL((ft_theta_kernel<true, FT_SLOTS / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
+            if (big) hipLaunchKernelGGL((ft_theta_kernel<true, FT_SLOTS_BIG / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, fixed, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
+            else hipLaunchKernelGGL((ft_theta_kernel<true, FT_SLOTS / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, fixed, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
         } else {
-            if (big) hipLaunchKernelGGL((ft_theta_kernel<false, FT_SLOTS_BIG / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
-            else hipLaunchKernelGGL((ft_theta_kernel<false, FT_SLOTS / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
+            if (big) hipLaunchKernelGGL((ft_theta_kernel<false, FT_SLOTS_BIG / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, fixed, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
+            else hipLaunchKernelGGL((ft_theta_kernel<false, FT_SLOTS / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, fixed, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
         }
         a.t1 = n_tiles; a.n_sample = 0;
         CVTMI_TRY(ft_launch_any(D, nprod, false, a, lds, st));
@@ -1016,24 +1091,24 @@ int launch_flat_f32_tfilter(int metric, int D, const float *X, const float *Xrow
                 static std::atomic<bool> attr_f[3][16] = {};
                 if (metric == CVTMI_METRIC_IP) {
                     (void)fs_set_lds((const void *)ft_finish_big_kernel<true, 4>, lds_b, attr_f[0]);
-                    hipLaunchKernelGGL((ft_finish_big_kernel<true, 4>), dim3(bgrid), dim3(1024), lds_b, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, (int)m, cstride, only2, bcount, blist, rm);
+                    hipLaunchKernelGGL((ft_finish_big_kernel<true, 4>), dim3(bgrid), dim3(1024), lds_b, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, (int)m, cstride, only2, bcount, blist, rm, fixed);
                 } else if (D % 16 == 0) {
                     (void)fs_set_lds((const void *)ft_finish_big_kernel<false, 8>, lds_b, attr_f[1]);
-                    hipLaunchKernelGGL((ft_finish_big_kernel<false, 8>), dim3(bgrid), dim3(1024), lds_b, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, (int)m, cstride, only2, bcount, blist, rm);
+                    hipLaunchKernelGGL((ft_finish_big_kernel<false, 8>), dim3(bgrid), dim3(1024), lds_b, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, (int)m, cstride, only2, bcount, blist, rm, fixed);
                 } else {
                     (void)fs_set_lds((const void *)ft_finish_big_kernel<false, 4>, lds_b, attr_f[2]);
-                    hipLaunchKernelGGL((ft_finish_big_kernel<false, 4>), dim3(bgrid), dim3(1024), lds_b, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, (int)m, cstride, only2, bcount, blist, rm);
+                    hipLaunchKernelGGL((ft_finish_big_kernel<false, 4>), dim3(bgrid), dim3(1024), lds_b, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, (int)m, cstride, only2, bcount, blist, rm, fixed);
                 }
                 return;
             }
             const unsigned grid = second ? (unsigned)rcap : (unsigned)m;
             uint32_t *rl = retry ? rlist : nullptr;
             if (metric == CVTMI_METRIC_IP)
-                hipLaunchKernelGGL((ft_finish_kernel<true, 4>), dim3(grid), dim3(256), 0, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, rcount, rl, rcap, second, (int)m, wide ? bcount : nullptr, blist, rm);
+                hipLaunchKernelGGL((ft_finish_kernel<true, 4>), dim3(grid), dim3(256), 0, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, rcount, rl, rcap, second, (int)m, wide ? bcount : nullptr, blist, rm, fixed);
             else if (D % 16 == 0)   // (the reference's L2 sums in 8 lanes when D % 16 == 0, in 4 lanes otherwise: space_l2.h:40-151)
-                hipLaunchKernelGGL((ft_finish_kernel<false, 8>), dim3(grid), dim3(256), 0, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, rcount, rl, rcap, second, (int)m, wide ? bcount : nullptr, blist, rm);
+                hipLaunchKernelGGL((ft_finish_kernel<false, 8>), dim3(grid), dim3(256), 0, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, rcount, rl, rcap, second, (int)m, wide ? bcount : nullptr, blist, rm, fixed);
             else
-                hipLaunchKernelGGL((ft_finish_kernel<false, 4>), dim3(grid), dim3(256), 0, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, rcount, rl, rcap, second, (int)m, wide ? bcount : nullptr, blist, rm);
+                hipLaunchKernelGGL((ft_finish_kernel<false, 4>), dim3(grid), dim3(256), 0, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, rcount, rl, rcap, second, (int)m, wide ? bcount : nullptr, blist, rm, fixed);
         };
         hipLaunchKernelGGL(ft_bucket_kernel, dim3(FT_GRID), dim3(FT_BUCKET_T), bucket_lds, st, rec, wcnt, cap, thr, cnt, cand, chunks, qper, (int)m, redo + a0, nw, nullptr, nullptr, fcap);
         finish(0);

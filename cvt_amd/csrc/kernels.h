@@ -294,6 +294,8 @@ bool flat_u8_gfilter_shape(int D);
 int launch_gather_labels(int64_t *ids, int64_t count, const int64_t *labels, hipStream_t st);
 // ids[i] = ids[i] >= 0 ? ids[i] + base : -1
 int launch_offset_labels(int64_t *ids, int64_t count, int64_t base, hipStream_t st);
+// *out = how many of flags[0 .. count) are non-zero
+int launch_count_nonzero(const uint32_t *flags, int64_t count, uint32_t *out, hipStream_t st);
 
 // ---- sq8.hip ----
 // den[n] = float(max(1e-12, sqrt(sum_i double(x_i * x_i))))   (int8_quan.cc:46-52)

@@ -194,6 +194,8 @@ int cvtmi_set_device(int device);
  *                     measured: 385 .. 512 queries 0.74 -> 0.51 ms on 1 M x 128-d, 1000 queries unchanged -- its registers spill)
  *   "hnsw_top_lds"    entries of an HNSW traversal's top queue kept in LDS (default 256; 0 = all)
  *   "hnsw_slots"      cap on HNSW traversals per CU (0 = what LDS allows, at most 32)
+ *   "flat_count_redo" 1 = every flat search counts the queries its threshold filter / fp32 stream handed to the exact kernels
+ *                     (cvtmi_flat_last_redo; the count is copied back and waited for inside the call); 0 (default) = not counted
  *   "scans_dbg" / "flat_f32_dbg"  measurement switches of the small-batch scan and of the fp32 stream (phases skipped: results are WRONG
  *                     when non-zero; development only) */
 int cvtmi_set_tuning(const char *name, int64_t value);
@@ -453,6 +455,10 @@ int cvtmi_flat_search_dev(cvtmi_flat_t h, const void *q, int64_t nq, int k, void
  * candidate list of the pipeline.  cvtmi_set_tuning("flat_variant", 1) allows the exact kernels only, 2 prefers the pipeline;
  * cvtmi_set_tuning("flat_f32_stream", 0 / 1 / 2) = never / choose / wherever it applies. */
 int cvtmi_flat_last_search(cvtmi_flat_t h, int *filtered, int64_t *max_candidates);
+/* Measurement hook: *redone = how many queries of the last search on h the exact kernels answered because the fp32 threshold
+ * filter, the uint8 threshold filter or the fp32 stream flagged them (bound not covering the query, sample not filled, lists over);
+ * 0 for a search those paths answered whole or did not take; -1 when cvtmi_set_tuning("flat_count_redo", 1) was not in force. */
+int cvtmi_flat_last_redo(cvtmi_flat_t h, int64_t *redone);
 /* Row shards of an exhaustive index (BruteforceSearch<dist_t>::searchKnn over rows split across GPUs: config 3's 5 GB of
  * uint8 rows shard like config 4's codes).  Rows added without labels report label = id_base + row; the sharded searches
  * return the global k best -- float distances, or the int32 distances of the uint8 metric (same 4-byte fields) -- identical
