@@ -777,6 +777,45 @@ def pca_project(mean, vectors, x, l2norm=True):
     return y
 
 
+
+def pca_covariance(x):
+    """cvtmi_pca_covariance: (mean [din] fp32, cov [din][din] float64) of the rows of x, with the arithmetic of
+    include/cvtmi.h ("PCA training").  numpy in -> numpy out (host entry); a torch CUDA tensor in -> torch tensors out
+    (device entry, current stream)."""
+    n, din = x.shape
+    if _is_torch(x):
+        import torch
+        mean = torch.empty(din, dtype=torch.float32, device=x.device)
+        cov = torch.empty((din, din), dtype=torch.float64, device=x.device)
+        _check(lib().cvtmi_pca_covariance_dev(_ptr(x), C.c_int64(n), C.c_int(din), _ptr(mean), _ptr(cov), _stream()))
+        return mean, cov
+    x = _np(x, np.float32)
+    mean = np.empty(din, dtype=np.float32)
+    cov = np.empty((din, din), dtype=np.float64)
+    _check(lib().cvtmi_pca_covariance(_ptr(x), C.c_int64(n), C.c_int(din), _ptr(mean), _ptr(cov)))
+    return mean, cov
+
+
+def pca_train(x, dout):
+    """cv::PCA(x, noArray(), DATA_AS_ROW, dout) as cvtmi_pca_train computes it: (mean [din], vectors [dout][din],
+    values [dout]), the values descending.  numpy in -> numpy out (host entry); a torch CUDA tensor in -> torch tensors
+    out (device entry, current stream)."""
+    n, din = x.shape
+    if _is_torch(x):
+        import torch
+        mean = torch.empty(din, dtype=torch.float32, device=x.device)
+        vectors = torch.empty((dout, din), dtype=torch.float32, device=x.device)
+        values = torch.empty(dout, dtype=torch.float32, device=x.device)
+        _check(lib().cvtmi_pca_train_dev(_ptr(x), C.c_int64(n), C.c_int(din), C.c_int(dout), _ptr(mean), _ptr(vectors),
+                                         _ptr(values), _stream()))
+        return mean, vectors, values
+    x = _np(x, np.float32)
+    mean = np.empty(din, dtype=np.float32)
+    vectors = np.empty((max(dout, 0), din), dtype=np.float32)
+    values = np.empty(max(dout, 0), dtype=np.float32)
+    _check(lib().cvtmi_pca_train(_ptr(x), C.c_int64(n), C.c_int(din), C.c_int(dout), _ptr(mean), _ptr(vectors), _ptr(values)))
+    return mean, vectors, values
+
 def sq8_decode(vmin, vdiff, codes):
     n, d = codes.shape
     if _is_torch(codes):

@@ -1,6 +1,7 @@
 // pca_utils.cc -- see pca_utils.h.  Reference: pca_train_project/pca_online/pca_utils.cc:16-35.
 #include "pca_utils.h"
 
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -68,6 +69,43 @@ void PCAUtils::loadModel(const std::string &filename)
     mean = read_opencv_matrix(text, "mean");
     if (mean.rows != 1 || mean.cols != eigenvectors.cols)
         throw std::runtime_error("PCAUtils: mean must be 1 x " + std::to_string(eigenvectors.cols));
+}
+
+void PCAUtils::train(const float *data, int num, int dim, int num_reduced_dim)
+{
+    Mat32f m, e, v;
+    m.create(1, dim > 0 ? dim : 1);
+    e.create(num_reduced_dim > 0 ? num_reduced_dim : 1, dim > 0 ? dim : 1);
+    v.create(num_reduced_dim > 0 ? num_reduced_dim : 1, 1);
+    if (cvtmi_pca_train(data, num, dim, num_reduced_dim, m.data.data(), e.data.data(), v.data.data()) != CVTMI_OK)
+        throw std::runtime_error(std::string("cvt_amd: ") + cvtmi_last_error());
+    mean = std::move(m);
+    eigenvectors = std::move(e);
+    eigenvalues = std::move(v);
+}
+
+// one !!opencv-matrix node in the layout of FileStorage (and of pca_train_project/model/*.yml): "%.8e", three numbers on the
+// first data line and four on each of the others
+static void write_opencv_matrix(FILE *f, const char *name, const Mat32f &m)
+{
+    fprintf(f, "%s: !!opencv-matrix\n   rows: %d\n   cols: %d\n   dt: f\n   data: [", name, m.rows, m.cols);
+    for (size_t i = 0; i < m.data.size(); ++i) {
+        if (i > 0) fprintf(f, (i >= 3 && (i - 3) % 4 == 0) ? ",\n      " : ",");
+        fprintf(f, " %.8e", (double)m.data[i]);
+    }
+    fprintf(f, " ]\n");
+}
+
+void PCAUtils::saveModel(const std::string &filename) const
+{
+    if (eigenvectors.empty()) throw std::runtime_error("PCAUtils: no model to save");
+    FILE *f = fopen(filename.c_str(), "w");
+    if (!f) throw std::runtime_error("PCAUtils: cannot write " + filename);
+    fprintf(f, "%%YAML:1.0\n---\nname: PCA\n");
+    write_opencv_matrix(f, "vectors", eigenvectors);
+    write_opencv_matrix(f, "values", eigenvalues);
+    write_opencv_matrix(f, "mean", mean);
+    if (fclose(f) != 0) throw std::runtime_error("PCAUtils: cannot write " + filename);
 }
 
 void PCAUtils::reduceDim(const float *data, int num, int dim, Mat32f &reduceMat)

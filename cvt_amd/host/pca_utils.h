@@ -32,6 +32,12 @@ public:
         return &inst;
     }
     void loadModel(const std::string &filename);  // throws std::runtime_error on a missing / malformed file
+    // cv::PCA(data, noArray(), DATA_AS_ROW, num_reduced_dim) (train/src/opencv_utils.hpp:27-39) on the MI355X
+    // (cvtmi_pca_train): fills the model in the shapes loadModel gives it; throws std::runtime_error on failure
+    void train(const float *data, int num, int dim, int num_reduced_dim);
+    // cv::PCA::write into FileStorage YAML (name, vectors, values, mean); every float with 9 significant digits, so
+    // loadModel reads back the same bits.  Throws std::runtime_error when the file cannot be written.
+    void saveModel(const std::string &filename) const;
 
     void reduceDim(const float *data, int num, int dim, Mat32f &reduceMat);  // NOLINT
     void reduceDim(const Mat32f &mat, Mat32f &reduceMat);                    // NOLINT

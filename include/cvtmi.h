@@ -514,6 +514,38 @@ int cvtmi_pca_project(const float *mean, const float *vectors, int din, int dout
 int cvtmi_pca_project_dev(const float *mean, const float *vectors, int din, int dout, const float *x,
                           int64_t n, int l2norm, float *y, void *stream);
 
+/* ---------------------------------------------------------------- PCA training --------------- */
+/* The reference trains its models with cv::PCA(data, noArray(), DATA_AS_ROW, dout) (pca_train_project/train/src/
+ * train.cpp, opencv_utils.hpp:27-39).  OpenCV is absent here: PARITY UNPINNED.  What runs is this arithmetic:
+ *   1. mean[j] = float(sum_r (double)x[r][j] / n): column sums in double over a fixed partition of the rows,
+ *      the partials combined in a fixed order (no atomics);
+ *   2. d[r][j] = x[r][j] - mean[j], rounded to fp32 (OpenCV centres a CV_32F matrix in fp32);
+ *   3. cov[i][j] = (sum_r (double)d[r][i] * (double)d[r][j]) / n  (OpenCV's COVAR_NORMAL | COVAR_ROWS | COVAR_SCALE:
+ *      divided by n, not n - 1).  Every product of two floats is exact in double; only the double additions round.
+ *      Only the tiles on and below the diagonal are computed and mirrored, so cov is bitwise symmetric; rows are
+ *      split into blocks that depend on (n, din) alone and the partials are summed in block order, so the same
+ *      input gives the same bits on every call, host entry and device entry alike.  Two passes: the mean first,
+ *      then the centred product (the one-pass X^T X - n mu mu^T loses (|mu| / sigma)^2 of its relative accuracy);
+ *   4. eigendecomposition of cov in double on the device by rocSOLVER's dsyevd, loaded at run time (librocsolver.so.0:
+ *      processes that never train never load it; CVTMI_EUNSUPPORTED if it cannot be loaded); a solve that does
+ *      not converge is CVTMI_EHIP;
+ *   5. the dout largest eigenvalues in descending order; each eigenvector's sign makes its largest-magnitude
+ *      component positive, the lowest index winning ties (OpenCV's signs are arbitrary); values = float(lambda),
+ *      vectors = float(v).
+ * Limits: din % 4 == 0, 4 <= din <= 2048, 1 <= dout <= min(din, n); anything else is CVTMI_EINVAL.  OpenCV quietly
+ * shortens the model when n < din (its "scrambled" covariance); these entries reject that instead.
+ * Host entries copy x to the device once: CVTMI_ENOMEM when x, the partial sums, the covariance and the solver's
+ * workspace do not fit in the device's free memory.  _dev entries take device pointers and return after the
+ * work on `stream` is complete. */
+/* mean [din] fp32; cov [din][din] float64, exactly symmetric */
+int cvtmi_pca_covariance(const float *x, int64_t n, int din, float *mean, double *cov);
+int cvtmi_pca_covariance_dev(const float *x, int64_t n, int din, float *mean, double *cov, void *stream);
+/* mean [din], vectors [dout][din], values [dout]: the three matrices of the model file ("mean" 1 x din,
+ * "vectors" dout x din, "values" dout x 1) */
+int cvtmi_pca_train(const float *x, int64_t n, int din, int dout, float *mean, float *vectors, float *values);
+int cvtmi_pca_train_dev(const float *x, int64_t n, int din, int dout, float *mean, float *vectors, float *values,
+                        void *stream);
+
 /* ---------------------------------------------------------------- codebook training ---------- */
 /* TrainPQ::CoarseQuan / ProdQuan (opq/train_codebook/train_PQ_codebook.cpp:150-244).  The reference calls
  * yael's kmeans(d, n, k, niter = 0, v, nt, seed = 1, redo = 1, ...), which is not vendored: PARITY UNPINNED.
