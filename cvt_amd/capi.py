@@ -561,7 +561,8 @@ class FlatIndex:
 
 
 class HnswIndex:
-    """cvtmi_hnsw_*: batched search over a graph file written by the reference's HierarchicalNSW::saveIndex."""
+    """cvtmi_hnsw_*: batched search over a graph file written by the reference's HierarchicalNSW::saveIndex, or built on the GPU
+    (hnsw_build)."""
     def __init__(self, index_bytes, metric, D):
         self.h = C.c_void_p()
         self.D = D
@@ -578,6 +579,14 @@ class HnswIndex:
             self.close()
         except Exception:
             pass
+
+    def save(self):
+        """cvtmi_hnsw_save: the reference's saveIndex file of this graph, as bytes"""
+        n = C.c_int64(0)
+        _check(lib().cvtmi_hnsw_save(self.h, C.c_void_p(0), C.c_int64(0), C.byref(n)))
+        buf = np.empty(n.value, dtype=np.uint8)
+        _check(lib().cvtmi_hnsw_save(self.h, _ptr(buf), C.c_int64(buf.size), C.byref(n)))
+        return buf.tobytes()
 
     @property
     def ntotal(self):
@@ -636,6 +645,37 @@ def _hnsw_search_adc_rerank(self, opq, q, k, ef, rerank=None, rotate=True):
 
 
 HnswIndex.search_adc_rerank = _hnsw_search_adc_rerank
+
+
+def hnsw_build(x, metric, M, ef_construction, labels=None, max_batch=0):
+    """cvtmi_hnsw_build[_dev]: a HierarchicalNSW graph over the rows x [n][D] (numpy, or a CUDA tensor with labels on the same
+    device), batch-synchronous on the GPU (max_batch = 1: the reference's sequential insertion; 0: the default schedule)."""
+    n, D = x.shape
+    idx = HnswIndex.__new__(HnswIndex)
+    idx.h = C.c_void_p()
+    idx.D = D
+    if _is_torch(x):
+        import torch
+        assert x.is_contiguous() and x.dtype == torch.float32
+        lab = None
+        if labels is not None:
+            lab = labels if _is_torch(labels) else torch.as_tensor(np.ascontiguousarray(labels, dtype=np.uint64).view(np.int64))
+            lab = lab.to(device=x.device, dtype=torch.int64).contiguous()
+        _check(lib().cvtmi_hnsw_build_dev(_ptr(x), C.c_int64(n), C.c_int(D), C.c_int(metric), C.c_int(M), C.c_int(ef_construction),
+                                          _ptr(lab), C.c_int(max_batch), C.byref(idx.h), _stream()))
+        return idx
+    x = _np(x, np.float32)
+    lab = None if labels is None else _np(labels, np.uint64)
+    _check(lib().cvtmi_hnsw_build(_ptr(x), C.c_int64(n), C.c_int(D), C.c_int(metric), C.c_int(M), C.c_int(ef_construction), _ptr(lab),
+                                  C.c_int(max_batch), C.byref(idx.h)))
+    return idx
+
+
+def hnsw_build_phases():
+    """[traversal ms, selection ms, back-link ms, batches, host ms] of the last hnsw_build run with set_tuning("hnsw_build_phases", 1)"""
+    ms = (C.c_double * 5)()
+    _check(lib().cvtmi_hnsw_build_phases(ms))
+    return list(ms)
 
 
 class _PinnedOwner:

@@ -14,6 +14,8 @@
 #include <numeric>
 #include <thread>
 #include <vector>
+#include <cmath>
+#include <random>
 
 #include "host_util.h"
 #include "kernels.h"
@@ -503,6 +505,9 @@ int cvtmi_set_tuning(const char *name, int64_t value)
     if (!strcmp(name, "opq_small_zero_copy")) { g_small_zero_copy = value != 0; return CVTMI_OK; }
     if (!strcmp(name, "host_spin_us")) { g_host_spin_us = value < 0 ? 0 : (int)value; return CVTMI_OK; }
     if (!strcmp(name, "hnsw_top_lds")) { set_hnsw_top_lds((int)value); return CVTMI_OK; }
+    if (!strcmp(name, "hnsw_build_frac")) { set_hnsw_build_frac((int)std::min<int64_t>(value, 1 << 30)); return CVTMI_OK; }
+    if (!strcmp(name, "hnsw_build_cap")) { set_hnsw_build_cap((int)std::min<int64_t>(value, 1 << 30)); return CVTMI_OK; }
+    if (!strcmp(name, "hnsw_build_phases")) { set_hnsw_build_phases((int)value); return CVTMI_OK; }
     if (!strcmp(name, "hnsw_adc_tables")) { set_hnsw_adc_tables((int)value); return CVTMI_OK; }
     if (!strcmp(name, "hnsw_slots")) { g_hnsw_slots_cap = (int)value; return CVTMI_OK; }
     if (!strcmp(name, "flat_u8_tfilter")) { set_flat_u8_tfilter((int)value); return CVTMI_OK; }
@@ -2716,6 +2721,13 @@ struct cvtmi_hnsw_s {
     int device = 0, metric = 0, D = 0;
     HnswDevGraph g{};
     DevBuf vec, links0, labels, upper_off, upper;
+    // what cvtmi_hnsw_save needs beyond the device graph: the header fields as the file (or the build) set them, and the number
+    // of upper levels of every element
+    std::vector<int32_t> levels;
+    uint64_t max_elements = 0, M = 0, efc = 0;
+    double mult = 0.0;
+    int32_t hdr_maxlevel = 0;
+    uint32_t hdr_enterpoint = 0;
     std::mutex pool_mu;
     std::vector<HnswScratch *> pool;
     int slots_per_cu_max = 32, cus = 256;
@@ -2775,7 +2787,6 @@ int cvtmi_hnsw_load(const void *file, int64_t bytes, int metric, int D, cvtmi_hn
     auto rd = [&](void *dst, size_t nb) { memcpy(dst, p, nb); p += nb; };
     rd(&offsetLevel0, 8); rd(&max_elements, 8); rd(&cur_count, 8); rd(&size_per, 8); rd(&label_off, 8); rd(&offsetData, 8);
     rd(&maxlevel, 4); rd(&enterpoint, 4); rd(&maxM, 8); rd(&maxM0, 8); rd(&M, 8); rd(&mult, 8); rd(&efc, 8);
-    (void)M; (void)mult; (void)efc;
     if (size_per != 4 + 4 * maxM0 + 4 * (uint64_t)D + 8 || offsetData != 4 + 4 * maxM0 || label_off != offsetData + 4 * (uint64_t)D ||
         offsetLevel0 != 0 || cur_count > max_elements || maxM0 > 4096 || maxM > 4096)
         return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: header does not describe %d-d fp32 vectors (size_data_per_element=%llu)", D,
@@ -2862,7 +2873,156 @@ int cvtmi_hnsw_load(const void *file, int64_t bytes, int metric, int D, cvtmi_hn
     h->g.upper_off = h->upper_off.as<int64_t>(); h->g.upper = h->upper.as<uint32_t>();
     h->g.n = n; h->g.D = D; h->g.maxM = (int)maxM; h->g.maxM0 = (int)maxM0; h->g.maxlevel = n > 0 ? maxlevel : 0;
     h->g.enterpoint = enterpoint;
+    h->levels.swap(levels);
+    h->max_elements = max_elements; h->M = M; h->efc = efc; h->mult = mult;
+    h->hdr_maxlevel = maxlevel; h->hdr_enterpoint = enterpoint;
     *out = h;
+    return CVTMI_OK;
+}
+
+// Graph construction (hnswalg.h:584-684), batch-synchronous: hnsw_build.hip.  The constructor's fields (:104-127): maxM = M,
+// maxM0 = 2 M, mult = 1 / ln M, ef_construction = max(efc, M); levels are the draws of std::default_random_engine(100) in row
+// order (getRandomLevel, :143-148), made here on the host as the reference makes them.
+static int hnsw_build_impl(const float *x, bool dev, int64_t n, int D, int metric, int M, int efc, const uint64_t *labels, int max_batch,
+                           cvtmi_hnsw_t *out, hipStream_t st)
+{
+    if (out) *out = nullptr;
+    if (!x || !out || n < 1 || D < 1 || (metric != CVTMI_METRIC_IP && metric != CVTMI_METRIC_L2F) || M < 2 || efc < 1 || max_batch < 0)
+        return fail(CVTMI_EINVAL, "cvtmi_hnsw_build: bad arguments (n >= 1, D >= 1, metric IP or L2F, M >= 2, ef_construction >= 1, max_batch >= 0)");
+    if (M > 32) return fail(CVTMI_EINVAL, "cvtmi_hnsw_build: M=%d > 32 (a level-0 list of 2 M links is one wave)", M);
+    const int efe = efc > M ? efc : M;
+    if (efe > hnsw_ef_max()) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_build: ef_construction=%d > %d", efe, hnsw_ef_max());
+    if (n > 0x7fffffffLL) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_build: n too large");
+    if (D > 4096) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_build: D=%d > 4096", D);
+    const int maxM = M, maxM0 = 2 * M;
+    const double mult = 1 / log(1.0 * M);
+    std::vector<int32_t> levels;
+    std::vector<int64_t> uoff;
+    std::vector<int64_t> lab;
+    int32_t maxlevel = 0;
+    uint32_t ep = 0;
+    int64_t upper_words = 0;
+    try {
+        levels.resize((size_t)n);
+        uoff.assign((size_t)n, -1);
+        std::default_random_engine rng(100);
+        std::uniform_real_distribution<double> u01(0.0, 1.0);
+        for (int64_t i = 0; i < n; ++i) {
+            levels[(size_t)i] = (int32_t)(-log(u01(rng)) * mult);
+            if (levels[(size_t)i] > 0) { uoff[(size_t)i] = upper_words; upper_words += (int64_t)levels[(size_t)i] * (maxM + 1); }
+            if (i == 0 || levels[(size_t)i] > maxlevel) { maxlevel = levels[(size_t)i]; ep = (uint32_t)i; }
+        }
+        if (!labels) { lab.resize((size_t)n); for (int64_t i = 0; i < n; ++i) lab[(size_t)i] = i; }
+    } catch (const std::exception &) {
+        return fail(CVTMI_ENOMEM, "cvtmi_hnsw_build: out of host memory for %lld rows", (long long)n);
+    }
+    int devn = 0;
+    CVTMI_HIP(hipGetDevice(&devn));
+    cvtmi_hnsw_s *h = new (std::nothrow) cvtmi_hnsw_s();
+    if (!h) return fail(CVTMI_ENOMEM, "cvtmi_hnsw_build: out of host memory");
+    h->device = devn; h->metric = metric; h->D = D;
+    {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, devn) == hipSuccess && prop.multiProcessorCount > 0) h->cus = prop.multiProcessorCount;
+    }
+    const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    auto run = [&]() -> int {
+        const size_t vb = (size_t)n * D * 4, l0b = (size_t)n * (maxM0 + 1) * 4, ub = (size_t)upper_words * 4;
+        CVTMI_TRY(h->vec.reserve(vb));
+        CVTMI_TRY(h->links0.reserve(l0b));
+        CVTMI_TRY(h->labels.reserve((size_t)n * 8));
+        CVTMI_TRY(h->upper_off.reserve((size_t)n * 8));
+        CVTMI_TRY(h->upper.reserve(ub ? ub : 16));
+        CVTMI_HIP(hipMemcpyAsync(h->vec.p, x, vb, in, st));
+        CVTMI_HIP(hipMemsetAsync(h->links0.p, 0, l0b, st));
+        if (ub) CVTMI_HIP(hipMemsetAsync(h->upper.p, 0, ub, st));
+        if (labels) CVTMI_HIP(hipMemcpyAsync(h->labels.p, labels, (size_t)n * 8, in, st));
+        else CVTMI_HIP(hipMemcpyAsync(h->labels.p, lab.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+        CVTMI_HIP(hipMemcpyAsync(h->upper_off.p, uoff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+        h->g.vec = h->vec.as<float>(); h->g.links0 = h->links0.as<uint32_t>(); h->g.labels = h->labels.as<int64_t>();
+        h->g.upper_off = h->upper_off.as<int64_t>(); h->g.upper = h->upper.as<uint32_t>();
+        h->g.n = n; h->g.D = D; h->g.maxM = maxM; h->g.maxM0 = maxM0; h->g.maxlevel = maxlevel; h->g.enterpoint = ep;
+        // (launch_hnsw_build synchronises the stream before it returns: the host vectors above outlive every copy from them)
+        return launch_hnsw_build(h->g, h->links0.as<uint32_t>(), h->upper.as<uint32_t>(), levels.data(), metric, M, efe, max_batch,
+                                 h->cus, st);
+    };
+    const int rc = run();
+    if (rc != CVTMI_OK) { (void)hipStreamSynchronize(st); cvtmi_hnsw_destroy(h); return rc; }
+    h->levels.swap(levels);
+    h->max_elements = (uint64_t)n; h->M = (uint64_t)M; h->efc = (uint64_t)efe; h->mult = mult;
+    h->hdr_maxlevel = maxlevel; h->hdr_enterpoint = ep;
+    *out = h;
+    return CVTMI_OK;
+}
+
+int cvtmi_hnsw_build(const float *x, int64_t n, int D, int metric, int M, int ef_construction, const uint64_t *labels, int max_batch,
+                     cvtmi_hnsw_t *out)
+{
+    return hnsw_build_impl(x, false, n, D, metric, M, ef_construction, labels, max_batch, out, nullptr);
+}
+int cvtmi_hnsw_build_dev(const float *x, int64_t n, int D, int metric, int M, int ef_construction, const uint64_t *labels,
+                         int max_batch, cvtmi_hnsw_t *out, void *stream)
+{
+    return hnsw_build_impl(x, true, n, D, metric, M, ef_construction, labels, max_batch, out, (hipStream_t)stream);
+}
+int cvtmi_hnsw_build_phases(double *ms)
+{
+    if (!ms) return fail(CVTMI_EINVAL, "cvtmi_hnsw_build_phases: null pointer");
+    hnsw_build_phase_ms(ms);
+    return CVTMI_OK;
+}
+
+// saveIndex (:491-519): header, max_elements level-0 blocks (links, vector, label), then per element the size of its upper-level
+// block and the block.  Slots past cur_element_count are written as zeros.
+int cvtmi_hnsw_save(cvtmi_hnsw_t h, void *buf, int64_t cap, int64_t *bytes)
+{
+    CHECK_HN(h);
+    if (!bytes) return fail(CVTMI_EINVAL, "cvtmi_hnsw_save: null size pointer");
+    const int64_t n = h->g.n;
+    const uint64_t maxM = (uint64_t)h->g.maxM, maxM0 = (uint64_t)h->g.maxM0, D = (uint64_t)h->D;
+    const uint64_t link0 = 4 + 4 * maxM0, per = link0 + 4 * D + 8, upb = 4 * maxM + 4;
+    uint64_t total = 96 + h->max_elements * per + 4 * h->max_elements;
+    for (int64_t i = 0; i < n; ++i) total += upb * (uint64_t)h->levels[(size_t)i];
+    *bytes = (int64_t)total;
+    if (!buf) return CVTMI_OK;
+    if (cap < (int64_t)total) return fail(CVTMI_EINVAL, "cvtmi_hnsw_save: buffer of %lld bytes, the file needs %lld", (long long)cap,
+                                          (long long)total);
+    std::vector<uint32_t> links0, upper;
+    std::vector<float> vec;
+    std::vector<int64_t> labels, uoff;
+    size_t upper_words = 0;
+    for (int64_t i = 0; i < n; ++i) upper_words += (size_t)h->levels[(size_t)i] * (maxM + 1);
+    try {
+        links0.resize((size_t)n * (maxM0 + 1)); vec.resize((size_t)n * D); labels.resize((size_t)n); uoff.resize((size_t)n);
+        upper.resize(upper_words);
+    } catch (const std::exception &) {
+        return fail(CVTMI_ENOMEM, "cvtmi_hnsw_save: out of host memory");
+    }
+    if (n) {
+        CVTMI_HIP(hipMemcpy(links0.data(), h->links0.p, links0.size() * 4, hipMemcpyDeviceToHost));
+        CVTMI_HIP(hipMemcpy(vec.data(), h->vec.p, vec.size() * 4, hipMemcpyDeviceToHost));
+        CVTMI_HIP(hipMemcpy(labels.data(), h->labels.p, labels.size() * 8, hipMemcpyDeviceToHost));
+        CVTMI_HIP(hipMemcpy(uoff.data(), h->upper_off.p, uoff.size() * 8, hipMemcpyDeviceToHost));
+        if (upper_words) CVTMI_HIP(hipMemcpy(upper.data(), h->upper.p, upper_words * 4, hipMemcpyDeviceToHost));
+    }
+    uint8_t *p = static_cast<uint8_t *>(buf);
+    auto put = [&](const void *src, size_t nb) { memcpy(p, src, nb); p += nb; };
+    const uint64_t zero = 0, cnt = (uint64_t)n, offd = link0, offl = link0 + 4 * D;
+    put(&zero, 8); put(&h->max_elements, 8); put(&cnt, 8); put(&per, 8); put(&offl, 8); put(&offd, 8);
+    put(&h->hdr_maxlevel, 4); put(&h->hdr_enterpoint, 4);
+    put(&maxM, 8); put(&maxM0, 8); put(&h->M, 8); put(&h->mult, 8); put(&h->efc, 8);
+    for (int64_t i = 0; i < n; ++i) {
+        put(&links0[(size_t)i * (maxM0 + 1)], link0);
+        put(&vec[(size_t)i * D], 4 * D);
+        put(&labels[(size_t)i], 8);
+    }
+    memset(p, 0, (size_t)((h->max_elements - (uint64_t)n) * per));
+    p += (h->max_elements - (uint64_t)n) * per;
+    for (uint64_t i = 0; i < h->max_elements; ++i) {
+        const uint32_t sz = (int64_t)i < n ? (uint32_t)(upb * (uint64_t)h->levels[(size_t)i]) : 0u;
+        put(&sz, 4);
+        if (sz) put(&upper[(size_t)uoff[(size_t)i]], sz);
+    }
     return CVTMI_OK;
 }
 

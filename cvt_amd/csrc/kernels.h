@@ -368,4 +368,14 @@ void set_hnsw_top_lds(int v);
 void set_hnsw_adc_tables(int v);
 int hnsw_adc_state_floats(int MK);
 
+// ---- hnsw_build.hip ----
+// batch-synchronous construction into a zeroed graph: g.vec holds all n rows, links0 / upper are zero, g.upper_off is laid out
+// from `levels` (host, the drawn level of every row); returns when the graph is complete
+int launch_hnsw_build(const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, const int32_t *levels, int metric, int M, int efc,
+                      int max_batch, int cus, hipStream_t st);
+void set_hnsw_build_frac(int v);
+void set_hnsw_build_cap(int v);
+void set_hnsw_build_phases(int v);
+void hnsw_build_phase_ms(double *ms);   // [traversal, selection, back links, batches, host ms] of the last build with phases on
+
 }  // namespace cvtmi

@@ -3,7 +3,8 @@
 //  * SEARCH runs on the MI355X (cvtmi_hnsw_search: one wave per query, the reference's labels and distances
 //    bit for bit).  searchKnnBatch is the call that fills the GPU.
 //  * CONSTRUCTION is a host algorithm in the reference (one insertion at a time, every insertion sees the
-//    graph the previous ones left) and stays one here: addPoint follows hnswalg.h:584-684 -- level drawn from
+//    graph the previous ones left) and stays one here (addPointsGpu builds on the GPU instead, batch-synchronous:
+//    cvtmi_hnsw_build): addPoint follows hnswalg.h:584-684 -- level drawn from
 //    std::default_random_engine(100) (:139-149), greedy descent through the upper levels, a best-first search
 //    with ef_construction on every level the new node lives on (:152-216), neighbour selection by the
 //    "closer to the query than to any already selected neighbour" rule (:283-325), mutual links with
@@ -180,6 +181,34 @@ public:
             broken_ = true;
             throw std::runtime_error(err);
         }
+    }
+
+    // the whole graph built on the GPU in one call (cvtmi_hnsw_build: batch-synchronous insertion, max_batch = 1 is the sequential
+    // algorithm and the file addPoint would write; 0 = the default schedule).  The graph must be empty; its capacity becomes n.  The
+    // host structures are filled from the saved file, and the device graph is kept as the search handle.
+    void addPointsGpu(const void *rows, const labeltype *labels, size_t n, int max_batch = 0)
+    {
+        if (count_) throw std::runtime_error("HierarchicalNSW::addPointsGpu: the graph must be empty");
+        static_assert(sizeof(labeltype) == sizeof(uint64_t), "labels are 64-bit");
+        cvtmi_hnsw_t g = NULL;
+        if (cvtmi_hnsw_build((const float *)rows, (int64_t)n, (int)dim_, metric_, (int)M_, (int)efc_, (const uint64_t *)labels, max_batch,
+                             &g) != CVTMI_OK)
+            throw std::runtime_error(std::string("cvt_amd: ") + cvtmi_last_error());
+        int64_t bytes = 0;
+        std::vector<char> buf;
+        if (cvtmi_hnsw_save(g, NULL, 0, &bytes) == CVTMI_OK) {
+            buf.resize((size_t)bytes);
+            if (cvtmi_hnsw_save(g, buf.data(), bytes, &bytes) != CVTMI_OK) buf.clear();
+        }
+        if (buf.empty()) {
+            const std::string err = std::string("cvt_amd: ") + cvtmi_last_error();
+            cvtmi_hnsw_destroy(g);
+            throw std::runtime_error(err);
+        }
+        parse(buf);
+        if (dev_) cvtmi_hnsw_destroy(dev_);
+        dev_ = g;
+        dirty_ = false;
     }
 
     // the reference's file (:491-519)

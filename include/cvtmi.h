@@ -194,6 +194,10 @@ int cvtmi_set_device(int device);
  *                     measured: 385 .. 512 queries 0.74 -> 0.51 ms on 1 M x 128-d, 1000 queries unchanged -- its registers spill)
  *   "hnsw_top_lds"    entries of an HNSW traversal's top queue kept in LDS (default 256; 0 = all)
  *   "hnsw_slots"      cap on HNSW traversals per CU (0 = what LDS allows, at most 32)
+ *   "hnsw_build_frac" cvtmi_hnsw_build: a batch holds at most 1/value of the rows already inserted (default 32)
+ *   "hnsw_build_cap"  cvtmi_hnsw_build with max_batch = 0: rows per batch at most (default 8192).  Unlike the other keys these
+ *                     two change results: they are the schedule, and the graph depends on it (the schedule sweep of DESIGN.md 4.11)
+ *   "hnsw_build_phases" 1 = time the phases of cvtmi_hnsw_build (cvtmi_hnsw_build_phases)
  *   "flat_count_redo" 1 = every flat search counts the queries its threshold filter / fp32 stream handed to the exact kernels
  *                     (cvtmi_flat_last_redo; the count is copied back and waited for inside the call); 0 (default) = not counted
  *   "scans_dbg" / "flat_f32_dbg"  measurement switches of the small-batch scan and of the fp32 stream (phases skipped: results are WRONG
@@ -591,13 +595,42 @@ int cvtmi_opq_learn_rotation_dev(const float *x, int64_t n, int D, int M, int K,
  *   summation order of the reference's distance functions and both priority queues replay libstdc++'s
  *   push_heap / pop_heap (the reference compares by distance only, so heap mechanics decide ties): labels
  *   and distances are bit-identical to the reference's on the same graph.  k, ef <= 1024.
- * Graph construction (addPoint) is not offered here: graphs are built with the reference's tools. */
+ * Graphs are loaded from the reference's files or built on the GPU (cvtmi_hnsw_build, below). */
 int cvtmi_hnsw_load(const void *file, int64_t bytes, int metric, int D, cvtmi_hnsw_t *out);
 int cvtmi_hnsw_destroy(cvtmi_hnsw_t h);
 int64_t cvtmi_hnsw_ntotal(cvtmi_hnsw_t h);
 int cvtmi_hnsw_search(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int ef, float *dist, int64_t *labels);
 int cvtmi_hnsw_search_dev(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int ef, float *dist, int64_t *labels,
                           void *stream);
+/* Graph construction on the GPU, batch-synchronous.  Rows x [n][D] fp32 get internal ids 0 .. n-1 and the labels
+ * `labels` [n] (NULL = the row number).  The graph is the reference's HierarchicalNSW(space, n, M, ef_construction) after one
+ * addPoint per row (hnswalg.h:584-684), except for one rule: rows are inserted in BATCHES of consecutive rows, every row of a
+ * batch searches the graph as the earlier batches left it (rows of one batch do not see each other), and then the batch's back
+ * links are applied, for each target node in increasing source id, each exactly as mutuallyConnectNewElement applies it.
+ *   - header as the reference's constructor sets it: max_elements = n, maxM = M, maxM0 = 2 M, mult = 1 / ln M,
+ *     ef_construction = max(ef_construction, M); the level of row i is the i-th draw of std::default_random_engine(100)
+ *     through getRandomLevel (:143-148), so levels equal those of every sequential build of the same n rows;
+ *   - batches: at most max_batch rows (max_batch = 1: the reference's sequential insertion, and the file cvtmi_hnsw_save
+ *     writes is byte-identical to the reference's saveIndex), and at most 1/32 of the rows already inserted (at least one);
+ *     max_batch = 0 caps batches at 8192 rows.  A row whose level exceeds the current top level ends its batch;
+ *   - distances and queue mechanics as in cvtmi_hnsw_search: the graph is a pure function of (rows, labels, metric, M,
+ *     ef_construction, max_batch), whatever the stream, device or timing.  Rows must be finite.
+ * The result is an ordinary handle: every cvtmi_hnsw_search* entry works on it.  Arguments are checked before any device work;
+ * invalid ones (n < 1, D < 1, unknown metric, M < 2, ef_construction < 1, max_batch < 0, NULL x / out, and M > 32: a level-0
+ * list of 2 M links is one wave) return CVTMI_EINVAL with *out = NULL; max(ef_construction, M) > 1024 or D > 4096:
+ * CVTMI_EUNSUPPORTED.  cvtmi_hnsw_build_dev takes device rows and labels, runs on `stream` and returns when the graph is
+ * complete. */
+int cvtmi_hnsw_build(const float *x, int64_t n, int D, int metric, int M, int ef_construction, const uint64_t *labels, int max_batch,
+                     cvtmi_hnsw_t *out);
+int cvtmi_hnsw_build_dev(const float *x, int64_t n, int D, int metric, int M, int ef_construction, const uint64_t *labels,
+                         int max_batch, cvtmi_hnsw_t *out, void *stream);
+/* saveIndex (:491-519) of a built or loaded graph into buf[cap]; *bytes = the file's size (buf = NULL: only the size).  Slots
+ * between cur_element_count and max_elements (a loaded file's spare capacity) are written as zeros, where the reference writes
+ * whatever its allocation held: load -> save reproduces a file with max_elements == cur_element_count byte for byte. */
+int cvtmi_hnsw_save(cvtmi_hnsw_t h, void *buf, int64_t cap, int64_t *bytes);
+/* measurement hook: with cvtmi_set_tuning("hnsw_build_phases", 1), ms[5] = device milliseconds of the last build spent in
+ * traversal, selection and back links (bucketing included), its batch count, and host milliseconds (level draw, schedule) */
+int cvtmi_hnsw_build_phases(double *ms);
 /* HNSW over OPQ-compressed vectors (BASELINE config 5; not in the reference, whose HNSW holds fp32 vectors):
  * the same traversal over the same graph, but a node's distance is the ADC sum of the query's tables over the
  * node's PQ code (IVFOPQ.cpp:273-291 tables, :302-306 sum) -- M bytes gathered per neighbour instead of 4 D.
