@@ -5,7 +5,10 @@
 //     (distance, list) pairs; the visiting order does not matter because the scores are min-reduced);
 //   * per probed list: residual LUT (:273-291) and ADC scan of that list's entries (:300-306);
 //   * matchScore[f][videoId] = min(score, current), starting from threhold = 1.0 (:5, :262, :308).
-// Scores are sums of squares (>= +0), so the fp32 min is an unsigned-integer atomicMin on the bits.
+// Scores are sums of squares (>= +0), so the fp32 min is an unsigned-integer atomicMin on the bits.  A NaN score is stored
+// instead: std::min(score, current) is (current < score) ? current : score, so a NaN replaces the cell.  With a finite model
+// a NaN score comes only from a frame holding a NaN, every score of that frame is NaN, and the result does not depend on order
+// (its probed lists are 0 .. nk - 1: every distance is NaN, and a NaN never replaces the heap top).
 #include <algorithm>
 
 #include "block_topk.h"
@@ -456,7 +459,11 @@ __global__ __launch_bounds__(kBlock) void query_video_kernel(const float *__rest
             for (int m = 0; m < M; ++m) s = __fadd_rn(s, lut[m * 256 + c[m]]);
         }
         const int v = video_id[r];
-        if (v >= 0 && v < img_num) atomicMin(&ms[v], __float_as_uint(s));
+        const uint32_t sb = __float_as_uint(s);
+        if (v >= 0 && v < img_num) {
+            if ((sb & 0x7fffffffu) > 0x7f800000u) ms[v] = sb;  // NaN: std::min(score, current) returns the score (a NaN frame)
+            else atomicMin(&ms[v], sb);
+        }
     }
 }
 

@@ -268,7 +268,12 @@ int cvtmi_opq_search_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, 
  * nearest coarse lists and keep, per video, the minimum ADC score clamped at 1.0.
  * match_score[nq][img_num].  rotate as above.  The list-ordered copy of the entries is (re)built on the device by the
  * first query after an append (a stable counting sort; ~2.5 ms per million entries); entries whose list id is outside
- * [0, coarseK) are skipped; a video id outside [0, img_num) fails the call. */
+ * [0, coarseK) are skipped; a video id outside [0, img_num) fails the call.  nprobe > coarseK is clamped to coarseK;
+ * an nprobe above 128 (after the clamp) fails with CVTMI_EUNSUPPORTED.
+ * Non-finite frames score as in the reference's std::min fold: a frame holding a NaN probes lists 0 .. nprobe-1 and
+ * gets NaN in every video with an entry there (1.0 elsewhere); a frame whose scores are all +inf keeps 1.0.  Frames
+ * whose scores mix NaN and finite values (possible only with non-finite codebooks) depend on the reference's visiting
+ * order and are not matched. */
 int cvtmi_opq_query_video(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe,
                           int img_num, float *match_score);
 int cvtmi_opq_query_video_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe,

@@ -303,7 +303,8 @@ ORC_API void orc_adc_search(const float *q, int64_t nq, int D, const float *cent
  *     lists are pushed unconditionally, later ones replace the top when strictly closer
  *     (:248-259);  lists are then visited in heap-pop order = farthest first (:264-267).
  *   - matchScore[f][video] starts at 1.0 (threhold, :5, :262) and takes the min over
- *     every code of that video met in the probed lists (:308).
+ *     every code of that video met in the probed lists (:308), as std::min folds it: a NaN
+ *     score (a frame holding a NaN) leaves NaN in the cell.
  * Inverted lists are given CSR-style: list l owns entries [list_off[l], list_off[l+1]).
  * q must already be rotated. */
 ORC_API void orc_query_video(const float *q, int64_t nq, int D, const float *coarse, int coarseK,
@@ -333,7 +334,8 @@ ORC_API void orc_query_video(const float *q, int64_t nq, int D, const float *coa
                 float s = 0.0f;
                 for (int kk = 0; kk < M; ++kk) s += lut[kk * K + codes[j * M + kk]];
                 int v = video_id[j];
-                if (s < ms[v]) ms[v] = s; /* min(score, current), :308 */
+                /* std::min(score, current), :308, literally: a NaN score replaces the cell */
+                ms[v] = (ms[v] < s) ? ms[v] : s;
             }
         }
     }
