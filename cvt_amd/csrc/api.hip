@@ -498,7 +498,7 @@ int cvtmi_set_tuning(const char *name, int64_t value)
     if (!strcmp(name, "flat_f32_tfilter_min_rows")) { set_flat_f32_tfilter_min_rows((int)value); return CVTMI_OK; }
     if (!strcmp(name, "flat_f32_tfilter_sample")) { set_flat_f32_tfilter_sample((int)value); return CVTMI_OK; }
     if (!strcmp(name, "flat_f32_share")) {
-        if (value < 0 || value > 3) return fail(CVTMI_EINVAL, "cvtmi_set_tuning: flat_f32_share must be 0 .. 3");
+        if (value < 0 || value > 1) return fail(CVTMI_EINVAL, "cvtmi_set_tuning: flat_f32_share must be 0 or 1 (the eight- and twelve-wave forms are gone)");
         set_flat_f32_share((int)value);
         return CVTMI_OK;
     }

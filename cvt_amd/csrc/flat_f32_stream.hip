@@ -125,7 +125,8 @@ template <int NCH, bool PACKED = false> struct FsGeom {
 };
 
 // X: blocked fp32 rows (float4 c of the 64 rows of block b contiguous: ((b * D/4 + c) * 64 + r) float4); bias[n_tiles * 32];
-// gb[((q * NG + g) * FS_WAVES + wave) * 32 + j] = (best, second) of rows (wave + (g G + p) FS_WAVES) * 32 + j, p < G;
+// gb[((q * NG + g) * FS_WAVES + wave) * 32 + j] = (best, second) of rows (wave + (g G + p) FS_WAVES) * 32 + j, p < G (written only
+// for the groups the wave reaches: NG is that of the longest stream);
 // wm[q * FS_WAVES + wave] = the largest best of the wave (the finish derives its first threshold from these 1024 values)
 template <int NCH, int QB, bool PACKED = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void flat_f32_mstream_kernel(
@@ -316,8 +317,8 @@ __device__ __forceinline__ float fs_max(float a, float b)
 }
 
 // NW waves of 32 QB queries each, the first NF of them also request and convert the tiles (NF divides the 2 NCH pieces of a
-// tile into whole K steps).  <QB, 4, 4>: one wave per SIMD with up to 96 queries in its registers.  <1, 12, NCH>: three waves
-// per SIMD with 32 queries each -- a wave issues a vector instruction every ~5 cycles at best, so the vector work of a tile
+// tile into whole K steps).  <QB, 4, 4>, the one form instantiated: one wave per SIMD with up to 128 queries in its registers.
+// (<1, 12, NCH> and <2, 8, NCH>, several waves per SIMD, were removed: see fs_four on the host side.)  Why they were tried: a wave issues a vector instruction every ~5 cycles at best, so the vector work of a tile
 // (folding the scores into best / second, the conversion) only disappears behind the matrix instructions when several
 // waves share the SIMD.  Measured per pass on 1 M x 128-d: one wave per SIMD 254 us (256 queries) / 340 us (384), two waves per
 // SIMD in lock step 210 us (256), two waves alternating between a matrix and a vector phase 254 us, two waves with separate
@@ -682,6 +683,10 @@ __global__ __launch_bounds__(kBlock) void flat_f32_stream_collect_kernel(const F
 #pragma unroll
         for (int u = 0; u < U; ++u)
             if (v[u].x >= cut1) {
+                // NG counts the groups of the longest stream: a stream with fewer tiles wrote no entry for a group it does not
+                // reach, and what lies there was left by an earlier pass or search -- not a group of this query
+                const int64_t e = base + (int64_t)u * kBlock, wv = (e >> 5) & ((1 << a.ns_log) - 1), g = e >> (5 + a.ns_log);
+                if (((wv + ((g * a.G) << a.ns_log)) << 5) >= a.n) continue;
                 const int slot = atomicAdd(&nh_s, 1);
                 if (slot < kBlock * U) hit_s[slot] = make_uint4(__float_as_uint(v[u].x), __float_as_uint(v[u].y), (uint32_t)(base + (int64_t)u * kBlock), 0u);
             }
@@ -757,7 +762,15 @@ __global__ __launch_bounds__(kBlock) void flat_f32_stream_finish_kernel(const Fs
             uint32_t key[NK];
 #pragma unroll
             for (int j = 0; j < NK; ++j) key[j] = (j * 64 + lane < nl) ? best_s[j * 64 + lane] : 0u;
-            const uint32_t c = fs_wave_select(key, k, k);
+            // fs_wave_select stops at the first trial value exactly k keys reach (kmax = k): a truncated prefix of the k-th key,
+            // arbitrarily far below it when no (k + 1)-th key is near -- when only k groups are listed, below every second best
+            // too, so every listed group had all its rows evaluated and the query ran over FSF_KEEP.  The k-th largest itself is
+            // the smallest key that reaches it
+            const uint32_t c0 = fs_wave_select(key, k, k);
+            uint32_t m = 0xffffffffu;
+#pragma unroll
+            for (int j = 0; j < NK; ++j) m = (key[j] >= c0 && key[j] < m) ? key[j] : m;
+            const uint32_t c = fs_wave_min_u32(m);
             if (lane == 0) theta_s = c;
         };
         if (nl <= 256) sel(std::integral_constant<int, 4>());
@@ -865,27 +878,19 @@ void set_flat_f32_nt(int v) { g_fs_nt = v; }
 // non-temporal row loads: measured better wherever the stream kernel is bound by the rows (one query 0.119 -> 0.106 ms,
 // 64 queries 0.147 -> 0.14, the shared ring 1.09 -> 1.07 at 1000), worse at three query blocks per wave (0.155 -> 0.165)
 static bool fs_nt(bool shared, int qb) { return g_fs_nt == 2 || (g_fs_nt == 1 && (shared || qb <= 2)); }
-static std::atomic<int> g_fs_share{0};   // cvtmi_set_tuning("flat_f32_share"): 0 = choose, 1 = four waves x 32 QB queries, 2 = FS_MANY waves x 32 queries
+static std::atomic<int> g_fs_share{0};   // cvtmi_set_tuning("flat_f32_share"): 0 = choose, 1 = the four-wave shared ring (the same)
 void set_flat_f32_share(int v) { g_fs_share = v; }
-// the shared-ring kernel wants whole K steps per wave: D / 16 a multiple of the wave count
-constexpr int FS_MANY = 12;   // waves of the many-wave form of the shared-ring kernel (three per SIMD)
-// round 6, "flat_f32_share" 3: eight waves (two per SIMD) of 64 queries each -- 512 queries per pass instead of 384 (1000 queries: two
-// passes over the rows instead of three)
-static bool fs_wide() { return g_fs_share == 3; }
-static int fs_many_queries() { return fs_wide() ? 8 * 64 : 32 * FS_MANY; }
-// Round 6: the eight- / twelve-wave forms are no longer chosen, only asked for ("flat_f32_share" 2 / 3).  A width sweep against the
-// exact kernels found ONE query of ~10^5 (2 M x 64-d rows, 1000 queries, L2: the row at rank 99 missing, tools/f32_tfilter_widths.py)
-// that both of them answer wrongly and the four-wave form, the private rings and the threshold filter answer correctly -- not
-// understood, so not trusted.  What is known: deterministic (the same query and row on every run, whatever the non-temporal hints), it
-// needs the whole 2 M rows (the first 1.9 M: right) AND the query at its place in a pass of 334 or 500 queries -- the same query in the same
-// wave of a pass of 200 queries is answered correctly, as it is in passes that start at query 60 or 64.  Batches of 16 queries and more over 262 144
-// rows and more go through flat_f32_tfilter.hip anyway; what is left to the shared ring are large batches on smaller tables.
-static bool fs_eight(int D) { return g_fs_share >= 2 && (D == 64 || D == 128); }
+// The eight- and twelve-wave forms of the shared-ring kernel (round 6, "flat_f32_share" 3 / 2: more queries per pass) are gone.  A width
+// sweep against the exact kernels found ONE query of ~10^5 they answered wrongly (2 M x 64-d rows, L2, 1000 queries in passes of 334 or
+// 500, the row at rank 99 missing) that the four-wave form answers correctly.  At the same pass split the four-wave form computes the
+// same scores (one accumulator chain per 32 queries, the same operand conversion) and hands them to the same collect and finish
+// kernels, so the defect sat in what only the many-wave forms do -- waves that compute without feeding, several waves per SIMD sharing
+// one ring -- and was never pinned to a line; the forms were not chosen by the dispatch, so they were removed rather than kept untrusted.
 static bool fs_four(int D) { return (D / 16) % 4 == 0; }
 int flat_f32_stream_qmax(int D)
 {
     if (D != 32 && D != 64 && D != 96 && D != 128 && D != 192 && D != 256) return 0;
-    return fs_eight(D) ? fs_many_queries() : (fs_four(D) ? 128 : 32) * fs_qb_max(D / 16);
+    return (fs_four(D) ? 128 : 32) * fs_qb_max(D / 16);
 }
 static bool fs_shared(int D, int64_t nq) { return nq > 32 * fs_qb_max(D / 16); }
 // the most queries a pass of the private-ring kernel takes (more go to the shared ring, up to flat_f32_stream_qmax)
@@ -930,29 +935,6 @@ int launch_flat_f32_bias(float *X, int D, int metric, int64_t row0, int64_t row1
 struct FsStreamArgs {
     const float *X, *bias; int64_t n_tiles; const float *q; int nq, G, NG; float2 *gb; float *wm; uint32_t *redo, *cnt;
 };
-template <int NCH>
-static int fs_launch_eight(const FsStreamArgs &a, hipStream_t st)
-{
-    if constexpr (NCH == 4 || NCH == 8) {
-        static std::atomic<bool> attr_set[16] = {};
-        const size_t lds = FssGeom<NCH, NCH>::LDS;
-        if (fs_wide()) {
-            static std::atomic<bool> attr_set_w[16] = {};
-            CVTMI_TRY(fs_set_lds((const void *)flat_f32_mshare_kernel<NCH, 2, 8, NCH>, lds, attr_set_w));
-            hipLaunchKernelGGL((flat_f32_mshare_kernel<NCH, 2, 8, NCH>), dim3(FSS_STREAMS), dim3(64 * 8), lds, st, a.X, a.bias, a.n_tiles, a.q,
-                               a.nq, a.G, a.NG, a.gb, a.wm, a.redo, a.cnt, g_fs_dbgflags | (fs_nt(true, 1) ? 16 : 0));
-            CVTMI_HIP(hipGetLastError());
-            return CVTMI_OK;
-        }
-        CVTMI_TRY(fs_set_lds((const void *)flat_f32_mshare_kernel<NCH, 1, FS_MANY, NCH>, lds, attr_set));
-        hipLaunchKernelGGL((flat_f32_mshare_kernel<NCH, 1, FS_MANY, NCH>), dim3(FSS_STREAMS), dim3(64 * FS_MANY), lds, st, a.X, a.bias, a.n_tiles, a.q,
-                           a.nq, a.G, a.NG, a.gb, a.wm, a.redo, a.cnt, g_fs_dbgflags | (fs_nt(true, 1) ? 16 : 0));
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
-    } else {
-        return fail(CVTMI_EINVAL, "flat_f32_stream: eight waves at D=%d", 16 * NCH);
-    }
-}
 template <int NCH, int QB>
 static int fs_launch_packed_qb(const FsStreamArgs &a, const void *pack, hipStream_t st)
 {
@@ -1025,11 +1007,10 @@ int launch_flat_f32_stream(int metric, int D, const float *X, const float *bias,
     float *qbuf = reinterpret_cast<float *>(list + (size_t)nq * FSF_LIST);
     const FsStreamArgs sa = { X, bias, (n + 31) / 32, q, (int)nq, G, NG, gb, wm, redo, cnt };
     const int qb = shared ? (int)((nq + 127) / 128) : (int)((nq + 31) / 32);
-    const bool eight = shared && fs_eight(D);
     // round 6: up to 32 queries over the bf16 operand copy of the rows when the handle keeps one (half the bytes, one product per term)
     const bool packed = pack != nullptr && pstats != nullptr && !shared && qb <= 3 && g_fs_packed.load() != 0;
 #define CVTMI_FS(NCH_) \
-    case NCH_: CVTMI_TRY(packed ? fs_launch_packed<NCH_>(qb, sa, pack, st) : eight ? fs_launch_eight<NCH_>(sa, st) : shared ? (fs_launch_qb<NCH_, true>(qb, sa, st)) : (fs_launch_qb<NCH_, false>(qb, sa, st))); break;
+    case NCH_: CVTMI_TRY(packed ? fs_launch_packed<NCH_>(qb, sa, pack, st) : shared ? (fs_launch_qb<NCH_, true>(qb, sa, st)) : (fs_launch_qb<NCH_, false>(qb, sa, st))); break;
     switch (D / 16) {
         CVTMI_FS(2) CVTMI_FS(4) CVTMI_FS(6) CVTMI_FS(8) CVTMI_FS(12) CVTMI_FS(16)
         default: return fail(CVTMI_EUNSUPPORTED, "flat_f32_stream: D=%d", D);

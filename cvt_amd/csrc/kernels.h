@@ -214,7 +214,7 @@ int flat_f32_stream_qmax(int D);
 int flat_f32_stream_private_max(int D);   // queries per pass of the private-ring kernel
 int get_flat_f32_dbg();
 void set_flat_f32_dbg(int v);     // timing experiments, results wrong when non-zero
-void set_flat_f32_share(int v);   // shared-ring kernel: 0 choose, 1 four waves x 32 QB queries, 2 eight waves x 32 queries
+void set_flat_f32_share(int v);   // shared-ring kernel: 0 choose, 1 four waves x 32 QB queries (the only form)
 void set_flat_f32_nt(int v);     // 0 = never, 1 = choose (default), 2 = always: non-temporal hint on the stream kernels' row loads
 bool flat_f32_stream_applies(int metric, int D, int64_t n, int k);
 // round 6 (flat_f32_tfilter.hip): batches (any width that is a multiple of 4 up to 2048-d, >= 262 144 rows, k <= 128) as a threshold filter: queries in LDS, the rows'

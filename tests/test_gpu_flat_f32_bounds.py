@@ -31,7 +31,7 @@ def amd():
 def _oracle(orc, metric, x, q, k):
     """the checker on every query, the queries split over threads (each call is one C loop that releases the GIL)"""
     flavour = 4 if metric == IP else 8
-    parts = max(1, min(len(q), os.cpu_count() or 1))
+    parts = max(1, min(len(q), int(os.environ.get("OMP_NUM_THREADS", 16))))
     chunks = [c for c in np.array_split(np.arange(len(q)), parts) if len(c)]
     with cf.ThreadPoolExecutor(len(chunks)) as ex:
         res = list(ex.map(lambda c: orc.flat_search(metric, x, q[c], k, flavour=flavour), chunks))

@@ -216,7 +216,7 @@ def test_hnsw_config5_scale(amd, orc):
     x, q = xd.cpu().numpy(), qd.cpu().numpy()
     path = os.path.join(tempfile.gettempdir(), "cvt_test_c5.hnsw")
     rh = ob.RefHnsw()
-    rh.build(0, x, path, 16, 40, threads=os.cpu_count() or 8)
+    rh.build(0, x, path, 16, 40, threads=int(os.environ.get("OMP_NUM_THREADS", 16)))
     blob = open(path, "rb").read()
     ix = amd.HnswIndex(blob, 0, D)
     assert ix.ntotal == n

@@ -13,7 +13,7 @@ ix = cvt_amd.FlatIndex(0, D); ix.add(torch.randn((n, D), generator=g, device=dev
 lib = cvt_amd.lib()
 out = (C.c_ulonglong * 16)()
 names = ["barrier", "products", "update", "requests", "vmcnt wait", "convert", "-", "-"]
-for share in (2, 1):
+for share in (1,):
     cvt_amd.set_tuning("flat_f32_share", share)
     nq = 256
     q = torch.randn((nq, D), generator=g, device=dev)
