@@ -469,7 +469,14 @@ def topk_merge(in_d, in_i, k):
 
 
 def topk_select(scores, k):
-    """scores [nq][n] (numpy, host) -> k smallest (score, index) per row"""
+    """scores [nq][n] -> k smallest (score, index) per row; torch device tensors stay on the device (current stream)"""
+    if _is_torch(scores):
+        import torch
+        nq, n = scores.shape
+        d = torch.empty((nq, k), dtype=torch.float32, device=scores.device)
+        i = torch.empty((nq, k), dtype=torch.int64, device=scores.device)
+        _check(lib().cvtmi_topk_select_dev(_ptr(scores), C.c_int64(nq), C.c_int64(n), C.c_int(k), _ptr(d), _ptr(i), _stream()))
+        return d, i
     scores = _np(scores, np.float32)
     nq, n = scores.shape
     d = np.empty((nq, k), dtype=np.float32); i = np.empty((nq, k), dtype=np.int64)

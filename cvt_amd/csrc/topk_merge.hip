@@ -7,6 +7,11 @@
 // (block_topk.h).  The payload is the candidate's position in the input; lists are ordered by
 // ascending id range and each list is (distance, id)-sorted, so position order equals id order among
 // equal distances -- exactly the tie rule the selection needs.
+//
+// Order: the key is f32_key of the distance with -0.0 taken as +0.0, so ties between the two zeros are broken by position
+// like any other tie (the reference's (float, uint) pair order).  NaN is not ordered by the reference's operator<; here it
+// follows the f32_key total order: sign-bit NaNs before -inf, +NaNs after +inf, each by its bit pattern, and 0x7fffffff
+// keyed as 0x7ffffffe (KEY_MAX marks "not a candidate").  Ties under that order, NaNs included, go by position.
 #include "block_topk.h"
 #include "kernels.h"
 
@@ -47,8 +52,13 @@ __global__ __launch_bounds__(kBlock) void topk_merge_kernel(const float *__restr
             pay[r] = (uint32_t)i;
             key[r][0] = KEY_MAX;
             if (i < n_cand && (in_id == nullptr || id_of(i) >= 0)) {
-                const uint32_t kk = f32_key(dist_of(i));
-                key[r][0] = kk == KEY_MAX ? KEY_MAX - 1 : kk;  // keep the "not a candidate" code free
+                // f32_key with the sign-bit side moved up by one (-u instead of ~u): the same order, except that -0.0 lands on
+                // +0.0's key 0x80000000 (the reference's pair order: equal, tie by id).  Bits only, no compare: the int32 patterns
+                // of uint8-L2 distances are never touched, and the output re-reads the input, so a -0.0 keeps its sign there.
+                const uint32_t u = __float_as_uint(dist_of(i));
+                const uint32_t m = (uint32_t)((int32_t)u >> 31);
+                const uint32_t kk = (u ^ (m | 0x80000000u)) - m;
+                key[r][0] = kk < KEY_MAX - 1 ? kk : KEY_MAX - 1;  // keep the "not a candidate" code free
             }
         }
         topk_tile<1, MERGE_R, CAP, TRIG>(tk, k, tile, key, pay);

@@ -391,13 +391,24 @@ void IVFOPQ::LoadIndex(string srcFile)
 // ---- opq/src/common.h helpers ----
 std::vector<std::pair<float, unsigned> > get_sort_results(const std::vector<float> &match_score, int results_per_query)
 {
-    // the k smallest (score, index) pairs, selected on the device
+    // the k smallest (score, index) pairs.  As in the reference, t holds results_per_query entries and those beyond
+    // match_score.size() stay value-initialised (0, 0).
     const int n = (int)match_score.size();
     std::vector<std::pair<float, unsigned> > t(results_per_query > 0 ? results_per_query : 0);
     if (n == 0 || results_per_query <= 0) return t;
-    // (the device selection takes k <= CVTMI_K_MAX = 2048; entries beyond stay value-initialised, as the reference's partial_sort_copy
-    //  leaves those beyond match_score.size())
-    const int k = results_per_query > CVTMI_K_MAX ? CVTMI_K_MAX : results_per_query;
+    bool has_nan = false;
+    for (int i = 0; i < n && !has_nan; ++i) has_nan = match_score[i] != match_score[i];
+    if (has_nan || results_per_query > CVTMI_K_MAX) {
+        // NaN has no place in operator< on pairs, so the reference's result depends on the heap inside
+        // std::partial_sort_copy; and the device selection takes k <= CVTMI_K_MAX.  Both go through the reference's own
+        // operation on the host.
+        std::vector<std::pair<float, unsigned> > all(n);
+        for (int i = 0; i < n; ++i) all[i] = std::make_pair(match_score[i], (unsigned)i);
+        std::partial_sort_copy(all.begin(), all.end(), t.begin(), t.end());
+        return t;
+    }
+    // on the device: -0.0 and +0.0 tie and go by index, like the pairs
+    const int k = std::min(results_per_query, n);
     std::vector<float> od(k);
     std::vector<int64_t> oi(k);
     if (cvtmi_topk_select(match_score.data(), 1, n, k, od.data(), oi.data()) != CVTMI_OK) {

@@ -83,7 +83,9 @@ private:
     int m_coarseK, m_pq_m, m_pq_k, m_pq_step, m_featDim, m_imgNum, m_maxIndexNum, m_imgCap;
 };
 
-// k smallest (score, index) ascending: get_sort_results of opq/src/common.h:25-37 (device top-k merge)
+// k smallest (score, index) ascending: get_sort_results of opq/src/common.h:25-37.  Always results_per_query entries, those past
+// match_score.size() (0, 0).  Device selection (cvtmi_topk_select, -0.0 == +0.0, ties by index); scores holding a NaN and
+// results_per_query > CVTMI_K_MAX go through the reference's std::partial_sort_copy on the host.
 std::vector<std::pair<float, unsigned> > get_sort_results(const std::vector<float> &match_score, int results_per_query);
 std::string get_base_name(const std::string path);
 void get_vector_of_strings_from_file_lines(const std::string file_name, std::vector<std::string> &out);

@@ -32,7 +32,8 @@ int main(int argc, char *argv[])
             vector<float> score_total(img_num, 0.0f);
             for (int j = 0; j < frame_num; j++)
                 for (int k = 0; k < img_num; k++) score_total.at(k) += score.at(j).at(k);
-            int show = min(num_show, img_num);
+            // all num_show entries, as the reference prints them: those past img_num are (0, 0) and name video 0
+            int show = num_show;
             vector<pair<float, unsigned> > result = get_sort_results(score_total, show);
             fout << queryPaths.at(i) << "  " << i << endl;
             for (int j = 0; j < show; j++) fout << get_base_name(ivfpq_search.m_imgLocation[result.at(j).second].ptr) << " ";

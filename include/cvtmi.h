@@ -351,7 +351,11 @@ int cvtmi_host_free(void *p);
 /* Exchange step of a row-sharded search: merge L sorted (distance, id) lists per query
  * (in_dist / in_ids [nq][L][k], id < 0 = padding, lists ordered by ascending id range) into the
  * k smallest pairs.  Same shape as FLANN-MPI's ResultsMerger
- * (retrieval/vlindex/lib/FLANN/mpi/index.h:74-108). */
+ * (retrieval/vlindex/lib/FLANN/mpi/index.h:74-108).
+ * Order of cvtmi_topk_merge, cvtmi_topk_select and cvtmi_shard_merge_topk_dev: (distance, position) with -0.0 == +0.0,
+ * as std::pair<float, uint> orders them; the distances returned are the input's bits (a -0.0 stays -0.0).  NaN, which that
+ * order leaves out, is ranked by its bits: sign-bit NaNs before -inf, +NaNs after +inf (0x7fffffff ties with 0x7ffffffe),
+ * ties by position.  Padding: (+inf, -1). */
 int cvtmi_topk_merge(const float *in_dist, const int64_t *in_ids, int64_t nq, int L, int k,
                      float *dist, int64_t *ids);
 int cvtmi_topk_merge_dev(const float *in_dist, const int64_t *in_ids, int64_t nq, int L, int k,
@@ -430,7 +434,10 @@ int cvtmi_shard_merge_topk_dev(cvtmi_comm_t c, const float *local_dist, const in
                                float *dist, int64_t *ids, void *stream);
 
 /* get_sort_results (opq/src/common.h:25-37): the k smallest (score, index) pairs of scores[nq][n],
- * ascending; rows short of k entries are padded with (+inf, -1).  1 <= k <= CVTMI_K_MAX. */
+ * ascending; rows short of k entries are padded with (+inf, -1).  1 <= k <= CVTMI_K_MAX.  Order as cvtmi_topk_merge above
+ * (-0.0 == +0.0, NaN by its bits).  The reference returns k pairs with (0, 0) past n, and its order of NaN scores depends on
+ * std::partial_sort_copy's heap: the host mirror (cvt_amd/host/IVFOPQ.cpp) asks for min(k, n) entries and runs rows that
+ * hold a NaN, and k > CVTMI_K_MAX, through the reference's own operation on the host. */
 int cvtmi_topk_select(const float *scores, int64_t nq, int64_t n, int k, float *dist, int64_t *ids);
 int cvtmi_topk_select_dev(const float *scores, int64_t nq, int64_t n, int k, float *dist, int64_t *ids,
                           void *stream);

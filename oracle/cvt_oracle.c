@@ -215,7 +215,9 @@ static int pair_cmp_qsort(const void *pa, const void *pb)
 }
 
 /* k smallest (score, index) pairs ascending == std::partial_sort_copy of common.h:34.
- * Writes min(k, n) entries, returns that count. */
+ * Writes min(k, n) entries, returns that count.  Not for scores that hold a NaN: pair_less is then no strict weak
+ * order, qsort's result is unspecified and is not the reference's (which depends on partial_sort_copy's heap); the
+ * same holds for orc_video_rank below. */
 ORC_API int64_t orc_topk_pairs(const float *scores, const int64_t *ids /* NULL -> 0..n-1 */,
                                int64_t n, int64_t k, float *out_d, int64_t *out_id)
 {

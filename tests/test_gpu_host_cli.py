@@ -350,3 +350,89 @@ def test_ivfopq_mirror_concurrent_searchtopk(tmp_path):
     # larger batches through the pipelined host-pointer entry (chunks alternating between two scratch sets / streams)
     out = run([os.path.join(BIN, "opq_concurrent"), "100000", "3", "4", "5000", "10"], cwd=str(tmp_path))
     assert out.strip().endswith("OK"), out
+
+
+def _ranked(stdout):
+    """the `id: score` lines opq_query prints for its first query, as (id, score) with NaN for "nan" / "-nan\""""
+    import re
+    out = []
+    for line in stdout.splitlines():
+        m = re.match(r"^(\d+): (\S+)$", line)
+        if m:
+            s = m.group(2)
+            out.append((int(m.group(1)), float("nan") if s.lstrip("-") == "nan" else float(s)))
+    return out
+
+
+def _check_ranking(got, rd, ri, ctx):
+    assert [g[0] for g in got] == ri.tolist(), ctx
+    for (_, s), want in zip(got, rd):
+        if np.isnan(want):
+            assert np.isnan(s), (ctx, s, want)
+        else:
+            assert abs(s - float(want)) <= 1e-5 * abs(float(want)), (ctx, s, want)   # text output: 6 significant digits
+
+
+RANKING_CASES = {  # name: (videos, NaN frame, --nearest, --show)
+    "nan_show_3": (9, True, 2, 3),
+    "nan_show_past_videos": (9, True, 2, 13),
+    "show_past_videos": (9, False, 3, 13),
+    "many_videos_show_2100": (2200, False, 2, 2100),
+    "many_videos_show_2048": (2200, False, 2, 2048),
+}
+
+
+@pytest.mark.parametrize("case", list(RANKING_CASES))
+def test_opq_query_cli_ranking_matches_reference(tmp_path, case):
+    """multi_frame_index_test's main (opq_query) against the reference's own Query -> fp32 frame sum -> get_sort_results:
+    a query with a NaN frame (its scores hold NaN, ranked by the reference's partial_sort_copy), --show above the video count
+    (all num_show entries are printed, those past the videos as (0, 0) naming video 0), and 2200 one-frame videos with
+    --show 2100 > CVTMI_K_MAX.  Ids exactly, NaN as NaN, other scores to the 6 digits of the text output."""
+    from oracle import binding as ob
+    if not ob.ref_available():
+        pytest.skip("oracle/_ref not built")
+    nv, with_nan, nk, show = RANKING_CASES[case]
+    rng = np.random.default_rng(23 if nv < 100 else 24)
+    D, M, K, coarseK = 32, 4, 64, 6
+    coarse = (rng.normal(size=(coarseK, D)) * 0.3).astype(np.float32)
+    books = (rng.normal(size=(M, K, D // M)) * 0.05).astype(np.float32)
+    perm = rng.permutation(D).astype(np.int32)
+    inv = np.argsort(perm)
+    nrows = (lambda: int(rng.integers(2, 6))) if nv < 100 else (lambda: 1)
+    vids = [(coarse[v % coarseK][inv] + 0.05 * rng.normal(size=(nrows(), D))).astype(np.float32) for v in range(nv)]
+    names = []
+    for v, x in enumerate(vids):
+        f = tmp_path / ("v%04d_feat.bin" % v)
+        x.tofile(f)
+        names.append(str(f))
+    (tmp_path / "list.txt").write_text("\n".join(names) + "\n")
+    model = str(tmp_path / "model.bin")
+    ob.write_opq_model(model, coarse, books, perm)
+    (tmp_path / "idx").mkdir()
+    run([os.path.join(BIN, "opq_index"), model, str(tmp_path / "list.txt"), str(tmp_path / "idx"), str(nv)], cwd=str(tmp_path))
+    idx_file = str(tmp_path / "idx" / os.listdir(tmp_path / "idx")[0])
+    q = np.stack([vids[1][0], vids[4][-1], vids[7][0]]).astype(np.float32) + np.float32(0.01)
+    if with_nan:
+        q[1, 5] = np.nan
+    else:
+        q = q[[0, 2]]
+    q.tofile(tmp_path / "q.bin")
+    out = run([os.path.join(BIN, "opq_query"), model, idx_file, str(tmp_path / "res.txt"), str(tmp_path / "q.bin"), "--nearest", str(nk),
+               "--show", str(show)], cwd=str(tmp_path))
+    ref = ob.RefOPQ(coarse, books, perm)
+    try:
+        assert ref.index(vids) == nv
+        ms = ref.query(q, nk, nv)
+        total = np.zeros(nv, np.float32)
+        for f in range(ms.shape[0]):                                         # multi_frame_index_test.cpp:60-67, fp32, frame order
+            total += ms[f]
+        rd, ri = ref.sort_results(total, show)
+    finally:
+        ref.close()
+    if with_nan:
+        assert np.isnan(total).any() and not np.isnan(total).all()          # NaN among finite scores
+    got = _ranked(out)
+    assert len(got) == show, len(got)
+    _check_ranking(got, rd, ri, case)
+    shown = (tmp_path / "res.txt").read_text().splitlines()[1].split()
+    assert shown == ["v%04d_feat" % i for i in ri]                          # padded entries name video 0, as in the reference
