@@ -9,14 +9,14 @@ region starts.
 
 Headline workload:
   N = 1   BASELINE.json configs[1]: SIFT-1M (synthetic SIFT-shaped 128-d rows), OPQ M=16 K=256, top-100, nq = 10 000.
-          The same line carries "sift1b": the N > 1 headline workload on this one GPU (the N = 1 point of its curve),
-          and "secondary": rotation / encode / SQ8 / fp32 flat search / config 3 (10 M x 512-d uint8 flat search) /
+          With --full the same line carries "sift1b": the N > 1 headline workload on this one GPU (the N = 1 point of its
+          curve), and "secondary": rotation / encode / SQ8 / fp32 flat search / config 3 (10 M x 512-d uint8 flat search) /
           the IVF query shape / config 5 (HNSW).
   N > 1   BASELINE.json configs[3], the north-star multi-GPU case: SIFT-1B-shaped -- --large-rows (2^30) synthetic
           rows, generated, rotated and encoded on device, ROW-SHARDED over the N ranks (2 GB of codes per GPU at
           N = 8), the same nq = 10 000 queries on every rank, all-gather + merge: "scaling": "strong" (total work
           fixed).  A 16 MB database is not a multi-GPU workload; what N GPUs do with it (row-sharded, and as N
-          replicas) is reported under "sift1m_row_sharded" / "sift1m_replicas", never as `value`.
+          replicas) is reported under "sift1m_row_sharded" / "sift1m_replicas" (--full), never as `value`.
 
 Ranks find each other over cvt_amd/rendezvous.py (plain TCP around the launcher's RANK / WORLD_SIZE / MASTER_*):
 barriers, the max-over-ranks clock and the hand-over of the communicator id need no torch.distributed, and every rank reports
@@ -27,6 +27,14 @@ barriers, the max-over-ranks clock and the hand-over of the communicator id need
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --dump-outputs DIR    # also write the last timed step's results to DIR/*.npy
+    python bench.py --full                # also everything beside the headline (see below)
+
+A plain run does only what the headline needs: set-up (codebooks, index), warm-up, the timed steps, --dump-outputs, and the
+result line -- its roofline and encode rate come from the set-up and the timed steps themselves.  --full adds every other
+measurement and check, each outside the timed steps and after them: N = 1 "host_pointer_api", "small_batch_latency",
+"sift1b", "recall_at_1", the CPU baselines with their identity checks and "secondary"; N > 1 the oracle identity sample,
+"recall_at_1", "cpu_baseline", "same_workload_on_one_gpu" and the SIFT-1M row-sharded / replica figures.  The headline figures
+of the two kinds of run are the same measurement.
 
 --dump-outputs DIR: after the timed steps, the answer of the LAST timed step -- what a caller of the headline search receives --
 goes to DIR/distances.npy (float32, [nq][k]) and DIR/ids.npy (the int64 row ids as float64, exact below 2^53); N > 1: rank 0's
@@ -35,10 +43,10 @@ DIR/sampled_rows.npy.  Every input is generated from fixed seeds, so two builds 
 output for output.
 
 The N > 1 line proves what it measured: `rccl_ranks` / `collectives_per_search` from the library's own counters
-(cvtmi_comm_info), `identical_to_oracle_sample` (every rank scans ITS shard with the CPU oracle for a few queries, rank 0 merges
-the per-shard lists with the oracle's merge and compares ids and distance bits with the GPUs' merged answer -- the shape of
-FLANN-MPI's local search + offset + reduce, retrieval/vlindex/lib/FLANN/mpi/index.h:196-226, :74-108), `recall_at_1` and a
-`cpu_baseline` from that same oracle run.  If the RCCL communicator cannot be created (fewer devices than ranks, creation
+(cvtmi_comm_info) and, with --full, `identical_to_oracle_sample` (every rank scans ITS shard with the CPU oracle for a few
+queries, rank 0 merges the per-shard lists with the oracle's merge and compares ids and distance bits with the GPUs' merged
+answer -- the shape of FLANN-MPI's local search + offset + reduce, retrieval/vlindex/lib/FLANN/mpi/index.h:196-226, :74-108),
+`recall_at_1` and a `cpu_baseline` from that same oracle run.  If the RCCL communicator cannot be created (fewer devices than ranks, creation
 fails or times out) the line still appears, with "error" and the result of the same library path over the host transport.
 """
 import argparse
@@ -81,7 +89,7 @@ def parse_args():
     ap.add_argument("--splits", type=int, default=0)
     ap.add_argument("--variant", type=int, default=-1, help="scan kernel variant (cvtmi.h), -1 = library default")
     ap.add_argument("--large-rows", type=int, default=1 << 30,
-                    help="total rows of the SIFT-1B-shaped workload (0 = skip at N = 1)")
+                    help="total rows of the SIFT-1B-shaped workload (N = 1: --full only, 0 = skip)")
     ap.add_argument("--large-nq", type=int, default=10_000)
     ap.add_argument("--large-data", choices=["sift", "random"], default="sift",
                     help="sift = synthetic rows rotated + encoded on device; random = uniform random code bytes "
@@ -91,27 +99,32 @@ def parse_args():
     ap.add_argument("--comm-timeout", type=float, default=180.0,
                     help="seconds the RCCL communicator creation may take before the ranks fall back to the host transport")
     ap.add_argument("--n1-point", type=int, default=1,
-                    help="N > 1: rank 0 also runs the SAME workload alone on its GPU afterwards (all rows, same queries, no collective) -> "
+                    help="N > 1, --full: rank 0 also runs the SAME workload alone on its GPU afterwards (all rows, same queries, no collective) -> "
                          "'same_workload_on_one_gpu' and 'speedup_over_one_gpu' in the line (0 = skip)")
     ap.add_argument("--oracle-queries", type=int, default=8,
-                    help="N > 1: queries every rank scans over its own shard with the CPU oracle (identity check + cpu_baseline; 0 = skip)")
-    ap.add_argument("--cpu-sample", type=int, default=256, help="queries timed on the CPU baseline (0 = skip)")
+                    help="N > 1, --full: queries every rank scans over its own shard with the CPU oracle (identity check + cpu_baseline; 0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=256, help="--full: queries timed on the CPU baseline (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=-1,
-                    help="threads of the all-cores CPU leg (-1 = all logical cores, 0 = skip)")
-    ap.add_argument("--recall-sample", type=int, default=1000)
+                    help="--full: threads of the all-cores CPU leg (-1 = all logical cores, 0 = skip)")
+    ap.add_argument("--recall-sample", type=int, default=1000, help="--full: queries of recall_at_1")
     ap.add_argument("--ref-rows", type=int, default=1_000_000,
-                    help="rows of the index the reference itself builds for cpu_baseline: the headline's own size by default, ~12 s of its Add (0 = skip)")
+                    help="--full: rows of the index the reference itself builds for cpu_baseline: the headline's own size by default, ~12 s of its Add (0 = skip)")
     ap.add_argument("--ref-queries", type=int, default=1024, help="queries of the reference leg (~4 s at 1 M rows)")
     ap.add_argument("--hnsw-nodes", type=int, default=1_000_000, help="nodes of the config-5 graph (secondary.hnsw_c5)")
-    ap.add_argument("--only", default="", help="development: comma list of secondary sections to run (rotation_encode, opq_m8, opq_rotation_learning, "
+    ap.add_argument("--only", default="", help="development, with --full: comma list of secondary sections to run (rotation_encode, opq_m8, opq_rotation_learning, "
                                                "sq8, flat_f32, flat_u8_c3, ivf_query, hnsw_c5); default all")
-    ap.add_argument("--host-api", type=int, default=1, help="0 = skip the host-pointer leg (its 4096-query pieces are scan launches too)")
+    ap.add_argument("--host-api", type=int, default=1, help="--full: 0 = skip the host-pointer leg (its 4096-query pieces are scan launches too)")
     ap.add_argument("--tune", default="", help="development: cvtmi_set_tuning pairs, name=value,name=value")
     ap.add_argument("--secondary", type=int, default=1,
-                    help="N = 1: also measure rotation / encode / SQ8 / flat searches / config 5 (0 = skip)")
+                    help="N = 1, --full: also measure rotation / encode / SQ8 / flat searches / config 5 (0 = skip)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="write the last timed step's distances and ids to DIR/*.npy (at most 64 MB: a seeded sample of rows above)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beside the headline (off: set-up, warm-up, timed steps, result line)")
+    args = ap.parse_args()
+    if args.only and not args.full:
+        ap.error("--only selects secondary sections, which run with --full only")
+    return args
 
 
 DUMP_MAX_BYTES = 64 << 20
@@ -404,7 +417,7 @@ def run_sift1b(ctx, q, steps, warmup):
     if fits == 0:
         return {"error": "not enough free HBM for %d code rows per GPU" % (l1 - l0)}, None
     ql = q[:min(args.large_nq, ctx.nq)].contiguous()
-    ns = min(args.recall_sample, 256, ql.shape[0])
+    ns = min(args.recall_sample, 256, ql.shape[0]) if args.full else 0
     t0 = time.perf_counter()
     big, enc_rows, enc_t = ctx.build_index(l0, l1, data=args.large_data, seed=0xC0FFEE, nn_q=ql[:ns] if ns > 0 else None)
     torch.cuda.synchronize(); t_build = time.perf_counter() - t0
@@ -446,7 +459,8 @@ def run_sift1b(ctx, q, steps, warmup):
         res["rccl_ranks"] = c1["world"] if c1["transport"] == "rccl" else 0
         res["collectives_per_search"] = round((c1["collectives"] - c0["collectives"]) / max(steps, 1), 3)
     if ctx.world > 1:
-        shard_evidence(ctx, big, l0, ql, out, res)
+        if args.full:
+            shard_evidence(ctx, big, l0, ql, out, res)
     elif ctx.nn is not None:
         ns = ctx.nn[0].shape[0]
         res["recall_at_1"] = round(float((out[1][:ns, 0] == ctx.nn[1]).float().mean().item()), 4)
@@ -521,7 +535,7 @@ def headline_n1(ctx, q):
         "encode": {"rows_per_s": round(enc_rows / enc_time, 1),
                    "what": "rotate (MFMA GEMM) + PQ encode (cvtmi_opq_rotate_encode) + append of the 1 M rows"},
     }
-    if not args.host_api:   # (profiling runs: every scan launch of the process is then a headline launch)
+    if not args.full or not args.host_api:   # (profiling runs: every scan launch of the process is then a headline launch)
         return result, idx, out
     # the reference's API takes host pointers: the same step through cvtmi_opq_search (queries up, results down over
     # PCIe)
@@ -601,7 +615,7 @@ def headline_multi(ctx, q):
     extra = {}
     # The N = 1 point of THIS curve, measured in THIS run: rank 0 alone, every row on its one GPU, the same queries, no collective --
     # so the line carries its own speed-up (the N = 1 line's headline is BASELINE configs[1], another workload).  The others wait.
-    if args.n1_point:
+    if args.full and args.n1_point:
         one = None
         if ctx.rank == 0:
             try:
@@ -635,27 +649,27 @@ def headline_multi(ctx, q):
             extra["same_workload_on_one_gpu"] = one
             if "value" in one:
                 extra["speedup_over_one_gpu"] = round(res["value"] / one["value"], 3)
-    # the small database on N GPUs, for the record: row-sharded through the same library path, and as N replicas
-    r0, r1 = cvt.shard_range(args.rows, ctx.rank, world)
-    shard, _, _ = ctx.build_index(r0, r1)
-    fn = ctx.searcher(shard)
-    el2, _ = ctx.timed(lambda: fn(q), args.steps, args.warmup)
-    extra["sift1m_row_sharded"] = {
-        "value": round(nq * args.steps / el2, 1), "unit": "queries/s", "ms_per_step": round(el2 / args.steps * 1e3, 4),
-        "what": "the 1 M-row database row-sharded x%d (%d rows per GPU), all %d queries on every rank, all-gather + "
-                "merge: "
-                "strong scaling of a 16 MB problem" % (world, r1 - r0, nq)}
-    shard.close()
-    rep, _, _ = ctx.build_index(0, args.rows)
-    q_mine = ctx.synth.sift_like(nq, D, seed=0xBEEF + 7919 * ctx.rank, device=ctx.dev) if ctx.rank else q
-    el3, _ = ctx.timed(lambda: rep.search(q_mine, k, rotate=True), args.steps, args.warmup)
-    extra["sift1m_replicas"] = {
-        "value": round(world * nq * args.steps / el3, 1), "unit": "queries/s",
-            "ms_per_step": round(el3 / args.steps * 1e3, 4),
-        "what": "code matrix replicated x%d, every rank serves its own batch of %d queries, no collective: N "
-                "independent "
-                "replicas (Nx by construction)" % (world, nq)}
-    rep.close()
+    if args.full:   # the small database on N GPUs, for the record: row-sharded through the same library path, and as N replicas
+        r0, r1 = cvt.shard_range(args.rows, ctx.rank, world)
+        shard, _, _ = ctx.build_index(r0, r1)
+        fn = ctx.searcher(shard)
+        el2, _ = ctx.timed(lambda: fn(q), args.steps, args.warmup)
+        extra["sift1m_row_sharded"] = {
+            "value": round(nq * args.steps / el2, 1), "unit": "queries/s", "ms_per_step": round(el2 / args.steps * 1e3, 4),
+            "what": "the 1 M-row database row-sharded x%d (%d rows per GPU), all %d queries on every rank, all-gather + "
+                    "merge: "
+                    "strong scaling of a 16 MB problem" % (world, r1 - r0, nq)}
+        shard.close()
+        rep, _, _ = ctx.build_index(0, args.rows)
+        q_mine = ctx.synth.sift_like(nq, D, seed=0xBEEF + 7919 * ctx.rank, device=ctx.dev) if ctx.rank else q
+        el3, _ = ctx.timed(lambda: rep.search(q_mine, k, rotate=True), args.steps, args.warmup)
+        extra["sift1m_replicas"] = {
+            "value": round(world * nq * args.steps / el3, 1), "unit": "queries/s",
+                "ms_per_step": round(el3 / args.steps * 1e3, 4),
+            "what": "code matrix replicated x%d, every rank serves its own batch of %d queries, no collective: N "
+                    "independent "
+                    "replicas (Nx by construction)" % (world, nq)}
+        rep.close()
     if ctx.rank != 0:
         return None
     rf = res["scan"] or {"queries_per_pass": None}
@@ -836,18 +850,19 @@ def main():
     q = ctx.synth.sift_like(ctx.nq, D, seed=0xBEEF, device=ctx.dev)  # identical on every rank
     if ctx.world == 1:
         result, idx, out = headline_n1(ctx, q)
-        if args.large_rows > 0:
+        if args.full and args.large_rows > 0:
             try:
                 result["sift1b"] = run_sift1b(ctx, q, max(1, min(args.steps, 2)), 1)[0]
             except ctx.cvt.CvtmiError as e:
                 result["sift1b"] = {"error": str(e)}
         # outside the timed region: recall@1, the CPU baseline and the secondary kernels
-        recall_at_1(ctx, q, out[1], result)
-        if args.cpu_sample > 0:
+        if args.full:
+            recall_at_1(ctx, q, out[1], result)
+        if args.full and args.cpu_sample > 0:
             cpu_baseline_opq(ctx, idx, q, out, result)
             cpu_baseline_reference(ctx, q, result)
         idx.close()
-        if args.secondary:
+        if args.full and args.secondary:
             try:
                 result["secondary"] = secondary(ctx)
             except Exception as e:  # the headline line must survive a failing side measurement

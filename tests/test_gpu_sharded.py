@@ -298,11 +298,13 @@ def test_flat_row_shards_match_single_handle(world, metric, D, n, tmp_path, orc)
         assert int(z["failed"]) == 1 and int(z["failed_now"]) == 1 and int(z["again"]) == 1, (r, int(z["failed"]), int(z["failed_now"]), int(z["again"]))
 
 
-def _bench_line(extra, timeout=600, gpus=2, large_rows=1 << 22):
-    """`python bench.py --gpus N ...` with NO launcher around it and no RANK / WORLD_SIZE in the environment"""
+def _bench_line(extra, timeout=600, gpus=2, large_rows=1 << 22, full=True):
+    """`python bench.py --gpus N [--full] ...` with NO launcher around it and no RANK / WORLD_SIZE in the environment (--full: the
+    line's identity evidence and the N = 1 point of its curve)"""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--nq", "600", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus)] + (["--full"] if full else []) + [
+           "--nq", "600", "--steps", "2", "--warmup", "1",
            "--rows", "200000", "--large-rows", str(large_rows), "--oracle-queries", "8", "--comm-timeout", "60"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, stdin=subprocess.DEVNULL)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -354,6 +356,27 @@ def test_bench_gpus2_without_second_gpu_still_prints_a_line():
     line = _bench_line([])
     _check_evidence(line)
     assert "RCCL needs one device per rank" in line["error"]
+
+
+PLAIN_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "roofline"}
+
+
+def test_bench_plain_n1_line_is_the_headline_alone():
+    """without --full an N = 1 run sets up, warms up, times its steps and prints the headline: none of the side measurements"""
+    line = _bench_line([], gpus=1, full=False)
+    assert set(line) == PLAIN_KEYS | {"encode"}, sorted(set(line) ^ (PLAIN_KEYS | {"encode"}))
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["higher_is_better"] is True and line["roofline"]["bound"] == "lds"
+
+
+def test_bench_plain_gpus2_line_keeps_its_exchange_counters():
+    """without --full an N > 1 line still says how it exchanged (the library's counters over the timed steps), and nothing more"""
+    line = _bench_line(["--backend", "host"], full=False)
+    assert set(line) == PLAIN_KEYS | {"transport", "rccl_ranks", "collectives_per_search", "sift1b"}, sorted(set(line))
+    assert line["n_gpus"] == 2 and line["value"] > 0 and "error" not in line
+    assert line["transport"] == "custom" and line["rccl_ranks"] == 0 and line["collectives_per_search"] == 1.0
+    assert "recall_at_1" not in line["sift1b"]
 
 
 def test_bench_gpus2_failing_rank_still_prints_a_line():

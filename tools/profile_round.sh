@@ -21,7 +21,7 @@ python $REPO/tools/pmc_summary.py /tmp/prof_stats > $OUT/${TAG}_kernel_trace_sum
 grep '"metric"' $OUT/stats_run.log > $OUT/${TAG}_bench_under_rocprof.json
 # 1b. the whole N = 1 line as the driver runs it (sift1b + secondary configs: their kernels, and the scan kernel's 2^30-row launches)
 rm -rf /tmp/prof_full
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_full -o $TAG -- python $REPO/bench.py --cpu-sample 0 --recall-sample 0 --steps 10 --warmup 3 > $OUT/stats_full_run.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_full -o $TAG -- python $REPO/bench.py --full --cpu-sample 0 --recall-sample 0 --steps 10 --warmup 3 > $OUT/stats_full_run.log 2>&1
 echo "full stats rc=$?"
 cp $(ls /tmp/prof_full/*/*kernel_stats.csv /tmp/prof_full/*kernel_stats.csv 2>/dev/null | head -1) $OUT/${TAG}_kernel_stats_full_line.csv
 grep '"metric"' $OUT/stats_full_run.log > $OUT/${TAG}_bench_full_line_under_rocprof.json
