@@ -122,6 +122,64 @@ struct DistADC {
     __device__ __forceinline__ float finish(uint32_t id, const Early &e) const { return a.M == 16 ? sum16(e.v) : (*this)(id); }
 };
 
+// The result queue of searchKnn (:718-726) compares std::pair<dist_t, labeltype> with operator<: "neither distance is less" falls
+// through to the label -- for equal distances, for +0.0f beside -0.0f, and for a NaN beside anything.
+__device__ __forceinline__ bool hn_pair_less(float da, int64_t la, float db, int64_t lb)
+{
+    return da < db || (!(db < da) && la < lb);
+}
+__device__ __forceinline__ void hn_result_push_heap(float *od, int64_t *ol, int hole, float d, int64_t l)   // __push_heap on the pairs
+{
+    int parent = (hole - 1) / 2;
+    while (hole > 0 && hn_pair_less(od[parent], ol[parent], d, l)) {
+        od[hole] = od[parent]; ol[hole] = ol[parent];
+        hole = parent;
+        parent = (hole - 1) / 2;
+    }
+    od[hole] = d; ol[hole] = l;
+}
+// One lane, m <= k entries written in ascending pop order.  Without a NaN operator< is a strict weak order and labels are distinct,
+// so the queue's output is THE ascending sequence: an insertion pass over runs of equivalent distances, every distance moving
+// with its label.  With a NaN it is no order at all (NaN is "equivalent" to everything) and what the reference returns is a
+// property of push_heap / pop_heap alone: they are replayed, pushes in pop order (back to front), pop_heap leaving each maximum
+// at the end of the shrinking array -- which is the ascending output.
+__device__ __forceinline__ void hn_order_result(float *od, int64_t *ol, int m, bool nan)
+{
+    if (!nan) {
+        for (int i = 1; i < m; ++i) {
+            const float d = od[i];
+            const int64_t l = ol[i];
+            int j = i - 1;
+            while (j >= 0 && hn_pair_less(d, l, od[j], ol[j])) { od[j + 1] = od[j]; ol[j + 1] = ol[j]; --j; }
+            if (j != i - 1) { od[j + 1] = d; ol[j + 1] = l; }
+        }
+        return;
+    }
+    for (int i = 0, j = m - 1; i < j; ++i, --j) {
+        const float d = od[i]; od[i] = od[j]; od[j] = d;
+        const int64_t l = ol[i]; ol[i] = ol[j]; ol[j] = l;
+    }
+    for (int i = 1; i < m; ++i) hn_result_push_heap(od, ol, i, od[i], ol[i]);
+    for (int len = m - 1; len >= 1; --len) {   // __pop_heap + __adjust_heap
+        const float vd = od[len];
+        const int64_t vl = ol[len];
+        od[len] = od[0]; ol[len] = ol[0];
+        int hole = 0, second = 0;
+        while (second < (len - 1) / 2) {
+            second = 2 * (second + 1);
+            if (hn_pair_less(od[second], ol[second], od[second - 1], ol[second - 1])) --second;
+            od[hole] = od[second]; ol[hole] = ol[second];
+            hole = second;
+        }
+        if ((len & 1) == 0 && second == (len - 2) / 2) {
+            second = 2 * (second + 1);
+            od[hole] = od[second - 1]; ol[hole] = ol[second - 1];
+            hole = second - 1;
+        }
+        hn_result_push_heap(od, ol, hole, vd, vl);
+    }
+}
+
 template <class DIST>
 __global__ __launch_bounds__(64, 8) void hnsw_search_kernel(const HnswArgs a)  // <= 64 VGPRs: 8 waves per SIMD, the traversal lives on queries in flight
 {
@@ -251,28 +309,20 @@ __global__ __launch_bounds__(64, 8) void hnsw_search_kernel(const HnswArgs a)  /
             continue;
         }
         while (top_n > a.k) hn_pop(top, top_n, lane);
-        // pops come out in non-increasing distance: write them back to front, then order ties by label,
-        // which is the (dist, label) order of the reference's result queue (:719-726)
+        // pops come out in non-increasing distance: write them back to front, then give them the order of the reference's result
+        // queue (:718-726), a std::priority_queue of (dist, label) pairs that takes them in pop order
         const int m = top_n;
+        bool nan = false;
         for (int i = m - 1; i >= 0; --i) {
             const HnEnt e = top.get(0);
+            nan |= e.d != e.d;
             if (w) {
                 a.out_d[(int64_t)qi * a.k + i] = e.d;
                 a.out_label[(int64_t)qi * a.k + i] = a.raw_ids ? (int64_t)e.id : a.labels[e.id];
             }
             hn_pop(top, top_n, lane);
         }
-        if (w) {
-            float *od = a.out_d + (int64_t)qi * a.k;
-            int64_t *ol = a.out_label + (int64_t)qi * a.k;
-            for (int i = 1; i < m; ++i) {
-                const float d = od[i];
-                const int64_t l = ol[i];
-                int j = i - 1;
-                while (j >= 0 && od[j] == d && ol[j] > l) { ol[j + 1] = ol[j]; --j; }
-                ol[j + 1] = l;
-            }
-        }
+        if (w) hn_order_result(a.out_d + (int64_t)qi * a.k, a.out_label + (int64_t)qi * a.k, m, nan);
     }
 }
 

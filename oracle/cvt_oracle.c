@@ -870,6 +870,38 @@ static void hn_pop(hn_heap *h)
     h->n--;
 }
 
+/* the same two libstdc++ routines over (dist, label) pairs compared by pair_less: the result queue of searchKnn */
+static void hn_pair_push_heap(orc_pair *first, int64_t hole, orc_pair v)
+{
+    int64_t parent = (hole - 1) / 2;
+    while (hole > 0 && pair_less(&first[parent], &v)) {
+        first[hole] = first[parent];
+        hole = parent;
+        parent = (hole - 1) / 2;
+    }
+    first[hole] = v;
+}
+static void hn_pair_pop_heap(orc_pair *first, int64_t n) /* n entries -> n - 1; the old maximum is dropped */
+{
+    if (n > 1) {
+        const int64_t len = n - 1;
+        const orc_pair value = first[len];
+        int64_t hole = 0, second = 0;
+        while (second < (len - 1) / 2) {
+            second = 2 * (second + 1);
+            if (pair_less(&first[second], &first[second - 1])) second--;
+            first[hole] = first[second];
+            hole = second;
+        }
+        if ((len & 1) == 0 && second == (len - 2) / 2) {
+            second = 2 * (second + 1);
+            first[hole] = first[second - 1];
+            hole = second - 1;
+        }
+        hn_pair_push_heap(first, hole, value);
+    }
+}
+
 typedef struct {
     uint64_t offsetLevel0, max_elements, cur_count, size_per_elem, label_offset, offsetData;
     int32_t maxlevel; uint32_t enterpoint;
@@ -963,8 +995,14 @@ static void hn_search_core(const hn_index *ixp, hn_dist_fn dist, void *ctx, int 
             res[m].d = top.a[0].d; res[m].id = (int64_t)lab; ++m;
             hn_pop(&top);
         }
-        qsort(res, (size_t)m, sizeof(orc_pair), pair_cmp_qsort);  /* the (dist, label) order of `results` (:719-726) */
-        for (int64_t i = 0; i < m; ++i) { out_d[qi * k + i] = res[i].d; out_label[qi * k + i] = res[i].id; }
+        /* `results` (:718-726) is a std::priority_queue of (dist, label) pairs under std::less: pushed in this order, popped
+         * from the back of the output.  Restated, not sorted: with a NaN among the distances pair_less is no strict weak
+         * order, and which order comes out is then a property of push_heap / pop_heap alone. */
+        for (int64_t i = 0; i < m; ++i) hn_pair_push_heap(res, i, res[i]);
+        for (int64_t i = m - 1; i >= 0; --i) {
+            out_d[qi * k + i] = res[0].d; out_label[qi * k + i] = res[0].id;
+            hn_pair_pop_heap(res, i + 1);
+        }
     }
     free(visited); free(top.a); free(cand.a); free(res);
 }

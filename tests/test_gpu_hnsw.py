@@ -30,8 +30,8 @@ def test_hnsw_golden(amd, orc, golden, case):
     d, lab = ix.search(g[case + "_q"], k, ef)
     assert np.array_equal(lab, g[case + "_l"]), case
     assert np.array_equal(bits(d), bits(g[case + "_d"])), case
-    # other (k, ef) pairs against the oracle: ef < k, ef = 1, k = 1, large ef
-    for k2, ef2 in ((1, 1), (20, 5), (3, 64), (50, 300), (64, 1024)):
+    # other (k, ef) pairs against the oracle: ef < k, ef = 1, k = 1, large ef, k = ef, both at the limit (k > n: padded)
+    for k2, ef2 in ((1, 1), (20, 5), (3, 64), (50, 300), (64, 1024), (10, 10), (255, 255), (1024, 1024)):
         od, ol = orc.hnsw_search(g[case + "_index"].tobytes(), metric, D, g[case + "_q"], k2, ef2)
         d2, l2 = ix.search(g[case + "_q"], k2, ef2)
         assert np.array_equal(l2, ol) and np.array_equal(bits(d2), bits(od)), (case, k2, ef2)
@@ -88,15 +88,14 @@ def vectors_of(blob, D):
     return np.ascontiguousarray(raw[:cur, off_data:off_data + 4 * D]).view(np.float32).reshape(cur, D)
 
 
-@pytest.mark.parametrize("case,M,K", [("ip128", 16, 256), ("ip32", 8, 64), ("l2f16", 4, 256)])
-def test_hnsw_over_opq_codes(amd, orc, golden, case, M, K):
-    """BASELINE config 5: the reference-built graph traversed with ADC distances over PQ codes (dense rotation,
-    codes from the GPU encoder).  Specification = the oracle's traversal with the oracle's ADC arithmetic."""
+def opq_over_graph(amd, orc, blob, D, M, K):
+    """An OPQ handle holding one code row per node of the graph file `blob`, internal-id order (dense rotation where the MFMA GEMM
+    is built, D % 32 == 0, else the reference's own permutation "rotation"; codebooks sampled from the rotated rows; codes from the
+    GPU encoder, which must equal the oracle's).  Returns (opq, books, codes, rot, x, mk): rot rotates as the oracle does, x = the
+    graph's vectors, mk(books) makes another handle of the same model."""
     from cvt_amd import synth
-    g = golden.hnsw
-    metric, D, n, _, _, k, ef = (int(v) for v in g[case + "_meta"])
-    blob = g[case + "_index"].tobytes()
     x = vectors_of(blob, D)
+    n = x.shape[0]
     if D % 32 == 0:
         R = synth.random_rotation(D, seed=3)                  # dense rotation: MFMA GEMM (built for D = 32 .. 128)
         mk = lambda books: amd.OpqIndex(np.zeros((1, D), np.float32), books, R=R)
@@ -114,37 +113,57 @@ def test_hnsw_over_opq_codes(amd, orc, golden, case, M, K):
     opq.add_codes(codes)
     _, ocodes = orc.pq_encode(xr, np.zeros((1, D), np.float32), books)
     assert np.array_equal(codes, ocodes)
-    ix = amd.HnswIndex(blob, metric, D)
-    q = g[case + "_q"]
-    for k2, ef2 in ((k, ef), (10, 40), (1, 1)):
+    return opq, books, ocodes, rot, x, mk
+
+
+def check_search_adc(amd, orc, ix, opq, blob, books, ocodes, rot, q, pairs, tag):
+    """ix.search_adc == the oracle's traversal with the oracle's ADC arithmetic, for every (k, ef) of `pairs`, tables in the
+    scratch (default) and copied into LDS -- the same traversal"""
+    for k2, ef2 in pairs:
         od, ol = orc.hnsw_search_adc(blob, books, ocodes, rot(q), k2, ef2)
-        for tables_in_lds in (0, 1):   # round 5: the tables are read from the scratch (default) or copied into LDS -- the same traversal
+        for tables_in_lds in (0, 1):
             amd.set_tuning("hnsw_adc_tables", tables_in_lds)
             try:
                 d, lab = ix.search_adc(opq, q, k2, ef2)
             finally:
                 amd.set_tuning("hnsw_adc_tables", 0)
-            assert np.array_equal(lab, ol), (case, k2, ef2, tables_in_lds)
-            assert np.array_equal(bits(d), bits(od)), (case, k2, ef2, tables_in_lds)
-    # mismatched handles are refused
-    small = mk(books)
-    small.add_codes(codes[:10])
-    with pytest.raises(amd.CvtmiError):
-        ix.search_adc(small, q, 5, 10)
-    # exact re-rank of the ADC result list (cvtmi_hnsw_search_adc_rerank): the ADC traversal's `rerank` best nodes, their fp32
-    # distances in the reference's summation order (the oracle's orc_dist, default flavour), the k smallest, ties in ADC order
-    labels_of = np.frombuffer(blob, np.uint8)  # labels of the golden graphs are read back through a plain search
-    for k2, ef2, rr in ((5, 40, 40), (10, 64, 30), (1, 16, 8)):
+            assert np.array_equal(lab, ol), (tag, k2, ef2, tables_in_lds)
+            assert np.array_equal(bits(d), bits(od)), (tag, k2, ef2, tables_in_lds)
+
+
+def check_search_adc_rerank(orc, ix, opq, blob, metric, D, books, ocodes, rot, x, q, triples, tag):
+    """exact re-rank of the ADC result list (cvtmi_hnsw_search_adc_rerank): the ADC traversal's `rerank` best nodes, their fp32
+    distances in the reference's summation order (the oracle's orc_dist, default flavour), the k smallest, ties in ADC order"""
+    lab2row = {int(l): r for r, l in enumerate(_graph_labels(blob, D))}
+    for k2, ef2, rr in triples:
         d, lab = ix.search_adc_rerank(opq, q, k2, ef2, rr)
         _, cand = orc.hnsw_search_adc(blob, books, ocodes, rot(q), rr, ef2)       # labels of the ADC list, ADC order
-        lab2row = {int(l): r for r, l in enumerate(_graph_labels(blob, D))}
         for qi in range(q.shape[0]):
             rows = [lab2row[int(l)] for l in cand[qi] if l >= 0]
             ex = np.array([orc.dist(metric, 4, q[qi], x[r]) for r in rows], dtype=np.float32)
             order = np.argsort(ex, kind="stable")[:k2]
             want_l = [int(cand[qi][j]) for j in order]
-            assert lab[qi, :len(want_l)].tolist() == want_l, (case, k2, ef2, rr, qi)
-            assert np.array_equal(bits(d[qi, :len(want_l)]), bits(ex[order])), (case, k2, ef2, rr, qi)
+            assert lab[qi, :len(want_l)].tolist() == want_l, (tag, k2, ef2, rr, qi)
+            assert np.array_equal(bits(d[qi, :len(want_l)]), bits(ex[order])), (tag, k2, ef2, rr, qi)
+
+
+@pytest.mark.parametrize("case,M,K", [("ip128", 16, 256), ("ip32", 8, 64), ("l2f16", 4, 256)])
+def test_hnsw_over_opq_codes(amd, orc, golden, case, M, K):
+    """BASELINE config 5: the reference-built graph traversed with ADC distances over PQ codes (dense rotation,
+    codes from the GPU encoder).  Specification = the oracle's traversal with the oracle's ADC arithmetic."""
+    g = golden.hnsw
+    metric, D, n, _, _, k, ef = (int(v) for v in g[case + "_meta"])
+    blob = g[case + "_index"].tobytes()
+    opq, books, ocodes, rot, x, mk = opq_over_graph(amd, orc, blob, D, M, K)
+    ix = amd.HnswIndex(blob, metric, D)
+    q = g[case + "_q"]
+    check_search_adc(amd, orc, ix, opq, blob, books, ocodes, rot, q, ((k, ef), (10, 40), (1, 1)), case)
+    # mismatched handles are refused
+    small = mk(books)
+    small.add_codes(ocodes[:10])
+    with pytest.raises(amd.CvtmiError):
+        ix.search_adc(small, q, 5, 10)
+    check_search_adc_rerank(orc, ix, opq, blob, metric, D, books, ocodes, rot, x, q, ((5, 40, 40), (10, 64, 30), (1, 16, 8)), case)
     with pytest.raises(amd.CvtmiError):
         ix.search_adc_rerank(opq, q, 10, 40, 5)                                   # rerank < k is refused
 
