@@ -253,6 +253,37 @@ class OpqIndex:
                                            C.c_int(nprobe), C.c_int(img_num), _ptr(ms)))
         return ms
 
+    def search_ivf(self, q, nprobe, k, rotate=True, out=None):
+        """Row-level IVF search (cvtmi_opq_search_ivf): the k nearest entries among the nprobe nearest coarse lists of every query:
+        (distances [nq][k] float32, ids [nq][k] int64), padded with (+inf, -1)."""
+        nq = q.shape[0]
+        if _is_torch(q):
+            import torch
+            if out is None:
+                d = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+                i = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+            else:
+                d, i = out
+            _check(lib().cvtmi_opq_search_ivf_dev(self.h, _ptr(q), C.c_int64(nq), C.c_int(1 if rotate else 0), C.c_int(nprobe),
+                                                  C.c_int(k), _ptr(d), _ptr(i), _stream()))
+            return d, i
+        q = _np(q, np.float32)
+        if out is None:
+            d = np.empty((nq, k), dtype=np.float32); i = np.empty((nq, k), dtype=np.int64)
+        else:
+            d, i = out
+            assert d.dtype == np.float32 and i.dtype == np.int64 and d.shape == (nq, k) and i.shape == (nq, k)
+            assert d.flags.c_contiguous and i.flags.c_contiguous
+        _check(lib().cvtmi_opq_search_ivf(self.h, _ptr(q), C.c_int64(nq), C.c_int(1 if rotate else 0), C.c_int(nprobe), C.c_int(k),
+                                          _ptr(d), _ptr(i)))
+        return d, i
+
+    def last_ivf_plan(self):
+        """grid of the last search_ivf on this handle (cvtmi_opq_last_ivf_plan)"""
+        o = (C.c_int64 * 8)()
+        _check(lib().cvtmi_opq_last_ivf_plan(self.h, o))
+        return dict(rule=o[0], G=o[1], groups=o[2], pieces=o[3], rows_per_piece=o[4], parts=o[5], part_bytes=o[6], entry_bytes=o[7])
+
     def set_param(self, name, value):
         _check(lib().cvtmi_opq_set_param(self.h, name.encode(), C.c_int64(value)))
 

@@ -62,6 +62,7 @@ using namespace cvtmi;
 // the stream it was last used on and an event recorded when that call returned: the next lessee on ANOTHER stream waits first.
 struct OpqScratch {
     DevBuf s_qrot, s_part_d, s_part_id, s_lut, s_gthr, s_qlut, s_qp, s_spill, s_items, s_probe;
+    DevBuf s_ivf;              // partial lists of an IVF search (ivf_search.hip)
     ScanHPlan hplan;                       // the item table s_items holds ...
     int64_t hplan_n = -1, hplan_nq = -1;   // ... and the (rows, queries, forced splits, planner settings) it was built for
     int hplan_splits = 0, hplan_key = 0;
@@ -73,7 +74,7 @@ struct OpqScratch {
     bool pending = false, busy = false;
     void release_all()
     {
-        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &io_q, &io_d, &io_i }) b->release();
+        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &io_q, &io_d, &io_i }) b->release();
         io_pin.release();
         if (own) (void)hipStreamDestroy(own);
         if (done) (void)hipEventDestroy(done);
@@ -102,6 +103,11 @@ struct cvtmi_opq_s {
     DevBuf csr_codes, csr_videos, csr_off, csr_scratch, csr_stats;
     int64_t csr_kept = 0, csr_longest = 0;  // entries in the CSR copy (list ids outside [0, coarseK) are dropped), longest list
     int32_t csr_vmin = 0, csr_vmax = -1;    // range of the video ids it holds
+    // insertion index of every entry of the CSR copy (uint32, CSR order): what cvtmi_opq_search_ivf reports ids from.  Allocated and
+    // filled only once an IVF search has been asked for on the handle (want_entry); rebuilt with the copy, invalid whenever it is
+    DevBuf csr_entry;
+    bool want_entry = false, csr_entry_valid = false;
+    int64_t ivf_last[8] = {};               // grid of the last IVF search (cvtmi_opq_last_ivf_plan), written under pool_mu
     // scratch of the calls that run one at a time (query_video: probe lists, rotated queries)
     DevBuf s_qrot, s_probe, s_rot;
     // Searches (cvtmi_opq_search*) run CONCURRENTLY, as the reference's QueryThrehold de facto may (opq/src/IVFOPQ.cpp:322-422 only
@@ -234,6 +240,7 @@ struct FlatLease {
     ~FlatLease() { close(); }
 };
 
+static std::atomic<int> g_ivf_part_cap_mb{256};   // cvtmi_set_tuning("ivf_part_cap_mb"): room for the partial lists of an IVF search
 static int use_device(int dev)
 {
     int cur = -1;
@@ -534,6 +541,11 @@ int cvtmi_set_tuning(const char *name, int64_t value)
     if (!strcmp(name, "flat_small_zero_copy")) { g_flat_small_zero_copy = value != 0; return CVTMI_OK; }
     if (!strcmp(name, "opq_host_zero_copy")) { g_host_zero_copy = value != 0; return CVTMI_OK; }
     if (!strcmp(name, "scan_tail_splits")) { set_scan_tail_splits((int)value); return CVTMI_OK; }
+    if (!strcmp(name, "ivf_part_cap_mb")) {
+        if (value < 0 || value > 4096) return fail(CVTMI_EINVAL, "cvtmi_set_tuning: ivf_part_cap_mb must be 0 .. 4096");
+        g_ivf_part_cap_mb = (int)value;
+        return CVTMI_OK;
+    }
     if (!strcmp(name, "sq8_flags")) { set_sq8_flags((int)value); return CVTMI_OK; }
     if (!strcmp(name, "sq8_wave_blocks")) {
         if (value < 1 || value > 64) return fail(CVTMI_EINVAL, "cvtmi_set_tuning: sq8_wave_blocks must be 1..64");
@@ -607,7 +619,7 @@ int cvtmi_opq_destroy(cvtmi_opq_t h)
     if (h->d_R) (void)hipFree(h->d_R);
     if (h->d_perm) (void)hipFree(h->d_perm);
     h->codes.release(); h->lists.release(); h->videos.release(); h->codes_rot.release(); h->codes16.release();
-    h->csr_codes.release(); h->csr_videos.release(); h->csr_off.release(); h->csr_scratch.release(); h->csr_stats.release();
+    h->csr_codes.release(); h->csr_videos.release(); h->csr_off.release(); h->csr_scratch.release(); h->csr_stats.release(); h->csr_entry.release();
     h->s_qrot.release(); h->s_probe.release(); h->s_rot.release();
     for (OpqScratch *c : h->pool) { c->release_all(); delete c; }
     h->pool.clear();
@@ -781,7 +793,7 @@ static int opq_add_common(cvtmi_opq_t h, const uint8_t *codes, const int32_t *li
     }
     if (kind == hipMemcpyHostToDevice) CVTMI_HIP(stream_wait(st));
     h->n = total;
-    h->csr_valid = false;
+    h->csr_valid = false; h->csr_entry_valid = false;
     return CVTMI_OK;
 }
 
@@ -815,7 +827,7 @@ int cvtmi_opq_ntotal(cvtmi_opq_t h, int64_t *n)
 int cvtmi_opq_reset(cvtmi_opq_t h)
 {
     CHECK_H_SERIAL(h, nullptr);
-    h->n = 0; h->has_lists = false; h->has_videos = false; h->csr_valid = false; h->rot_n = 0; h->pad_n = 0;
+    h->n = 0; h->has_lists = false; h->has_videos = false; h->csr_valid = false; h->csr_entry_valid = false; h->rot_n = 0; h->pad_n = 0;
     return CVTMI_OK;
 }
 
@@ -830,10 +842,12 @@ int cvtmi_opq_set_id_base(cvtmi_opq_t h, int64_t base)
 // by a counting sort (query_video.hip); only 16 bytes of statistics come back to the host
 static int opq_build_csr(cvtmi_opq_t h, hipStream_t st)
 {
-    if (h->csr_valid) return CVTMI_OK;
+    if (h->csr_valid && (!h->want_entry || h->csr_entry_valid)) return CVTMI_OK;
     const int64_t n = h->n;
     const int M = h->m.M, L = h->m.coarseK;
     int nb = 1;
+    h->csr_valid = false; h->csr_entry_valid = false;
+    if (h->want_entry) CVTMI_TRY(h->csr_entry.reserve(std::max<size_t>((size_t)n * 4, 16)));
     CVTMI_TRY(h->csr_scratch.reserve(csr_scratch_bytes(n, L, &nb)));
     CVTMI_TRY(h->csr_codes.reserve(std::max<size_t>((size_t)n * M, 16)));
     CVTMI_TRY(h->csr_videos.reserve(std::max<size_t>((size_t)n * 4, 16)));
@@ -841,7 +855,7 @@ static int opq_build_csr(cvtmi_opq_t h, hipStream_t st)
     CVTMI_TRY(h->csr_stats.reserve(16));
     CVTMI_TRY(launch_csr_build(h->has_lists ? h->lists.as<int32_t>() : nullptr, h->has_videos ? h->videos.as<int32_t>() : nullptr,
                                h->codes.as<uint8_t>(), n, L, M, h->csr_scratch.p, h->csr_off.as<int64_t>(), h->csr_codes.as<uint8_t>(),
-                               h->csr_videos.as<int32_t>(), h->csr_stats.p, st));
+                               h->csr_videos.as<int32_t>(), h->csr_stats.p, st, h->want_entry ? h->csr_entry.as<uint32_t>() : nullptr));
     struct { int64_t longest; int32_t vmin, vmax; } stats;
     int64_t kept = 0;
     CVTMI_HIP(hipMemcpyAsync(&stats, h->csr_stats.p, sizeof stats, hipMemcpyDeviceToHost, st));
@@ -849,6 +863,7 @@ static int opq_build_csr(cvtmi_opq_t h, hipStream_t st)
     CVTMI_HIP(stream_wait(st));
     h->csr_longest = stats.longest; h->csr_vmin = stats.vmin; h->csr_vmax = stats.vmax; h->csr_kept = kept;
     h->csr_valid = true;
+    h->csr_entry_valid = h->want_entry;
     return CVTMI_OK;
 }
 
@@ -1527,6 +1542,119 @@ int cvtmi_opq_query_video(cvtmi_opq_t h, const float *q, int64_t nq, int rotate,
         CVTMI_HIP(stream_wait(st));
         return CVTMI_OK;
     }
+}
+
+// ---- IVF search: the k nearest ENTRIES of the nprobe nearest lists (ivf_search.hip) ----
+// Concurrency as for query_video: shared lock + leased scratch set; the first search after an append (or the first IVF search of
+// a handle whose list-ordered copy has no insertion indices yet) rebuilds the copy under the exclusive lock.
+static int opq_ivf_prepare(cvtmi_opq_t h, hipStream_t st)
+{
+    {
+        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+        if (h->csr_valid && h->csr_entry_valid) return CVTMI_OK;
+    }
+    Serial serial(h->sync, st);
+    OpqExclusive excl(h, st);
+    h->want_entry = true;
+    return opq_build_csr(h, st);
+}
+static int opq_search_ivf_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64_t nq, int rotate, int nprobe, int k, float *dist, int64_t *ids,
+                                 hipStream_t st)
+{
+    if (!h->csr_valid || !h->csr_entry_valid) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf: the index changed while the search was being prepared");
+    const float *q_rot = q;
+    if (rotate && (h->m.perm || h->m.R)) {
+        CVTMI_TRY(S.s_qrot.reserve((size_t)nq * h->m.D * sizeof(float)));
+        CVTMI_TRY(opq_rotate_impl(h, q, nq, S.s_qrot.as<float>(), st));
+        q_rot = S.s_qrot.as<float>();
+    }
+    const size_t probe_bytes = ((size_t)nq * nprobe * sizeof(int32_t) + 15) / 16 * 16;
+    CVTMI_TRY(S.s_probe.reserve(probe_bytes + coarse_probe_scratch_bytes(nq, nprobe)));
+    CVTMI_TRY(launch_coarse_probe(h->m, q_rot, nq, nprobe, S.s_probe.as<int32_t>(), st, S.s_probe.as<char>() + probe_bytes));
+    const IvfPlan plan = plan_ivf_search(nq, nprobe, k, h->csr_longest, (size_t)g_ivf_part_cap_mb.load() << 20);
+    const size_t pb = ivf_part_bytes(plan, nq, k);
+    if (pb) CVTMI_TRY(S.s_ivf.reserve(pb));
+    {
+        std::lock_guard<std::mutex> g(h->pool_mu);
+        const int64_t v[8] = { plan.rule, plan.G, plan.groups, plan.pieces, plan.rows_per_piece, plan.parts(), (int64_t)pb, (int64_t)h->csr_entry.cap };
+        for (int i = 0; i < 8; ++i) h->ivf_last[i] = v[i];
+    }
+    return launch_ivf_search(h->m, q_rot, nq, nprobe, S.s_probe.as<int32_t>(), h->csr_off.as<int64_t>(), h->csr_codes.as<uint8_t>(),
+                             h->csr_entry.as<uint32_t>(), k, h->id_base, plan, pb ? S.s_ivf.p : nullptr, dist, ids, st);
+}
+// arguments first, before anything touches the device
+static int opq_search_ivf_check(cvtmi_opq_t h, const float *q, int64_t nq, int *nprobe, int k, const float *dist, const int64_t *ids)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf: null handle");
+    if (!q || !dist || !ids || nq < 0) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf: bad arguments");
+    if (*nprobe < 1) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf: nprobe=%d", *nprobe);
+    if (k < 1 || k > CVTMI_K_MAX) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf: k=%d outside 1..%d", k, CVTMI_K_MAX);
+    if (*nprobe > h->m.coarseK) *nprobe = h->m.coarseK;
+    if (*nprobe > 128) return fail(CVTMI_EUNSUPPORTED, "cvtmi_opq_search_ivf: nprobe=%d outside 1..128", *nprobe);
+    if (h->m.K > 256 || h->m.M > 16) return fail(CVTMI_EUNSUPPORTED, "cvtmi_opq_search_ivf: K=%d M=%d outside K <= 256, M <= 16", h->m.K, h->m.M);
+    if (h->n >= ((int64_t)1 << 32)) return fail(CVTMI_EUNSUPPORTED, "cvtmi_opq_search_ivf: %lld entries: ids travel as 32-bit payloads", (long long)h->n);
+    return CVTMI_OK;
+}
+
+int cvtmi_opq_search_ivf_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k, float *dist, int64_t *ids, void *stream)
+{
+    CVTMI_TRY(opq_search_ivf_check(h, q, nq, &nprobe, k, dist, ids));
+    CVTMI_TRY(use_device(h->device));
+    if (nq == 0) return CVTMI_OK;
+    hipStream_t st = (hipStream_t)stream;
+    for (int attempt = 0;; ++attempt) {   // (an append between the preparation and the shared lock sends the search round again)
+        CVTMI_TRY(opq_ivf_prepare(h, st));
+        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
+        OpqLease lease;
+        CVTMI_TRY(lease.open(h, st, false));
+        return opq_search_ivf_leased(h, *lease.s, q, nq, rotate, nprobe, k, dist, ids, st);
+    }
+}
+
+// host pointers: queries in and the two result arrays out through the leased set's staging buffers and its own stream
+int cvtmi_opq_search_ivf(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k, float *dist, int64_t *ids)
+{
+    CVTMI_TRY(opq_search_ivf_check(h, q, nq, &nprobe, k, dist, ids));
+    CVTMI_TRY(use_device(h->device));
+    if (nq == 0) return CVTMI_OK;
+    for (int attempt = 0;; ++attempt) {
+        CVTMI_TRY(opq_ivf_prepare(h, nullptr));
+        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
+        OpqLease lease;
+        CVTMI_TRY(lease.open(h, nullptr, true));
+        OpqScratch &S = *lease.s;
+        hipStream_t st = lease.st;
+        const size_t qb = (size_t)nq * h->m.D * sizeof(float), db = (size_t)nq * k * sizeof(float), ib = (size_t)nq * k * sizeof(int64_t);
+        CVTMI_TRY(S.io_q.reserve(qb));
+        CVTMI_TRY(S.io_d.reserve(db));
+        CVTMI_TRY(S.io_i.reserve(ib));
+        CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
+        CVTMI_TRY(opq_search_ivf_leased(h, S, S.io_q.as<float>(), nq, rotate, nprobe, k, S.io_d.as<float>(), S.io_i.as<int64_t>(), st));
+        CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(hipMemcpyAsync(ids, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(stream_wait(st));
+        return CVTMI_OK;
+    }
+}
+
+int cvtmi_opq_last_ivf_plan(cvtmi_opq_t h, int64_t out[8])
+{
+    if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_opq_last_ivf_plan: null");
+    std::lock_guard<std::mutex> g(h->pool_mu);
+    for (int i = 0; i < 8; ++i) out[i] = h->ivf_last[i];
+    out[7] = (int64_t)h->csr_entry.cap;
+    return CVTMI_OK;
+}
+
+int cvtmi_opq_ivf_plan(int64_t nq, int nprobe, int k, int64_t longest_list, int cus, int64_t out[6])
+{
+    if (!out || nq < 1 || nprobe < 1 || k < 1 || k > CVTMI_K_MAX || longest_list < 0) return fail(CVTMI_EINVAL, "cvtmi_opq_ivf_plan: bad arguments");
+    const IvfPlan p = plan_ivf_search(nq, nprobe, k, longest_list, (size_t)g_ivf_part_cap_mb.load() << 20, cus > 0 ? cus : 256);
+    const int64_t v[6] = { p.rule, p.G, p.groups, p.pieces, p.rows_per_piece, p.parts() };
+    for (int i = 0; i < 6; ++i) out[i] = v[i];
+    return CVTMI_OK;
 }
 
 int cvtmi_opq_set_param(cvtmi_opq_t h, const char *name, int64_t value)

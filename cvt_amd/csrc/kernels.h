@@ -169,7 +169,24 @@ int launch_query_video(const OpqModelDev &m, const float *q_rot, int64_t nq, int
 // stats_out (16 bytes, device): int64 longest list, int32 min / max video id
 size_t csr_scratch_bytes(int64_t n, int L, int *nb_out);
 int launch_csr_build(const int32_t *lists, const int32_t *videos, const uint8_t *codes, int64_t n, int L, int M, void *scratch,
-                     int64_t *list_off, uint8_t *out_codes, int32_t *out_videos, void *stats_out, hipStream_t st);
+                     int64_t *list_off, uint8_t *out_codes, int32_t *out_videos, void *stats_out, hipStream_t st,
+                     uint32_t *out_entry = nullptr);   // out_entry: [n] insertion index per entry of the copy, or null
+
+// ---- ivf_search.hip ----  k smallest (score, id) over the probed lists of every query (cvtmi_opq_search_ivf)
+// one workgroup per (query, group of G consecutive probe slots, piece of rows_per_piece rows of each list of the group)
+struct IvfPlan {
+    int G = 1, groups = 1, pieces = 1, rows_per_piece = 1;
+    int rule = 1;   // which grid rule decided (plan_ivf_search)
+    int parts() const { return groups * pieces; }   // partial lists per query; 1 = the scan writes the result itself
+};
+// pure host logic; longest = rows of the longest list, part_cap = bytes the partial lists may take, cus = 0: the device's CU count
+IvfPlan plan_ivf_search(int64_t nq, int nprobe, int k, int64_t longest, size_t part_cap, int cus = 0);
+size_t ivf_part_bytes(const IvfPlan &p, int64_t nq, int k);
+// probe [nq][nprobe] (launch_coarse_probe); list_off / codes / entry: the list-ordered copy with its insertion indices;
+// part: ivf_part_bytes() of scratch (may be null when that is 0); out_d / out_id [nq][k], padded with (+inf, -1)
+int launch_ivf_search(const OpqModelDev &m, const float *q_rot, int64_t nq, int nprobe, const int32_t *probe, const int64_t *list_off,
+                      const uint8_t *codes, const uint32_t *entry, int k, int64_t id_base, const IvfPlan &p, void *part, float *out_d,
+                      int64_t *out_id, hipStream_t st);
 
 // ---- flat.hip ----
 int flat_plan_splits(int64_t n, int64_t nq, int qtile);

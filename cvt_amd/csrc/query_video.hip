@@ -257,6 +257,8 @@ int launch_coarse_probe(const OpqModelDev &m, const float *q_rot, int64_t nq, in
 //            every lane copies its entry to  list_off[l] + cursor + rank  -- insertion order inside a list is kept, which is
 //            the order m_ivfList holds them in and SaveIndex writes them in (IVFOPQ.cpp:167, :557-575).
 // Entries whose list id is outside [0, L) (-1: a row no centroid could claim) are dropped, as before.
+// out_entry (optional): the insertion index of every entry of the copy, written by the same scatter -- only handles that
+// have been asked for an IVF search (ivf_search.hip) pass it, the others keep their footprint.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void csr_count_kernel(const int32_t *__restrict__ lists, int64_t n, int L, uint32_t *__restrict__ hist)
 {
@@ -310,7 +312,7 @@ __global__ __launch_bounds__(64) void csr_scatter_kernel(const int32_t *__restri
                                                          const uint8_t *__restrict__ codes, int64_t n, int L, int M, int key_bits,
                                                          uint32_t *__restrict__ hist, const int64_t *__restrict__ list_off,
                                                          uint8_t *__restrict__ out_codes, int32_t *__restrict__ out_videos,
-                                                         int32_t *__restrict__ vstats)
+                                                         int32_t *__restrict__ vstats, uint32_t *__restrict__ out_entry)
 {
     const int lane = threadIdx.x;
     const int64_t per = (n + gridDim.x - 1) / gridDim.x;
@@ -345,6 +347,7 @@ __global__ __launch_bounds__(64) void csr_scatter_kernel(const int32_t *__restri
             }
             const int v = videos ? videos[i] : (int32_t)i;
             out_videos[o] = v;
+            if (out_entry) out_entry[o] = (uint32_t)i;  // where the entry came from: its insertion index (cvtmi_opq_search_ivf reports id_base + that)
             vmin = v < vmin ? v : vmin;
             vmax = v > vmax ? v : vmax;
         }
@@ -367,7 +370,7 @@ size_t csr_scratch_bytes(int64_t n, int L, int *nb_out)
 
 // scratch: csr_scratch_bytes(); list_off [L + 1]; stats_out (device): [0] longest list (int64), then int32 min / max video id at byte 8 / 12
 int launch_csr_build(const int32_t *lists, const int32_t *videos, const uint8_t *codes, int64_t n, int L, int M, void *scratch,
-                     int64_t *list_off, uint8_t *out_codes, int32_t *out_videos, void *stats_out, hipStream_t st)
+                     int64_t *list_off, uint8_t *out_codes, int32_t *out_videos, void *stats_out, hipStream_t st, uint32_t *out_entry)
 {
     int nb = 1;
     const size_t sb = csr_scratch_bytes(n, L, &nb);
@@ -391,7 +394,7 @@ int launch_csr_build(const int32_t *lists, const int32_t *videos, const uint8_t 
         int key_bits = 1;
         while ((1 << key_bits) < L) ++key_bits;
         hipLaunchKernelGGL(csr_scatter_kernel, dim3(nb), dim3(64), 0, st, lists, videos, codes, n, L, M, key_bits, hist, list_off,
-                           out_codes, out_videos, vst);
+                           out_codes, out_videos, vst, out_entry);
         CVTMI_HIP(hipGetLastError());
     }
     return CVTMI_OK;

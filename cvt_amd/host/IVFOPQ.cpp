@@ -28,7 +28,7 @@ IVFOPQ::~IVFOPQ()
     if (m_h) cvtmi_opq_destroy(m_h);
     delete[] m_imgLocation;
 }
-std::string IVFOPQ::lastError() const { return cvtmi_last_error(); }
+std::string IVFOPQ::lastError() const { return m_err.empty() ? std::string(cvtmi_last_error()) : m_err; }
 long long IVFOPQ::numEntries() const
 {
     int64_t total = 0, n = 0;
@@ -206,12 +206,24 @@ void IVFOPQ::QueryThrehold(string featFile, vector<vector<float> > &matchScore, 
 
 int IVFOPQ::SearchTopK(const float *q, int nq, int k, float *dist, long long *ids)
 {
+    m_err.clear();
     if (!ensureHandle()) return 0;
     static_assert(sizeof(long long) == sizeof(int64_t), "id width");
     if (m_hs.size() > 1)
         return cvtmi_opq_search_sharded_all(m_hs.data(), m_comms.data(), (int)m_hs.size(), q, nq, /*rotate=*/1, k, dist, (int64_t *)ids) == CVTMI_OK ? 1 : 0;
     if (m_comm) return cvtmi_opq_search_sharded(m_h, m_comm, q, nq, /*rotate=*/1, k, dist, (int64_t *)ids) == CVTMI_OK ? 1 : 0;
     return cvtmi_opq_search(m_h, q, nq, /*rotate=*/1, k, dist, (int64_t *)ids) == CVTMI_OK ? 1 : 0;
+}
+
+int IVFOPQ::SearchTopKProbe(const float *q, int nq, int nprobe, int k, float *dist, long long *ids)
+{
+    m_err.clear();
+    if (!ensureHandle()) return 0;
+    if (m_hs.size() > 1 || m_comm) {
+        m_err = "SearchTopKProbe: the IVF search runs on one GPU; not available after SetShard / SetDevices";
+        return 0;
+    }
+    return cvtmi_opq_search_ivf(m_h, q, nq, /*rotate=*/1, nprobe, k, dist, (int64_t *)ids) == CVTMI_OK ? 1 : 0;
 }
 
 void IVFOPQ::SetShard(cvtmi_comm_s *comm, long long id_base)

@@ -45,6 +45,10 @@ public:
     long long numEntries() const;
     // k smallest (ADC distance, entry id) per query over every entry; needs coarseK == 1.  q is RAW (un-rotated).
     int SearchTopK(const float *q, int nq, int k, float *dist, long long *ids);
+    // k smallest (ADC distance, entry id) per query over the entries of its nprobe nearest coarse lists (cvtmi_opq_search_ivf):
+    // the row-level query of a coarseK > 1 model, whose Query() only scores videos.  q is RAW (un-rotated); rows short of k are
+    // padded with (+inf, -1).  1 ok / 0 failure (lastError()); single-GPU only: fails once SetShard / SetDevices is in force.
+    int SearchTopKProbe(const float *q, int nq, int nprobe, int k, float *dist, long long *ids);
     std::string lastError() const;
     // row-sharded operation (one process per GPU): this object holds the row block that starts at global
     // row id_base; with a communicator set (cvtmi_comm_t, include/cvtmi.h) SearchTopK returns the GLOBAL top k on every
@@ -80,6 +84,7 @@ private:
     std::vector<float> m_coarse, m_books;
     std::vector<float> m_R;               // dense rotation (SetRotation): replaces the permutation when present
     std::vector<int> m_reorder;
+    std::string m_err;                    // a failure of this class's own making (lastError() prefers it to the library's message)
     int m_coarseK, m_pq_m, m_pq_k, m_pq_step, m_featDim, m_imgNum, m_maxIndexNum, m_imgCap;
 };
 

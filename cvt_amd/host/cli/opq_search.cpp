@@ -4,8 +4,10 @@
 // search (retrieval/vlindex/lib/FLANN/mpi/index.h:196-226): every rank indexes a contiguous block of rows, searches it,
 // then ONE all-gather of the per-shard top-k + merge (inside libcvtmi: cvtmi_opq_search_sharded).
 //
-//   opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]
+//   opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--nprobe N] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]
 //
+// --nprobe N: the IVF form -- per query the k nearest entries of its N nearest coarse lists (IVFOPQ::SearchTopKProbe), which is how a
+// model with coarseK > 1 is searched row by row; one GPU, one process; same result file.  Without it nothing changes: coarseK == 1 only.
 // --rotation: a dense D x D rotation (raw fp32, e.g. opq_train --learn-rotation) instead of the model's permutation (IVFOPQ::LoadRotation).
 // model: LoadModel format with coarseK == 1; feature files: raw fp32 [n][D] (IVFOPQ.cpp:451-457).
 // --gpus N: ONE process drives the N GPUs (IVFOPQ::SetDevices: ncclCommInitAll + grouped all-gathers inside libcvtmi) -- the
@@ -38,6 +40,7 @@
 using namespace std;
 
 static string g_rotation;   // --rotation: dense rotation file (IVFOPQ::LoadRotation) applied after every LoadModel
+static int g_nprobe = 0;    // --nprobe: > 0 = search through IVFOPQ::SearchTopKProbe
 
 struct Shared {
     pthread_barrier_t bar;
@@ -167,7 +170,7 @@ static int run_single_process(int gpus, const string &model, const string &db, c
     const int D = index.dim();
     const long long n = file_rows(db, D), nq = file_rows(qf, D);
     if (n < 0 || nq < 0) { fprintf(stderr, "cannot stat the feature files\n"); return 1; }
-    if (index.SetDevices(gpus, n) != 1) return 1;
+    if (g_nprobe == 0 && index.SetDevices(gpus, n) != 1) return 1;
     {
         ifstream fin(db.c_str(), ios::binary);
         const long long chunk = 1 << 18;
@@ -186,7 +189,10 @@ static int run_single_process(int gpus, const string &model, const string &db, c
     }
     vector<float> dist((size_t)nq * k);
     vector<long long> ids((size_t)nq * k);
-    if (nq > 0 && index.SearchTopK(q.data(), (int)nq, k, dist.data(), ids.data()) != 1) {
+    const int ok = nq <= 0 ? 1
+                 : g_nprobe > 0 ? index.SearchTopKProbe(q.data(), (int)nq, g_nprobe, k, dist.data(), ids.data())
+                                : index.SearchTopK(q.data(), (int)nq, k, dist.data(), ids.data());
+    if (ok != 1) {
         fprintf(stderr, "search failed: %s\n", index.lastError().c_str());
         return 1;
     }
@@ -209,16 +215,20 @@ int main(int argc, char *argv[])
     bool forked = false;
     string transport = "rccl";
     vector<string> pos;
+    bool nprobe_given = false;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--k") && i + 1 < argc) k = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--fork")) forked = true;
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--transport") && i + 1 < argc) transport = argv[++i];
         else if (!strcmp(argv[i], "--rotation") && i + 1 < argc) g_rotation = argv[++i];
+        else if (!strcmp(argv[i], "--nprobe") && i + 1 < argc) { g_nprobe = atoi(argv[++i]); nprobe_given = true; }
         else pos.push_back(argv[i]);
     }
-    if (pos.size() != 4 || k < 1 || k > 128 || gpus < 1 || (transport != "rccl" && transport != "shm")) {
-        cerr << "usage: opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]" << endl;
+    // (--nprobe: one GPU, one process, and any k the library takes)
+    const bool bad_probe = nprobe_given && (g_nprobe < 1 || gpus != 1 || forked || transport != "rccl");
+    if (pos.size() != 4 || k < 1 || k > (nprobe_given ? CVTMI_K_MAX : 128) || gpus < 1 || (transport != "rccl" && transport != "shm") || bad_probe) {
+        cerr << "usage: opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--nprobe N] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]" << endl;
         return 2;
     }
     const bool use_shm = transport == "shm";

@@ -100,6 +100,8 @@ int cvtmi_set_device(int device);
  *   "scan_tail_splits" adc_scan16q, query groups past the last full round of workgroups: 0 (default) = cut them into 2 / 4 / 8 row
  *                     splits while that still leaves at most one workgroup per CU (a last round is only expensive while it leaves CUs
  *                     empty: 4256 queries over 1 M rows 2.11 -> 2.79 M queries/s, 10 000 queries unchanged); -1 = never; S > 0 = S splits
+ *   "ivf_part_cap_mb" cvtmi_opq_search_ivf: megabytes the partial lists of one search may take in the leased scratch set (default 256,
+ *                     0 = none: one workgroup per query); a grid that needs more is cut coarser (rule 4 of cvtmi_opq_ivf_plan)
  *   "scan_pad_m"      1 (default) = an OPQ index with M < 16 is searched by the M = 16 scan kernels over rows padded to 16 code bytes
  *                     with zeros (derived copies: 32 bytes per row) and per-query tables padded with all-zero tables -- M = 8 at
  *                     10 000 queries x 1 M rows: 9.8 -> 3.2 ms, and every M from 1 to 15 is searchable; 0 = the row-per-lane
@@ -276,6 +278,33 @@ int cvtmi_opq_query_video(cvtmi_opq_t h, const float *q, int64_t nq, int rotate,
                           int img_num, float *match_score);
 int cvtmi_opq_query_video_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe,
                               int img_num, float *match_score, void *stream);
+
+/* Row-level IVF search: the k nearest ENTRIES among the nprobe nearest coarse lists -- the query an index with coarseK > 1 is
+ * built for, where cvtmi_opq_query_video only returns per-video minima.  Rotation and probing are cvtmi_opq_query_video's
+ * (the nprobe smallest (sequential fp32 distance, list) pairs of IVFOPQ.cpp:238-260; nprobe > coarseK is clamped, more than 128
+ * after the clamp fails with CVTMI_EUNSUPPORTED; a query holding a NaN probes lists 0 .. nprobe-1).  An entry of probed list l
+ * scores the sum over m ascending of table[m][code[m]], the table built from the residual q - coarse[l] (IVFOPQ.cpp:273-306);
+ * the score is NOT clamped at 1.0.  dist[nq][k] / ids[nq][k]: the k smallest (score, id) pairs ascending, id = id_base +
+ * insertion index as cvtmi_opq_search reports it; rows short of k are padded with (+inf, -1); an entry scoring +inf is a real
+ * result and precedes the padding; entries whose list id is outside [0, coarseK) never appear.  A NaN query returns NaN
+ * distances and min(k, entries of its lists) distinct entries in an unspecified order.  1 <= k <= CVTMI_K_MAX, K <= 256,
+ * M <= 16, fewer than 2^32 entries.  On a coarseK == 1 model the call returns what cvtmi_opq_search returns.
+ * NULL pointers, nq < 0, nprobe < 1 or k out of range fail with CVTMI_EINVAL before any device work; nq == 0 does nothing.
+ * The first IVF search on a handle adds a uint32 insertion-index array to the list-ordered copy (4 bytes per entry; handles
+ * that only run cvtmi_opq_query_video never allocate it); like the copy it is rebuilt by the first search after an append.
+ * Searches run concurrently with each other and with cvtmi_opq_query_video / cvtmi_opq_search. */
+int cvtmi_opq_search_ivf(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k,
+                         float *dist, int64_t *ids);
+int cvtmi_opq_search_ivf_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k,
+                             float *dist, int64_t *ids, void *stream);
+/* Measurement hooks.  The grid cvtmi_opq_search_ivf would run for nq queries, nprobe lists each, the longest list holding
+ * longest_list rows (pure host logic: no device needed; cus = 0 assumes 256): out = { rule, probe slots per workgroup G, groups per
+ * query, pieces per list, rows per piece, partial lists per query }.  rule 1 = one workgroup per query (no merge), 2 = probe slots
+ * cut into groups, 3 = long lists cut into pieces as well, 4 = fewer parts than wanted because the partial lists had to fit.
+ * cvtmi_opq_last_ivf_plan: the same six numbers of the handle's last IVF search, then out[6] = bytes of its partial lists and
+ * out[7] = bytes the handle holds for the insertion-index array (0 until the first IVF search). */
+int cvtmi_opq_ivf_plan(int64_t nq, int nprobe, int k, int64_t longest_list, int cus, int64_t out[6]);
+int cvtmi_opq_last_ivf_plan(cvtmi_opq_t h, int64_t out[8]);
 
 /* Tuning / measurement hooks (no effect on results).
  *   "splits"   row splits per query group of the scan (0 = automatic)
