@@ -1254,11 +1254,11 @@ ScanPlan plan_scan(const OpqModelDev &m, int64_t n_rows, int64_t nq, int k, int 
     // Round 5 swept the table size as well (tools/sweep_scan_dispatch.py, profiles/r05_scan_dispatch_sweep.txt): on a code matrix that
     // still fits the Infinity Cache (<= 256 MB: 16 M rows) the persistent grid stays ahead up to 512 queries (10 M rows: 64 / 128 / 256 /
     // 512 queries 0.37 / 0.57 / 0.84 / 1.63 ms against 0.53 / 0.67 / 0.96 / 1.81), level from 1000; and it is ahead from ~33 queries on, not
-    // 100 (what the small-batch form does not take: api.hip scans_chosen).  Beyond 16 M rows the two are within a few per cent.
+    // 100 (what the small-batch form does not take: api_opq.hip scans_chosen).  Beyond 16 M rows the two are within a few per cent.
     if (want_variant == 7) {
         const bool resident = n_rows * 16 <= (96LL << 20), near = n_rows * 16 <= (256LL << 20);
         want_variant = (m.M == 16 && n_rows >= 131072 && nq >= 33 && ((resident && nq <= 3200) || (near && nq <= 512))) ? 6 : 3;
-        // one to three queries on a table too large for the small-batch form (api.hip scans_chosen): adc_scan16q takes four queries or
+        // one to three queries on a table too large for the small-batch form (api_opq.hip scans_chosen): adc_scan16q takes four queries or
         // more, and what is left below it -- the fp32-table / row-per-lane kernels -- needs 1.9-2.9 ms on 100 M rows against 1.2 ms here
         if (m.M == 16 && !near && nq < 4) want_variant = 6;
     }

@@ -1,0 +1,460 @@
+// api_hnsw.hip -- the HNSW handle of the C ABI (include/cvtmi.h): load / build / save, the search, the search over OPQ codes (ADC)
+// with and without the exact re-rank.
+#include <string.h>
+
+#include <cmath>
+#include <random>
+
+#include "api_internal.h"
+
+// ================================================================ HNSW search ==================
+// The graph is immutable once loaded and searchKnn is a pure read in the reference (hnswalg.h:688-728): searches on one handle run side
+// by side, each on a leased scratch set (visited bits, spilled queues, re-rank lists, host staging) and the stream of its caller (the
+// host-pointer entries: the set's own stream).
+
+int cvtmi_hnsw_load(const void *file, int64_t bytes, int metric, int D, cvtmi_hnsw_t *out)
+{
+    if (!file || !out || D < 1 || (metric != CVTMI_METRIC_IP && metric != CVTMI_METRIC_L2F))
+        return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: bad arguments (metric must be IP or L2F)");
+    if (bytes < 96) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: not a saveIndex file (too short)");
+    const uint8_t *f = static_cast<const uint8_t *>(file), *p = f;
+    uint64_t offsetLevel0, max_elements, cur_count, size_per, label_off, offsetData, maxM, maxM0, M, efc;
+    int32_t maxlevel; uint32_t enterpoint; double mult;
+    auto rd = [&](void *dst, size_t nb) { memcpy(dst, p, nb); p += nb; };
+    rd(&offsetLevel0, 8); rd(&max_elements, 8); rd(&cur_count, 8); rd(&size_per, 8); rd(&label_off, 8); rd(&offsetData, 8);
+    rd(&maxlevel, 4); rd(&enterpoint, 4); rd(&maxM, 8); rd(&maxM0, 8); rd(&M, 8); rd(&mult, 8); rd(&efc, 8);
+    if (size_per != 4 + 4 * maxM0 + 4 * (uint64_t)D + 8 || offsetData != 4 + 4 * maxM0 || label_off != offsetData + 4 * (uint64_t)D ||
+        offsetLevel0 != 0 || cur_count > max_elements || maxM0 > 4096 || maxM > 4096)
+        return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: header does not describe %d-d fp32 vectors (size_data_per_element=%llu)", D,
+                    (unsigned long long)size_per);
+    // the header is untrusted: the product below must not wrap, and the counts size host allocations
+    if (max_elements > ((uint64_t)bytes - 96) / size_per) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: truncated level-0 block");
+    if (cur_count > 0 && maxlevel < 0) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: negative maxlevel");
+    const int64_t n = (int64_t)cur_count;
+    const uint8_t *l0 = p;
+    p += max_elements * size_per;
+    std::vector<float> vec;
+    std::vector<uint32_t> links0, upper;
+    std::vector<int64_t> labels, uoff;
+    std::vector<int32_t> levels;  // upper levels a node has link blocks for
+    const uint64_t links_per = 4 * maxM + 4;
+    try {
+        vec.resize((size_t)n * D);
+        links0.resize((size_t)n * (maxM0 + 1));
+        labels.resize((size_t)n);
+        uoff.assign((size_t)n, -1);
+        levels.assign((size_t)n, 0);
+        for (int64_t i = 0; i < n; ++i) {
+            const uint8_t *e = l0 + (uint64_t)i * size_per;
+            memcpy(&links0[(size_t)i * (maxM0 + 1)], e, 4 * (maxM0 + 1));
+            if (links0[(size_t)i * (maxM0 + 1)] > maxM0) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: corrupt link count");
+            memcpy(&vec[(size_t)i * D], e + offsetData, 4 * (size_t)D);
+            uint64_t lab; memcpy(&lab, e + label_off, 8);
+            labels[(size_t)i] = (int64_t)lab;
+        }
+        for (uint64_t i = 0; i < max_elements; ++i) {
+            if ((uint64_t)(f + bytes - p) < 4) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: truncated link lists");
+            uint32_t sz; memcpy(&sz, p, 4); p += 4;
+            if (sz) {
+                if ((uint64_t)(f + bytes - p) < sz || sz % links_per != 0) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: corrupt link list");
+                if ((int64_t)i < n) {
+                    uoff[(size_t)i] = (int64_t)upper.size();
+                    levels[(size_t)i] = (int32_t)(sz / links_per);
+                    upper.resize(upper.size() + sz / 4);
+                    memcpy(&upper[(size_t)uoff[(size_t)i]], p, sz);
+                }
+                p += sz;
+            }
+        }
+    } catch (const std::exception &) {
+        return fail(CVTMI_ENOMEM, "cvtmi_hnsw_load: out of host memory for %llu elements", (unsigned long long)cur_count);
+    }
+    // every link must point inside the graph, and a link at level L at a node that HAS a level-L block: the kernel
+    // follows them without further checks (hnsw.hip: a.upper + a.upper_off[cur] + (level - 1) * (maxM + 1))
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t *l = &links0[(size_t)i * (maxM0 + 1)];
+        for (uint32_t j = 1; j <= l[0]; ++j) if (l[j] >= (uint64_t)n) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: link out of range");
+        for (int32_t lv = 1; lv <= levels[(size_t)i]; ++lv) {
+            const uint32_t *u = &upper[(size_t)uoff[(size_t)i] + (size_t)(lv - 1) * (maxM + 1)];
+            if (u[0] > maxM) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: corrupt upper link count");
+            for (uint32_t j = 1; j <= u[0]; ++j) {
+                if (u[j] >= (uint64_t)n) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: link out of range");
+                if (levels[u[j]] < lv) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: level-%d link to a node without that level", lv);
+            }
+        }
+    }
+    if (n > 0 && (enterpoint >= (uint64_t)n || levels[enterpoint] < maxlevel))
+        return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: bad entry point");
+    int dev = 0;
+    CVTMI_HIP(hipGetDevice(&dev));  // no device: fails here, there is no CPU path
+    cvtmi_hnsw_s *h = new (std::nothrow) cvtmi_hnsw_s();
+    if (!h) return fail(CVTMI_ENOMEM, "cvtmi_hnsw_load: out of host memory");
+    h->device = dev; h->metric = metric; h->D = D;
+    {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) h->cus = prop.multiProcessorCount;
+    }
+    auto up = [&](DevBuf &b, const void *src, size_t nb) -> int {
+        CVTMI_TRY(b.reserve(nb ? nb : 16));
+        if (nb) CVTMI_HIP(hipMemcpy(b.p, src, nb, hipMemcpyHostToDevice));
+        return CVTMI_OK;
+    };
+    int rc = up(h->vec, vec.data(), vec.size() * 4);
+    if (rc == CVTMI_OK) rc = up(h->links0, links0.data(), links0.size() * 4);
+    if (rc == CVTMI_OK) rc = up(h->labels, labels.data(), labels.size() * 8);
+    if (rc == CVTMI_OK) rc = up(h->upper_off, uoff.data(), uoff.size() * 8);
+    if (rc == CVTMI_OK) rc = up(h->upper, upper.data(), upper.size() * 4);
+    if (rc != CVTMI_OK) { cvtmi_hnsw_destroy(h); return rc; }
+    h->g.vec = h->vec.as<float>(); h->g.links0 = h->links0.as<uint32_t>(); h->g.labels = h->labels.as<int64_t>();
+    h->g.upper_off = h->upper_off.as<int64_t>(); h->g.upper = h->upper.as<uint32_t>();
+    h->g.n = n; h->g.D = D; h->g.maxM = (int)maxM; h->g.maxM0 = (int)maxM0; h->g.maxlevel = n > 0 ? maxlevel : 0;
+    h->g.enterpoint = enterpoint;
+    h->levels.swap(levels);
+    h->max_elements = max_elements; h->M = M; h->efc = efc; h->mult = mult;
+    h->hdr_maxlevel = maxlevel; h->hdr_enterpoint = enterpoint;
+    *out = h;
+    return CVTMI_OK;
+}
+
+// Graph construction (hnswalg.h:584-684), batch-synchronous: hnsw_build.hip.  The constructor's fields (:104-127): maxM = M,
+// maxM0 = 2 M, mult = 1 / ln M, ef_construction = max(efc, M); levels are the draws of std::default_random_engine(100) in row
+// order (getRandomLevel, :143-148), made here on the host as the reference makes them.
+static int hnsw_build_impl(const float *x, bool dev, int64_t n, int D, int metric, int M, int efc, const uint64_t *labels, int max_batch,
+                           cvtmi_hnsw_t *out, hipStream_t st)
+{
+    if (out) *out = nullptr;
+    if (!x || !out || n < 1 || D < 1 || (metric != CVTMI_METRIC_IP && metric != CVTMI_METRIC_L2F) || M < 2 || efc < 1 || max_batch < 0)
+        return fail(CVTMI_EINVAL, "cvtmi_hnsw_build: bad arguments (n >= 1, D >= 1, metric IP or L2F, M >= 2, ef_construction >= 1, max_batch >= 0)");
+    if (M > 32) return fail(CVTMI_EINVAL, "cvtmi_hnsw_build: M=%d > 32 (a level-0 list of 2 M links is one wave)", M);
+    const int efe = efc > M ? efc : M;
+    if (efe > hnsw_ef_max()) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_build: ef_construction=%d > %d", efe, hnsw_ef_max());
+    if (n > 0x7fffffffLL) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_build: n too large");
+    if (D > 4096) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_build: D=%d > 4096", D);
+    const int maxM = M, maxM0 = 2 * M;
+    const double mult = 1 / log(1.0 * M);
+    std::vector<int32_t> levels;
+    std::vector<int64_t> uoff;
+    std::vector<int64_t> lab;
+    int32_t maxlevel = 0;
+    uint32_t ep = 0;
+    int64_t upper_words = 0;
+    try {
+        levels.resize((size_t)n);
+        uoff.assign((size_t)n, -1);
+        std::default_random_engine rng(100);
+        std::uniform_real_distribution<double> u01(0.0, 1.0);
+        for (int64_t i = 0; i < n; ++i) {
+            levels[(size_t)i] = (int32_t)(-log(u01(rng)) * mult);
+            if (levels[(size_t)i] > 0) { uoff[(size_t)i] = upper_words; upper_words += (int64_t)levels[(size_t)i] * (maxM + 1); }
+            if (i == 0 || levels[(size_t)i] > maxlevel) { maxlevel = levels[(size_t)i]; ep = (uint32_t)i; }
+        }
+        if (!labels) { lab.resize((size_t)n); for (int64_t i = 0; i < n; ++i) lab[(size_t)i] = i; }
+    } catch (const std::exception &) {
+        return fail(CVTMI_ENOMEM, "cvtmi_hnsw_build: out of host memory for %lld rows", (long long)n);
+    }
+    int devn = 0;
+    CVTMI_HIP(hipGetDevice(&devn));
+    cvtmi_hnsw_s *h = new (std::nothrow) cvtmi_hnsw_s();
+    if (!h) return fail(CVTMI_ENOMEM, "cvtmi_hnsw_build: out of host memory");
+    h->device = devn; h->metric = metric; h->D = D;
+    {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, devn) == hipSuccess && prop.multiProcessorCount > 0) h->cus = prop.multiProcessorCount;
+    }
+    const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    auto run = [&]() -> int {
+        const size_t vb = (size_t)n * D * 4, l0b = (size_t)n * (maxM0 + 1) * 4, ub = (size_t)upper_words * 4;
+        CVTMI_TRY(h->vec.reserve(vb));
+        CVTMI_TRY(h->links0.reserve(l0b));
+        CVTMI_TRY(h->labels.reserve((size_t)n * 8));
+        CVTMI_TRY(h->upper_off.reserve((size_t)n * 8));
+        CVTMI_TRY(h->upper.reserve(ub ? ub : 16));
+        CVTMI_HIP(hipMemcpyAsync(h->vec.p, x, vb, in, st));
+        CVTMI_HIP(hipMemsetAsync(h->links0.p, 0, l0b, st));
+        if (ub) CVTMI_HIP(hipMemsetAsync(h->upper.p, 0, ub, st));
+        if (labels) CVTMI_HIP(hipMemcpyAsync(h->labels.p, labels, (size_t)n * 8, in, st));
+        else CVTMI_HIP(hipMemcpyAsync(h->labels.p, lab.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+        CVTMI_HIP(hipMemcpyAsync(h->upper_off.p, uoff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+        h->g.vec = h->vec.as<float>(); h->g.links0 = h->links0.as<uint32_t>(); h->g.labels = h->labels.as<int64_t>();
+        h->g.upper_off = h->upper_off.as<int64_t>(); h->g.upper = h->upper.as<uint32_t>();
+        h->g.n = n; h->g.D = D; h->g.maxM = maxM; h->g.maxM0 = maxM0; h->g.maxlevel = maxlevel; h->g.enterpoint = ep;
+        // (launch_hnsw_build synchronises the stream before it returns: the host vectors above outlive every copy from them)
+        return launch_hnsw_build(h->g, h->links0.as<uint32_t>(), h->upper.as<uint32_t>(), levels.data(), metric, M, efe, max_batch,
+                                 h->cus, st);
+    };
+    const int rc = run();
+    if (rc != CVTMI_OK) { (void)hipStreamSynchronize(st); cvtmi_hnsw_destroy(h); return rc; }
+    h->levels.swap(levels);
+    h->max_elements = (uint64_t)n; h->M = (uint64_t)M; h->efc = (uint64_t)efe; h->mult = mult;
+    h->hdr_maxlevel = maxlevel; h->hdr_enterpoint = ep;
+    *out = h;
+    return CVTMI_OK;
+}
+
+int cvtmi_hnsw_build(const float *x, int64_t n, int D, int metric, int M, int ef_construction, const uint64_t *labels, int max_batch,
+                     cvtmi_hnsw_t *out)
+{
+    return hnsw_build_impl(x, false, n, D, metric, M, ef_construction, labels, max_batch, out, nullptr);
+}
+int cvtmi_hnsw_build_dev(const float *x, int64_t n, int D, int metric, int M, int ef_construction, const uint64_t *labels,
+                         int max_batch, cvtmi_hnsw_t *out, void *stream)
+{
+    return hnsw_build_impl(x, true, n, D, metric, M, ef_construction, labels, max_batch, out, (hipStream_t)stream);
+}
+int cvtmi_hnsw_build_phases(double *ms)
+{
+    if (!ms) return fail(CVTMI_EINVAL, "cvtmi_hnsw_build_phases: null pointer");
+    hnsw_build_phase_ms(ms);
+    return CVTMI_OK;
+}
+
+// saveIndex (:491-519): header, max_elements level-0 blocks (links, vector, label), then per element the size of its upper-level
+// block and the block.  Slots past cur_element_count are written as zeros.
+int cvtmi_hnsw_save(cvtmi_hnsw_t h, void *buf, int64_t cap, int64_t *bytes)
+{
+    CHECK_HN(h);
+    if (!bytes) return fail(CVTMI_EINVAL, "cvtmi_hnsw_save: null size pointer");
+    const int64_t n = h->g.n;
+    const uint64_t maxM = (uint64_t)h->g.maxM, maxM0 = (uint64_t)h->g.maxM0, D = (uint64_t)h->D;
+    const uint64_t link0 = 4 + 4 * maxM0, per = link0 + 4 * D + 8, upb = 4 * maxM + 4;
+    uint64_t total = 96 + h->max_elements * per + 4 * h->max_elements;
+    for (int64_t i = 0; i < n; ++i) total += upb * (uint64_t)h->levels[(size_t)i];
+    *bytes = (int64_t)total;
+    if (!buf) return CVTMI_OK;
+    if (cap < (int64_t)total) return fail(CVTMI_EINVAL, "cvtmi_hnsw_save: buffer of %lld bytes, the file needs %lld", (long long)cap,
+                                          (long long)total);
+    std::vector<uint32_t> links0, upper;
+    std::vector<float> vec;
+    std::vector<int64_t> labels, uoff;
+    size_t upper_words = 0;
+    for (int64_t i = 0; i < n; ++i) upper_words += (size_t)h->levels[(size_t)i] * (maxM + 1);
+    try {
+        links0.resize((size_t)n * (maxM0 + 1)); vec.resize((size_t)n * D); labels.resize((size_t)n); uoff.resize((size_t)n);
+        upper.resize(upper_words);
+    } catch (const std::exception &) {
+        return fail(CVTMI_ENOMEM, "cvtmi_hnsw_save: out of host memory");
+    }
+    if (n) {
+        CVTMI_HIP(hipMemcpy(links0.data(), h->links0.p, links0.size() * 4, hipMemcpyDeviceToHost));
+        CVTMI_HIP(hipMemcpy(vec.data(), h->vec.p, vec.size() * 4, hipMemcpyDeviceToHost));
+        CVTMI_HIP(hipMemcpy(labels.data(), h->labels.p, labels.size() * 8, hipMemcpyDeviceToHost));
+        CVTMI_HIP(hipMemcpy(uoff.data(), h->upper_off.p, uoff.size() * 8, hipMemcpyDeviceToHost));
+        if (upper_words) CVTMI_HIP(hipMemcpy(upper.data(), h->upper.p, upper_words * 4, hipMemcpyDeviceToHost));
+    }
+    uint8_t *p = static_cast<uint8_t *>(buf);
+    auto put = [&](const void *src, size_t nb) { memcpy(p, src, nb); p += nb; };
+    const uint64_t zero = 0, cnt = (uint64_t)n, offd = link0, offl = link0 + 4 * D;
+    put(&zero, 8); put(&h->max_elements, 8); put(&cnt, 8); put(&per, 8); put(&offl, 8); put(&offd, 8);
+    put(&h->hdr_maxlevel, 4); put(&h->hdr_enterpoint, 4);
+    put(&maxM, 8); put(&maxM0, 8); put(&h->M, 8); put(&h->mult, 8); put(&h->efc, 8);
+    for (int64_t i = 0; i < n; ++i) {
+        put(&links0[(size_t)i * (maxM0 + 1)], link0);
+        put(&vec[(size_t)i * D], 4 * D);
+        put(&labels[(size_t)i], 8);
+    }
+    memset(p, 0, (size_t)((h->max_elements - (uint64_t)n) * per));
+    p += (h->max_elements - (uint64_t)n) * per;
+    for (uint64_t i = 0; i < h->max_elements; ++i) {
+        const uint32_t sz = (int64_t)i < n ? (uint32_t)(upb * (uint64_t)h->levels[(size_t)i]) : 0u;
+        put(&sz, 4);
+        if (sz) put(&upper[(size_t)uoff[(size_t)i]], sz);
+    }
+    return CVTMI_OK;
+}
+
+int cvtmi_hnsw_destroy(cvtmi_hnsw_t h)
+{
+    if (!h) return CVTMI_OK;
+    CHECK_HN(h);
+    h->vec.release(); h->links0.release(); h->labels.release(); h->upper_off.release(); h->upper.release();
+    (void)hipDeviceSynchronize();   // searches still in flight on other streams read the graph
+    h->pool.destroy();
+    h->magic = 0;
+    delete h;
+    return CVTMI_OK;
+}
+
+int64_t cvtmi_hnsw_ntotal(cvtmi_hnsw_t h) { return (h && h->magic == 0x484e5357u) ? h->g.n : -1; }
+
+// scratch of one traversal launch: `slots` concurrent queries (one wave each), a visited bit per node and the spilled queues per slot
+struct HnswPlan { int slots; int64_t words, gcap; };
+static int hnsw_plan(cvtmi_hnsw_t h, HnswScratch &S, int lds_dim, int64_t nq, int k, int ef, HnswPlan &pl, hipStream_t st)
+{
+    const int efe = ef > k ? ef : k;
+    int per_cu = (159 * 1024) / hnsw_lds_bytes(lds_dim, efe);  // query slots (one wave each) a CU's 160 KB of LDS hold
+    per_cu = per_cu > 32 ? 32 : (per_cu < 1 ? 1 : per_cu);
+    if (const int cap = g_hnsw_slots_cap.load(); cap > 0 && per_cu > cap) per_cu = cap;   // cvtmi_set_tuning("hnsw_slots"): measurement hook
+    // (filling the rounds of a batch evenly with fewer slots per CU was measured: no effect -- throughput grows with the traversals in
+    //  flight all the way to 32 per CU: 12 / 16 / 20 / 24 / 28 / 32 slots -> 144 / 164 / 178 / 184 / 192 / 201 K queries/s over codes at ef = 1000)
+    pl.slots = h->cus * per_cu;
+    if (pl.slots > nq) pl.slots = (int)nq;
+    pl.words = (h->g.n + 31) / 32 + 1;
+    int64_t gcap = (int64_t)efe * h->g.maxM0 * 2;
+    if (gcap > h->g.n) gcap = h->g.n;
+    gcap = gcap > hnsw_lcap() ? gcap - hnsw_lcap() : 0;
+    pl.gcap = gcap + 64;
+    CVTMI_TRY(S.s_vis.reserve((size_t)pl.slots * pl.words * 4));
+    CVTMI_TRY(S.s_cand.reserve((size_t)pl.slots * (pl.gcap + efe + 1) * 8));  // per slot: spilled top queue + spilled candidates
+    CVTMI_TRY(S.s_err.reserve(16));
+    CVTMI_HIP(hipMemsetAsync(S.s_err.p, 0, 8, st));  // [0] overflow flag, [1] query counter
+    return CVTMI_OK;
+}
+static int hnsw_check_overflow(HnswScratch &S, const char *who, int ef, hipStream_t st)
+{
+    int err = 0;
+    CVTMI_HIP(hipMemcpyAsync(&err, S.s_err.p, 4, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    if (err) return fail(CVTMI_EUNSUPPORTED, "%s: candidate queue overflow (ef=%d)", who, ef);
+    return CVTMI_OK;
+}
+
+static int hnsw_search_leased(cvtmi_hnsw_t h, HnswScratch &S, const float *q, int64_t nq, int k, int ef, float *dist, int64_t *labels, hipStream_t st)
+{
+    HnswPlan pl;
+    CVTMI_TRY(hnsw_plan(h, S, h->D, nq, k, ef, pl, st));
+    CVTMI_TRY(launch_hnsw_search(h->g, h->metric, q, nq, k, ef, dist, labels, S.s_vis.as<uint32_t>(), S.s_cand.p, pl.slots, pl.words,
+                                 pl.gcap, S.s_err.as<int>(), st));
+    return hnsw_check_overflow(S, "cvtmi_hnsw_search", ef, st);
+}
+
+static int hnsw_search_args(cvtmi_hnsw_t h, const char *who, const void *q, int64_t nq, int k, int ef, const void *dist, const void *labels)
+{
+    (void)h;
+    if (nq < 0 || (nq > 0 && (!q || !dist || !labels))) return fail(CVTMI_EINVAL, "%s: bad arguments", who);
+    if (k < 1 || k > hnsw_ef_max()) return fail(CVTMI_EUNSUPPORTED, "%s: k=%d outside 1..%d", who, k, hnsw_ef_max());
+    if (ef < 1 || ef > hnsw_ef_max()) return fail(CVTMI_EUNSUPPORTED, "%s: ef=%d outside 1..%d", who, ef, hnsw_ef_max());
+    if (nq > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "%s: nq too large", who);
+    return CVTMI_OK;
+}
+
+int cvtmi_hnsw_search_dev(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int ef, float *dist, int64_t *labels, void *stream)
+{
+    CHECK_HN(h);
+    CVTMI_TRY(hnsw_search_args(h, "cvtmi_hnsw_search", q, nq, k, ef, dist, labels));
+    if (nq == 0) return CVTMI_OK;
+    HnswLease lease;
+    CVTMI_TRY(lease.open(h, (hipStream_t)stream, false));
+    return hnsw_search_leased(h, *lease.s, q, nq, k, ef, dist, labels, lease.st);
+}
+
+// host pointers in and out: staged through the leased set's own buffers, on its own stream
+template <typename F> static int hnsw_host_call(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, float *dist, int64_t *labels, F &&run)
+{
+    HnswLease lease;
+    CVTMI_TRY(lease.open(h, nullptr, true));
+    HnswScratch &S = *lease.s;
+    hipStream_t st = lease.st;
+    const size_t qb = (size_t)nq * h->D * sizeof(float), db = (size_t)nq * k * 4, lb = (size_t)nq * k * 8;
+    CVTMI_TRY(S.io_q.reserve(qb));
+    CVTMI_TRY(S.io_d.reserve(db));
+    CVTMI_TRY(S.io_l.reserve(lb));
+    CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
+    CVTMI_TRY(run(S, S.io_q.as<float>(), S.io_d.as<float>(), S.io_l.as<int64_t>(), st));
+    CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(hipMemcpyAsync(labels, S.io_l.p, lb, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    return CVTMI_OK;
+}
+
+int cvtmi_hnsw_search(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int ef, float *dist, int64_t *labels)
+{
+    CHECK_HN(h);
+    CVTMI_TRY(hnsw_search_args(h, "cvtmi_hnsw_search", q, nq, k, ef, dist, labels));
+    if (nq == 0) return CVTMI_OK;
+    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
+        return hnsw_search_leased(h, S, dq, nq, k, ef, dd, dl, st);
+    });
+}
+
+// HNSW over OPQ-compressed vectors: the graph of `h`, distances = ADC over the codes held by `opq` (one code
+// row per graph node, appended in internal-id order).  Queries are rotated and their tables built by the OPQ
+// handle's own kernels, into a scratch set leased from the OPQ handle (so a later cvtmi_opq_add waits for this search);
+// the OPQ handle is held shared for the duration, like a search of its own.
+static int hnsw_search_adc_leased(cvtmi_hnsw_t h, HnswScratch &S, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef,
+                                  float *dist, int64_t *labels, hipStream_t st, int raw_ids)
+{
+    if (!opq) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc: null OPQ handle");
+    CVTMI_TRY(hnsw_search_args(h, "cvtmi_hnsw_search_adc", q, nq, k, ef, dist, labels));
+    if (opq->m.coarseK != 1) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_search_adc: needs an OPQ model with coarseK == 1");
+    if (opq->m.D != h->D) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc: OPQ model is %d-d, graph is %d-d", opq->m.D, h->D);
+    if (opq->device != h->device) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc: handles live on different devices");
+    if (nq == 0) return CVTMI_OK;
+    std::shared_lock<std::shared_timed_mutex> rd(opq->rw);
+    if (opq->n != h->g.n) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc: %lld code rows for %lld graph nodes", (long long)opq->n,
+                                      (long long)h->g.n);
+    OpqLease ol;
+    CVTMI_TRY(ol.open(opq, st, false));
+    OpqScratch &OS = *ol.s;
+    const float *q_rot = q;
+    if (rotate && (opq->m.perm || opq->m.R)) {
+        CVTMI_TRY(OS.s_qrot.reserve((size_t)nq * opq->m.D * sizeof(float)));
+        CVTMI_TRY(opq_rotate_impl(opq, q, nq, OS.s_qrot.as<float>(), st));
+        q_rot = OS.s_qrot.as<float>();
+    }
+    CVTMI_TRY(OS.s_lut.reserve((size_t)nq * opq->m.M * opq->m.K * sizeof(float)));
+    CVTMI_TRY(launch_lut(opq->m, q_rot, nq, nullptr, OS.s_lut.as<float>(), st));
+    HnswPlan pl;
+    const int state_floats = hnsw_adc_state_floats(opq->m.M * opq->m.K);   // one reading of the tuning flag for the slot count AND the launch
+    CVTMI_TRY(hnsw_plan(h, S, state_floats, nq, k, ef, pl, st));
+    CVTMI_TRY(launch_hnsw_search_adc(h->g, OS.s_lut.as<float>(), opq->codes.as<uint8_t>(), opq->m.M, opq->m.K, nq, k, ef, dist,
+                                     labels, S.s_vis.as<uint32_t>(), S.s_cand.p, pl.slots, pl.words, pl.gcap, S.s_err.as<int>(), st, raw_ids,
+                                     state_floats));
+    return hnsw_check_overflow(S, "cvtmi_hnsw_search_adc", ef, st);
+}
+
+int cvtmi_hnsw_search_adc_dev(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef, float *dist,
+                              int64_t *labels, void *stream)
+{
+    CHECK_HN(h);
+    HnswLease lease;
+    CVTMI_TRY(lease.open(h, (hipStream_t)stream, false));
+    return hnsw_search_adc_leased(h, *lease.s, opq, q, nq, rotate, k, ef, dist, labels, lease.st, 0);
+}
+
+// ADC traversal with a result list of `rerank` nodes, then their exact fp32 distances (the graph's own vectors, the summation
+// order of the reference's distance functions) and the k smallest; equal exact distances keep their ADC order
+static int hnsw_search_adc_rerank_leased(cvtmi_hnsw_t h, HnswScratch &S, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef,
+                                         int rerank, float *dist, int64_t *labels, hipStream_t st)
+{
+    if (k < 1 || k > CVTMI_K_MAX) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_search_adc_rerank: k=%d outside 1..%d", k, CVTMI_K_MAX);
+    if (rerank < k || rerank > hnsw_ef_max()) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc_rerank: rerank=%d outside k..%d", rerank, hnsw_ef_max());
+    if (nq < 0 || (nq > 0 && (!q || !dist || !labels))) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc_rerank: bad arguments");
+    if (nq == 0) return CVTMI_OK;
+    CVTMI_TRY(S.s_rr_d.reserve((size_t)nq * rerank * sizeof(float)));
+    CVTMI_TRY(S.s_rr_id.reserve((size_t)nq * rerank * sizeof(int64_t)));
+    CVTMI_TRY(hnsw_search_adc_leased(h, S, opq, q, nq, rotate, rerank, ef, S.s_rr_d.as<float>(), S.s_rr_id.as<int64_t>(), st, 1));
+    CVTMI_TRY(launch_hnsw_rerank(h->g, h->metric, q, nq, rerank, S.s_rr_id.as<int64_t>(), S.s_rr_d.as<float>(), st));
+    CVTMI_TRY(launch_topk_select(S.s_rr_d.as<float>(), S.s_rr_id.as<int64_t>(), nq, rerank, k, dist, labels, st));
+    return launch_gather_labels(labels, nq * k, h->g.labels, st);
+}
+
+int cvtmi_hnsw_search_adc_rerank_dev(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef, int rerank,
+                                     float *dist, int64_t *labels, void *stream)
+{
+    CHECK_HN(h);
+    HnswLease lease;
+    CVTMI_TRY(lease.open(h, (hipStream_t)stream, false));
+    return hnsw_search_adc_rerank_leased(h, *lease.s, opq, q, nq, rotate, k, ef, rerank, dist, labels, lease.st);
+}
+
+int cvtmi_hnsw_search_adc_rerank(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef, int rerank,
+                                 float *dist, int64_t *labels)
+{
+    CHECK_HN(h);
+    if (nq < 0 || k < 1 || (nq > 0 && (!q || !dist || !labels))) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc_rerank: bad arguments");
+    if (nq == 0) return CVTMI_OK;
+    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
+        return hnsw_search_adc_rerank_leased(h, S, opq, dq, nq, rotate, k, ef, rerank, dd, dl, st);
+    });
+}
+
+int cvtmi_hnsw_search_adc(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef, float *dist,
+                          int64_t *labels)
+{
+    CHECK_HN(h);
+    if (nq < 0 || k < 1 || (nq > 0 && (!q || !dist || !labels))) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc: bad arguments");
+    if (nq == 0) return CVTMI_OK;
+    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
+        return hnsw_search_adc_leased(h, S, opq, dq, nq, rotate, k, ef, dd, dl, st, 0);
+    });
+}

@@ -1,0 +1,286 @@
+// api_internal.h -- what the files of the C-ABI glue share (api.hip: library level, api_opq.hip, api_flat.hip, api_models.hip,
+// api_hnsw.hip): the scratch pool of a handle with its lease and its mutation ordering, the handle structs, and the few helpers
+// and tuning values that cross a file.  Everything a single file uses stays static in that file.
+#pragma once
+#include <functional>
+#include <new>
+#include <shared_mutex>
+#include <vector>
+
+#include "host_util.h"
+#include "kernels.h"
+#include "shard.h"
+
+namespace cvtmi {
+
+// What a per-call scratch set carries beside its buffers.  A handle keeps a small pool of sets: a search leases one for the duration
+// of the call, so searches on one handle overlap -- on the host (several threads inside the library) and on the device (several
+// streams).  The set remembers the stream it was last used on and an event recorded when that call returned: the next lessee on
+// ANOTHER stream waits for the event first.
+struct ScratchBase {
+    hipStream_t own = nullptr;      // stream of the host-pointer entry (created on first use)
+    hipEvent_t done = nullptr;
+    hipStream_t last = nullptr;
+    bool pending = false, busy = false;
+    void release_lease_state()
+    {
+        if (own) (void)hipStreamDestroy(own);
+        if (done) (void)hipEventDestroy(done);
+        own = nullptr; done = nullptr;
+    }
+};
+
+// the scratch sets of one handle, and the ordering between the calls that lease a set (Lease) and the calls that change the index
+template <class S> struct ScratchPool {
+    std::mutex mu;
+    std::vector<S *> sets;
+    hipEvent_t mutated = nullptr;   // recorded on the stream of the last mutation: searches on other streams wait for it
+    hipStream_t mut_stream = nullptr;
+    bool mut_pending = false;       // (never set on a handle nothing mutates: HNSW)
+    // a mutation on stream st, between the two calls (the caller holds the handle exclusively): the stream first waits for every
+    // search that is still in flight on another stream and for the last mutation, and the searches that follow wait for this one
+    void mutation_begin(hipStream_t st)
+    {
+        std::lock_guard<std::mutex> g(mu);
+        for (S *c : sets)
+            if (c->pending && c->last != st) (void)hipStreamWaitEvent(st, c->done, 0);
+        if (mut_pending && mut_stream != st) (void)hipStreamWaitEvent(st, mutated, 0);
+    }
+    void mutation_end(hipStream_t st)
+    {
+        if (!mutated) (void)hipEventCreateWithFlags(&mutated, hipEventDisableTiming);
+        if (mutated && hipEventRecord(mutated, st) == hipSuccess) { mut_stream = st; mut_pending = true; }
+    }
+    void destroy()
+    {
+        for (S *c : sets) { c->release_all(); delete c; }
+        sets.clear();
+        if (mutated) (void)hipEventDestroy(mutated);
+    }
+};
+
+// a scratch set of a handle for the duration of one call on stream st (nullptr + host = true: the set's own stream).  The caller
+// holds the handle's rw lock shared, where the handle has one.
+template <class S> struct Lease {
+    ScratchPool<S> *pool = nullptr;
+    S *s = nullptr;
+    hipStream_t st = nullptr;
+    bool used = false;
+    template <class H> int open(H *handle, hipStream_t stream, bool host)
+    {
+        pool = &handle->pool; st = stream;
+        {
+            std::lock_guard<std::mutex> g(pool->mu);
+            S *any = nullptr;
+            for (S *c : pool->sets) {
+                if (c->busy) continue;
+                if (!host && c->pending && c->last == stream) { s = c; break; }   // same stream as before: nothing to wait for
+                if (!any) any = c;
+            }
+            if (!s) s = any;
+            if (!s) {
+                s = new (std::nothrow) S();
+                if (!s) return fail(CVTMI_ENOMEM, S::kLeaseNoMemory);
+                pool->sets.push_back(s);
+            }
+            s->busy = true;
+        }
+        if (host) {
+            if (!s->own && hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking) != hipSuccess) { close(); return fail(CVTMI_EHIP, "hipStreamCreate failed"); }
+            st = s->own;
+        }
+        if (s->pending && s->last != st) (void)hipStreamWaitEvent(st, s->done, 0);
+        if (pool->mut_pending && pool->mut_stream != st) (void)hipStreamWaitEvent(st, pool->mutated, 0);
+        used = true;
+        return CVTMI_OK;
+    }
+    void close()
+    {
+        if (!s) return;
+        if (used) {
+            if (!s->done) (void)hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
+            if (s->done && hipEventRecord(s->done, st) == hipSuccess) { s->last = st; s->pending = true; }
+        }
+        std::lock_guard<std::mutex> g(pool->mu);
+        s->busy = false;
+        s = nullptr;
+    }
+    ~Lease() { close(); }
+    Lease() = default;
+    Lease(const Lease &) = delete;
+    Lease &operator=(const Lease &) = delete;
+};
+
+}  // namespace cvtmi
+
+using namespace cvtmi;   // (as every glue file did for itself: this header is theirs alone)
+
+// per-call scratch of an OPQ search: rotated queries, tables (fp32 + the quantised images of adc_scan16h), partial lists, shared
+// bounds, spill areas, the item table and the plan it was built from, the staging of the host-pointer entry
+struct OpqScratch : ScratchBase {
+    static constexpr const char *kLeaseNoMemory = "opq search: out of host memory";
+    DevBuf s_qrot, s_part_d, s_part_id, s_lut, s_gthr, s_qlut, s_qp, s_spill, s_items, s_probe;
+    DevBuf s_ivf;              // partial lists of an IVF search (ivf_search.hip)
+    ScanHPlan hplan;                       // the item table s_items holds ...
+    int64_t hplan_n = -1, hplan_nq = -1;   // ... and the (rows, queries, forced splits, planner settings) it was built for
+    int hplan_splits = 0, hplan_key = 0;
+    DevBuf io_q, io_d, io_i;   // device side of the host-pointer search (cvtmi_opq_search)
+    PinBuf io_pin;             // its pinned staging area
+    void release_all()
+    {
+        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &io_q, &io_d, &io_i }) b->release();
+        io_pin.release();
+        release_lease_state();
+    }
+};
+
+struct cvtmi_opq_s {
+    int device = 0;
+    HandleSync sync;
+    OpqModelDev m{};
+    float *d_coarse = nullptr, *d_books = nullptr, *d_R = nullptr;
+    int32_t *d_perm = nullptr;
+    // resident entries, insertion order
+    DevBuf codes, lists, videos;
+    DevBuf codes_rot;     // M = 16: rows rotated by (row & 15) bytes for adc_scan16q, built lazily at search time
+    int64_t rot_n = 0;    // rows of codes_rot that are up to date
+    DevBuf codes16;       // M < 16: the rows padded to 16 bytes with zeros, what the M = 16 scan kernels read (opq_pads; built lazily like codes_rot, which is then its rotation)
+    int64_t pad_n = 0;    // rows of codes16 that are up to date
+    int rot_kind = 0;     // what codes_rot holds: 0 = 16-byte rows (M = 16, or the padded copy) rotated by row & 15; 1 = the packed rotation of an M = 8 / 4 index (adc_scan_p.hip)
+    int64_t n = 0;
+    bool has_lists = false, has_videos = false;
+    int64_t id_base = 0;
+    // list-ordered (CSR) copy for the per-video query path, built lazily
+    bool csr_valid = false;
+    DevBuf csr_codes, csr_videos, csr_off, csr_scratch, csr_stats;
+    int64_t csr_kept = 0, csr_longest = 0;  // entries in the CSR copy (list ids outside [0, coarseK) are dropped), longest list
+    int32_t csr_vmin = 0, csr_vmax = -1;    // range of the video ids it holds
+    // insertion index of every entry of the CSR copy (uint32, CSR order): what cvtmi_opq_search_ivf reports ids from.  Allocated and
+    // filled only once an IVF search has been asked for on the handle (want_entry); rebuilt with the copy, invalid whenever it is
+    DevBuf csr_entry;
+    bool want_entry = false, csr_entry_valid = false;
+    int64_t ivf_last[8] = {};               // grid of the last IVF search (cvtmi_opq_last_ivf_plan), written under pool.mu
+    // scratch of the calls that run one at a time (query_video: probe lists, rotated queries)
+    DevBuf s_qrot, s_probe, s_rot;
+    // Searches (cvtmi_opq_search*) run CONCURRENTLY, as the reference's QueryThrehold de facto may (opq/src/IVFOPQ.cpp:322-422 only
+    // reads the index): each leases a scratch set from this pool for the duration of the call (OpqLease) and holds `rw` shared;
+    // everything else -- add / reset / reserve, the lazily built copies of the rows, the one-at-a-time entries above -- holds it
+    // exclusively (OpqExclusive, on top of the per-handle Serial that orders those calls among themselves).
+    std::shared_timed_mutex rw;
+    ScratchPool<OpqScratch> pool;
+    // tuning / measurement
+    int p_splits = 0, p_qtile = 0, p_profile = 0, p_variant = 7;
+    int p_encode = 0;  // 0 = choose, 1 = VALU encode, 2 = matrix-core filter + exact resolution
+    int p_prerot = 1;  // adc_scan16q reads a pre-rotated copy of the code rows (+16 bytes of HBM per row)
+    int p_tail = 1, p_groups_a = 0, p_splits_b = 0;  // two-region scan plan: on / forced shape (tests)
+    int p_lazy = 1, p_share = 1;  // adc_scan16q: lazy selection between checkpoints; row splits share their thresholds
+    int p_small = 1;              // 1 .. 8 queries take the small-batch path (adc_scan_h.hip) when the library chooses the scan (scan_variant 7)
+    static constexpr int kEvRing = 64;
+    hipEvent_t ev0[kEvRing] = {}, ev1[kEvRing] = {};
+    int ev_count = 0;  // scan launches recorded since the last cvtmi_opq_last_scan
+    int64_t last_bytes = 0;
+    int last_qt = 0, last_splits = 0;
+};
+
+// per-call scratch of a flat search
+struct FlatScratch : ScratchBase {
+    static constexpr const char *kLeaseNoMemory = "flat search: out of host memory";
+    DevBuf s_part_d, s_part_id, s_gthr, s_stage;
+    DevBuf f_stats, f_thr, f_marg, f_cnt, f_cand, f_sd, f_si, f_sd2, f_si2, f_seld, f_seli;   // matrix-core filter pipelines
+    DevBuf fs_redo, fs_scratch;                                                                // fp32 stream
+    DevBuf redo_count;                                                                         // "flat_count_redo": the count of the flags
+    DevBuf io_q, io_d, io_i;                                                                   // staging of the host-pointer entry
+    PinBuf io_pin;                  // small calls: [queries | distances | labels] in page-locked memory the kernels write into
+    void release_all()
+    {
+        for (DevBuf *b : { &s_part_d, &s_part_id, &s_gthr, &s_stage, &f_stats, &f_thr, &f_marg, &f_cnt, &f_cand, &f_sd, &f_si, &f_sd2,
+                           &f_si2, &f_seld, &f_seli, &fs_redo, &fs_scratch, &redo_count, &io_q, &io_d, &io_i })
+            b->release();
+        io_pin.release();
+        release_lease_state();
+    }
+};
+
+struct cvtmi_flat_s {
+    int device = 0;
+    // searches hold `rw` shared, everything that changes the index (add, reset, the lazily built operand copies) exclusively
+    std::shared_timed_mutex rw;
+    ScratchPool<FlatScratch> pool;
+    int metric = 0, D = 0;
+    size_t row_bytes = 0;
+    DevBuf data, labels, norms;  // norms: int32 |x-128|^2 per row, uint8 metric with D % 32 == 0 (MFMA path)
+    DevBuf add_stage;            // staging of host rows on their way into the blocked layout
+    int64_t n = 0;
+    int64_t id_base = 0;   // row r reports label id_base + r while labels are implicit (row shards, cvtmi_flat_set_id_base)
+    bool identity = true;  // label == row
+    // matrix-core filter of the fp32 search (flat_mfma.hip): bf16 operand copy of the rows, built on first use
+    DevBuf f_pack, f_bias, f_istats;   // f_istats: [0] max |x|^2, [1] rows with a non-finite value (of the operand copy)
+    int64_t f_pack_n = -1;      // rows the copy covers (-1: none)
+    DevBuf f_rows;              // fp32: row-major copy of the rows for the threshold filter's exact finish ("flat_f32_rows_copy"; the blocked layout gathers 16 of every 128 bytes it fetches)
+    int64_t f_rows_n = -1;      // rows it covers (-1: none)
+    bool f_rows_failed = false; // it did not fit once: not tried again on this handle
+    int f_pack_nch = 0;         // its K steps per row (the threshold filter of a width between two kernels pads with zeros)
+    bool f_nonfinite = false;   // a row holds inf / NaN: the filter is not used
+    std::atomic<int> f_last_filtered{0};    // how the last search was answered (0 exact, 1 filter pipeline, 2 fp32 stream, 3 fp32 threshold filter)
+    std::atomic<long long> f_last_worst{0};  // its largest candidate list
+    std::atomic<long long> f_last_redo{-1};  // queries of the last search the exact kernels answered under a redo flag (-1: not counted)
+    // fp32 stream (flat_f32_stream.hip): per-row score bias, statistics of the rows ([0] max |x|^2, [1] non-finite rows)
+    DevBuf fs_bias, fs_stats;
+    int64_t fs_stats_n = -1;    // index size the host copy of the statistics belongs to
+    bool fs_nonfinite = false;
+};
+
+// per-call scratch of an HNSW search: visited bits, spilled queues, re-rank lists, host staging
+struct HnswScratch : ScratchBase {
+    static constexpr const char *kLeaseNoMemory = "hnsw search: out of host memory";
+    DevBuf s_vis, s_cand, s_err, s_rr_d, s_rr_id, io_q, io_d, io_l;
+    void release_all()
+    {
+        for (DevBuf *b : { &s_vis, &s_cand, &s_err, &s_rr_d, &s_rr_id, &io_q, &io_d, &io_l }) b->release();
+        release_lease_state();
+    }
+};
+struct cvtmi_hnsw_s {
+    uint32_t magic = 0x484e5357u;
+    int device = 0, metric = 0, D = 0;
+    HnswDevGraph g{};
+    DevBuf vec, links0, labels, upper_off, upper;
+    // what cvtmi_hnsw_save needs beyond the device graph: the header fields as the file (or the build) set them, and the number
+    // of upper levels of every element
+    std::vector<int32_t> levels;
+    uint64_t max_elements = 0, M = 0, efc = 0;
+    double mult = 0.0;
+    int32_t hdr_maxlevel = 0;
+    uint32_t hdr_enterpoint = 0;
+    ScratchPool<HnswScratch> pool;
+    int slots_per_cu_max = 32, cus = 256;
+};
+
+using OpqLease = Lease<OpqScratch>;
+using FlatLease = Lease<FlatScratch>;
+using HnswLease = Lease<HnswScratch>;
+
+namespace cvtmi {
+
+extern thread_local std::string g_err;   // text of cvtmi_last_error (api.hip)
+// cvtmi_set_tuning values (defined and described in api.hip), by the file that reads them
+extern std::atomic<int> g_ivf_part_cap_mb, g_small_zero_copy, g_scan_bigk, g_scan_packed, g_scan_pad, g_host_zero_copy, g_host_chunks, g_scanh_key;   // api_opq.hip
+extern std::atomic<int64_t> g_scans_max_work;
+extern std::atomic<int> g_flat_f32_rows_copy, g_flat_u8_filter_min_nq, g_flat_u8_sample_passes, g_flat_small_zero_copy, g_flat_variant, g_flat_f32_stream, g_flat_count_redo;   // api_flat.hip
+extern std::atomic<int64_t> g_flat_u8_filter_min_rows, g_flat_u8_filter_min_work;
+extern std::atomic<int> g_sq8_host_small, g_hnsw_slots_cap;   // api_models.hip, api_hnsw.hip
+
+int use_device(int dev);
+int opq_rotate_impl(cvtmi_opq_t h, const float *x, int64_t n, float *y, hipStream_t st);   // api_opq.hip
+int sharded_local_failure(cvtmi_comm_t c);
+using ShardLocalSearch = std::function<int(int, const void *, float *, int64_t *)>;
+int sharded_all(cvtmi_comm_t *comms, int ndev, const void *q, size_t q_bytes, int64_t nq, int k, void *dist, int64_t *ids,
+                const int *devices, const ShardLocalSearch &local_search);
+
+}  // namespace cvtmi
+
+// the first lines of an entry that takes a handle: the handle is there (HNSW: and is one), its device is current
+#define CHECK_H(h) \
+    if (!(h)) return fail(CVTMI_EINVAL, "%s: null handle", __func__); \
+    CVTMI_TRY(use_device((h)->device))
+#define CHECK_HN(h) do { if (!(h) || (h)->magic != 0x484e5357u) return fail(CVTMI_EINVAL, "bad hnsw handle"); CVTMI_TRY(use_device((h)->device)); } while (0)

@@ -1,4 +1,4 @@
-// host_util.h -- host-side helpers shared by the C-ABI glue (api.hip, shard.hip): device buffers and the
+// host_util.h -- host-side helpers shared by the C-ABI glue (api*.hip, shard.hip): device buffers and the
 // per-handle serialisation of calls.
 #pragma once
 #include <atomic>

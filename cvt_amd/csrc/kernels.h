@@ -1,4 +1,4 @@
-// kernels.h -- internal launch interface between the C-ABI glue (api.hip) and the HIP kernels.
+// kernels.h -- internal launch interface between the C-ABI glue (api*.hip) and the HIP kernels.
 // All pointers are device pointers; every launcher is asynchronous on `st`.
 #pragma once
 #include <vector>
@@ -51,7 +51,7 @@ struct ScanPlan {
     // splits_b == 0: one region.  Partial results are laid out [nq][stride()][k].
     int groups_a = 0, splits_b = 0;
     int stride() const { return splits_b > splits ? splits_b : splits; }
-    // M < 16 served by the M = 16 kernels (api.hip opq_plan): the scan reads a copy of the rows padded to 16 bytes with zeros and
+    // M < 16 served by the M = 16 kernels (api_opq.hip opq_plan): the scan reads a copy of the rows padded to 16 bytes with zeros and
     // per-query tables padded with all-zero tables; real_M = the model's M (0: not padded)
     int real_M = 0;
     // round 6: M = 8 / M = 4 NATIVE (adc_scan_p.hip: adc_scan16p): the rows as they lie in memory, 16 / M of them per 16-byte load, from

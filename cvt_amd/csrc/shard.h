@@ -1,4 +1,4 @@
-// shard.h -- internal interface between the communicator (shard.hip) and the search entry points (api.hip).
+// shard.h -- internal interface between the communicator (shard.hip) and the search entry points (api_opq.hip, api_flat.hip; api.hip: sharded_all).
 #pragma once
 #include "host_util.h"
 

@@ -1,6 +1,6 @@
 // opq_concurrent -- T host threads calling IVFOPQ::SearchTopK on ONE index at the same time.  The reference's QueryThrehold only
 // reads the index (opq/src/IVFOPQ.cpp:322-422), so concurrent queries are de-facto legal there; here every search leases its own
-// scratch set and stream from the handle (csrc/api.hip: OpqLease), only add / reset and the lazily built row copy are exclusive:
+// scratch set and stream from the handle (csrc/api_internal.h: Lease), only add / reset and the lazily built row copy are exclusive:
 //   opq_concurrent [rows] [threads] [calls per thread] [queries per call] [k]
 // checks that every thread gets what a single thread gets, and prints the one-thread and the T-thread rate.
 #include <chrono>

@@ -40,7 +40,7 @@ def fs_qb_max(D):
 
 
 def _pass_size(D, nq):
-    """queries per pass of a batch (api.hip, flat_search_streamed; the four-wave shared ring at D / 16 % 4 == 0)"""
+    """queries per pass of a batch (api_flat.hip, flat_search_streamed; the four-wave shared ring at D / 16 % 4 == 0)"""
     qpriv = 32 * fs_qb_max(D)
     qmax = 4 * qpriv if (D // 16) % 4 == 0 else qpriv
     passes = -(-nq // qmax)
@@ -195,7 +195,7 @@ def test_stream_group_geometry(amd, orc, metric, D, n, forms):
     (L2F, 64, 1_000_003, (32, 4), 500),
 ])
 def test_stream_pass_geometry(amd, orc, metric, D, n, geom, per):
-    """1000 queries on the shared ring in passes of `per` (api.hip: per = ceil(nq / passes)), rows planted for queries in the first and
+    """1000 queries on the shared ring in passes of `per` (api_flat.hip: per = ceil(nq / passes)), rows planted for queries in the first and
     last wave of every pass and in its partial last wave; and just under twice a private-ring pass (two passes of the private ring,
     G and NG as fs_groups gives for 1024 streams).  The later passes write their redo flags and list counters at offset a: no query
     may be re-answered, every list must equal the exact kernels'"""

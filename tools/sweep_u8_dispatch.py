@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """uint8 flat search: the sample + filter pipeline against passes of 128 queries through the streaming kernel, over table and batch
-sizes (what the dispatch rule in api.hip flat_route is fitted to).  D / K / ROWS_LIST / NQS env."""
+sizes (what the dispatch rule in api_flat.hip flat_route is fitted to).  D / K / ROWS_LIST / NQS env."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
