@@ -47,9 +47,14 @@ def lib():
     return load_library()
 
 
+ESPACE = -7   # CVTMI_ESPACE: the result does not fit the caller's arrays
+
+
 def _check(rc):
     if rc != 0:
-        raise CvtmiError("cvtmi error %d: %s" % (rc, lib().cvtmi_last_error().decode(errors="replace")))
+        err = CvtmiError("cvtmi error %d: %s" % (rc, lib().cvtmi_last_error().decode(errors="replace")))
+        err.code = rc
+        raise err
 
 
 def _is_torch(a):
@@ -283,6 +288,53 @@ class OpqIndex:
         o = (C.c_int64 * 8)()
         _check(lib().cvtmi_opq_last_ivf_plan(self.h, o))
         return dict(rule=o[0], G=o[1], groups=o[2], pieces=o[3], rows_per_piece=o[4], parts=o[5], part_bytes=o[6], entry_bytes=o[7])
+
+    def range_search_ivf(self, q, nprobe, radius, rotate=True, want_video=False, out=None):
+        """Range search (cvtmi_opq_range_search_ivf): every entry of the nprobe nearest coarse lists of a query whose score is
+        < radius, in the order of the list-ordered copy.  Returns (lims [nq + 1] int64, distances, ids[, video ids]): the hits of
+        query f are [lims[f], lims[f + 1]).
+        Without `out` a count-only call sizes the arrays and a second call fills them (torch input: the first one is waited for).
+        With out = (lims, dist, ids[, video]) ONE call runs with the capacity of `dist`: numpy raises CvtmiError (code ESPACE)
+        when the hits do not fit; torch never waits -- read lims[-1] after synchronising, the arrays are untouched when it is
+        larger than their length."""
+        nq = q.shape[0]
+        dev = _is_torch(q)
+        if not dev:
+            q = _np(q, np.float32)
+
+        def call(cap, lims, d, i, v):
+            args = (self.h, _ptr(q), C.c_int64(nq), C.c_int(1 if rotate else 0), C.c_int(nprobe), C.c_float(float(radius)), C.c_int64(cap),
+                    _ptr(lims), _ptr(d), _ptr(i), _ptr(v))
+            if dev:
+                return lib().cvtmi_opq_range_search_ivf_dev(*args, _stream())
+            return lib().cvtmi_opq_range_search_ivf(*args)
+
+        def empty(n, dt):
+            if dev:
+                import torch
+                return torch.empty(n, dtype=getattr(torch, dt), device=q.device)
+            return np.empty(n, dtype=dt)
+
+        if out is not None:
+            lims, d, i = out[:3]
+            v = out[3] if len(out) > 3 else None
+            assert lims.shape[0] == nq + 1 and i.shape[0] == d.shape[0] and (v is None or v.shape[0] == d.shape[0])
+            _check(call(d.shape[0], lims, d, i, v))
+            return out
+        lims = empty(nq + 1, "int64")
+        _check(call(0, lims, None, None, None))
+        total = int(lims[nq])
+        d, i = empty(total, "float32"), empty(total, "int64")
+        v = empty(total, "int32") if want_video else None
+        if total:
+            _check(call(total, lims, d, i, v))
+        return (lims, d, i, v) if want_video else (lims, d, i)
+
+    def last_range_plan(self):
+        """grid of the last range_search_ivf on this handle (cvtmi_opq_last_range_plan)"""
+        o = (C.c_int64 * 8)()
+        _check(lib().cvtmi_opq_last_range_plan(self.h, o))
+        return dict(rule=o[0], G=o[1], groups=o[2], pieces=o[3], rows_per_piece=o[4], parts=o[5], spill=o[6], spill_bytes=o[7])
 
     def set_param(self, name, value):
         _check(lib().cvtmi_opq_set_param(self.h, name.encode(), C.c_int64(value)))

@@ -44,6 +44,7 @@ int fail(int code, const char *fmt, ...)
 
 // the values cvtmi_set_tuning sets (declared in api_internal.h for the files that read them)
 std::atomic<int> g_ivf_part_cap_mb{256};   // cvtmi_set_tuning("ivf_part_cap_mb"): room for the partial lists of an IVF search
+std::atomic<int64_t> g_ivf_range_spill{4096};   // cvtmi_set_tuning("ivf_range_spill"): hits a part of a range search may leave in the spill area
 std::atomic<int> g_hnsw_slots_cap{0};   // cvtmi_set_tuning("hnsw_slots"): cap on traversals per CU (0 = what LDS allows, at most 32)
 std::atomic<int> g_small_zero_copy{1};   // cvtmi_set_tuning("opq_small_zero_copy"): 1 .. 8-query host-pointer searches read / write the pinned staging area from the kernels
 std::atomic<int64_t> g_scans_max_work{(int64_t)48 << 20};   // cvtmi_set_tuning("scans_max_work"): rows x query groups up to which the OPQ small-batch form answers (scans_chosen)
@@ -244,6 +245,11 @@ int cvtmi_set_tuning(const char *name, int64_t value)
     if (!strcmp(name, "ivf_part_cap_mb")) {
         if (value < 0 || value > 4096) return fail(CVTMI_EINVAL, "cvtmi_set_tuning: ivf_part_cap_mb must be 0 .. 4096");
         g_ivf_part_cap_mb = (int)value;
+        return CVTMI_OK;
+    }
+    if (!strcmp(name, "ivf_range_spill")) {
+        if (value < 0) return fail(CVTMI_EINVAL, "cvtmi_set_tuning: ivf_range_spill must be >= 0");
+        g_ivf_range_spill = value;
         return CVTMI_OK;
     }
     if (!strcmp(name, "sq8_flags")) { set_sq8_flags((int)value); return CVTMI_OK; }

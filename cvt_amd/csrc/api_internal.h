@@ -121,14 +121,16 @@ struct OpqScratch : ScratchBase {
     static constexpr const char *kLeaseNoMemory = "opq search: out of host memory";
     DevBuf s_qrot, s_part_d, s_part_id, s_lut, s_gthr, s_qlut, s_qp, s_spill, s_items, s_probe;
     DevBuf s_ivf;              // partial lists of an IVF search (ivf_search.hip)
+    DevBuf s_range;            // range search (ivf_range.hip): probe order, part counts and offsets, spill area; host entry: lims behind them
     ScanHPlan hplan;                       // the item table s_items holds ...
     int64_t hplan_n = -1, hplan_nq = -1;   // ... and the (rows, queries, forced splits, planner settings) it was built for
     int hplan_splits = 0, hplan_key = 0;
     DevBuf io_q, io_d, io_i;   // device side of the host-pointer search (cvtmi_opq_search)
+    DevBuf io_v;               // ... and the video ids of a range search
     PinBuf io_pin;             // its pinned staging area
     void release_all()
     {
-        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &io_q, &io_d, &io_i }) b->release();
+        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &s_range, &io_q, &io_d, &io_i, &io_v }) b->release();
         io_pin.release();
         release_lease_state();
     }
@@ -160,6 +162,7 @@ struct cvtmi_opq_s {
     DevBuf csr_entry;
     bool want_entry = false, csr_entry_valid = false;
     int64_t ivf_last[8] = {};               // grid of the last IVF search (cvtmi_opq_last_ivf_plan), written under pool.mu
+    int64_t range_last[8] = {};             // ... and of the last range search (cvtmi_opq_last_range_plan)
     // scratch of the calls that run one at a time (query_video: probe lists, rotated queries)
     DevBuf s_qrot, s_probe, s_rot;
     // Searches (cvtmi_opq_search*) run CONCURRENTLY, as the reference's QueryThrehold de facto may (opq/src/IVFOPQ.cpp:322-422 only
@@ -265,7 +268,7 @@ namespace cvtmi {
 extern thread_local std::string g_err;   // text of cvtmi_last_error (api.hip)
 // cvtmi_set_tuning values (defined and described in api.hip), by the file that reads them
 extern std::atomic<int> g_ivf_part_cap_mb, g_small_zero_copy, g_scan_bigk, g_scan_packed, g_scan_pad, g_host_zero_copy, g_host_chunks, g_scanh_key;   // api_opq.hip
-extern std::atomic<int64_t> g_scans_max_work;
+extern std::atomic<int64_t> g_scans_max_work, g_ivf_range_spill;
 extern std::atomic<int> g_flat_f32_rows_copy, g_flat_u8_filter_min_nq, g_flat_u8_sample_passes, g_flat_small_zero_copy, g_flat_variant, g_flat_f32_stream, g_flat_count_redo;   // api_flat.hip
 extern std::atomic<int64_t> g_flat_u8_filter_min_rows, g_flat_u8_filter_min_work;
 extern std::atomic<int> g_sq8_host_small, g_hnsw_slots_cap;   // api_models.hip, api_hnsw.hip

@@ -1128,6 +1128,140 @@ int cvtmi_opq_ivf_plan(int64_t nq, int nprobe, int k, int64_t longest_list, int 
     return CVTMI_OK;
 }
 
+// ---- range search: every entry of the probed lists under a score radius (ivf_range.hip) ----
+// Concurrency and preparation are the IVF search's.  A call is a count (probe order, scan, offsets: lims is complete on the device)
+// and, where the caller gave room, a fill (fill + rescan, both predicated on the device on lims[nq] <= cap).
+struct OpqRangeCall {
+    IvfRangePlan plan;
+    IvfRangeBufs bufs;
+    const float *q_rot = nullptr;
+    int64_t *lims_scratch = nullptr;   // nq + 1 words behind the carved areas (the host entry's device lims)
+};
+static int opq_range_count_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64_t nq, int rotate, int nprobe, float radius, bool spill,
+                                  int64_t *lims, OpqRangeCall &c, hipStream_t st)
+{
+    if (!h->csr_valid || !h->csr_entry_valid) return fail(CVTMI_EINVAL, "cvtmi_opq_range_search_ivf: the index changed while the search was being prepared");
+    c.q_rot = q;
+    if (rotate && (h->m.perm || h->m.R)) {
+        CVTMI_TRY(S.s_qrot.reserve((size_t)nq * h->m.D * sizeof(float)));
+        CVTMI_TRY(opq_rotate_impl(h, q, nq, S.s_qrot.as<float>(), st));
+        c.q_rot = S.s_qrot.as<float>();
+    }
+    const size_t probe_bytes = ((size_t)nq * nprobe * sizeof(int32_t) + 15) / 16 * 16;
+    CVTMI_TRY(S.s_probe.reserve(probe_bytes + coarse_probe_scratch_bytes(nq, nprobe)));
+    CVTMI_TRY(launch_coarse_probe(h->m, c.q_rot, nq, nprobe, S.s_probe.as<int32_t>(), st, S.s_probe.as<char>() + probe_bytes));
+    c.plan = plan_ivf_range(nq, nprobe, h->csr_longest, spill ? g_ivf_range_spill.load() : 0, (size_t)g_ivf_part_cap_mb.load() << 20);
+    const size_t carved = ivf_range_carve(nullptr, c.plan, nq, nprobe, nullptr);
+    CVTMI_TRY(S.s_range.reserve(carved + ((size_t)nq + 1) * sizeof(int64_t)));
+    ivf_range_carve(S.s_range.p, c.plan, nq, nprobe, &c.bufs);
+    c.lims_scratch = reinterpret_cast<int64_t *>(S.s_range.as<char>() + carved);
+    {
+        std::lock_guard<std::mutex> g(h->pool.mu);
+        const IvfPlan &p = c.plan.grid;
+        const int64_t v[8] = { p.rule, p.G, p.groups, p.pieces, p.rows_per_piece, p.parts(), c.plan.spill,
+                               (int64_t)((size_t)nq * p.parts() * c.plan.spill * sizeof(unsigned long long)) };
+        for (int i = 0; i < 8; ++i) h->range_last[i] = v[i];
+    }
+    return launch_ivf_range_count(h->m, c.q_rot, nq, nprobe, S.s_probe.as<int32_t>(), h->csr_off.as<int64_t>(), h->csr_codes.as<uint8_t>(), radius,
+                                  c.plan, c.bufs, lims ? lims : c.lims_scratch, st);
+}
+static int opq_range_fill_leased(cvtmi_opq_t h, const OpqRangeCall &c, int64_t nq, int nprobe, float radius, const int64_t *lims, int64_t cap,
+                                 float *dist, int64_t *ids, int32_t *video, hipStream_t st)
+{
+    return launch_ivf_range_fill(h->m, c.q_rot, nq, nprobe, h->csr_off.as<int64_t>(), h->csr_codes.as<uint8_t>(), h->csr_entry.as<uint32_t>(),
+                                 h->csr_videos.as<int32_t>(), radius, h->id_base, c.plan, c.bufs, lims, cap, dist, ids, video, st);
+}
+// arguments first, before anything touches the device
+static int opq_range_check(cvtmi_opq_t h, const float *q, int64_t nq, int *nprobe, float radius, int64_t cap, const int64_t *lims, const float *dist,
+                           const int64_t *ids)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_opq_range_search_ivf: null handle");
+    if (!q || !lims || nq < 0 || cap < 0) return fail(CVTMI_EINVAL, "cvtmi_opq_range_search_ivf: bad arguments");
+    if (cap > 0 && (!dist || !ids)) return fail(CVTMI_EINVAL, "cvtmi_opq_range_search_ivf: cap=%lld without result arrays", (long long)cap);
+    if (*nprobe < 1) return fail(CVTMI_EINVAL, "cvtmi_opq_range_search_ivf: nprobe=%d", *nprobe);
+    if (radius != radius) return fail(CVTMI_EINVAL, "cvtmi_opq_range_search_ivf: the radius is NaN");
+    if (*nprobe > h->m.coarseK) *nprobe = h->m.coarseK;
+    if (*nprobe > 128) return fail(CVTMI_EUNSUPPORTED, "cvtmi_opq_range_search_ivf: nprobe=%d outside 1..128", *nprobe);
+    if (h->m.K > 256 || h->m.M > 16) return fail(CVTMI_EUNSUPPORTED, "cvtmi_opq_range_search_ivf: K=%d M=%d outside K <= 256, M <= 16", h->m.K, h->m.M);
+    if (h->n >= ((int64_t)1 << 32))
+        return fail(CVTMI_EUNSUPPORTED, "cvtmi_opq_range_search_ivf: %lld entries: positions travel as 32-bit payloads", (long long)h->n);
+    return CVTMI_OK;
+}
+
+int cvtmi_opq_range_search_ivf_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, float radius, int64_t cap, int64_t *lims,
+                                   float *dist, int64_t *ids, int32_t *video, void *stream)
+{
+    CVTMI_TRY(opq_range_check(h, q, nq, &nprobe, radius, cap, lims, dist, ids));
+    CVTMI_TRY(use_device(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (nq == 0) {
+        CVTMI_HIP(hipMemsetAsync(lims, 0, sizeof(int64_t), st));
+        return CVTMI_OK;
+    }
+    for (int attempt = 0;; ++attempt) {   // (an append between the preparation and the shared lock sends the search round again)
+        CVTMI_TRY(opq_ivf_prepare(h, st));
+        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
+        OpqLease lease;
+        CVTMI_TRY(lease.open(h, st, false));
+        OpqRangeCall c;
+        CVTMI_TRY(opq_range_count_leased(h, *lease.s, q, nq, rotate, nprobe, radius, cap > 0, lims, c, st));
+        if (cap == 0) return CVTMI_OK;   // a count-only call
+        return opq_range_fill_leased(h, c, nq, nprobe, radius, lims, cap, dist, ids, video, st);
+    }
+}
+
+// host pointers: the queries go up and lims comes back through the leased set's staging buffers -- the one wait the call needs to
+// know whether the result fits; then the three arrays, sized by lims[nq]
+int cvtmi_opq_range_search_ivf(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, float radius, int64_t cap, int64_t *lims,
+                               float *dist, int64_t *ids, int32_t *video)
+{
+    CVTMI_TRY(opq_range_check(h, q, nq, &nprobe, radius, cap, lims, dist, ids));
+    CVTMI_TRY(use_device(h->device));
+    lims[0] = 0;
+    if (nq == 0) return CVTMI_OK;
+    for (int attempt = 0;; ++attempt) {
+        CVTMI_TRY(opq_ivf_prepare(h, nullptr));
+        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
+        OpqLease lease;
+        CVTMI_TRY(lease.open(h, nullptr, true));
+        OpqScratch &S = *lease.s;
+        hipStream_t st = lease.st;
+        const size_t qb = (size_t)nq * h->m.D * sizeof(float);
+        CVTMI_TRY(S.io_q.reserve(qb));
+        CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
+        OpqRangeCall c;
+        CVTMI_TRY(opq_range_count_leased(h, S, S.io_q.as<float>(), nq, rotate, nprobe, radius, cap > 0, nullptr, c, st));
+        CVTMI_HIP(hipMemcpyAsync(lims, c.lims_scratch, ((size_t)nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(stream_wait(st));
+        const int64_t total = lims[nq];
+        if (cap == 0 && !dist && !ids && !video) return CVTMI_OK;   // a count-only call: lims is the answer
+        if (total > cap)
+            return fail(CVTMI_ESPACE, "cvtmi_opq_range_search_ivf: %lld hits, room for %lld (lims holds the sizes)", (long long)total, (long long)cap);
+        if (total == 0) return CVTMI_OK;
+        const size_t db = (size_t)total * sizeof(float), ib = (size_t)total * sizeof(int64_t), vb = (size_t)total * sizeof(int32_t);
+        CVTMI_TRY(S.io_d.reserve(db));
+        CVTMI_TRY(S.io_i.reserve(ib));
+        if (video) CVTMI_TRY(S.io_v.reserve(vb));
+        CVTMI_TRY(opq_range_fill_leased(h, c, nq, nprobe, radius, c.lims_scratch, total, S.io_d.as<float>(), S.io_i.as<int64_t>(),
+                                        video ? S.io_v.as<int32_t>() : nullptr, st));
+        CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(hipMemcpyAsync(ids, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
+        if (video) CVTMI_HIP(hipMemcpyAsync(video, S.io_v.p, vb, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(stream_wait(st));
+        return CVTMI_OK;
+    }
+}
+
+int cvtmi_opq_last_range_plan(cvtmi_opq_t h, int64_t out[8])
+{
+    if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_opq_last_range_plan: null");
+    std::lock_guard<std::mutex> g(h->pool.mu);
+    for (int i = 0; i < 8; ++i) out[i] = h->range_last[i];
+    return CVTMI_OK;
+}
+
 int cvtmi_opq_set_param(cvtmi_opq_t h, const char *name, int64_t value)
 {
     if (!h || !name) return fail(CVTMI_EINVAL, "cvtmi_opq_set_param: null");

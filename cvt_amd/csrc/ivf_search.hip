@@ -24,14 +24,13 @@
 #include <algorithm>
 
 #include "block_topk.h"
+#include "ivf_table.h"
 #include "kernels.h"
 
 namespace cvtmi {
 
 constexpr int IVF_CAP = 512, IVF_TRIG = 384;   // k <= 128; larger k: kBigCap / kBigTrig, as the generic exact scan
 constexpr unsigned long long IVF_NONE = ~0ull; // an empty slot of a partial list (no entry has key KEY_MAX)
-
-typedef uint32_t ivf_u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t ivf_key(float s)
 {
@@ -53,35 +52,6 @@ __device__ __forceinline__ void ivf_offer(TopKShared<1, CAP> &tk, int k, int til
         if (pend && key <= tk.thr_x[0] && !topk_push<1, CAP, TRIG>(tk, 0, key, pay, dummy)) return 1u;
         return 0u;
     });
-}
-
-// score of one row from its 16 code bytes (M = 16), m ascending
-__device__ __forceinline__ float ivf_score16(const float *lut, const ivf_u32x4 v)
-{
-    const uint32_t w[4] = { v.x, v.y, v.z, v.w };
-    float s = 0.0f;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) s = __fadd_rn(s, lut[m * 256 + ((w[m >> 2] >> (8 * (m & 3))) & 0xffu)]);
-    return s;
-}
-
-// any other M: the row's M bytes in one load where M is 8 or 4 (rows of the list-ordered copy are M-byte aligned), byte loads otherwise
-__device__ __forceinline__ float ivf_score_row(const float *lut, const uint8_t *__restrict__ c, int M)
-{
-    float s = 0.0f;
-    if (M == 8) {
-        const uint2 v = *reinterpret_cast<const uint2 *>(c);
-        const uint32_t w[2] = { v.x, v.y };
-#pragma unroll
-        for (int m = 0; m < 8; ++m) s = __fadd_rn(s, lut[m * 256 + ((w[m >> 2] >> (8 * (m & 3))) & 0xffu)]);
-    } else if (M == 4) {
-        const uint32_t w = *reinterpret_cast<const uint32_t *>(c);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) s = __fadd_rn(s, lut[m * 256 + ((w >> (8 * m)) & 0xffu)]);
-    } else {
-        for (int m = 0; m < M; ++m) s = __fadd_rn(s, lut[m * 256 + c[m]]);
-    }
-    return s;
 }
 
 // part == nullptr: the workgroup holds everything of its query (one group, one piece) and writes the result rows itself;
@@ -122,33 +92,7 @@ __global__ __launch_bounds__(kBlock) void ivf_search_kernel(const float *__restr
             v = __builtin_nontemporal_load(reinterpret_cast<const ivf_u32x4 *>(codes) + (b + tid));
             pay = entry[b + tid];
         }
-        for (int d = tid; d < D; d += kBlock) res[d] = __fsub_rn(q_rot[qi * D + d], coarse[(int64_t)l * D + d]);
-        __syncthreads();
-        for (int t = tid; t < M * 256; t += kBlock) {
-            const int m = t >> 8, j = t & 255;
-            float acc = __uint_as_float(0x7f800000u);
-            if (j < K) {
-                const float *c = books + ((int64_t)m * K + j) * step;
-                const float *rr = res + m * step;
-                acc = 0.0f;
-                if ((step & 3) == 0) {  // (16-byte aligned codewords: four dimensions per load, same operation order)
-                    for (int kk = 0; kk < step; kk += 4) {
-                        const float4 cv = *reinterpret_cast<const float4 *>(c + kk);
-                        const float4 rv = *reinterpret_cast<const float4 *>(rr + kk);
-                        const float d0 = __fsub_rn(rv.x, cv.x), d1 = __fsub_rn(rv.y, cv.y), d2 = __fsub_rn(rv.z, cv.z), d3 = __fsub_rn(rv.w, cv.w);
-                        acc = __fadd_rn(acc, __fmul_rn(d0, d0)); acc = __fadd_rn(acc, __fmul_rn(d1, d1));
-                        acc = __fadd_rn(acc, __fmul_rn(d2, d2)); acc = __fadd_rn(acc, __fmul_rn(d3, d3));
-                    }
-                } else {
-                    for (int kk = 0; kk < step; ++kk) {
-                        const float d = __fsub_rn(rr[kk], c[kk]);
-                        acc = __fadd_rn(acc, __fmul_rn(d, d));
-                    }
-                }
-            }
-            lut[t] = acc;
-        }
-        __syncthreads();
+        ivf_build_table(res, lut, q_rot + qi * D, coarse + (int64_t)l * D, books, D, M, K, step, tid);
         for (int64_t base = b; base < e; base += kBlock, ++tile) {
             const int64_t r = base + tid;
             const bool have = r < e;

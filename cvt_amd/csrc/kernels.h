@@ -188,6 +188,29 @@ int launch_ivf_search(const OpqModelDev &m, const float *q_rot, int64_t nq, int 
                       const uint8_t *codes, const uint32_t *entry, int k, int64_t id_base, const IvfPlan &p, void *part, float *out_d,
                       int64_t *out_id, hipStream_t st);
 
+// ---- ivf_range.hip ----  every entry of the probed lists with score < radius (cvtmi_opq_range_search_ivf)
+struct IvfRangePlan {
+    IvfPlan grid;        // one workgroup per part; grid.rule 4 = the spill area had to shrink
+    int64_t spill = 0;   // records a part may leave in its segment of the spill area; parts with more hits are walked again
+};
+// pure host logic; spill = records per part wanted ("ivf_range_spill"; 0 = a count-only call), cap_bytes = room for the spill area
+IvfRangePlan plan_ivf_range(int64_t nq, int nprobe, int64_t longest, int64_t spill, size_t cap_bytes, int cus = 0);
+struct IvfRangeBufs {
+    int32_t *order = nullptr;                     // [nq][nprobe] probed lists by list id
+    uint32_t *part_cnt = nullptr, *part_off = nullptr;   // [nq][parts] hits of a part, and where they start inside the query's
+    unsigned long long *spill = nullptr;          // [nq][parts][plan.spill] (score bits << 32 | position in the list-ordered copy)
+};
+// bytes of scratch the plan needs; with base != null the four areas are laid out in it
+size_t ivf_range_carve(void *base, const IvfRangePlan &p, int64_t nq, int nprobe, IvfRangeBufs *b);
+// order, scan, offsets: lims[nq + 1] (device) is complete when these have run
+int launch_ivf_range_count(const OpqModelDev &m, const float *q_rot, int64_t nq, int nprobe, const int32_t *probe, const int64_t *list_off,
+                           const uint8_t *codes, float radius, const IvfRangePlan &p, const IvfRangeBufs &b, int64_t *lims, hipStream_t st);
+// fill and rescan behind a count with the same arguments; both do nothing unless lims[nq] <= cap (checked on the device);
+// video may be null
+int launch_ivf_range_fill(const OpqModelDev &m, const float *q_rot, int64_t nq, int nprobe, const int64_t *list_off, const uint8_t *codes,
+                          const uint32_t *entry, const int32_t *videos, float radius, int64_t id_base, const IvfRangePlan &p,
+                          const IvfRangeBufs &b, const int64_t *lims, int64_t cap, float *dist, int64_t *ids, int32_t *video, hipStream_t st);
+
 // ---- flat.hip ----
 int flat_plan_splits(int64_t n, int64_t nq, int qtile);
 int flat_qtile(int64_t nq);

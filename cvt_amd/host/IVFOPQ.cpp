@@ -226,6 +226,29 @@ int IVFOPQ::SearchTopKProbe(const float *q, int nq, int nprobe, int k, float *di
     return cvtmi_opq_search_ivf(m_h, q, nq, /*rotate=*/1, nprobe, k, dist, (int64_t *)ids) == CVTMI_OK ? 1 : 0;
 }
 
+int IVFOPQ::RangeSearchProbe(const float *q, int nq, int nprobe, float radius, std::vector<long long> &lims, std::vector<float> &dist,
+                             std::vector<long long> &ids, std::vector<int> *videos)
+{
+    m_err.clear();
+    if (!ensureHandle()) return 0;
+    if (m_hs.size() > 1 || m_comm) {
+        m_err = "RangeSearchProbe: the range search runs on one GPU; not available after SetShard / SetDevices";
+        return 0;
+    }
+    static_assert(sizeof(int) == sizeof(int32_t), "video id width");
+    lims.assign((size_t)std::max(nq, 0) + 1, 0);
+    dist.clear(); ids.clear();
+    if (videos) videos->clear();
+    // sizes first, then the arrays at their exact length (nothing appends in between: the second call cannot come up short)
+    if (cvtmi_opq_range_search_ivf(m_h, q, nq, /*rotate=*/1, nprobe, radius, 0, (int64_t *)lims.data(), NULL, NULL, NULL) != CVTMI_OK) return 0;
+    const long long total = lims.back();
+    if (total == 0) return 1;
+    dist.resize((size_t)total); ids.resize((size_t)total);
+    if (videos) videos->resize((size_t)total);
+    return cvtmi_opq_range_search_ivf(m_h, q, nq, /*rotate=*/1, nprobe, radius, total, (int64_t *)lims.data(), dist.data(), (int64_t *)ids.data(),
+                                      videos ? (int32_t *)videos->data() : NULL) == CVTMI_OK ? 1 : 0;
+}
+
 void IVFOPQ::SetShard(cvtmi_comm_s *comm, long long id_base)
 {
     m_comm = comm; m_idBase = id_base;

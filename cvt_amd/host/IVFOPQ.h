@@ -49,6 +49,11 @@ public:
     // the row-level query of a coarseK > 1 model, whose Query() only scores videos.  q is RAW (un-rotated); rows short of k are
     // padded with (+inf, -1).  1 ok / 0 failure (lastError()); single-GPU only: fails once SetShard / SetDevices is in force.
     int SearchTopKProbe(const float *q, int nq, int nprobe, int k, float *dist, long long *ids);
+    // every entry of the nprobe nearest coarse lists of a query whose ADC distance is < radius (cvtmi_opq_range_search_ivf), in the
+    // order of the list-ordered copy: the hits of query f are [lims[f], lims[f + 1]) of dist / ids / videos (videos may be NULL).
+    // q is RAW (un-rotated).  1 ok / 0 failure (lastError()); single-GPU only, like SearchTopKProbe.
+    int RangeSearchProbe(const float *q, int nq, int nprobe, float radius, std::vector<long long> &lims, std::vector<float> &dist,
+                         std::vector<long long> &ids, std::vector<int> *videos = NULL);
     std::string lastError() const;
     // row-sharded operation (one process per GPU): this object holds the row block that starts at global
     // row id_base; with a communicator set (cvtmi_comm_t, include/cvtmi.h) SearchTopK returns the GLOBAL top k on every

@@ -4,10 +4,13 @@
 // search (retrieval/vlindex/lib/FLANN/mpi/index.h:196-226): every rank indexes a contiguous block of rows, searches it,
 // then ONE all-gather of the per-shard top-k + merge (inside libcvtmi: cvtmi_opq_search_sharded).
 //
-//   opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--nprobe N] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]
+//   opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--nprobe N [--radius R]] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]
 //
 // --nprobe N: the IVF form -- per query the k nearest entries of its N nearest coarse lists (IVFOPQ::SearchTopKProbe), which is how a
 // model with coarseK > 1 is searched row by row; one GPU, one process; same result file.  Without it nothing changes: coarseK == 1 only.
+// --radius R (with --nprobe only): the range form -- per query EVERY entry of its N nearest lists with distance < R
+// (IVFOPQ::RangeSearchProbe), in list order; result.txt then holds two lines per query, "<qid> ids: id ..." and "<qid> dists: d ...",
+// of that query's own length; --k is not used.
 // --rotation: a dense D x D rotation (raw fp32, e.g. opq_train --learn-rotation) instead of the model's permutation (IVFOPQ::LoadRotation).
 // model: LoadModel format with coarseK == 1; feature files: raw fp32 [n][D] (IVFOPQ.cpp:451-457).
 // --gpus N: ONE process drives the N GPUs (IVFOPQ::SetDevices: ncclCommInitAll + grouped all-gathers inside libcvtmi) -- the
@@ -41,6 +44,8 @@ using namespace std;
 
 static string g_rotation;   // --rotation: dense rotation file (IVFOPQ::LoadRotation) applied after every LoadModel
 static int g_nprobe = 0;    // --nprobe: > 0 = search through IVFOPQ::SearchTopKProbe
+static bool g_range = false;   // --radius: every entry under g_radius (IVFOPQ::RangeSearchProbe)
+static float g_radius = 0.0f;
 
 struct Shared {
     pthread_barrier_t bar;
@@ -187,6 +192,26 @@ static int run_single_process(int gpus, const string &model, const string &db, c
         ifstream fin(qf.c_str(), ios::binary);
         fin.read((char *)q.data(), sizeof(float) * q.size());
     }
+    if (g_range) {
+        vector<long long> lims, rids;
+        vector<float> rdist;
+        if (index.RangeSearchProbe(q.data(), (int)nq, g_nprobe, g_radius, lims, rdist, rids) != 1) {
+            fprintf(stderr, "search failed: %s\n", index.lastError().c_str());
+            return 1;
+        }
+        ofstream fout(out.c_str());
+        char num[64];
+        for (long long i = 0; i < nq; ++i) {
+            fout << i << " ids: ";
+            for (long long j = lims[i]; j < lims[i + 1]; ++j) fout << rids[(size_t)j] << " ";
+            fout << "\n" << i << " dists: ";
+            for (long long j = lims[i]; j < lims[i + 1]; ++j) { snprintf(num, sizeof num, "%.9g ", rdist[(size_t)j]); fout << num; }
+            fout << "\n";
+        }
+        cout << "opq_search: " << n << " rows, " << nq << " queries, " << lims.back() << " entries under radius " << g_radius << " in " << g_nprobe
+             << " lists each" << endl;
+        return 0;
+    }
     vector<float> dist((size_t)nq * k);
     vector<long long> ids((size_t)nq * k);
     const int ok = nq <= 0 ? 1
@@ -223,12 +248,13 @@ int main(int argc, char *argv[])
         else if (!strcmp(argv[i], "--transport") && i + 1 < argc) transport = argv[++i];
         else if (!strcmp(argv[i], "--rotation") && i + 1 < argc) g_rotation = argv[++i];
         else if (!strcmp(argv[i], "--nprobe") && i + 1 < argc) { g_nprobe = atoi(argv[++i]); nprobe_given = true; }
+        else if (!strcmp(argv[i], "--radius") && i + 1 < argc) { g_radius = strtof(argv[++i], NULL); g_range = true; }
         else pos.push_back(argv[i]);
     }
     // (--nprobe: one GPU, one process, and any k the library takes)
-    const bool bad_probe = nprobe_given && (g_nprobe < 1 || gpus != 1 || forked || transport != "rccl");
+    const bool bad_probe = (nprobe_given && (g_nprobe < 1 || gpus != 1 || forked || transport != "rccl")) || (g_range && (!nprobe_given || g_radius != g_radius));
     if (pos.size() != 4 || k < 1 || k > (nprobe_given ? CVTMI_K_MAX : 128) || gpus < 1 || (transport != "rccl" && transport != "shm") || bad_probe) {
-        cerr << "usage: opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--nprobe N] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]" << endl;
+        cerr << "usage: opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--nprobe N [--radius R]] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]" << endl;
         return 2;
     }
     const bool use_shm = transport == "shm";

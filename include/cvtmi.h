@@ -56,7 +56,8 @@ typedef enum cvtmi_status {
     CVTMI_EHIP = -3,         /* HIP runtime error / no device */
     CVTMI_ESTATE = -4,       /* handle not in a state that allows the call */
     CVTMI_EUNSUPPORTED = -5, /* shape outside what the kernels are built for */
-    CVTMI_ECOMM = -6         /* RCCL not loadable / a collective failed */
+    CVTMI_ECOMM = -6,        /* RCCL not loadable / a collective failed */
+    CVTMI_ESPACE = -7        /* the result does not fit the caller's arrays; lims holds the sizes (cvtmi_opq_range_search_ivf) */
 } cvtmi_status;
 
 typedef enum cvtmi_metric {
@@ -305,6 +306,40 @@ int cvtmi_opq_search_ivf_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rota
  * out[7] = bytes the handle holds for the insertion-index array (0 until the first IVF search). */
 int cvtmi_opq_ivf_plan(int64_t nq, int nprobe, int k, int64_t longest_list, int cus, int64_t out[6]);
 int cvtmi_opq_last_ivf_plan(cvtmi_opq_t h, int64_t out[8]);
+
+/* Range search over the probed lists: for every query, EVERY entry of its nprobe nearest coarse lists whose score is under
+ * `radius` -- the threshold test IVFOPQ::Query / QueryThrehold make (their cells start at 1.0 and fold with min(score, cell):
+ * IVFOPQ.cpp:5, :262, :308), reported per entry where cvtmi_opq_query_video reports per video.  Probing, rotation and the score
+ * of an entry are cvtmi_opq_search_ivf's (same clamp of nprobe, same limit of 128, a query holding a NaN probes lists
+ * 0 .. nprobe-1; no clamp of the score).
+ *   Hit      score < radius as an fp32 comparison, strict.  NaN scores never hit; a +inf score (a code byte >= K) never hits, not
+ *            even for radius = +inf, which returns every entry with a finite score.  radius <= 0 is valid and yields no hits; a
+ *            NaN radius fails with CVTMI_EINVAL.
+ *   Order    the hits of a query come in the order of the list-ordered copy (cvtmi_opq_get_entries): list id ascending, insertion
+ *            order inside a list -- whatever the probe order, the grid, the stream or the run.
+ *   Outputs  lims[nq + 1] (int64): lims[0] = 0, lims[f + 1] - lims[f] = hits of query f.  For hit i of the batch dist[i] = its
+ *            score, ids[i] = id_base + insertion index (the ids cvtmi_opq_search / cvtmi_opq_search_ivf report), and, where video is
+ *            not NULL, video[i] = the video id the entry was added with (its insertion index where none was given).  Entries whose
+ *            list id is outside [0, coarseK) never appear.  A coarseK == 1 model is one list holding everything.
+ *   Capacity cap = hits the caller's arrays hold.  lims is always written in full and exactly; dist / ids / video are written only
+ *            if lims[nq] <= cap and are left untouched otherwise.  cap == 0 with NULL dist / ids / video is the count-only call.
+ * Host entry: CVTMI_OK after writing the results (a count-only call: after writing lims), or CVTMI_ESPACE with lims valid and the
+ * arrays untouched.  Device entry: enqueues on `stream` and never waits for the device; the fill is predicated ON the device on
+ * lims[nq] <= cap, the call returns CVTMI_OK and the caller reads lims[nq] after synchronising.
+ * Checked before any device work: NULL h / q / lims, nq < 0, nprobe < 1, cap < 0, NULL dist or ids with cap > 0 -> CVTMI_EINVAL;
+ * K > 256, M > 16 or >= 2^32 entries -> CVTMI_EUNSUPPORTED.  nq == 0 writes lims[0] = 0 and nothing else.
+ * Concurrency, the list-ordered copy and its insertion indices are as for cvtmi_opq_search_ivf.
+ * cvtmi_set_tuning("ivf_range_spill", C) (default 4096; no effect on results): hits a workgroup may park in the leased scratch set
+ * while the sizes are not known yet; a workgroup that meets more walks its rows a second time once they are.  0 = every
+ * workgroup with a hit does, a huge value = none (the area is bounded by "ivf_part_cap_mb": C shrinks to fit). */
+int cvtmi_opq_range_search_ivf(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, float radius,
+                               int64_t cap, int64_t *lims, float *dist, int64_t *ids, int32_t *video);
+int cvtmi_opq_range_search_ivf_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, float radius,
+                                   int64_t cap, int64_t *lims, float *dist, int64_t *ids, int32_t *video, void *stream);
+/* The grid of the handle's last range search: out = { rule, probe slots per workgroup G, groups per query, pieces per list, rows per
+ * piece, parts (workgroups) per query, spill records per part, spill bytes }.  Rules 1-3 as cvtmi_opq_ivf_plan, except that lists are
+ * cut into pieces only where G == 1; rule 4 = the spill records per part were cut down to fit "ivf_part_cap_mb". */
+int cvtmi_opq_last_range_plan(cvtmi_opq_t h, int64_t out[8]);
 
 /* Tuning / measurement hooks (no effect on results).
  *   "splits"   row splits per query group of the scan (0 = automatic)
