@@ -804,6 +804,13 @@ def set_tuning(name, value):
     _check(lib().cvtmi_set_tuning(name.encode(), C.c_int64(int(value))))
 
 
+def get_tuning(name):
+    """the value a cvtmi_set_tuning key holds now (cvtmi_get_tuning): its default, or the last accepted value, normalised"""
+    v = C.c_int64(0)
+    _check(lib().cvtmi_get_tuning(name.encode(), C.byref(v)))
+    return v.value
+
+
 def kmeans(x, k, niter=0, seed=1):
     """cvtmi_kmeans: (centroids [k][d], assign [n], iterations)."""
     n, d = x.shape

@@ -1213,11 +1213,7 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16a_kernel(const ScanArg
     }
 }
 
-static int g_scan_seed = 1;
-void set_scan_seed(int v) { g_scan_seed = v != 0; }
-static std::atomic<int> g_scan_tail_splits{0};   // cvtmi_set_tuning("scan_tail_splits"): see plan_scan
-void set_scan_tail_splits(int v) { g_scan_tail_splits = v; }
-int scan_seed_enabled() { return g_scan_seed; }
+int scan_seed_enabled() { return tune_scan_seed.geti(); }
 
 // Row ids travel as 32-bit payloads: one launch covers at most 2^32-1 rows.
 static int cu_count()
@@ -1309,7 +1305,7 @@ ScanPlan plan_scan(const OpqModelDev &m, int64_t n_rows, int64_t nq, int k, int 
         // cvtmi_set_tuning("scan_tail_splits"): 0 = this rule, -1 = never, S > 0 = S splits whenever there is a remainder.
         const int64_t full = groups * best / slots;  // whole rounds of region A
         const int64_t rem = groups * best % slots;
-        const int tail_req = g_scan_tail_splits.load();
+        const int tail_req = tune_scan_tail_splits.geti();
         if (p.variant >= 3 && full >= 1 && rem != 0 && best == 1 && tail_req >= 0) {
             int64_t sb = 0;
             if (tail_req > 0) sb = tail_req;
@@ -1440,7 +1436,7 @@ int launch_adc_scan(const OpqModelDev &m, const uint8_t *codes, int64_t n_rows, 
     a.rows_per_split = rps;
     a.groups_a = a.groups; a.splits_b = 0; a.stride = plan.splits; a.rows_per_split_b = rps;
     a.part_d = part_d; a.part_id = part_id; a.out_d = nullptr; a.out_id = nullptr; a.lut_g = lut_scratch; a.codes_rot = codes_rot;
-    a.gthr = nullptr; a.lazy = lazy; a.seed = g_scan_seed; a.only = only;
+    a.gthr = nullptr; a.lazy = lazy; a.seed = tune_scan_seed.geti(); a.only = only;
     if (plan.variant >= 3 && m.M == 16 && plan.qtile == 8) {
         if (!lut_scratch) return fail(CVTMI_EINVAL, "adc_scan16q: table scratch missing");
         if (plan.real_M > 0) {   // M < 16 through these kernels: the model's own tables, all-zero ones behind them (codes = the padded rows)

@@ -1129,8 +1129,6 @@ __global__ __launch_bounds__(1024, 8) void scan16s_select_kernel(const ScanSArgs
     }
 }
 
-static int g_scans_dbg = 0;
-void set_scans_dbg(int v) { g_scans_dbg = v; }
 constexpr int SS_GMAX = 1024;   // collect workgroups at most (the selection kernel's prefix over them)
 constexpr int SS_GROUPS = 16;   // query groups the small-batch path takes (128 queries; the dispatch stops earlier, where the persistent grid catches up)
 static int scans_collect_max() { const int g = scanh_slots() / 2; return g < SS_GMAX ? g : SS_GMAX; }   // collect workgroups per group: one per CU
@@ -1168,7 +1166,7 @@ int launch_adc_scan_small(const OpqModelDev &m, const uint8_t *codes, const uint
     char *sc = reinterpret_cast<char *>(scratch) + ((size_t)SS_GROUPS * SS_WORDS * 4 + 63) / 64 * 64;
     a.wcnt = reinterpret_cast<uint32_t *>(sc);
     a.gcand = reinterpret_cast<unsigned long long *>(sc + (size_t)SS_GROUPS * scans_collect_max() * SQ_QT * 4);
-    a.out_d = dist; a.out_id = ids; a.dbg = g_scans_dbg;
+    a.out_d = dist; a.out_id = ids; a.dbg = tune_scans_dbg.geti();   // timing experiments, results wrong when non-zero
     const unsigned g = (unsigned)((n_rows + a.rows_per_wg - 1) / a.rows_per_wg);
     a.G = (int)g;
     // the histogram pass: few workgroups (every bin they share costs a global atomic each: 256 of them on ~240 hot bins took 70 us),
@@ -1579,17 +1577,7 @@ int launch_adc_scan_bigk(const OpqModelDev &m, const uint8_t *codes, const uint8
 // ---------------------------------------------------------------------------------------------------------------------
 // host side: the item table
 // ---------------------------------------------------------------------------------------------------------------------
-static int g_scanh_share_hist = 1;   // cvtmi_set_tuning("scanh_share_hist"): the segments of a query count their candidates in one histogram (bounds from the union)
-void set_scanh_share_hist(int v) { g_scanh_share_hist = v != 0; }
 size_t scanh_gthr_bytes(int64_t nq) { return ((size_t)(nq + 3) / 4 * 4 + (size_t)nq * SH_BINS) * sizeof(uint32_t); }
-static double g_scanh_fix = 160000.0;   // cvtmi_set_tuning("scanh_fix"): what an item of a group kept whole costs besides its rows, in row-equivalents (planner)
-void set_scanh_fix(double v) { g_scanh_fix = v > 0 ? v : 160000.0; }
-static int g_scanh_balance = 0;       // 0 = choose, 1 = equal shares of the flat (group x row) space, 2 = (group, split) blocks
-static int64_t g_scanh_min_rows = 16384;  // smallest share of a workgroup in the balanced plan
-static int g_scanh_tail = 0;              // (group, split) blocks: the groups of the last, partly filled round may be cut finer (measured: no gain, off)
-void set_scanh_tail(int v) { g_scanh_tail = v != 0; }
-void set_scanh_balance(int v) { g_scanh_balance = v; }
-void set_scanh_min_rows(int64_t v) { g_scanh_min_rows = v < 2048 ? 2048 : v; }
 
 // Workgroup slots of the device: a constant of the process once read (every grid and scratch size of a search derives from this ONE
 // value; cvtmi_opq_scan_plan plans for another CU count through scanh_plan's own parameter, never through shared state).
@@ -1615,8 +1603,11 @@ void scanh_plan(int64_t n_rows, int64_t nq, int splits, ScanHPlan &p, int cus)
     p.multi.clear();
     p.grid = 0; p.rounds = 0; p.stride = 1;
     if (groups <= 0 || n_rows <= 0) return;
+    // the planner settings of this plan (cvtmi_set_tuning; a set bumps g_scanh_key, so cached tables are rebuilt)
+    const double fix = (double)tune_scanh_fix.get();   // "scanh_fix": what an item of a group kept whole costs besides its rows, in row-equivalents
+    const bool tail = tune_scanh_tail.geti() != 0;     // "scanh_tail": (group, split) blocks: the groups of the last, partly filled round may be cut finer (measured: no gain, off)
     const bool resident = n_rows * 16 <= (96LL << 20);  // the pre-rotated rows stay in the Infinity Cache (and mostly in L2)
-    const bool balanced = splits <= 0 && n_rows <= MAX_SEG && g_scanh_balance == 1;   // (equal shares: only on request since the segments share their histograms -- row splits measure better, tools/sweep_scan_h.py)
+    const bool balanced = splits <= 0 && n_rows <= MAX_SEG && tune_scanh_balance.geti() == 1;   // (equal shares: only on request since the segments share their histograms -- row splits measure better, tools/sweep_scan_h.py)
     (void)resident;
     // (planner's own choice: equal shares when S = 1 would fill the slots between half and whole -- 1 M rows x 2500 queries: 1.02-1.07 ms
     //  against 1.24 for whole groups and 1.18 for adc_scan16q; with more groups than slots the shares cost an item more per workgroup
@@ -1625,7 +1616,7 @@ void scanh_plan(int64_t n_rows, int64_t nq, int splits, ScanHPlan &p, int cus)
     std::vector<Seg> segs;
     if (balanced) {
         const int64_t tg = (n_rows + TILE - 1) / TILE, total = groups * tg;
-        const int64_t min_tiles = std::max<int64_t>(1, g_scanh_min_rows / TILE);
+        const int64_t min_tiles = std::max<int64_t>(1, tune_scanh_min_rows.get() / TILE);   // "scanh_min_rows": smallest share of a workgroup in the balanced plan
         const int64_t P = std::max<int64_t>(1, std::min<int64_t>(slots, total / min_tiles));
         const auto bound = [&](int64_t w) {  // share boundary of workgroup w, in tiles; never closer than MINT tiles to a group boundary
             int64_t b = (int64_t)(((__int128)w * total) / P);
@@ -1668,7 +1659,7 @@ void scanh_plan(int64_t n_rows, int64_t nq, int splits, ScanHPlan &p, int cus)
             // measured best everywhere but at nq = 2500, where it is 2 % off).  Round 3's model -- rounds x (0.17 M + rows) with a discount
             // for a half-empty last round -- kept groups whole where two or four splits measure 15-20 % faster (nq = 1500, 2500, 3000).
             const auto makespan = [&](int64_t cand) {
-                const double W = g_scanh_fix * (0.5 + 0.5 / (double)cand) + (double)n_rows / (double)cand;
+                const double W = fix * (0.5 + 0.5 / (double)cand) + (double)n_rows / (double)cand;
                 const int64_t items = groups * cand, P = std::min<int64_t>(slots, items), cus = std::max<int64_t>(1, slots / 2);
                 const auto cnt = [&](int64_t w) -> int64_t { return w < P ? items / P + (w < items % P ? 1 : 0) : 0; };
                 double T = 0.0;
@@ -1712,9 +1703,8 @@ void scanh_plan(int64_t n_rows, int64_t nq, int splits, ScanHPlan &p, int cus)
         // tail at half its look-up rate.  (adc_scan16q's planner has the same option and rarely takes it: there a split costs 0.38 M
         // row-equivalents.)
         int64_t ga = groups, Sb = S;
-        if (splits <= 0 && S == 1 && groups > slots && groups % slots != 0 && g_scanh_tail) {
+        if (splits <= 0 && S == 1 && groups > slots && groups % slots != 0 && tail) {
             const int64_t rem = groups % slots;
-            const double fix = g_scanh_fix;
             double best = 1e300;
             for (int64_t cand = 1; cand <= 32 && n_rows / cand >= 16384; ++cand) {
                 const int64_t blocks = rem * cand;
@@ -1784,7 +1774,8 @@ int launch_adc_scan_h(const OpqModelDev &m, const uint8_t *codes, const uint8_t 
                        lut_g, reinterpret_cast<uint4 *>(qlut), reinterpret_cast<QuantParams *>(qp_g), lazy);
     CVTMI_HIP(hipGetLastError());
     if (gthr && plan.stride > 1) CVTMI_HIP(hipMemsetAsync(gthr, 0xff, (size_t)nq * sizeof(uint32_t), st));
-    uint32_t *ghist = (gthr && plan.stride > 1 && g_scanh_share_hist) ? gthr + (nq + 3) / 4 * 4 : nullptr;
+    // cvtmi_set_tuning("scanh_share_hist"): the segments of a query count their candidates in one histogram (bounds from the union)
+    uint32_t *ghist = (gthr && plan.stride > 1 && tune_scanh_share_hist.geti()) ? gthr + (nq + 3) / 4 * 4 : nullptr;
     if (ghist) CVTMI_HIP(hipMemsetAsync(ghist, 0, (size_t)nq * SH_BINS * sizeof(uint32_t), st));
     ScanHArgs a;
     a.ghist = ghist;

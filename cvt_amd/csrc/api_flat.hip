@@ -168,7 +168,7 @@ static int flat_search_rows(cvtmi_flat_t h, FlatScratch &S, int64_t n_rows, cons
 {
     // uint8: anything the filter pipeline did not take goes through the streaming matrix-core kernel, 128 queries per pass (its cost hardly
     // depends on k: 10 M x 512-d, k = 128: nq = 1000 40.6 -> 10 ms, nq = 4096 117 -> 40 ms against the row-tile kernels)
-    if (h->metric == CVTMI_METRIC_L2U8 && g_flat_variant != 1 && h->norms.p && nq >= 1 && flat_u8_mstream_applies(h->D, n_rows, std::min<int64_t>(nq, 128), k) &&
+    if (h->metric == CVTMI_METRIC_L2U8 && tune_flat_variant.geti() != 1 && h->norms.p && nq >= 1 && flat_u8_mstream_applies(h->D, n_rows, std::min<int64_t>(nq, 128), k) &&
         ((uintptr_t)q & 15) == 0 && (nq + 127) / 128 <= max_stream_passes && !only_if) {   // (a predicated run: the row-per-lane kernels, which take one)
         const int64_t passes = (nq + 127) / 128, per = (nq + passes - 1) / passes;   // balanced: 129 queries = 65 + 64
         const int NS = flat_u8_stream_slices();
@@ -227,7 +227,7 @@ static int flat_search_rows(cvtmi_flat_t h, FlatScratch &S, int64_t n_rows, cons
 // (h->f_last_redo, cvtmi_flat_last_redo).  Off by default: the count is copied back and waited for
 static int flat_count_redo(cvtmi_flat_t h, FlatScratch &S, const uint32_t *flags, int64_t nq, hipStream_t st)
 {
-    if (!g_flat_count_redo.load()) return CVTMI_OK;
+    if (!tune_flat_count_redo.geti()) return CVTMI_OK;
     CVTMI_TRY(S.redo_count.reserve(sizeof(uint32_t)));
     CVTMI_TRY(launch_count_nonzero(flags, nq, S.redo_count.as<uint32_t>(), st));
     uint32_t c = 0;
@@ -388,7 +388,7 @@ static int flat_search_filtered_u8(cvtmi_flat_t h, FlatScratch &S, const uint8_t
     // row-tile kernels' exact search of it (1.0-2.1 ms whatever the batch: every query block warms its thresholds up from scratch): up to
     // ten passes.  10 M x 512-d, k = 10 (tools/sweep_u8_sample.py, round 5): nq = 256 2.6 -> 1.6 ms, 384 / 512 3.9 -> 3.0, 640 / 768
     // 5.2 -> 4.5, 1000 6.3 -> 5.9-6.0, 1280 7.6 -> 7.4; equal at 1536, slower from 2048 on (16 passes 11.4 against 11.15 ms).
-    CVTMI_TRY(flat_search_rows(h, S, ns, q, nq, k, S.f_sd.as<float>(), S.f_si.as<int64_t>(), st, g_flat_u8_sample_passes.load()));
+    CVTMI_TRY(flat_search_rows(h, S, ns, q, nq, k, S.f_sd.as<float>(), S.f_si.as<int64_t>(), st, tune_flat_u8_sample_passes.geti()));
     CVTMI_TRY(stage(ns, n, S.f_sd.as<float>(), S.f_si.as<int64_t>(), dist, rows));
     h->f_last_worst = (long long)worst;
     if (worst > (uint32_t)cap) return CVTMI_OK;
@@ -423,21 +423,20 @@ struct FlatRoute { bool stream, tfilter, filt_f32, filt_u8, big_u8; };
 // another thread calls cvtmi_set_tuning between the two
 struct FlatTuning {
     int variant, f32_stream;
-    static FlatTuning now() { return { g_flat_variant.load(), g_flat_f32_stream.load() }; }
+    static FlatTuning now() { return { tune_flat_variant.geti(), tune_flat_f32_stream.geti() }; }
 };
 static FlatRoute flat_route(const cvtmi_flat_s *h, const void *q, int64_t nq, int k, const FlatTuning &tun)
 {
-    const int g_flat_variant = tun.variant, g_flat_f32_stream = tun.f32_stream;  // (this call's snapshot shadows the globals)
     FlatRoute r = { false, false, false, false, false };
     const bool aligned = ((uintptr_t)q & 15) == 0;
     // fp32: one stream over the rows (flat_f32_stream.hip).  flat_variant 2 asks for the older sample + filter pipeline, 1 for the exact kernels
-    const bool f32_fast = ((g_flat_variant == 0 && g_flat_f32_stream == 1) || (g_flat_variant != 1 && g_flat_f32_stream == 2)) && aligned &&
+    const bool f32_fast = ((tun.variant == 0 && tun.f32_stream == 1) || (tun.variant != 1 && tun.f32_stream == 2)) && aligned &&
                           h->fs_bias.p && h->fs_stats.p;
     r.stream = f32_fast && flat_f32_stream_applies(h->metric, h->D, h->n, k);
     r.tfilter = f32_fast && flat_f32_tfilter_applies(h->metric, h->D, h->n, nq, k);   // batches as a threshold filter (round 6), widths up to 512-d
-    r.filt_f32 = g_flat_variant != 1 && aligned && nq <= 65535 &&
-                 flat_filter_applies(h->metric, h->D, g_flat_variant == 2 ? std::max<int64_t>(h->n, 131072) : h->n,
-                                     g_flat_variant == 2 ? std::max<int64_t>(nq, 16) : nq, k) && h->n >= 2 * 65536;
+    r.filt_f32 = tun.variant != 1 && aligned && nq <= 65535 &&
+                 flat_filter_applies(h->metric, h->D, tun.variant == 2 ? std::max<int64_t>(h->n, 131072) : h->n,
+                                     tun.variant == 2 ? std::max<int64_t>(nq, 16) : nq, k) && h->n >= 2 * 65536;
     // uint8: large batches go through the filter pipeline with the software-pipelined (LDS-DMA) kernel -- measured at 10 M x 512-d:
     // 4096 queries 27.4 -> 21.0 ms, 512 queries 4.6 -> 3.8 ms; smaller batches are one stream over the raw rows (flat_search_rows).
     // flat_variant 2 forces the pipeline wherever it applies, 1 forbids it.
@@ -448,14 +447,14 @@ static FlatRoute flat_route(const cvtmi_flat_s *h, const void *q, int64_t nq, in
     // queries on, at every width and table size measured (128 / 256 / 512-d, 0.6 .. 10 M rows, k = 10 / 64) -- 10 M x 512-d from 129
     // queries (2.2 -> 1.6 ms), 2 M x 512-d from 129 as well (256 queries: 1.47 ms under the old rule, which took the pipeline with a
     // row-tile sample, 0.49 now), 1 M x 128-d from ~1000; below that the two are within 5-20 % with the passes ahead.
-    const bool u8_auto = g_flat_variant == 0 && flat_u8_gfilter_shape(h->D) && nq >= g_flat_u8_filter_min_nq.load() &&
-                         h->n >= g_flat_u8_filter_min_rows.load() && k <= 64 &&
-                         (double)h->n * (double)h->D * (double)nq >= 1e9 * (double)g_flat_u8_filter_min_work.load();
-    r.filt_u8 = (g_flat_variant == 2 || u8_auto) && h->metric == CVTMI_METRIC_L2U8 && aligned && nq <= 65535 * 256 && h->norms.p &&
+    const bool u8_auto = tun.variant == 0 && flat_u8_gfilter_shape(h->D) && nq >= tune_flat_u8_filter_min_nq.geti() &&
+                         h->n >= tune_flat_u8_filter_min_rows.get() && k <= 64 &&
+                         (double)h->n * (double)h->D * (double)nq >= 1e9 * (double)tune_flat_u8_filter_min_work.get();
+    r.filt_u8 = (tun.variant == 2 || u8_auto) && h->metric == CVTMI_METRIC_L2U8 && aligned && nq <= 65535 * 256 && h->norms.p &&
                 flat_u8_filter_applies(h->D, std::max<int64_t>(h->n, 262144), std::max<int64_t>(nq, 256), k) && h->n >= 2 * 65536;
     // k > 128 (round 6, flat_u8_tfilter.hip): the stream and the pipeline above stop at 128 / 64 neighbours, the exact kernels behind them
     // take one query per workgroup (2 M x 512-d, 1000 queries: k = 128 3.9 ms, k = 129 139 ms)
-    r.big_u8 = (g_flat_variant == 0 || (g_flat_variant == 2 && k > 128)) && h->metric == CVTMI_METRIC_L2U8 && aligned && h->norms.p && flat_u8_tfilter_applies(h->D, h->n, nq, k);
+    r.big_u8 = (tun.variant == 0 || (tun.variant == 2 && k > 128)) && h->metric == CVTMI_METRIC_L2U8 && aligned && h->norms.p && flat_u8_tfilter_applies(h->D, h->n, nq, k);
     return r;
 }
 
@@ -492,13 +491,14 @@ static int flat_prepare(cvtmi_flat_t h, const void *q, int64_t nq, int k, hipStr
             r = flat_route(h, q, nq, k, tun);
             need_fs = (r.stream || r.tfilter) && h->fs_stats_n != h->n;
             // the threshold filter reads the copy, and so do the stream kernels for small batches on tables of its size
-            const bool tf = (r.tfilter || (r.stream && h->D % 16 == 0 && flat_f32_tfilter_nch(h->D) == h->D / 16 && h->n >= flat_f32_tfilter_min_rows())) &&
+            const bool tf = (r.tfilter || (r.stream && h->D % 16 == 0 && flat_f32_tfilter_nch(h->D) == h->D / 16 && h->n >= tune_flat_f32_tfilter_min_rows.get())) &&
                             !h->fs_nonfinite;
             want_nch = tf ? flat_f32_tfilter_nch(h->D) : h->D / 16;
             need_f32 = (h->f_pack_n != h->n || h->f_pack_nch != want_nch) &&
                        (tf ? !need_fs : (r.filt_f32 && !(r.stream && !need_fs && !h->fs_nonfinite)));   // (the stream answers: no copy needed)
             need_u8 = (r.filt_u8 || r.big_u8) && h->f_pack_n != h->n;
-            need_rm = tf && g_flat_f32_rows_copy.load() != 0 && h->D >= g_flat_f32_rows_copy.load() && h->D % 4 == 0 && h->f_rows_n != h->n &&
+            const int rows_copy = tune_flat_f32_rows_copy.geti();
+            need_rm = tf && rows_copy != 0 && h->D >= rows_copy && h->D % 4 == 0 && h->f_rows_n != h->n &&
                       !h->f_rows_failed;
             if (!need_fs && !need_f32 && !need_u8 && !need_rm) return CVTMI_OK;
         }
@@ -574,7 +574,7 @@ static int flat_search_leased(cvtmi_flat_t h, FlatScratch &S, const void *q, int
     bool done = false;
     long long worst0 = 0;
     h->f_last_worst = worst0;
-    h->f_last_redo = g_flat_count_redo.load() ? 0 : -1;   // (the routes with redo flags overwrite it)
+    h->f_last_redo = tune_flat_count_redo.geti() ? 0 : -1;   // (the routes with redo flags overwrite it)
     int how = 0;
     const FlatRoute r = flat_route(h, q, nq, k, tun);
     if (r.stream || r.tfilter) {
@@ -716,7 +716,7 @@ int cvtmi_flat_search(cvtmi_flat_t h, const void *q, int64_t nq, int k, void *di
     // are a tenth of such a call.  The queries go up from a page-locked staging area (a truly asynchronous copy), and the last kernel of
     // the search writes the lists straight into that area (device-visible host memory) -- no copy engine on the way back.
     const size_t qn = (size_t)nq * h->row_bytes, dn = (size_t)nq * k * 4, in = (size_t)nq * k * 8;
-    if (g_flat_small_zero_copy.load() && qn <= ((size_t)64 << 10) && dn + in <= ((size_t)768 << 10)) {
+    if (tune_flat_small_zero_copy.geti() && qn <= ((size_t)64 << 10) && dn + in <= ((size_t)768 << 10)) {
         const size_t qoff = (qn + 255) & ~(size_t)255, doff = (dn + 255) & ~(size_t)255;
         CVTMI_TRY(S.io_pin.reserve(std::max(qoff + doff + in, (size_t)1 << 20)));
         void *pin_dev = nullptr;

@@ -1,6 +1,6 @@
 // api_internal.h -- what the files of the C-ABI glue share (api.hip: library level, api_opq.hip, api_flat.hip, api_models.hip,
 // api_hnsw.hip): the scratch pool of a handle with its lease and its mutation ordering, the handle structs, and the few helpers
-// and tuning values that cross a file.  Everything a single file uses stays static in that file.
+// that cross a file.  Everything a single file uses stays static in that file.
 #pragma once
 #include <functional>
 #include <new>
@@ -266,12 +266,7 @@ using HnswLease = Lease<HnswScratch>;
 namespace cvtmi {
 
 extern thread_local std::string g_err;   // text of cvtmi_last_error (api.hip)
-// cvtmi_set_tuning values (defined and described in api.hip), by the file that reads them
-extern std::atomic<int> g_ivf_part_cap_mb, g_small_zero_copy, g_scan_bigk, g_scan_packed, g_scan_pad, g_host_zero_copy, g_host_chunks, g_scanh_key;   // api_opq.hip
-extern std::atomic<int64_t> g_scans_max_work, g_ivf_range_spill;
-extern std::atomic<int> g_flat_f32_rows_copy, g_flat_u8_filter_min_nq, g_flat_u8_sample_passes, g_flat_small_zero_copy, g_flat_variant, g_flat_f32_stream, g_flat_count_redo;   // api_flat.hip
-extern std::atomic<int64_t> g_flat_u8_filter_min_rows, g_flat_u8_filter_min_work;
-extern std::atomic<int> g_sq8_host_small, g_hnsw_slots_cap;   // api_models.hip, api_hnsw.hip
+extern std::atomic<int> g_scanh_key;   // bumped by a REPLAN tuning key (api.hip); api_opq.hip compares it
 
 int use_device(int dev);
 int opq_rotate_impl(cvtmi_opq_t h, const float *x, int64_t n, float *y, hipStream_t st);   // api_opq.hip

@@ -104,7 +104,7 @@ int cvtmi_sq8_encode(const float *vmin, const float *vdiff, int d, float *x, int
     {
         const size_t mb = up256((size_t)d * sizeof(float)), xb = up256((size_t)n * d * sizeof(float)), cb = up256((size_t)n * d);
         const size_t nb = up256((size_t)n * sizeof(float));   // row norms of the widths that take two passes
-        if (g_sq8_host_small.load() && 2 * mb + xb + cb + nb <= SQ8_HOST_SMALL) {
+        if (tune_sq8_host_small.geti() && 2 * mb + xb + cb + nb <= SQ8_HOST_SMALL) {
             Sq8HostLease lease;
             CVTMI_TRY(lease.open());
             void *pd_ = nullptr;
@@ -168,7 +168,7 @@ static int sq8_decode_host_mode(const float *vmin, const float *vdiff, int d, co
     if (n == 0) return CVTMI_OK;
     {   // small calls: out of the page-locked scratch area (see Sq8HostScratch)
         const size_t mb = up256((size_t)d * sizeof(float)), xb = up256((size_t)n * d * sizeof(float)), cb = up256((size_t)n * d);
-        if (g_sq8_host_small.load() && 2 * mb + xb + cb <= SQ8_HOST_SMALL) {
+        if (tune_sq8_host_small.geti() && 2 * mb + xb + cb <= SQ8_HOST_SMALL) {
             Sq8HostLease lease;
             CVTMI_TRY(lease.open());
             void *pd_ = nullptr;

@@ -454,7 +454,7 @@ static int opq_search_h(cvtmi_opq_t h, OpqScratch &S, const float *q_rot, int64_
 // re-sum still adds the model's M entries in the reference's order first.  Costs 16 + 16 bytes per row of derived copies.
 static bool opq_pads(const cvtmi_opq_s *h)
 {
-    return g_scan_pad.load() && h->m.M >= 1 && h->m.M < 16 && h->m.K >= 1 && h->m.K <= 256 && h->m.D <= 256;
+    return tune_scan_pad_m.geti() && h->m.M >= 1 && h->m.M < 16 && h->m.K >= 1 && h->m.K <= 256 && h->m.D <= 256;
 }
 static ScanPlan opq_plan(cvtmi_opq_t h, int64_t nq, int k)
 {
@@ -465,7 +465,7 @@ static ScanPlan opq_plan(cvtmi_opq_t h, int64_t nq, int k)
         // (planned as at least four queries: below that plan_scan prefers the fp32-table kernels, which build their tables from the codebooks)
         // M = 8 / 4 natively (adc_scan16p: 16 / M rows per 16-byte load; needs the pre-rotated copy): planned in units of loads -- a load
         // costs what an M = 16 row costs, so the split decision sees n / RPL "rows"
-        const bool packed = g_scan_packed.load() && (h->m.M == 8 || h->m.M == 4) && h->p_prerot && h->p_variant != 4 && h->p_variant != 5;
+        const bool packed = tune_scan_packed_m.geti() && (h->m.M == 8 || h->m.M == 4) && h->p_prerot && h->p_variant != 4 && h->p_variant != 5;
         const int64_t n_plan = packed ? (h->n * h->m.M + 15) / 16 : h->n;
         ScanPlan pp = plan_scan(m16, n_plan, std::max<int64_t>(nq, 4), k, 0, h->p_splits, h->p_variant == 4 || h->p_variant == 5 ? h->p_variant : 3);
         if (pp.variant >= 3 && pp.variant <= 5) {
@@ -497,7 +497,7 @@ static int opq_prepare(cvtmi_opq_t h, int64_t nq, int k, hipStream_t st)
         packed = plan.packed;
         padded = plan.real_M > 0 && !packed;
         const bool want_rot = h->p_prerot && ((h->m.M == 16 && (plan.variant >= 3 || scans_applies(h->m, h->n, nq, k) ||
-                                                                (g_scan_bigk.load() && scank_applies(h->m, h->n, nq, k)))) || padded || packed);
+                                                                (tune_scan_bigk.geti() && scank_applies(h->m, h->n, nq, k)))) || padded || packed);
         if (!padded && !want_rot) return CVTMI_OK;
         const bool pad_ok = !padded || (h->pad_n == h->n && h->codes16.cap >= (size_t)h->n * 16);
         const bool rot_ok = !want_rot || (h->rot_n == h->n && h->rot_kind == (packed ? 1 : 0) &&
@@ -557,7 +557,7 @@ static int opq_prepare(cvtmi_opq_t h, int64_t nq, int k, hipStream_t st)
 static bool scans_chosen(const cvtmi_opq_s *h, int64_t nq, int k)
 {
     return h->p_variant == 7 && h->p_splits == 0 && h->p_qtile == 0 && h->p_small && scans_applies(h->m, h->n, nq, k) &&
-           h->n * ((nq + 7) / 8) <= g_scans_max_work.load();
+           h->n * ((nq + 7) / 8) <= tune_scans_max_work.get();
 }
 
 // the dispatch a search would take, for inspection and for the CPU tests that pin the rules (include/cvtmi.h)
@@ -613,7 +613,7 @@ static int opq_search_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64
         CVTMI_TRY(opq_rotate_impl(h, q, nq, S.s_qrot.as<float>(), st));
         q_rot = S.s_qrot.as<float>();
     }
-    if (g_scan_bigk.load() && h->p_variant == 7 && h->p_qtile == 0 && h->p_splits == 0 && scank_applies(h->m, h->n, nq, k)) {
+    if (tune_scan_bigk.geti() && h->p_variant == 7 && h->p_qtile == 0 && h->p_splits == 0 && scank_applies(h->m, h->n, nq, k)) {
         // k = 129 .. 2048 (round 6): sampled histogram bound, candidate lists, one selection workgroup per query (adc_scan_h.hip); the
         // queries it could not answer (a list that overflowed, a crowded band, tables that bound nothing) are flagged and go through the
         // exact kernel behind it.  Batches whose candidate lists would pass 1 GB go in pieces.
@@ -736,7 +736,7 @@ int cvtmi_opq_search(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int 
     const bool q_pinned = host_pinned(q), out_pinned = host_pinned(dist) && host_pinned(ids);
     float *zd = nullptr;
     int64_t *zi = nullptr;
-    if (out_pinned && g_host_zero_copy.load()) {
+    if (out_pinned && tune_opq_host_zero_copy.geti()) {
         void *pd = nullptr, *pi = nullptr;
         if (hipHostGetDevicePointer(&pd, dist, 0) == hipSuccess && hipHostGetDevicePointer(&pi, ids, 0) == hipSuccess && pd && pi) {
             zd = static_cast<float *>(pd); zi = static_cast<int64_t *>(pi);
@@ -744,7 +744,7 @@ int cvtmi_opq_search(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int 
             (void)hipGetLastError();
         }
     }
-    int64_t per = g_host_chunks.load();
+    int64_t per = tune_opq_host_chunk.geti();
     const int64_t per_default = per > 0 ? per : 4096;
     if (per <= 0 || nq < per + per / 4 || zd) per = nq;
     // (zero-copy results keep the batch whole only while its QUERIES fit the staging guard below: past that -- more than 131 072
@@ -809,7 +809,7 @@ int cvtmi_opq_search(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int 
     // Small batches (the reference's call pattern: a handful of frames per Query; here whatever takes the small-batch path, up to 128
     // queries): the copies are a third of such a call.  The table kernel reads the queries and the selection kernel writes the results straight from / to the pinned staging area (page-locked
     // host memory is device-visible: one PCIe read of the queries, posted writes of the lists) -- no copy engine in the chain.
-    if (chunks == 1 && g_small_zero_copy.load() && h->n > 0 && scans_chosen(h, nq, k)) {
+    if (chunks == 1 && tune_opq_small_zero_copy.geti() && h->n > 0 && scans_chosen(h, nq, k)) {
         OpqScratch &S = *lease[0].s;
         hipStream_t st = lease[0].st;
         void *pin_dev = nullptr;
@@ -1042,7 +1042,7 @@ static int opq_search_ivf_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, i
     const size_t probe_bytes = ((size_t)nq * nprobe * sizeof(int32_t) + 15) / 16 * 16;
     CVTMI_TRY(S.s_probe.reserve(probe_bytes + coarse_probe_scratch_bytes(nq, nprobe)));
     CVTMI_TRY(launch_coarse_probe(h->m, q_rot, nq, nprobe, S.s_probe.as<int32_t>(), st, S.s_probe.as<char>() + probe_bytes));
-    const IvfPlan plan = plan_ivf_search(nq, nprobe, k, h->csr_longest, (size_t)g_ivf_part_cap_mb.load() << 20);
+    const IvfPlan plan = plan_ivf_search(nq, nprobe, k, h->csr_longest, (size_t)tune_ivf_part_cap_mb.geti() << 20);
     const size_t pb = ivf_part_bytes(plan, nq, k);
     if (pb) CVTMI_TRY(S.s_ivf.reserve(pb));
     {
@@ -1122,7 +1122,7 @@ int cvtmi_opq_last_ivf_plan(cvtmi_opq_t h, int64_t out[8])
 int cvtmi_opq_ivf_plan(int64_t nq, int nprobe, int k, int64_t longest_list, int cus, int64_t out[6])
 {
     if (!out || nq < 1 || nprobe < 1 || k < 1 || k > CVTMI_K_MAX || longest_list < 0) return fail(CVTMI_EINVAL, "cvtmi_opq_ivf_plan: bad arguments");
-    const IvfPlan p = plan_ivf_search(nq, nprobe, k, longest_list, (size_t)g_ivf_part_cap_mb.load() << 20, cus > 0 ? cus : 256);
+    const IvfPlan p = plan_ivf_search(nq, nprobe, k, longest_list, (size_t)tune_ivf_part_cap_mb.geti() << 20, cus > 0 ? cus : 256);
     const int64_t v[6] = { p.rule, p.G, p.groups, p.pieces, p.rows_per_piece, p.parts() };
     for (int i = 0; i < 6; ++i) out[i] = v[i];
     return CVTMI_OK;
@@ -1150,7 +1150,7 @@ static int opq_range_count_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, 
     const size_t probe_bytes = ((size_t)nq * nprobe * sizeof(int32_t) + 15) / 16 * 16;
     CVTMI_TRY(S.s_probe.reserve(probe_bytes + coarse_probe_scratch_bytes(nq, nprobe)));
     CVTMI_TRY(launch_coarse_probe(h->m, c.q_rot, nq, nprobe, S.s_probe.as<int32_t>(), st, S.s_probe.as<char>() + probe_bytes));
-    c.plan = plan_ivf_range(nq, nprobe, h->csr_longest, spill ? g_ivf_range_spill.load() : 0, (size_t)g_ivf_part_cap_mb.load() << 20);
+    c.plan = plan_ivf_range(nq, nprobe, h->csr_longest, spill ? tune_ivf_range_spill.get() : 0, (size_t)tune_ivf_part_cap_mb.geti() << 20);
     const size_t carved = ivf_range_carve(nullptr, c.plan, nq, nprobe, nullptr);
     CVTMI_TRY(S.s_range.reserve(carved + ((size_t)nq + 1) * sizeof(int64_t)));
     ivf_range_carve(S.s_range.p, c.plan, nq, nprobe, &c.bufs);

@@ -10,7 +10,6 @@
 namespace cvtmi {
 
 // ---- error plumbing: thread-local message + status codes, nothing throws across the C ABI ----
-void set_error(const char *fmt, ...);
 int fail(int code, const char *fmt, ...);
 
 #define CVTMI_HIP(expr)                                                                          \

@@ -1214,9 +1214,6 @@ void flat_u8_rowtile_kernel(const FlatMfmaArgs a)
     }
 }
 
-static int g_flat_u8_opt = 0;
-void set_flat_u8_opt(int v) { g_flat_u8_opt = v; }
-
 // Queries per workgroup of the MFMA paths, 0 = shape not covered (caller falls back to the dot4 kernel).
 // More queries per workgroup = fewer passes over the rows; what bounds it is LDS: two row tiles
 // (32 x (D + 16) bytes each) next to the selection buffers (8 * CAP bytes per query, CAP >= k + 32).
@@ -1274,6 +1271,7 @@ int launch_flat_u8_mfma(int D, const uint8_t *data, const int32_t *norms, int64_
 #undef CVTMI_FM
     } else {
         const size_t lds = (size_t)2 * 32 * (D + 16);
+        const int u8_opt = tune_flat_u8_opt.geti();
 #define CVTMI_RT1(NW, CAP, DMAX, OPT)                                                                                   \
     do {                                                                                                                \
         CVTMI_HIP(hipFuncSetAttribute((const void *)flat_u8_rowtile_kernel<NW, CAP, DMAX, OPT>,                         \
@@ -1282,9 +1280,9 @@ int launch_flat_u8_mfma(int D, const uint8_t *data, const int32_t *norms, int64_
     } while (0)
 #define CVTMI_RT(NW, CAP, DMAX)                                                                                         \
     do {                                                                                                                \
-        if (NW == 8 && DMAX == 512 && g_flat_u8_opt == 0) CVTMI_RT1(NW, CAP, DMAX, 0);                                  \
-        else if (NW == 8 && DMAX == 512 && g_flat_u8_opt == 1) CVTMI_RT1(NW, CAP, DMAX, 1);                             \
-        else if (NW == 8 && DMAX == 512 && g_flat_u8_opt == 2) CVTMI_RT1(NW, CAP, DMAX, 2);                             \
+        if (NW == 8 && DMAX == 512 && u8_opt == 0) CVTMI_RT1(NW, CAP, DMAX, 0);                                         \
+        else if (NW == 8 && DMAX == 512 && u8_opt == 1) CVTMI_RT1(NW, CAP, DMAX, 1);                                    \
+        else if (NW == 8 && DMAX == 512 && u8_opt == 2) CVTMI_RT1(NW, CAP, DMAX, 2);                                    \
         else if (NW == 8 && DMAX == 512) CVTMI_RT1(NW, CAP, DMAX, 3);                                                   \
         else CVTMI_RT1(NW, CAP, DMAX, 0);                                                                               \
     } while (0)

@@ -868,18 +868,15 @@ static int fs_qb_max(int nch)
     while (qb > 1 && qb * (8 * nch + 48) > 368) --qb;
     return qb;
 }
-static std::atomic<int> g_fs_dbgflags{0};     // timing experiments (results wrong when non-zero): cvtmi_set_tuning("flat_f32_dbg")
-void set_flat_f32_dbg(int v) { g_fs_dbgflags = v; }
-int get_flat_f32_dbg() { return g_fs_dbgflags.load(); }
-static std::atomic<int> g_fs_packed{1};  // cvtmi_set_tuning("flat_f32_packed"): 1 = small batches stream the bf16 operand copy when there is one
-void set_flat_f32_packed(int v) { g_fs_packed = v != 0; }
-static std::atomic<int> g_fs_nt{1};      // cvtmi_set_tuning("flat_f32_nt"): 0 = never, 1 = choose, 2 = always
-void set_flat_f32_nt(int v) { g_fs_nt = v; }
+// cvtmi_set_tuning("flat_f32_nt"): 0 = never, 1 = choose, 2 = always
 // non-temporal row loads: measured better wherever the stream kernel is bound by the rows (one query 0.119 -> 0.106 ms,
 // 64 queries 0.147 -> 0.14, the shared ring 1.09 -> 1.07 at 1000), worse at three query blocks per wave (0.155 -> 0.165)
-static bool fs_nt(bool shared, int qb) { return g_fs_nt == 2 || (g_fs_nt == 1 && (shared || qb <= 2)); }
-static std::atomic<int> g_fs_share{0};   // cvtmi_set_tuning("flat_f32_share"): 0 = choose, 1 = the four-wave shared ring (the same)
-void set_flat_f32_share(int v) { g_fs_share = v; }
+static bool fs_nt(bool shared, int qb)
+{
+    const int nt = tune_flat_f32_nt.geti();
+    return nt == 2 || (nt == 1 && (shared || qb <= 2));
+}
+// cvtmi_set_tuning("flat_f32_share"): 0 = choose, 1 = the four-wave shared ring -- the same form, so nothing reads the key any more.
 // The eight- and twelve-wave forms of the shared-ring kernel (round 6, "flat_f32_share" 3 / 2: more queries per pass) are gone.  A width
 // sweep against the exact kernels found ONE query of ~10^5 they answered wrongly (2 M x 64-d rows, L2, 1000 queries in passes of 334 or
 // 500, the row at rank 99 missing) that the four-wave form answers correctly.  At the same pass split the four-wave form computes the
@@ -965,7 +962,7 @@ static int fs_launch_stream(const FsStreamArgs &a, hipStream_t st)
         const size_t lds = FssGeom<NCH, 4>::LDS;
         CVTMI_TRY(fs_set_lds((const void *)flat_f32_mshare_kernel<NCH, QB, 4, 4>, lds, attr_set));
         hipLaunchKernelGGL((flat_f32_mshare_kernel<NCH, QB, 4, 4>), dim3(FSS_STREAMS), dim3(256), lds, st, a.X, a.bias, a.n_tiles, a.q, a.nq, a.G, a.NG,
-                           a.gb, a.wm, a.redo, a.cnt, g_fs_dbgflags | (fs_nt(true, QB) ? 16 : 0));
+                           a.gb, a.wm, a.redo, a.cnt, tune_flat_f32_dbg.geti() | (fs_nt(true, QB) ? 16 : 0));   // "flat_f32_dbg": timing experiments (results wrong when non-zero)
     } else {
         const size_t lds = (size_t)4 * FsGeom<NCH>::WAVE_LDS;
         CVTMI_TRY(fs_set_lds((const void *)flat_f32_mstream_kernel<NCH, QB>, lds, attr_set));
@@ -1008,7 +1005,7 @@ int launch_flat_f32_stream(int metric, int D, const float *X, const float *bias,
     const FsStreamArgs sa = { X, bias, (n + 31) / 32, q, (int)nq, G, NG, gb, wm, redo, cnt };
     const int qb = shared ? (int)((nq + 127) / 128) : (int)((nq + 31) / 32);
     // round 6: up to 32 queries over the bf16 operand copy of the rows when the handle keeps one (half the bytes, one product per term)
-    const bool packed = pack != nullptr && pstats != nullptr && !shared && qb <= 3 && g_fs_packed.load() != 0;
+    const bool packed = pack != nullptr && pstats != nullptr && !shared && qb <= 3 && tune_flat_f32_packed.geti() != 0;   // "flat_f32_packed": 1 = small batches stream the bf16 operand copy when there is one
 #define CVTMI_FS(NCH_) \
     case NCH_: CVTMI_TRY(packed ? fs_launch_packed<NCH_>(qb, sa, pack, st) : shared ? (fs_launch_qb<NCH_, true>(qb, sa, st)) : (fs_launch_qb<NCH_, false>(qb, sa, st))); break;
     switch (D / 16) {

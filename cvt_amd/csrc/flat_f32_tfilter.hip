@@ -810,15 +810,12 @@ __global__ __launch_bounds__(1024) void ft_finish_big_kernel(const float *__rest
 }  // namespace
 
 // ---- host side ----
-static std::atomic<int> g_ft_on{4};        // cvtmi_set_tuning("flat_f32_tfilter"): 0 = the stream kernels for every batch, 1 .. 3 = products, 4 = choose
-static std::atomic<int> g_ft_min_rows{262144};   // "flat_f32_tfilter_min_rows": smallest table that takes the pipeline
 // "flat_f32_tfilter_sample": the sample is about 1 / this of the rows; 0 (default) = 3 .. 32 by the table's bytes and k -- the sample pass costs bytes / div, the
 // candidates k x div: sqrt(1280 x GB of rows / k) within 3 .. 32 (tools/f32_sample_sweep.py, profiles/r06_f32_sample_sweep.txt: 1 M x 128-d k = 10 0.41 -> 0.36 ms per
 // 1000 queries, 4 M x 128-d 1.31 -> 1.04, 524 288 x 512-d 0.82 -> 0.71; k = 100 keeps 5: above 8 its lists run over on tight data)
-static std::atomic<int> g_ft_sample_div{0};
 static int ft_sample_div(int k, int64_t n, int D)
 {
-    const int v = g_ft_sample_div.load();
+    const int v = tune_flat_f32_tfilter_sample.geti();
     if (v) return v;
     const double want = std::sqrt(1280.0 * ((double)n * D * 4e-9) / (double)k);
     return std::max(3, std::min(32, (int)(want + 0.5)));   // (3, not 5, since the sample pass keeps its maxima in registers: 1 M x 128-d, k = 100 0.419 -> 0.403 ms)
@@ -829,23 +826,6 @@ static float ft_fixed_margin(bool ip, int D, int nprod)
     const double e = (double)nprod * D + 1.0 + (ip ? 0.0 : D / 2.0) + D / 4.0 + 10.0 + (nprod == 3 ? 384.0 : (nprod == 2 ? 128.0 : 0.0));
     return (float)std::max(0x1p-13, 2.0 * e * 0x1p-24);
 }
-static std::atomic<int> g_ft_bigk{1};      // "flat_f32_tfilter_bigk": 1 = k = 129 .. 2048 through the pipeline (4096 sample maxima, lists of 32 768, ft_finish_big_kernel), 0 = exact kernels
-static std::atomic<int> g_ft_wide_band{1};   // "flat_f32_tfilter_wide_band": 1 = queries with more than FT_KEEP rows inside the margin band get a second finish (ft_finish_big_kernel), 0 = the exact kernels
-static std::atomic<int> g_ft_retry{0};     // "flat_f32_tfilter_retry": 1 = a second filter pass for the queries whose candidate lists ran over, 0 (default) = the exact kernels at once
-static std::atomic<int> g_ft_one_max{1 << 30}; // "flat_f32_tfilter_one": largest batch that multiplies one product (with the staged bucket pass one product wins at every
-                                           // batch size measured: 1000 queries 0.74 -> 0.64 ms, 4096 2.9 -> 2.5, 10 000 7.0 -> 6.5; two products beyond this many queries)
-static std::atomic<int> g_ft_min_nq{0};    // cvtmi_set_tuning("flat_f32_tfilter_min"): smallest batch that takes the pipeline; 0 = choose (ft_auto_min): 65 - 97 at the widths the
-                                           // stream kernels take (up to 64 queries they stream the operand copy's first terms: 1 M x 128-d, 16 / 64 queries
-                                           // 0.079 / 0.096 ms against 0.112 / 0.125 here, level at 80-96), 16 elsewhere (against the exact kernels)
-void set_flat_f32_tfilter(int v) { g_ft_on = v < 0 ? 0 : (v > 4 ? 4 : v); }
-void set_flat_f32_tfilter_one(int v) { g_ft_one_max = v < 0 ? 0 : v; }
-void set_flat_f32_tfilter_wide_band(int v) { g_ft_wide_band = v != 0; }
-void set_flat_f32_tfilter_retry(int v) { g_ft_retry = v != 0; }
-void set_flat_f32_tfilter_bigk(int v) { g_ft_bigk = v != 0; }
-void set_flat_f32_tfilter_min_rows(int v) { g_ft_min_rows = v < 32768 ? 32768 : v; }
-int64_t flat_f32_tfilter_min_rows() { return g_ft_min_rows.load(); }
-void set_flat_f32_tfilter_sample(int v) { g_ft_sample_div = v < 0 ? 0 : (v > 64 ? 64 : v); }
-void set_flat_f32_tfilter_min(int v) { g_ft_min_nq = v < 0 ? 0 : v; }
 // widths: the K steps (16 dimensions each) of a row tile stay in a wave's registers (RT tiles of 32 rows: RT x K steps x terms x 4 registers
 // <= 128, 256 with one wave per SIMD; 96 / 128 K steps in two halves of 48 / 64).  A kernel exists for 2 / 4 / 6 / 8 / 10 / 12 / 16 / 24 / 32 /
 // 48 / 64 / 96 / 128 K steps; a width in between (any multiple of 4 up to 2048: 100-d, 200-d, 300-d ...) runs on the next one over
@@ -861,6 +841,8 @@ int flat_f32_tfilter_nch(int D)
 bool flat_f32_tfilter_width(int D) { return flat_f32_tfilter_nch(D) != 0; }
 // smallest batch under "flat_f32_tfilter_min" 0: beyond what one pass of the private-ring stream takes over the operand copy where that is
 // ahead (128-d: 96 queries 0.125 against 0.143 ms here; 64-d: 80 queries 0.137 against 0.129), 16 at widths the stream does not take
+// (up to 64 queries the stream kernels read the operand copy's first terms: 1 M x 128-d, 16 / 64 queries 0.079 / 0.096 ms against
+// 0.112 / 0.125 here, level at 80-96)
 static int ft_auto_min(int D, int k)
 {
     // (no stream kernel: the exact kernels are the alternative -- tools/f32_tiny_batches.py, profiles/r06_f32_tiny_batches.txt: one query over 524 288 x 512-d
@@ -893,8 +875,10 @@ static int ft_rt(int nch, int nprod)
 //  1024 3.50 / 3.56, 1536 258 / 4.1 -- three products cost in proportion to the rows, one product's band overflows somewhere past k = 1024: one up to 768
 static int ft_nprod(int D, int64_t nq, int k)
 {
-    const int mode = g_ft_on.load();
-    return ft_products(D, mode == 4 ? (k > 768 ? 3 : (nq <= g_ft_one_max.load() ? 1 : 2)) : mode);
+    const int mode = tune_flat_f32_tfilter.geti();
+    // ("flat_f32_tfilter_one" has no limit by default: with the staged bucket pass one product wins at every batch size measured,
+    //  1000 queries 0.74 -> 0.64 ms, 4096 2.9 -> 2.5, 10 000 7.0 -> 6.5)
+    return ft_products(D, mode == 4 ? (k > 768 ? 3 : (nq <= tune_flat_f32_tfilter_one.geti() ? 1 : 2)) : mode);
 }
 // queries a workgroup holds
 static int ft_qcap(int nch, int nprod)
@@ -952,16 +936,18 @@ static bool ft_sample_fills(int D, int64_t n, int64_t nq, int k)
 }
 bool flat_f32_tfilter_applies(int metric, int D, int64_t n, int64_t nq, int k)
 {
-    return g_ft_on.load() && (metric == CVTMI_METRIC_IP || metric == CVTMI_METRIC_L2F) && flat_f32_tfilter_width(D) &&
+    const int64_t min_rows = tune_flat_f32_tfilter_min_rows.get();
+    const int min_nq = tune_flat_f32_tfilter_min.geti();
+    return tune_flat_f32_tfilter.geti() && (metric == CVTMI_METRIC_IP || metric == CVTMI_METRIC_L2F) && flat_f32_tfilter_width(D) &&
            // (k > 128: nothing else is fast on a small table either -- from 65 536 rows and 48 k, where the sample still fills its slots; measured in
            //  tools/flat_bigk_small_tables.py, profiles/r06_flat_bigk_small_tables.txt: 100 000 x 128-d, 1000 queries, k = 129 2.3 -> 0.58 ms)
            // (k <= 128 at the widths the stream kernels do not take: the exact kernels are all there is under 262 144 rows -- from 65 536 rows on,
            //  rows wider than 512-d with more than 32 neighbours from 129 queries; tools/f32_small_tables.py, profiles/r06_f32_small_tables.txt:
            //  100 000 x 512-d, 1000 queries, k = 10 2.97 -> 0.30 ms)
-           (n >= g_ft_min_rows.load() || (k > 128 && n >= std::max<int64_t>(65536, 48 * (int64_t)k) && (D <= 512 || nq >= 16)) ||
-            (k <= 128 && n >= std::min<int64_t>(65536, g_ft_min_rows.load()) && flat_f32_stream_qmax(D) == 0 && (D <= 512 || k <= 32 || nq >= 129))) && n < 0xffffffe0LL &&
-           k >= 1 && k <= CVTMI_K_MAX && g_ft_bigk.load() + (k <= 128) > 0 &&   // (k > 128: the stream kernels do not take it -- every batch size comes here)
-           (k > 128 || nq >= (g_ft_min_nq.load() > 0 ? g_ft_min_nq.load() : ft_auto_min(D, k))) && nq >= 1 && ft_sample_fills(D, n, nq, k);
+           (n >= min_rows || (k > 128 && n >= std::max<int64_t>(65536, 48 * (int64_t)k) && (D <= 512 || nq >= 16)) ||
+            (k <= 128 && n >= std::min<int64_t>(65536, min_rows) && flat_f32_stream_qmax(D) == 0 && (D <= 512 || k <= 32 || nq >= 129))) && n < 0xffffffe0LL &&
+           k >= 1 && k <= CVTMI_K_MAX && tune_flat_f32_tfilter_bigk.geti() + (k <= 128) > 0 &&   // (k > 128: the stream kernels do not take it -- every batch size comes here)
+           (k > 128 || nq >= (min_nq > 0 ? min_nq : ft_auto_min(D, k))) && nq >= 1 && ft_sample_fills(D, n, nq, k);
 }
 // records a wave region holds: three times what 1 M SIFT-like rows gave per wave at k = 100, scaled with k beyond 128
 static uint32_t ft_rec_cap(int64_t m, int k)
@@ -1058,7 +1044,7 @@ int launch_flat_f32_tfilter(int metric, int D, const float *X, const float *Xrow
         CVTMI_HIP(hipMemsetAsync(smax, 0, (size_t)m * nslots * sizeof(uint32_t), st));
         FtArgs a;
         a.pack = reinterpret_cast<const uint4 *>(pack); a.bias = bias; a.n_tiles = n_tiles; a.Q = q + a0 * D; a.D = D; a.nq = (int)m; a.chunks = chunks; a.qper = qper;
-        a.smax = smax; a.nslots = nslots; a.thr = thr; a.rec = rec; a.wcnt = wcnt; a.cap = cap; a.qlist = nullptr; a.qcount = nullptr; a.dbg = get_flat_f32_dbg();
+        a.smax = smax; a.nslots = nslots; a.thr = thr; a.rec = rec; a.wcnt = wcnt; a.cap = cap; a.qlist = nullptr; a.qcount = nullptr; a.dbg = tune_flat_f32_dbg.geti();
         const size_t lds = (size_t)(qper / 32) * nch * nt * 1024 + FT_SLACK + (size_t)qper * 2 * sizeof(float);
         a.t1 = n_tiles;
         a.n_sample = ft_n_sample(D, n, k, nprod, chunks);
@@ -1075,14 +1061,14 @@ int launch_flat_f32_tfilter(int metric, int D, const float *X, const float *Xrow
         a.t1 = n_tiles; a.n_sample = 0;
         CVTMI_TRY(ft_launch_any(D, nprod, false, a, lds, st));
         if (a.dbg & 8) continue;   // timing experiments: the filter passes alone (results stale)
-        const bool retry = g_ft_retry.load() != 0 && !big;
+        const bool retry = tune_flat_f32_tfilter_retry.geti() != 0 && !big;
         const size_t bucket_lds = (size_t)FT_STAGE * (sizeof(uint2) + sizeof(uint16_t));
         {
             static std::atomic<bool> attr_k[16] = {};
             CVTMI_TRY(fs_set_lds((const void *)ft_bucket_kernel, bucket_lds, attr_k));
         }
         const int rcap = std::min<int>(qcap, (int)((m + 31) / 32 * 32));   // queries one second attempt takes (a single chunk)
-        const bool wide = !big && D >= 256 && g_ft_wide_band.load() != 0;   // (narrow rows: the exact kernels' turn costs less than this launch on every call)
+        const bool wide = !big && D >= 256 && tune_flat_f32_tfilter_wide_band.geti() != 0;   // (narrow rows: the exact kernels' turn costs less than this launch on every call)
         auto finish = [&](int second) {
             if (big || second == 2) {   // k = 129 .. 2048: the candidates' keys in LDS, a bitonic sort of the exact distances (2: the second chance of the other form's wide bands)
                 const int cstride = big ? FT_CAP_BIG : FT_CAP, only2 = big ? 0 : 1;

@@ -1240,34 +1240,21 @@ __global__ __launch_bounds__(kBlock) void flat_u8_finish_kernel(const uint32_t *
 // bit 1 no survivor tests.  What they showed on 10 M x 512-d, nq = 4096 (tools/bench_flat_u8_opt.py, DBG=0,2,3): filter kernel 18.7 ms,
 // without the tests 17.6, without tests and DMA 14.4 = 2.8 P int-op/s -- against 3.2-3.5 P for a loop of nothing but matrix
 // instructions on random bytes (tools/ubench/mfma_i8_feed.hip; 4.4-4.9 P on constant bytes: the ceiling is the power the operands draw)
-static int g_u8_dbg = 0;
-int set_flat_u8_dbg(int v)
-{
-#ifdef CVTMI_GF_DBG
-    g_u8_dbg = v;
-    return CVTMI_OK;
-#else
-    (void)v;
-    return CVTMI_EUNSUPPORTED;
-#endif
-}
-static int g_u8_gfilter = 1;  // cvtmi_set_tuning("flat_u8_gfilter"): 1 = the software-pipelined filter kernel where it applies (D = 64 .. 512, power of two)
-void set_flat_u8_gfilter(int v) { g_u8_gfilter = v; }  // 0 off, 1 choose, 2 two 4-wave workgroups per CU, 3 one 8-wave workgroup per CU, 4 one wave per SIMD x 128 queries
-bool flat_u8_gfilter_shape(int D) { return g_u8_gfilter && (D == 64 || D == 128 || D == 256 || D == 512); }
+// (cvtmi_set_tuning("flat_u8_dbg"), which only such a build accepts)
+// cvtmi_set_tuning("flat_u8_gfilter"): 1 = the software-pipelined filter kernel where it applies (D = 64 .. 512, power of two);
+// 0 off, 1 choose, 2 two 4-wave workgroups per CU, 3 one 8-wave workgroup per CU, 4 one wave per SIMD x 128 queries
+bool flat_u8_gfilter_shape(int D) { return tune_flat_u8_gfilter.geti() && (D == 64 || D == 128 || D == 256 || D == 512); }
 
 // 1 .. 128 queries over raw rows: stream + minima (the selection is launch_flat_u8_mstream_finish, flat.hip)
 constexpr int MSTREAM_BLOCKS = 256;   // one 4-wave workgroup per CU (one wave per SIMD); 192 / 240 / 252 / 255 measured the same or worse
-static int g_mstream_min_nq = 1;       // measurement hook (flat_u8_mstream_min): below it the row-per-lane / row-tile kernels answer
-void set_flat_u8_mstream_min(int v) { g_mstream_min_nq = v; }
+// measurement hook (flat_u8_mstream_min): below it the row-per-lane / row-tile kernels answer
 // Smallest table the stream takes.  Structural bound: the selection needs k waves with at least one 32-row tile each (k <= 128: 4096 rows);
 // waves without a tile publish "no minimum" and are never looked at.  It was 262 144 (eight tiles per wave) until a sweep over table
 // sizes (round 5, tools/sweep_flat_small_tables.py) showed the row-tile kernels 2-20x behind on everything smaller: 65 536 x 512-d,
-// 16 / 100 / 1000 queries 0.39 / 0.84 / 1.06 ms against 0.046 / 0.060 / 0.47.
-static std::atomic<int64_t> g_mstream_min_rows{4096};   // cvtmi_set_tuning("flat_u8_mstream_min_rows")
-void set_flat_u8_mstream_min_rows(int64_t v) { g_mstream_min_rows = v < 4096 ? 4096 : v; }
+// 16 / 100 / 1000 queries 0.39 / 0.84 / 1.06 ms against 0.046 / 0.060 / 0.47.  (cvtmi_set_tuning("flat_u8_mstream_min_rows"))
 bool flat_u8_mstream_applies(int D, int64_t n, int64_t nq, int k)
 {
-    return (D == 128 || D == 256 || D == 512) && nq >= g_mstream_min_nq && nq <= 128 && n >= g_mstream_min_rows.load() && n < 0x7fffffff && k <= 128 &&
+    return (D == 128 || D == 256 || D == 512) && nq >= tune_flat_u8_mstream_min.geti() && nq <= 128 && n >= tune_flat_u8_mstream_min_rows.get() && n < 0x7fffffff && k <= 128 &&
            n / 32 / 64 / (MSTREAM_BLOCKS * 4) + 2 <= 160;   // rounds a finish slice can span (FIN_MAXR, flat.hip): 331 M rows
 }
 // entries of the tile-group minima array: groups of MS_GROUP tiles per wave, (group, wave) major
@@ -1336,8 +1323,9 @@ int launch_flat_u8_filter(const uint8_t *q, int64_t nq, int D, const uint4 *pack
     const int64_t tile_begin = row_begin / 32, tile_end = (n + 31) / 32;
     if (tile_end <= tile_begin) return CVTMI_OK;
     if (flat_u8_gfilter_shape(D)) {  // the software-pipelined kernel
-        const bool two = g_u8_gfilter == 2;   // two 4-wave workgroups per CU: measured 15 % slower than one 8-wave workgroup (16 matrix instructions per barrier)
-        const bool wide4 = g_u8_gfilter == 4 && D >= 128;   // one wave per SIMD, 96-128 queries per wave (flat_u8_gfilter_wide_kernel): measured equal at nq = 4096, 10 % slower at nq = 1000
+        const int gfilter = tune_flat_u8_gfilter.geti(), dbg = tune_flat_u8_dbg.geti();
+        const bool two = gfilter == 2;   // two 4-wave workgroups per CU: measured 15 % slower than one 8-wave workgroup (16 matrix instructions per barrier)
+        const bool wide4 = gfilter == 4 && D >= 128;   // one wave per SIMD, 96-128 queries per wave (flat_u8_gfilter_wide_kernel): measured equal at nq = 4096, 10 % slower at nq = 1000
         const int qpb = wide4 ? (D == 512 ? 384 : 512) : (two ? 128 : 256);
         const int64_t qblocks = (nq + qpb - 1) / qpb;
         const int64_t want = two ? 512 : 256;                                     // workgroups resident at a time
@@ -1362,14 +1350,14 @@ int launch_flat_u8_filter(const uint8_t *q, int64_t nq, int D, const uint4 *pack
         const size_t lds = (size_t)(NB) * (G) * (N) * 64 * sizeof(uint4);                                                        \
         CVTMI_HIP(hipFuncSetAttribute((const void *)flat_u8_gfilter_kernel<N, NW, G, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
         hipLaunchKernelGGL((flat_u8_gfilter_kernel<N, NW, G, NB>), g, dim3(64 * (NW)), lds, st, q, nq, pack, norms, n, sample_d, k, tile_begin, tile_end, \
-                           tps, pair_cap, pair_cnt, pairs, (int)qblocks, g_u8_dbg);                                              \
+                           tps, pair_cap, pair_cnt, pairs, (int)qblocks, dbg);                                                   \
     } while (0)
 #define CVTMI_GW(N, AQ, NB)                                                                                                      \
     do {                                                                                                                         \
         const size_t lds = (size_t)(NB) * (N) * 64 * sizeof(uint4);                                                              \
         CVTMI_HIP(hipFuncSetAttribute((const void *)flat_u8_gfilter_wide_kernel<N, AQ, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
         hipLaunchKernelGGL((flat_u8_gfilter_wide_kernel<N, AQ, NB>), g, dim3(256), lds, st, q, nq, pack, norms, n, sample_d, k, tile_begin, tile_end, \
-                           tps, pair_cap, pair_cnt, pairs, (int)qblocks, g_u8_dbg);                                              \
+                           tps, pair_cap, pair_cnt, pairs, (int)qblocks, dbg);                                                   \
     } while (0)
         if (wide4) {
             switch (D / 32) {

@@ -446,34 +446,25 @@ static int ut_launch(bool maxmode, const UtArgs &a, size_t lds, hipStream_t st)
 
 }  // namespace
 
-static std::atomic<int> g_ut_on{1};   // cvtmi_set_tuning("flat_u8_tfilter"): 1 = uint8 searches with k = 129 .. 2048 take this pipeline, 0 = the exact kernels
+// cvtmi_set_tuning("flat_u8_tfilter"): 1 = uint8 searches with k = 129 .. 2048 take this pipeline, 0 = the exact kernels
 // "flat_u8_tfilter_min_k" / "_min_nq": k <= 128 from this k and this batch on.  Measured (tools/flat_u8_bigk.py, profiles/r06_flat_u8_tfilter.txt; 1 M x 256-d,
 // 2 M x 512-d, 10 M x 128-d, 10 M x 512-d; k = 10 / 64 / 100 / 128): from 128 queries on this pipeline is level with or ahead of both the
 // streaming passes and the sample + filter pipeline of flat_mfma.hip at every point (k = 10: 0.9-1.0 x at 128 queries, 0.75-0.95 x from 256;
 // k = 100: 0.7 x at 128 queries, 0.42-0.55 x from 256); below, one streaming pass over the raw rows wins
-static std::atomic<int> g_ut_min_k{1}, g_ut_min_nq{129}, g_ut_min_nq_k65{97};   // ("_min_nq_k65": the batch bound for k = 65 .. 128, where a streaming pass costs more)
-static std::atomic<int64_t> g_ut_min_rows{262144};   // "flat_u8_tfilter_min_rows": tables under it (from 65 536 rows) come here from "flat_u8_tfilter_small_min_nq" queries on
-static std::atomic<int> g_ut_small_min_nq{129};   // (tools/flat_u8_small_tables.py, profiles/r06_flat_u8_small_tables.txt: ahead of the streaming passes from 129 queries on at every size, 2-6 x at 1000)
-static std::atomic<int> g_ut_sample{0};   // "flat_u8_tfilter_sample": the sample pass takes one tile group in this many (0: by k -- 8 up to k = 512, 5 up to 1024, 3 beyond)
-void set_flat_u8_tfilter(int v) { g_ut_on = v != 0; }
-void set_flat_u8_tfilter_min_rows(int64_t v) { g_ut_min_rows = v < 65536 ? 65536 : v; }
-void set_flat_u8_tfilter_small_min_nq(int v) { g_ut_small_min_nq = v < 1 ? 1 : v; }
-void set_flat_u8_tfilter_min_k(int v) { g_ut_min_k = v < 1 ? 1 : v; }
-void set_flat_u8_tfilter_min_nq(int v) { g_ut_min_nq = v < 1 ? 1 : v; }
-void set_flat_u8_tfilter_min_nq_k65(int v) { g_ut_min_nq_k65 = v < 1 ? 1 : v; }
-void set_flat_u8_tfilter_sample(int v) { g_ut_sample = v < 0 ? 0 : v > 64 ? 64 : v; }
+// ("_min_nq_k65": the batch bound for k = 65 .. 128, where a streaming pass costs more)
+// "flat_u8_tfilter_min_rows": tables under it (from 65 536 rows) come here from "flat_u8_tfilter_small_min_nq" queries on
+// (tools/flat_u8_small_tables.py, profiles/r06_flat_u8_small_tables.txt: ahead of the streaming passes from 129 queries on at every size, 2-6 x at 1000)
+// "flat_u8_tfilter_sample": the sample pass takes one tile group in this many (0: by k -- 8 up to k = 512, 5 up to 1024, 3 beyond)
 // Workgroups that hold different queries walk the same rows in the same order on the same XCD ("chunks" of a pass): the rows come from
 // HBM once and from the caches behind it for the others -- as many chunks as the sample's slots allow (4096 / chunks of them are filled;
 // twice k wanted), "flat_u8_tfilter_chunks" caps it
-static std::atomic<int> g_ut_chunks{4};
-void set_flat_u8_tfilter_chunks(int v) { g_ut_chunks = v >= 4 ? 4 : (v >= 2 ? 2 : 1); }
-static int ut_chunks_max(int k) { return std::min(g_ut_chunks.load(), k <= 512 ? 4 : (k <= 1024 ? 2 : 1)); }
+static int ut_chunks_max(int k) { return std::min(tune_flat_u8_tfilter_chunks.geti(), k <= 512 ? 4 : (k <= 1024 ? 2 : 1)); }
 static int ut_rt(int ks) { return ks >= 12 ? 2 : (ks >= 4 ? 3 : 4); }   // row tiles per wave: RT x 4 KS + 16 RT registers of 256 (four at 128-d: 5 % faster on large
                                                                           // tables, but a third fewer tile groups -- sample slots -- on small ones: three)
 bool flat_u8_tfilter_width(int D) { return D % 32 == 0 && D >= 32 && D <= 512; }   // (a kernel per K-step count: 32 .. 512 bytes per row in steps of 32)
 bool flat_u8_tfilter_applies(int D, int64_t n, int64_t nq, int k)
 {
-    if (!g_ut_on.load() || !flat_u8_tfilter_width(D) || n >= 0x7fffffe0LL || nq < 1 || k > CVTMI_K_MAX) return false;
+    if (!tune_flat_u8_tfilter.geti() || !flat_u8_tfilter_width(D) || n >= 0x7fffffe0LL || nq < 1 || k > CVTMI_K_MAX) return false;
     if (k > 128) {   // smaller tables too, while the sample can fill 1.25 k slots (two per wave that gets a tile group): nothing else is fast there
         const int ks = D / 32, rt = ut_rt(ks);
         const int64_t groups = (n + 32 * rt - 1) / (32 * rt);
@@ -482,21 +473,22 @@ bool flat_u8_tfilter_applies(int D, int64_t n, int64_t nq, int k)
     // widths the streaming kernel does not take (it exists at 128 / 256 / 512-d): the row-tile kernels behind cost 0.1 .. 4 ms whatever the batch -- every
     // batch of two queries or more comes here (1 M x 96-d, 8 queries: 0.43 -> 0.08 ms)
     const bool has_stream = D == 128 || D == 256 || D == 512;
-    if (!has_stream && n >= 65536 && nq >= 2 && k >= g_ut_min_k.load()) {
+    const int min_k = tune_flat_u8_tfilter_min_k.geti(), min_nq = tune_flat_u8_tfilter_min_nq.geti();
+    if (!has_stream && n >= 65536 && nq >= 2 && k >= min_k) {
         const int ks = D / 32, rt = ut_rt(ks);
         const int64_t groups = (n + 32 * rt - 1) / (32 * rt);
         if (8 * std::min<int64_t>(groups, UT_GRID * UT_WAVES / 4) >= 5 * (int64_t)k) return true;
     }
-    if (n < g_ut_min_rows.load()) {   // small tables, k <= 128: large batches only (the stream's passes are short there), and while the sample fills its slots
+    if (n < tune_flat_u8_tfilter_min_rows.get()) {   // small tables, k <= 128: large batches only (the stream's passes are short there), and while the sample fills its slots
         const int ks = D / 32, rt = ut_rt(ks);
         const int64_t groups = (n + 32 * rt - 1) / (32 * rt);
-        if (n < 65536 || nq < g_ut_small_min_nq.load() || k < g_ut_min_k.load() || 8 * std::min<int64_t>(groups, UT_GRID * UT_WAVES / 4) < 5 * (int64_t)k) return false;
+        if (n < 65536 || nq < tune_flat_u8_tfilter_small_min_nq.geti() || k < min_k || 8 * std::min<int64_t>(groups, UT_GRID * UT_WAVES / 4) < 5 * (int64_t)k) return false;
         return true;
     }
     // (the lower batch bound also for tables of a GB and more at any k: 10 M x 128-d, 96 queries, k = 10 0.43 -> 0.31 ms, 10 M x 512-d 1.15 -> 0.97; at 1 M x 256-d
     //  the streaming pass is still ahead there, 0.113 against 0.123)
     const bool low = k > 64 || (double)n * D >= 1e9;
-    return (k >= g_ut_min_k.load() && nq >= (low ? std::min(g_ut_min_nq.load(), g_ut_min_nq_k65.load()) : g_ut_min_nq.load()));
+    return (k >= min_k && nq >= (low ? std::min(min_nq, tune_flat_u8_tfilter_min_nq_k65.geti()) : min_nq));
 }
 // the sample pass takes one tile group in so many: about k x div rows pass the threshold (~0.7 x 4096 x div at k = 2048)
 // Measured (tools/flat_u8_sample_sweep.py, profiles/r06_flat_u8_sample_sweep.txt: 0.26 .. 5 GB of rows, k = 10 .. 1024): the sample pass costs
@@ -504,7 +496,7 @@ bool flat_u8_tfilter_applies(int D, int64_t n, int64_t nq, int k)
 // cent everywhere; beyond ~4096 / k the lists and the waves' record regions run over (the call falls back)
 static int ut_sample_div(int k, int64_t n, int D)
 {
-    if (g_ut_sample.load()) return g_ut_sample.load();
+    if (const int v = tune_flat_u8_tfilter_sample.geti()) return v;
     const double want = std::sqrt(8000.0 * ((double)n * D * 1e-9) / (double)k);
     const int hi = std::min(32, std::max(3, 4096 / k));
     return std::max(2, std::min(hi, (int)(want + 0.5)));

@@ -422,11 +422,9 @@ int launch_hnsw_rerank(const HnswDevGraph &g, int metric, const float *q, int64_
 // ef = 1000) was measured: fp32 ef = 1000 174 K -> 151 K queries/s, ADC 101 K -> 97 K at 1 M nodes -- the query slots lost per CU cost more than
 // the HBM levels of the heap walks, which the wave-wide pop already crosses in one or two round trips.  cvtmi_set_tuning("hnsw_top_lds", n),
 // 0 = everything.
-static std::atomic<int> g_hnsw_top_lds{ 256 };
-void set_hnsw_top_lds(int v) { g_hnsw_top_lds = v < 0 ? 0 : v; }
 int hnsw_top_lds(int ef)
 {
-    const int cap = g_hnsw_top_lds.load();
+    const int cap = tune_hnsw_top_lds.geti();
     const int want = ef + 1;
     return cap > 0 && cap < want ? (cap < 16 ? 16 : cap) : want;
 }
@@ -435,9 +433,7 @@ int hnsw_lds_bytes(int state_floats, int ef)
     return (int)(((state_floats + 3) & ~3) * sizeof(float) + (size_t)(hnsw_top_lds(ef) + HN_LCAP) * sizeof(HnEnt));
 }
 // cvtmi_set_tuning("hnsw_adc_tables"): 0 = a query's fp32 tables are read from the scratch lut_kernel wrote (default), 1 = copied into LDS
-static std::atomic<int> g_hnsw_adc_tables_lds{ 0 };
-void set_hnsw_adc_tables(int v) { g_hnsw_adc_tables_lds = v != 0; }
-int hnsw_adc_state_floats(int MK) { return g_hnsw_adc_tables_lds.load() ? MK : 0; }   // per-slot query state of the ADC traversal, in floats
+int hnsw_adc_state_floats(int MK) { return tune_hnsw_adc_tables.geti() ? MK : 0; }   // per-slot query state of the ADC traversal, in floats
 int hnsw_ef_max() { return HN_EF_MAX; }
 int hnsw_lcap() { return HN_LCAP; }
 

@@ -397,15 +397,9 @@ __global__ __launch_bounds__(64) void hnsw_build_link_kernel(const HbArgs a)
 }
 
 // ---- host driver -----------------------------------------------------------------------------------------------------------------
-// Default schedule: a batch holds at most 1 / g_hb_frac of the rows already in the graph (at least one), and at most g_hb_cap rows.
-static std::atomic<int> g_hb_frac{ 32 };
-static std::atomic<int> g_hb_cap{ 8192 };
-static std::atomic<int> g_hb_phases{ 0 };
+// Default schedule: a batch holds at most 1 / "hnsw_build_frac" of the rows already in the graph (at least one), and at most "hnsw_build_cap" rows.
 static double g_hb_ms[5];
 static std::mutex g_hb_ms_mu;
-void set_hnsw_build_frac(int v) { g_hb_frac = v < 1 ? 1 : v; }
-void set_hnsw_build_cap(int v) { g_hb_cap = v < 1 ? 1 : v; }
-void set_hnsw_build_phases(int v) { g_hb_phases = v != 0; }
 void hnsw_build_phase_ms(double *ms)
 {
     std::lock_guard<std::mutex> g(g_hb_ms_mu);
@@ -416,8 +410,8 @@ struct HbBatch { int64_t s, e; int maxlevel; uint32_t ep; int64_t toff; int ntas
 
 void hnsw_build_schedule(const int32_t *levels, int64_t n, int max_batch, std::vector<int64_t> &bounds)
 {
-    const int64_t frac = g_hb_frac.load();
-    const int64_t cap = max_batch > 0 ? max_batch : g_hb_cap.load();
+    const int64_t frac = tune_hnsw_build_frac.geti();
+    const int64_t cap = max_batch > 0 ? max_batch : tune_hnsw_build_cap.geti();
     bounds.clear();
     bounds.push_back(0);
     if (n == 0) return;
@@ -512,7 +506,7 @@ int launch_hnsw_build(const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, 
     const bool ip = metric == CVTMI_METRIC_IP;
     const int lanes = (g.D % 4 != 0) ? 1 : (ip ? 4 : (g.D % 16 == 0 ? 8 : 4));
     const size_t sel_lds = (size_t)(2 * efc1 + 128) * sizeof(HnEnt) + 64 * 4 + 16;
-    const bool timing = g_hb_phases.load() != 0;
+    const bool timing = tune_hnsw_build_phases.geti() != 0;
     std::vector<hipEvent_t> ev;
     auto mark = [&]() -> int {
         if (!timing) return CVTMI_OK;

@@ -6,6 +6,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "tuning.h"
 
 namespace cvtmi {
 
@@ -101,10 +102,9 @@ struct Tmp {
 // Waiting for a stream from a host-pointer entry: a blocking hipStreamSynchronize parks the thread on an interrupt, which costs tens of
 // microseconds to wake from -- as much again as a whole small search.  Short waits therefore poll (hipStreamQuery) for up to
 // cvtmi_set_tuning("host_spin_us") microseconds (default 200) before they block.
-extern std::atomic<int> g_host_spin_us;
 inline hipError_t stream_wait(hipStream_t st)
 {
-    const int budget = g_host_spin_us.load(std::memory_order_relaxed);
+    const int budget = tune_host_spin_us.geti();
     if (budget > 0) {
         const auto t0 = std::chrono::steady_clock::now();
         for (int i = 0;; ++i) {

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "common.h"
+#include "tuning.h"
 
 namespace cvtmi {
 
@@ -120,12 +121,7 @@ int launch_adc_scan_bigk(const OpqModelDev &m, const uint8_t *codes, const uint8
                          uint32_t **flags_out, hipStream_t st);
 size_t scanh_qlut_bytes(int64_t nq);
 size_t scanh_qp_bytes(int64_t nq);
-void set_scanh_balance(int v);       // 0 = choose, 1 = equal shares of the flat (group x row) space, 2 = (group, split) blocks
-void set_scanh_min_rows(int64_t v);  // smallest share of a workgroup in the balanced plan
-void set_scanh_tail(int v);
-void set_scanh_share_hist(int v);
-void set_scanh_fix(double v);
-size_t scanh_gthr_bytes(int64_t nq);   // adc_scan16h: [nq] shared bounds + [nq][256] shared histograms          // 1 (default) = the groups of the last, partly filled round of blocks may be cut finer
+size_t scanh_gthr_bytes(int64_t nq);   // adc_scan16h: [nq] shared bounds + [nq][256] shared histograms
 // part_d / part_id: [nq][plan.stride][k]; out_d / out_id: the final [nq][k] lists (groups scanned in one piece write there); lut_g: nq * 16 * 256 floats; qlut / qp_g / spill: scanh_*_bytes; gthr: nq words or null
 int launch_adc_scan_h(const OpqModelDev &m, const uint8_t *codes, const uint8_t *codes_rot, int64_t n_rows, int64_t id_base,
                       const float *q_rot, int64_t nq, int k, const ScanHPlan &plan, const ScanItem *items_dev, float *part_d,
@@ -135,8 +131,7 @@ int scan_seed_enabled();
 // adc_scan_h.hip: 1 .. 8 queries -- global bound from a histogram pass, candidate lists, selection by the last workgroup (3 launches,
 // the rotation of RAW queries folded into the first when rotate != 0)
 bool scans_applies(const OpqModelDev &m, int64_t n_rows, int64_t nq, int k);
-bool scans_fuses_rotation(const OpqModelDev &m);
-void set_scans_dbg(int v);   // timing experiments, results wrong when non-zero   // else the caller rotates and passes rotate = 0
+bool scans_fuses_rotation(const OpqModelDev &m);   // else the caller rotates and passes rotate = 0
 size_t scans_scratch_bytes();
 int launch_adc_scan_small(const OpqModelDev &m, const uint8_t *codes, const uint8_t *codes_rot, int64_t n_rows, int64_t id_base, const float *q,
                           int rotate, int64_t nq, int k, float *dist, int64_t *ids, float *lut_g, void *qlut, void *qp_g, void *scratch, int lazy,
@@ -158,8 +153,6 @@ int launch_coarse_probe(const OpqModelDev &m, const float *q_rot, int64_t nq, in
                         hipStream_t st, void *scratch = nullptr);
 size_t coarse_probe_scratch_bytes(int64_t nq, int nprobe);   // the few-queries form's partial lists (placed behind the probe array)
 // coarse top-nprobe through the matrix-core filter (assign_mfma.hip): same probes as the exact kernels
-void set_probe_variant(int v);
-void set_scan_seed(int v);  // adc_scan16q / 16a: 1 (default) = first thresholds from a histogram of the split's first 2048 rows
 bool coarse_probe_filter_applies(const float *q, int64_t nq, int d, const float *cent, int k, int nprobe);
 int launch_coarse_probe_filtered(const float *q, int64_t nq, int d, const float *cent, int k, int nprobe, int32_t *probe, hipStream_t st);
 int launch_query_video(const OpqModelDev &m, const float *q_rot, int64_t nq, int nprobe, const int32_t *probe,
@@ -252,10 +245,6 @@ int launch_flat_block(const float *src, int64_t n, int D, int64_t row0, float *d
 // exact distances of the candidates); D % 16 == 0, 16 <= D <= 256, up to flat_f32_stream_qmax(D) queries per pass
 int flat_f32_stream_qmax(int D);
 int flat_f32_stream_private_max(int D);   // queries per pass of the private-ring kernel
-int get_flat_f32_dbg();
-void set_flat_f32_dbg(int v);     // timing experiments, results wrong when non-zero
-void set_flat_f32_share(int v);   // shared-ring kernel: 0 choose, 1 four waves x 32 QB queries (the only form)
-void set_flat_f32_nt(int v);     // 0 = never, 1 = choose (default), 2 = always: non-temporal hint on the stream kernels' row loads
 bool flat_f32_stream_applies(int metric, int D, int64_t n, int k);
 // round 6 (flat_f32_tfilter.hip): batches (any width that is a multiple of 4 up to 2048-d, >= 262 144 rows, k <= 128) as a threshold filter: queries in LDS, the rows'
 // bf16 operand copy (launch_flat_pack) in registers, per-query thresholds from sample maxima, candidate lists, exact finish;
@@ -267,15 +256,6 @@ size_t flat_f32_tfilter_scratch(int64_t nq, int k);
 // Xrows: row-major copy of the rows (launch_flat_unblock) for the exact finish, or null (it gathers from the blocked layout: eight times the bytes)
 int launch_flat_f32_tfilter(int metric, int D, const float *X, const float *Xrows, const void *pack, const uint32_t *pstats, const float *bias, const uint32_t *stats, int64_t n,
                             const float *q, int64_t nq, int k, void *scratch, float *out_d, int64_t *out_i, uint32_t *redo, hipStream_t st);
-void set_flat_f32_tfilter(int v);
-void set_flat_f32_tfilter_min(int v);
-void set_flat_f32_tfilter_one(int v);
-void set_flat_f32_tfilter_retry(int v);
-void set_flat_f32_tfilter_wide_band(int v);
-void set_flat_f32_tfilter_bigk(int v);
-void set_flat_f32_tfilter_sample(int v);
-void set_flat_f32_tfilter_min_rows(int v);
-int64_t flat_f32_tfilter_min_rows();
 size_t flat_f32_stream_scratch(int D, int64_t n, int64_t nq_pass);
 // round 6 (flat_u8_tfilter.hip): uint8 L2 batches (from 128 queries; any batch when k = 129 .. CVTMI_K_MAX; 32 .. 512-d in steps of 32,
 // >= 262 144 rows) as a threshold filter over the int8 operand copy
@@ -286,29 +266,18 @@ bool flat_u8_tfilter_applies(int D, int64_t n, int64_t nq, int k);
 size_t flat_u8_tfilter_scratch(int D, int64_t n, int64_t nq, int k);
 int launch_flat_u8_tfilter(int D, const void *pack, const int32_t *norms, int64_t n, const uint8_t *q, int64_t nq, int k, void *scratch, float *out_d,
                            int64_t *out_i, uint32_t *flags, hipStream_t st);
-void set_flat_u8_tfilter(int v);
-void set_flat_u8_tfilter_min_k(int v);
-void set_flat_u8_tfilter_min_rows(int64_t v);
-void set_flat_u8_tfilter_small_min_nq(int v);
-void set_flat_u8_tfilter_min_nq(int v);
-void set_flat_u8_tfilter_min_nq_k65(int v);
-void set_flat_u8_tfilter_sample(int v);
-void set_flat_u8_tfilter_chunks(int v);
 // bias[r] (and zeroed padding rows) for rows [row0, row1); stats[0] = max |x|^2 bits, stats[1] = non-finite rows (both accumulate)
 int launch_flat_f32_bias(float *X, int D, int metric, int64_t row0, int64_t row1, float *bias, uint32_t *stats, hipStream_t st);
 // redo[nq], cnt[nq] (zeroed inside): redo is set to 1 for queries the exact kernels must answer
 int launch_flat_f32_stream(int metric, int D, const float *X, const float *bias, const uint32_t *stats, int64_t n, const float *q, int64_t nq,
                            int k, void *scratch, float *out_d, int64_t *out_i, uint32_t *redo, uint32_t *cnt, hipStream_t st, const void *pack = nullptr,
                            const uint32_t *pstats = nullptr, const float *Xrows = nullptr);   // Xrows: row-major copy of the rows for the exact distances, or null
-void set_flat_f32_packed(int v);   // 1 (default): up to 32 queries stream the bf16 operand copy (launch_flat_pack) when pack / pstats are given
 int flat_u8_mfma_qtile(int D, int k, int64_t nq);  // queries per workgroup, 0 = shape not covered
 int flat_u8_mfma_splits(int64_t n, int64_t nq, int qt);
 // gthr: nq uint32 scratch (set to 0xff.. inside) through which the row splits of a query share their k-th best
 int launch_flat_u8_mfma(int D, const uint8_t *data, const int32_t *norms, int64_t n, const uint8_t *q, int64_t nq, int k,
                         int splits, float *part_d, int64_t *part_id, uint32_t *gthr, hipStream_t st);
 // ids[i] = ids[i] >= 0 ? labels[ids[i]] : -1
-void set_flat_u8_opt(int v);
-int set_flat_u8_dbg(int v);   // -DCVTMI_GF_DBG builds only
 // uint8 L2, 1..128 queries: matrix-core stream over the raw rows keeping tile / wave minima (flat_mfma.hip) + selection (flat.hip)
 bool flat_u8_mstream_applies(int D, int64_t n, int64_t nq, int k);
 size_t flat_u8_mstream_scratch(int64_t n, int64_t nq, int *nqp, int *waves);
@@ -319,17 +288,9 @@ int launch_flat_u8_mstream(int D, const uint8_t *data, const int32_t *norms, int
 int launch_flat_u8_mstream_finish(int D, const uint8_t *data, int64_t n, const uint8_t *q, int64_t nq, int k, const int32_t *wmin, int G,
                                   const int32_t *tmin, int nqp, int tile_group, float *part_d, int64_t *part_id, float *out_d, int64_t *out_rows, hipStream_t st);
 int flat_u8_stream_slices();
-void set_flat_u8_mstream_min(int v);
-void set_flat_u8_mstream_min_rows(int64_t v);
-void set_sq8_wave_blocks(int v);
-void set_sq8_encode_wave(int v);
-void set_sq8_filter(int v);
-void set_scan_tail_splits(int v);
-void set_sq8_flags(int v);
 size_t flat_u8_stream_scratch(int64_t n, int64_t nq, int *slices, int64_t *ld);
 int launch_flat_u8_stream(int D, const uint8_t *data, const int32_t *norms, int64_t n, const uint8_t *q, int64_t nq, int k, float *scratch,
                           float *part_d, int64_t *part_id, float *out_d, int64_t *out_rows, hipStream_t st);
-void set_flat_u8_gfilter(int v);   // flat_mfma.hip: the software-pipelined (LDS-DMA) uint8 filter kernel on / off
 bool flat_u8_gfilter_shape(int D);
 int launch_gather_labels(int64_t *ids, int64_t count, const int64_t *labels, hipStream_t st);
 // ids[i] = ids[i] >= 0 ? ids[i] + base : -1
@@ -368,7 +329,6 @@ int launch_kmeans_assign_exact(const float *x, int64_t ld, int64_t n, int d, con
 // splits * n entries each
 int launch_kmeans_assign_split(const float *x, int64_t ld, int64_t n, int d, const float *cent, int k, int32_t *assign, int splits,
                                float *part_d, int32_t *part_i, hipStream_t st);
-void set_assign_variant(int v);  // 0 = choose, 1 = exact kernels, 2 = filter wherever it applies
 int launch_kmeans_assign(const float *x, int64_t ld, int64_t n, int d, const float *cent, int k, int32_t *assign,
                          unsigned long long *changed, hipStream_t st);
 // cent[c] = float(double sum of the rows assigned to c, ascending row order / count); empty clusters untouched
@@ -404,8 +364,6 @@ int hnsw_lds_bytes(int state_floats, int ef);
 int hnsw_ef_max();
 int hnsw_lcap();
 int hnsw_top_lds(int ef);
-void set_hnsw_top_lds(int v);
-void set_hnsw_adc_tables(int v);
 int hnsw_adc_state_floats(int MK);
 
 // ---- hnsw_build.hip ----
@@ -413,9 +371,6 @@ int hnsw_adc_state_floats(int MK);
 // from `levels` (host, the drawn level of every row); returns when the graph is complete
 int launch_hnsw_build(const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, const int32_t *levels, int metric, int M, int efc,
                       int max_batch, int cus, hipStream_t st);
-void set_hnsw_build_frac(int v);
-void set_hnsw_build_cap(int v);
-void set_hnsw_build_phases(int v);
 void hnsw_build_phase_ms(double *ms);   // [traversal, selection, back links, batches, host ms] of the last build with phases on
 
 }  // namespace cvtmi

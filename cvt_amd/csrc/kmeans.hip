@@ -222,22 +222,20 @@ __global__ __launch_bounds__(kBlock) void kmeans_residual_kernel(const float *__
     }
 }
 
-static int g_assign_variant = 0;  // 0 = choose, 1 = exact kernels for every row, 2 = matrix-core filter wherever it applies
-void set_assign_variant(int v) { g_assign_variant = v; }
-
 int launch_kmeans_assign(const float *x, int64_t ld, int64_t n, int d, const float *cent, int k, int32_t *assign,
                          unsigned long long *changed, hipStream_t st)
 {
     if (n <= 0) return CVTMI_OK;
+    const int variant = tune_assign_variant.geti();   // 0 = choose, 1 = exact kernels for every row, 2 = matrix-core filter wherever it applies
     // 32 <= d <= 128: matrix-core filter + exact resolution of the rows it cannot decide (assign_mfma.hip); same result
-    if (g_assign_variant != 1 && assign_filter_applies(x, ld, g_assign_variant == 2 && n < 4096 ? 4096 : n, d, cent, k) && n < 0x7fffffff)
+    if (variant != 1 && assign_filter_applies(x, ld, variant == 2 && n < 4096 ? 4096 : n, d, cent, k) && n < 0x7fffffff)
         return launch_assign_filtered(x, ld, n, d, cent, k, assign, changed, st);
     // Few rows against many centroids -- the reference's index build is IVFOPQ::Add of ONE video, a few hundred frames over 8192 lists
     // (opq/src/IVFOPQ.cpp:135-163): with one thread per row walking every centroid such a call took 7.6 ms whatever its size (round 5,
     // tools/sweep_add_video.py).  The centroid range is cut over enough workgroups to fill the chip and folded in ascending order (the
     // same strict '<': same assignment), as the filter does for the rows it cannot decide.  The scratch is shared: the stream is drained
     // before the lock is given back, as in launch_assign_filtered.
-    if (g_assign_variant != 1 && changed == nullptr && n < 4096 && k >= 256 && d <= 128) {
+    if (variant != 1 && changed == nullptr && n < 4096 && k >= 256 && d <= 128) {
         // One grow-only scratch PER DEVICE with its own lock (round 6): handles on different devices (IVFOPQ::SetDevices adds
         // to them in turn) neither wait for each other nor free and reallocate each other's buffer.  Callers on one device still take
         // turns, and the stream is drained under the lock -- this entry is not capturable into a graph, like launch_assign_filtered.

@@ -195,9 +195,6 @@ __global__ __launch_bounds__(kBlock) void coarse_probe_tile_kernel(const float *
     }
 }
 
-static int g_probe_variant = 0;  // cvtmi_set_tuning("probe_variant"): 0 choose, 1 exact kernels only, 2 matrix-core filter wherever it applies
-void set_probe_variant(int v) { g_probe_variant = v; }
-
 // scratch the few-queries form needs behind the probe array: per (query, split) nprobe keys + nprobe list ids
 constexpr int PROBE_SPLITS_MAX = 64;
 // below this many queries the split form runs; from 256 on the matrix-core filter (assign_mfma.hip) applies and is faster (8192 lists:
@@ -211,9 +208,10 @@ size_t coarse_probe_scratch_bytes(int64_t nq, int nprobe)
 
 int launch_coarse_probe(const OpqModelDev &m, const float *q_rot, int64_t nq, int nprobe, int32_t *probe, hipStream_t st, void *scratch)
 {
+    const int variant = tune_probe_variant.geti();   // 0 choose, 1 exact kernels only, 2 matrix-core filter wherever it applies
     // few queries, many lists: every CU takes a range of the centroids (64 frames x 8192 lists on the 16-queries-per-workgroup kernel
     // below: four workgroups, 2.05 ms)
-    if (scratch && g_probe_variant == 0 && m.coarseK >= 1024 && nq > 0 && coarse_probe_scratch_bytes(nq, nprobe) > 0 && nprobe >= 1 && nprobe <= 128) {
+    if (scratch && variant == 0 && m.coarseK >= 1024 && nq > 0 && coarse_probe_scratch_bytes(nq, nprobe) > 0 && nprobe >= 1 && nprobe <= 128) {
         int splits = (m.coarseK + kBlock - 1) / kBlock;
         if (splits > PROBE_SPLITS_MAX) splits = PROBE_SPLITS_MAX;
         const int chunk = ((m.coarseK + splits - 1) / splits + kBlock - 1) / kBlock * kBlock;
@@ -226,7 +224,7 @@ int launch_coarse_probe(const OpqModelDev &m, const float *q_rot, int64_t nq, in
         CVTMI_HIP(hipGetLastError());
         return CVTMI_OK;
     }
-    if (g_probe_variant != 1 && coarse_probe_filter_applies(q_rot, g_probe_variant == 2 ? std::max<int64_t>(nq, 256) : nq, m.D, m.coarse, m.coarseK, nprobe))
+    if (variant != 1 && coarse_probe_filter_applies(q_rot, variant == 2 ? std::max<int64_t>(nq, 256) : nq, m.D, m.coarse, m.coarseK, nprobe))
         return launch_coarse_probe_filtered(q_rot, nq, m.D, m.coarse, m.coarseK, nprobe, probe, st);
     if (nq >= 64 && nprobe <= 128 && m.D <= 256) {
         const size_t lds = ((size_t)CPT_Q * m.D + (size_t)m.D * (CPT_TILE + 1)) * sizeof(float);

@@ -20,7 +20,5 @@ int comm_take_deferred(cvtmi_comm_t c);
 int comm_exchange_merge(cvtmi_comm_t c, int64_t nq, int k, int status, float *dist, int64_t *ids, hipStream_t st);
 // the communicators of one process (cvtmi_comm_create_all): grouped all-gathers, merge on comms[0]'s device
 int comm_exchange_merge_all(cvtmi_comm_t *comms, int ndev, int64_t nq, int k, const int *status, float *dist, int64_t *ids);
-void comm_set_force_rccl(int v);
-void comm_set_check_status(int v);
 
 }  // namespace cvtmi

@@ -103,14 +103,13 @@ int rccl_ready(RcclApi **out)
             return ::cvtmi::fail(CVTMI_ECOMM, "%s failed: %s (%s:%d)", #expr, (api)->GetErrorString(r__), __FILE__, __LINE__); \
     } while (0)
 
-int g_force_rccl = 0;  // cvtmi_set_tuning("comm_force_rccl"): world == 1 communicators go through RCCL too (tests on a 1-GPU box)
+// cvtmi_set_tuning("comm_force_rccl"): world == 1 communicators go through RCCL too (tests on a 1-GPU box)
 // cvtmi_set_tuning("comm_check_status"): what happens to the ranks' status words after every all-gather.
 //   2 (default) deferred: a kernel behind the merge looks at them on the device; if any rank failed it overwrites the call's results with
 //     (+inf, -1) and leaves (code, rank) in a host-mapped word of the communicator -- no stream synchronisation.  The error is returned by
 //     the NEXT call on the communicator, by cvtmi_comm_status, and by the host-pointer entries at once (they synchronise for their copy anyway).
 //   1 immediate: read back + stream synchronisation inside the call (every rank returns CVTMI_ECOMM from the failing call itself).
 //   0 ignored (only this rank's own failure is reported).
-int g_check_status = 2;
 constexpr size_t kSlotHeader = 16;
 
 constexpr uint32_t kCommMagic = 0x434f4d4du;
@@ -118,9 +117,6 @@ constexpr uint32_t kCommMagic = 0x434f4d4du;
 inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 }  // namespace
-
-void comm_set_force_rccl(int v) { g_force_rccl = v; }
-void comm_set_check_status(int v) { g_check_status = v; }
 
 }  // namespace cvtmi
 
@@ -255,7 +251,7 @@ int comm_take_deferred(cvtmi_comm_t c)
 // every rank's status word -> host; non-zero anywhere: CVTMI_ECOMM on every rank
 static int comm_check_statuses(cvtmi_comm_t c, size_t slot, int own_status, hipStream_t st)
 {
-    if (g_check_status != 1) return own_status == CVTMI_OK ? CVTMI_OK : fail(CVTMI_ECOMM, "the local search of rank %d failed with %d", c->rank, own_status);
+    if (tune_comm_check_status.geti() != 1) return own_status == CVTMI_OK ? CVTMI_OK : fail(CVTMI_ECOMM, "the local search of rank %d failed with %d", c->rank, own_status);
     if (!c->h_status) {
         c->h_status = new (std::nothrow) uint32_t[c->world];
         if (!c->h_status) return fail(CVTMI_ENOMEM, "communicator: out of host memory");
@@ -276,7 +272,7 @@ int comm_exchange_merge(cvtmi_comm_t c, int64_t nq, int k, int status, float *di
     if (nq <= 0) return CVTMI_OK;
     const size_t slot = comm_slot_bytes(nq, k);
     const std::string own = status != CVTMI_OK ? std::string(cvtmi_last_error()) : std::string();
-    const bool deferred = g_check_status == 2 && c->world > 1;
+    const bool deferred = tune_comm_check_status.geti() == 2 && c->world > 1;
     if (deferred) CVTMI_TRY(comm_sticky_ready(c));
     // what an earlier search left behind is reported AFTER this rank has entered the collective: the other ranks are on their way into it
     const int earlier = comm_take_deferred(c);
@@ -383,7 +379,7 @@ int cvtmi_comm_create(const void *id, int rank, int world, cvtmi_comm_t *out)
     if (!out) return fail(CVTMI_EINVAL, "cvtmi_comm_create: null out");
     *out = nullptr;
     if (world < 1 || rank < 0 || rank >= world) return fail(CVTMI_EINVAL, "cvtmi_comm_create: rank %d of %d", rank, world);
-    if ((world > 1 || g_force_rccl) && !id) return fail(CVTMI_EINVAL, "cvtmi_comm_create: null id");
+    if ((world > 1 || tune_comm_force_rccl.geti()) && !id) return fail(CVTMI_EINVAL, "cvtmi_comm_create: null id");
     int dev = 0;
     CVTMI_HIP(hipGetDevice(&dev));
     cvtmi_comm_s *c = new (std::nothrow) cvtmi_comm_s();
@@ -392,7 +388,7 @@ int cvtmi_comm_create(const void *id, int rank, int world, cvtmi_comm_t *out)
     // the word of the deferred status check is allocated HERE, before anybody is inside a collective: a rank that cannot get it fails at
     // creation, not on its way into a search's all-gather (where its peers would wait for ever)
     if (world > 1) { const int rs = comm_sticky_ready(c); if (rs != CVTMI_OK) { delete c; return rs; } }
-    if (world > 1 || g_force_rccl) {
+    if (world > 1 || tune_comm_force_rccl.geti()) {
         RcclApi *api = nullptr;
         int rc = rccl_ready(&api);
         if (rc != CVTMI_OK) { if (c->h_sticky) (void)hipHostFree(c->h_sticky); delete c; return rc; }

@@ -345,14 +345,12 @@ static bool sq8_wave_aligned(const void *x, const void *codes, const void *vmin,
 {
     return ((uintptr_t)x & 15) == 0 && ((uintptr_t)codes & 3) == 0 && ((uintptr_t)vmin & 15) == 0 && ((uintptr_t)vdiff & 15) == 0;
 }
-static bool sq8_filter_on();
-static int g_sq8_encode_wave = 1;
+static bool sq8_filter_on() { return tune_sq8_filter.geti() != 0; }   // cvtmi_set_tuning("sq8_filter"): 0 = the exact chain for every element (the round 2 - 4 kernels)
 // (conservative: both the training and the encode dispatch take the wave kernels under these conditions)
 static bool sq8_wave_takes(int d, int64_t n, const void *x, const void *codes, const void *vmin, const void *vdiff)
 {
-    return g_sq8_encode_wave && sq8_filter_on() && sq8_wave_width(d) && n >= (d > 512 ? 1 : 4096) && sq8_wave_aligned(x, codes, vmin, vdiff);
+    return tune_sq8_encode_wave.geti() && sq8_filter_on() && sq8_wave_width(d) && n >= (d > 512 ? 1 : 4096) && sq8_wave_aligned(x, codes, vmin, vdiff);
 }   // cvtmi_set_tuning("sq8_encode_wave"): 0 = the tile kernel for every width
-void set_sq8_encode_wave(int v) { g_sq8_encode_wave = v; }
 
 static int launch_sq8_encode_group(const float *vmin, const float *vdiff, int d, float *x, int64_t n, int l2norm, int write_back, uint8_t *codes, hipStream_t st);
 int launch_sq8_encode_rows(const float *vmin, const float *vdiff, int d, float *x, int64_t n, int l2norm, int write_back,
@@ -360,10 +358,10 @@ int launch_sq8_encode_rows(const float *vmin, const float *vdiff, int d, float *
 {
     if (n <= 0) return CVTMI_OK;
     // 64-d / 128-d rows (round 6): several rows per wave through the same decision filter (sq8_encode_group_f_kernel)
-    if (g_sq8_encode_wave && sq8_filter_on() && (d == 64 || d == 128) && n >= 4096 && sq8_wave_aligned(x, codes, vmin, vdiff))
+    if (tune_sq8_encode_wave.geti() && sq8_filter_on() && (d == 64 || d == 128) && n >= 4096 && sq8_wave_aligned(x, codes, vmin, vdiff))
         return launch_sq8_encode_group(vmin, vdiff, d, x, n, l2norm, write_back, codes, st);
     // (rows wider than the tile kernel's 512 floats: at every row count -- the two-pass kernels' norm pass alone costs 100 us for ONE row)
-    if (g_sq8_encode_wave && sq8_wave_width(d) && n >= (d > 512 ? 1 : 4096) && sq8_wave_aligned(x, codes, vmin, vdiff) && (d <= 512 || sq8_filter_on()))
+    if (tune_sq8_encode_wave.geti() && sq8_wave_width(d) && n >= (d > 512 ? 1 : 4096) && sq8_wave_aligned(x, codes, vmin, vdiff) && (d <= 512 || sq8_filter_on()))
         return launch_sq8_encode_wave(vmin, vdiff, d, x, n, l2norm, write_back, codes, st);
     if (sq8_tile_ok(d, x, codes, vmin, vdiff)) {
         Sq8Args a{};
@@ -1329,11 +1327,7 @@ __global__ __launch_bounds__(kBlock) void sq8_encode_group_f_kernel(const float 
 }
 static bool sq8_group_width(int d) { return d == 64 || d == 128; }
 
-static std::atomic<int> g_sq8_flags{1};    // cvtmi_set_tuning("sq8_flags"): bit 0 = wave sums on DPP instead of the ds_bpermute butterfly
-void set_sq8_flags(int v) { g_sq8_flags = v; }
-static std::atomic<int> g_sq8_filter{1};   // cvtmi_set_tuning("sq8_filter"): 0 = the exact chain for every element (the round 2 - 4 kernels)
-void set_sq8_filter(int v) { g_sq8_filter = v != 0 ? 1 : 0; }
-static bool sq8_filter_on() { return g_sq8_filter.load() != 0; }
+// cvtmi_set_tuning("sq8_flags"): bit 0 = wave sums on DPP instead of the ds_bpermute butterfly
 constexpr int64_t SQ8_SAMPLE_ROWS = 8192;   // rows of the training pass that seeds every wave's extremes
 
 // ---- the sign of a zero minimum (round 5) ----------------------------------------------------------------------------------
@@ -1404,12 +1398,10 @@ static void launch_sq8_train_wave_f(int NF, bool norm, unsigned blocks, hipStrea
     if (norm) launch_sq8_train_wave_f_n<true>(NF, blocks, st, x, n, kmin, kmax, seeded, flags);
     else launch_sq8_train_wave_f_n<false>(NF, blocks, st, x, n, kmin, kmax, seeded, flags);
 }
-static int g_sq8_wave_blocks = 3;
-void set_sq8_wave_blocks(int v) { g_sq8_wave_blocks = v; }
 static unsigned sq8_group_blocks(int64_t n, int d)
 {
     const int64_t groups = (n * d + 255) / 256, per_wg = kBlock / 64;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + per_wg - 1) / per_wg, 256 * g_sq8_wave_blocks));
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + per_wg - 1) / per_wg, 256 * tune_sq8_wave_blocks.geti()));
 }
 static void launch_sq8_train_group(int d, bool norm, unsigned blocks, hipStream_t st, const float *x, int64_t n, uint32_t *kmin, uint32_t *kmax, int seeded)
 {
@@ -1452,14 +1444,14 @@ int launch_sq8_train(const float *x, int64_t n, int d, int l2norm, float *den_sc
         } else if ((wave_f || (l2norm && (d == 256 || d == 512))) && (((uintptr_t)x) & 15) == 0 && n >= (wave_f && d > 512 ? 1 : 4096)) {
             // whole rows per wave, no LDS tile (the tile kernel's phases serialise behind its barriers: 3.3 TB/s at d = 512)
             const int64_t rows_per_wg = kBlock / 64;
-            const unsigned blocks = (unsigned)std::min<int64_t>((n + rows_per_wg - 1) / rows_per_wg, 256 * g_sq8_wave_blocks);
+            const unsigned blocks = (unsigned)std::min<int64_t>((n + rows_per_wg - 1) / rows_per_wg, 256 * tune_sq8_wave_blocks.geti());
             if (wave_f) {
                 // sample pass over the first rows (its extremes seed every wave of the main pass: "new extreme" is rare from the start),
                 // then the rest; both through the filter kernel, the sample unseeded
                 const int64_t ns = n >= 8 * SQ8_SAMPLE_ROWS ? SQ8_SAMPLE_ROWS : 0;
                 const float *xr = x + ns * d;
                 const unsigned sblocks = (unsigned)((ns / 16 + rows_per_wg - 1) / rows_per_wg);   // 16 rows per wave of the sample
-                const int fl = g_sq8_flags.load();
+                const int fl = tune_sq8_flags.geti();
                 if (ns) launch_sq8_train_wave_f(d / 256, l2norm != 0, sblocks, st, x, ns, kmin, kmax, 0, fl);
                 launch_sq8_train_wave_f(d / 256, l2norm != 0, blocks, st, xr, n - ns, kmin, kmax, ns ? 1 : 0, fl);
             } else if (d == 512) hipLaunchKernelGGL((sq8_train_wave_kernel<2>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax);
@@ -1494,9 +1486,9 @@ static int launch_sq8_encode_wave(const float *vmin, const float *vdiff, int d, 
                                   uint8_t *codes, hipStream_t st)
 {
     const int64_t rows_per_wg = kBlock / 64;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + rows_per_wg - 1) / rows_per_wg, 256 * g_sq8_wave_blocks);
-    if (g_sq8_filter.load()) {
-        const int fl = g_sq8_flags.load();
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + rows_per_wg - 1) / rows_per_wg, 256 * tune_sq8_wave_blocks.geti());
+    if (sq8_filter_on()) {
+        const int fl = tune_sq8_flags.geti();
 #define CVTMI_SQ8_ENC(NF_)                                                                                                                                    \
         do {                                                                                                                                                  \
             if (l2norm) hipLaunchKernelGGL((sq8_encode_wave_f_kernel<NF_, true>), dim3(blocks), dim3(kBlock), 0, st, vmin, vdiff, x, n, write_back, codes, fl); \

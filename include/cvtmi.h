@@ -204,6 +204,9 @@ int cvtmi_set_device(int device);
  *   "scans_dbg" / "flat_f32_dbg"  measurement switches of the small-batch scan and of the fp32 stream (phases skipped: results are WRONG
  *                     when non-zero; development only) */
 int cvtmi_set_tuning(const char *name, int64_t value);
+/* The value a key holds now: its default, or what the last accepted cvtmi_set_tuning made of its argument (clamped, snapped).
+ * A null argument or an unknown key gives CVTMI_EINVAL; no device is needed. */
+int cvtmi_get_tuning(const char *name, int64_t *value);
 
 /* ---------------------------------------------------------------- OPQ model + code index ---- */
 /*
