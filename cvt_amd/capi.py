@@ -189,6 +189,33 @@ class OpqIndex:
         tot = int(off[-1])
         return off, vid[:tot], codes[:tot]
 
+    # ---- removal ----
+    def _remove(self, fn, ids, dt, extra, want_remap):
+        n0 = self.ntotal
+        removed = C.c_int64(0)
+        if _is_torch(ids):
+            import torch
+            assert ids.dtype == getattr(torch, dt) and ids.is_cuda
+            remap = torch.empty(n0, dtype=torch.int64, device=ids.device) if want_remap else None
+            _check(getattr(lib(), fn + "_dev")(self.h, _ptr(ids), C.c_int64(ids.shape[0]), *extra, C.byref(removed), _ptr(remap), _stream()))
+        else:
+            ids = _np(ids, dt).reshape(-1)
+            remap = np.empty(n0, dtype=np.int64) if want_remap else None
+            _check(getattr(lib(), fn)(self.h, _ptr(ids), C.c_int64(ids.shape[0]), *extra, C.byref(removed), _ptr(remap)))
+        return (removed.value, remap) if want_remap else removed.value
+
+    def remove_videos(self, video_ids, renumber=False, want_remap=False):
+        """Drop every entry whose video id is in `video_ids` (cvtmi_opq_remove_videos; int32, numpy or a torch device tensor).  The kept
+        entries close up in insertion order; renumber=True lowers every kept video id by the number of distinct removed ids below
+        it.  Returns the number of entries dropped, with want_remap (dropped, remap): remap[i] = new insertion index of old entry
+        i, or -1."""
+        return self._remove("cvtmi_opq_remove_videos", video_ids, "int32", (C.c_int(1 if renumber else 0),), want_remap)
+
+    def remove_ids(self, ids, want_remap=False):
+        """Drop every entry whose id (id_base + insertion index, what the searches report) is in `ids` (cvtmi_opq_remove_ids; int64,
+        numpy or a torch device tensor).  Returns like remove_videos."""
+        return self._remove("cvtmi_opq_remove_ids", ids, "int64", (), want_remap)
+
     # ---- query ----
     def lut(self, q_rot, list_id=None):
         nq = q_rot.shape[0]

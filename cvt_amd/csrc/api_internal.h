@@ -165,6 +165,8 @@ struct cvtmi_opq_s {
     int64_t range_last[8] = {};             // ... and of the last range search (cvtmi_opq_last_range_plan)
     // scratch of the calls that run one at a time (query_video: probe lists, rotated queries)
     DevBuf s_qrot, s_probe, s_rot;
+    DevBuf rm_scratch;         // removal (opq_remove.hip): bitmap, tile offsets, the table of removal ids, the chunk-sized row scratch
+    int64_t p_rm_chunk = 0;    // "remove_chunk": rows the move works on at a time (0 = the default)
     // Searches (cvtmi_opq_search*) run CONCURRENTLY, as the reference's QueryThrehold de facto may (opq/src/IVFOPQ.cpp:322-422 only
     // reads the index): each leases a scratch set from this pool for the duration of the call (OpqLease) and holds `rw` shared;
     // everything else -- add / reset / reserve, the lazily built copies of the rows, the one-at-a-time entries above -- holds it

@@ -1,5 +1,5 @@
 // api_opq.hip -- the OPQ / IVFOPQ handle of the C ABI (include/cvtmi.h): model, encode, add, the list-ordered copy, the exhaustive
-// search and its sharded forms, the per-video query, the IVF search, parameters.
+// search and its sharded forms, the per-video query, the IVF search, removal, parameters.
 #include <string.h>
 
 #include <algorithm>
@@ -103,7 +103,7 @@ int cvtmi_opq_destroy(cvtmi_opq_t h)
     if (h->d_perm) (void)hipFree(h->d_perm);
     h->codes.release(); h->lists.release(); h->videos.release(); h->codes_rot.release(); h->codes16.release();
     h->csr_codes.release(); h->csr_videos.release(); h->csr_off.release(); h->csr_scratch.release(); h->csr_stats.release(); h->csr_entry.release();
-    h->s_qrot.release(); h->s_probe.release(); h->s_rot.release();
+    h->s_qrot.release(); h->s_probe.release(); h->s_rot.release(); h->rm_scratch.release();
     h->pool.destroy();
     for (int e = 0; e < cvtmi_opq_s::kEvRing; ++e) {
         if (h->ev0[e]) (void)hipEventDestroy(h->ev0[e]);
@@ -1262,6 +1262,130 @@ int cvtmi_opq_last_range_plan(cvtmi_opq_t h, int64_t out[8])
     return CVTMI_OK;
 }
 
+// ---- removal: one stable compaction of the resident arrays on the device (opq_remove.hip) ----
+// The set is either a sorted table of distinct video ids (host memory: it is uploaded into the scratch) or a device array of entry
+// ids.  Everything the call needs is reserved before the first row moves; the host waits once, for the kept count, BEFORE the move:
+// a call that drops nothing then leaves the handle and its derived copies alone.
+static int opq_remove_common(cvtmi_opq_t h, const int32_t *table, int64_t T, const int64_t *ids_dev, int64_t n_ids, bool by_ids, int renumber,
+                             int64_t *removed, int64_t *remap_dev, hipStream_t st)
+{
+    if (removed) *removed = 0;
+    const int64_t n = h->n;
+    if (n == 0) return CVTMI_OK;
+    const RmPlan p = rm_plan(n, h->m.M, by_ids ? 0 : T, h->p_rm_chunk);
+    CVTMI_TRY(h->rm_scratch.reserve(p.bytes));
+    void *S = h->rm_scratch.p;
+    if (by_ids) {
+        CVTMI_TRY(launch_rm_mark_ids(p, S, ids_dev, n_ids, h->id_base, st));
+    } else {
+        if (T > 0) CVTMI_HIP(hipMemcpyAsync(static_cast<char *>(S) + p.off_table, table, (size_t)T * 4, hipMemcpyHostToDevice, st));
+        CVTMI_TRY(launch_rm_mark_videos(p, S, h->has_videos ? h->videos.as<int32_t>() : nullptr, st));
+    }
+    int64_t kept = 0;
+    CVTMI_HIP(hipMemcpyAsync(&kept, static_cast<char *>(S) + p.off_total, sizeof kept, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    if (kept < 0 || kept > n) return fail(CVTMI_ESTATE, "cvtmi_opq_remove: kept count %lld of %lld entries", (long long)kept, (long long)n);
+    const int64_t dropped = n - kept;
+    const bool shift = !by_ids && renumber && T > 0;   // ids of the set below a kept one lower it, whether or not they are in the index
+    if (dropped == 0 && !shift) {
+        if (remap_dev) CVTMI_TRY(launch_rm_fill_remap(remap_dev, n, 1, st));
+        return CVTMI_OK;
+    }
+    if (!h->has_videos) {   // the implicit video ids (insertion indices) become an array, as for the first explicit id of an append
+        CVTMI_TRY(h->videos.grow((size_t)std::max<int64_t>(n, 4096) * 4, 0, st));
+        CVTMI_TRY(fill_i32(h->videos.as<int32_t>(), 0, n, 0, 1, st));
+        h->has_videos = true;
+    }
+    if (dropped == 0) {   // only video ids change: the code rows and their rotated / padded copies stay valid
+        CVTMI_TRY(launch_rm_renumber(p, S, h->videos.as<int32_t>(), st));
+        if (remap_dev) CVTMI_TRY(launch_rm_fill_remap(remap_dev, n, 1, st));
+        h->csr_valid = false; h->csr_entry_valid = false;
+        return CVTMI_OK;
+    }
+    CVTMI_TRY(launch_rm_move(p, S, h->codes.as<uint8_t>(), h->has_lists ? h->lists.as<int32_t>() : nullptr, h->videos.as<int32_t>(), shift ? 1 : 0,
+                             remap_dev, st));
+    h->n = kept;
+    h->rot_n = 0; h->pad_n = 0; h->csr_valid = false; h->csr_entry_valid = false;
+    if (removed) *removed = dropped;
+    return CVTMI_OK;
+}
+
+// arguments first, before anything touches the device
+static int opq_remove_check(const char *fn, cvtmi_opq_t h, const void *set, int64_t count)
+{
+    if (!h) return fail(CVTMI_EINVAL, "%s: null handle", fn);
+    if (count < 0 || (count > 0 && !set)) return fail(CVTMI_EINVAL, "%s: bad arguments", fn);
+    return CVTMI_OK;
+}
+
+// the distinct ids of the set, ascending
+static int opq_remove_table(const int32_t *ids, int64_t nv, std::vector<int32_t> &tab)
+{
+    try {
+        tab.assign(ids, ids + nv);
+    } catch (...) {
+        return fail(CVTMI_ENOMEM, "cvtmi_opq_remove_videos: out of host memory");
+    }
+    std::sort(tab.begin(), tab.end());
+    tab.erase(std::unique(tab.begin(), tab.end()), tab.end());
+    return CVTMI_OK;
+}
+
+int cvtmi_opq_remove_videos_dev(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, int renumber, int64_t *removed, int64_t *remap, void *stream)
+{
+    CVTMI_TRY(opq_remove_check(__func__, h, video_ids, nv));
+    CHECK_H_SERIAL(h, stream);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int32_t> raw, tab;
+    if (nv > 0) {   // the set is sorted on the host: it comes down first (4 bytes per id)
+        try {
+            raw.resize((size_t)nv);
+        } catch (...) {
+            return fail(CVTMI_ENOMEM, "cvtmi_opq_remove_videos: out of host memory");
+        }
+        CVTMI_HIP(hipMemcpyAsync(raw.data(), video_ids, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(stream_wait(st));
+        CVTMI_TRY(opq_remove_table(raw.data(), nv, tab));
+    }
+    return opq_remove_common(h, tab.data(), (int64_t)tab.size(), nullptr, 0, false, renumber, removed, remap, st);
+}
+
+int cvtmi_opq_remove_videos(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, int renumber, int64_t *removed, int64_t *remap)
+{
+    CVTMI_TRY(opq_remove_check(__func__, h, video_ids, nv));
+    CHECK_H_SERIAL(h, nullptr);
+    std::vector<int32_t> tab;
+    if (nv > 0) CVTMI_TRY(opq_remove_table(video_ids, nv, tab));
+    const int64_t n0 = h->n;
+    Tmp dm;
+    if (remap && n0 > 0) CVTMI_TRY(dm.alloc((size_t)n0 * sizeof(int64_t)));
+    CVTMI_TRY(opq_remove_common(h, tab.data(), (int64_t)tab.size(), nullptr, 0, false, renumber, removed, dm.as<int64_t>(), nullptr));
+    if (dm.p) CVTMI_HIP(hipMemcpy(remap, dm.p, (size_t)n0 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    else CVTMI_HIP(stream_wait(nullptr));
+    return CVTMI_OK;
+}
+
+int cvtmi_opq_remove_ids_dev(cvtmi_opq_t h, const int64_t *ids, int64_t n_ids, int64_t *removed, int64_t *remap, void *stream)
+{
+    CVTMI_TRY(opq_remove_check(__func__, h, ids, n_ids));
+    CHECK_H_SERIAL(h, stream);
+    return opq_remove_common(h, nullptr, 0, ids, n_ids, true, 0, removed, remap, (hipStream_t)stream);
+}
+
+int cvtmi_opq_remove_ids(cvtmi_opq_t h, const int64_t *ids, int64_t n_ids, int64_t *removed, int64_t *remap)
+{
+    CVTMI_TRY(opq_remove_check(__func__, h, ids, n_ids));
+    CHECK_H_SERIAL(h, nullptr);
+    const int64_t n0 = h->n;
+    Tmp di, dm;
+    if (n_ids > 0 && n0 > 0) CVTMI_TRY(di.upload(ids, (size_t)n_ids * sizeof(int64_t)));
+    if (remap && n0 > 0) CVTMI_TRY(dm.alloc((size_t)n0 * sizeof(int64_t)));
+    CVTMI_TRY(opq_remove_common(h, nullptr, 0, di.as<int64_t>(), di.p ? n_ids : 0, true, 0, removed, dm.as<int64_t>(), nullptr));
+    if (dm.p) CVTMI_HIP(hipMemcpy(remap, dm.p, (size_t)n0 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    else CVTMI_HIP(stream_wait(nullptr));
+    return CVTMI_OK;
+}
+
 int cvtmi_opq_set_param(cvtmi_opq_t h, const char *name, int64_t value)
 {
     if (!h || !name) return fail(CVTMI_EINVAL, "cvtmi_opq_set_param: null");
@@ -1277,6 +1401,11 @@ int cvtmi_opq_set_param(cvtmi_opq_t h, const char *name, int64_t value)
         return CVTMI_OK;
     }
     if (!strcmp(name, "profile")) { h->p_profile = value != 0; return CVTMI_OK; }
+    if (!strcmp(name, "remove_chunk")) {
+        if (value < 0 || value > ((int64_t)1 << 32)) return fail(CVTMI_EINVAL, "cvtmi_opq_set_param: remove_chunk must be 0 .. 2^32 rows");
+        h->p_rm_chunk = value ? rm_chunk_rows(value) : 0;   // whole tiles
+        return CVTMI_OK;
+    }
     if (!strcmp(name, "scan_lazy")) { h->p_lazy = value != 0; return CVTMI_OK; }
     if (!strcmp(name, "scan_small")) { h->p_small = value != 0; return CVTMI_OK; }
     if (!strcmp(name, "scan_share")) { h->p_share = value != 0; return CVTMI_OK; }

@@ -165,6 +165,27 @@ int launch_csr_build(const int32_t *lists, const int32_t *videos, const uint8_t 
                      int64_t *list_off, uint8_t *out_codes, int32_t *out_videos, void *stats_out, hipStream_t st,
                      uint32_t *out_entry = nullptr);   // out_entry: [n] insertion index per entry of the copy, or null
 
+// ---- opq_remove.hip ----  stable compaction of the insertion-ordered entry arrays (cvtmi_opq_remove_videos / _ids)
+constexpr int kRmTile = 256;                    // rows of a tile: the unit of the kept counts, of a workgroup of the move, of "remove_chunk"
+constexpr int64_t kRmChunkDefault = 1 << 22;    // rows the move works on at a time (96 MB of scratch at M = 16)
+int64_t rm_chunk_rows(int64_t wanted);          // "remove_chunk" as it is used: 0 = the default, rounded up to whole tiles
+// the areas of one call inside its scratch: bitmap of the dropped rows, tile counts / offsets, the two scan levels, the sorted
+// table of distinct removal ids (the caller copies T ids to off_table before the mark), the chunk-sized row scratch
+struct RmPlan {
+    int64_t n = 0, ntiles = 0, chunk = 0, T = 0;
+    int nblk = 0, M = 0;
+    size_t off_drop = 0, off_tile = 0, off_bsum = 0, off_boff = 0, off_total = 0, off_table = 0, off_codes = 0, off_lists = 0, off_videos = 0, bytes = 0;
+};
+RmPlan rm_plan(int64_t n, int M, int64_t table_len, int64_t chunk_rows);
+// mark + scan (n > 0): afterwards the int64 at off_total holds the kept count.  videos null = implicit ids (the insertion index)
+int launch_rm_mark_videos(const RmPlan &p, void *scratch, const int32_t *videos, hipStream_t st);
+int launch_rm_mark_ids(const RmPlan &p, void *scratch, const int64_t *ids, int64_t n_ids, int64_t id_base, hipStream_t st);
+// the chunked move behind a mark: lists may be null (no list array), remap [n] may be null; renumber != 0: kept video ids drop by
+// their rank in the table
+int launch_rm_move(const RmPlan &p, void *scratch, uint8_t *codes, int32_t *lists, int32_t *videos, int renumber, int64_t *remap, hipStream_t st);
+int launch_rm_renumber(const RmPlan &p, void *scratch, int32_t *videos, hipStream_t st);   // the renumbering alone, in place
+int launch_rm_fill_remap(int64_t *remap, int64_t n, int identity, hipStream_t st);         // remap[i] = i, or -1
+
 // ---- ivf_search.hip ----  k smallest (score, id) over the probed lists of every query (cvtmi_opq_search_ivf)
 // one workgroup per (query, group of G consecutive probe slots, piece of rows_per_piece rows of each list of the group)
 struct IvfPlan {

@@ -249,6 +249,34 @@ int IVFOPQ::RangeSearchProbe(const float *q, int nq, int nprobe, float radius, s
                                       videos ? (int32_t *)videos->data() : NULL) == CVTMI_OK ? 1 : 0;
 }
 
+int IVFOPQ::RemoveVideos(const std::vector<int> &videoIds)
+{
+    m_err.clear();
+    if (!ensureHandle()) return -1;
+    if (m_hs.size() > 1 || m_comm) {
+        m_err = "RemoveVideos: removal runs on one GPU; not available after SetShard / SetDevices";
+        return -1;
+    }
+    static_assert(sizeof(int) == sizeof(int32_t), "video id width");
+    // only ids that name a video: the renumbering counts every id of the set, and m_imgLocation loses the same slots
+    std::vector<int32_t> ids;
+    for (size_t i = 0; i < videoIds.size(); ++i)
+        if (videoIds[i] >= 0 && videoIds[i] < m_imgNum) ids.push_back(videoIds[i]);
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    int64_t removed = 0;
+    if (cvtmi_opq_remove_videos(m_h, ids.data(), (int64_t)ids.size(), /*renumber=*/1, &removed, NULL) != CVTMI_OK) return -1;
+    int kept = 0;
+    size_t next = 0;
+    for (int i = 0; i < m_imgNum; ++i) {
+        if (next < ids.size() && ids[next] == i) { ++next; continue; }
+        if (kept != i) m_imgLocation[kept] = m_imgLocation[i];
+        ++kept;
+    }
+    m_imgNum = kept;
+    return (int)removed;
+}
+
 void IVFOPQ::SetShard(cvtmi_comm_s *comm, long long id_base)
 {
     m_comm = comm; m_idBase = id_base;

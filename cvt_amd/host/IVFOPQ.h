@@ -54,6 +54,11 @@ public:
     // q is RAW (un-rotated).  1 ok / 0 failure (lastError()); single-GPU only, like SearchTopKProbe.
     int RangeSearchProbe(const float *q, int nq, int nprobe, float radius, std::vector<long long> &lims, std::vector<float> &dist,
                          std::vector<long long> &ids, std::vector<int> *videos = NULL);
+    // drop the videos with these ids (their position in IndexDatabase's list / the index file) from the index on the device
+    // (cvtmi_opq_remove_videos with renumber): the videos behind them move up, m_imgLocation and numImages() follow, and SaveIndex
+    // then writes exactly the file IndexDatabase writes over the kept feature files alone.  Ids outside [0, numImages()) and
+    // duplicates are ignored.  Returns the number of entries removed, or -1 (lastError()); single-GPU only, like SearchTopKProbe.
+    int RemoveVideos(const std::vector<int> &videoIds);
     std::string lastError() const;
     // row-sharded operation (one process per GPU): this object holds the row block that starts at global
     // row id_base; with a communicator set (cvtmi_comm_t, include/cvtmi.h) SearchTopK returns the GLOBAL top k on every

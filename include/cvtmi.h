@@ -344,6 +344,46 @@ int cvtmi_opq_range_search_ivf_dev(cvtmi_opq_t h, const float *q, int64_t nq, in
  * cut into pieces only where G == 1; rule 4 = the spill records per part were cut down to fit "ivf_part_cap_mb". */
 int cvtmi_opq_last_range_plan(cvtmi_opq_t h, int64_t out[8]);
 
+/* Removal: drop entries from the resident index on the device (faiss remove_ids; the reference itself can only rebuild).
+ *   Set      cvtmi_opq_remove_videos drops every entry whose video id is in video_ids[nv] -- the id it was added with, or its
+ *            insertion index where none was ever given.  cvtmi_opq_remove_ids drops every entry whose id is in ids[n_ids] -- id_base +
+ *            insertion index, what cvtmi_opq_search / _search_ivf / _range_search_ivf report.  Both sets may be unsorted, may hold
+ *            duplicates and may name ids that are not in the index (ignored); any int32 is a valid video id, negative values and
+ *            both extremes included.  The result never depends on the order or multiplicity of the set.
+ *   Result   The kept entries close up in insertion order: kept entry number j (counting from 0 in the old order) has insertion
+ *            index j afterwards and reports id_base + j.  Codes, list ids and video ids move together; entries whose list id is
+ *            outside [0, coarseK) move like any other.  *removed (may be NULL) = entries dropped.  remap (may be NULL) has room for
+ *            the OLD cvtmi_opq_ntotal: remap[i] = new insertion index of old entry i, or -1 if it was dropped.  cvtmi_opq_ntotal
+ *            reports the new count, a later cvtmi_opq_add_codes appends behind the kept entries.
+ *   renumber == 0: kept entries keep their video ids.  On a handle whose video ids were implicit the call first makes them an
+ *            array (as cvtmi_opq_add_codes does for the first explicit id), so an entry keeps its old number although its
+ *            insertion index changed.  renumber != 0: a kept video id v becomes v - (number of DISTINCT ids in video_ids that are
+ *            smaller than v) -- the numbering IVFOPQ::IndexDatabase would have produced had the removed files never been in its
+ *            list; ids of the set count whether or not they occur in the index.  cvtmi_opq_remove_ids never touches video ids,
+ *            apart from making implicit ones an array when at least one entry is dropped.
+ *   Equivalence  Afterwards every entry of the handle (cvtmi_opq_search, _search_sharded, _query_video, _search_ivf,
+ *            _range_search_ivf, _get_entries, cvtmi_hnsw_search_adc* over it) answers exactly as a new handle of the same model and
+ *            id_base would that had been given only the kept entries in their order, with the video ids as described: bit for bit,
+ *            distances, ids, lims, order of the hits and list_off.  The derived copies of the rows (rotated / padded rows, the
+ *            list-ordered copy) are rebuilt by the first search that needs them, as after an append.  A call that drops nothing
+ *            leaves the handle, those copies included, as it was (*removed = 0, remap the identity) -- unless renumber lowers video
+ *            ids, which are then rewritten in place.  A call that drops everything leaves an empty, usable index.
+ *   Calling  Mutating and exclusive, like cvtmi_opq_add_codes.  NULL handle, a negative count, a NULL set with a positive count ->
+ *            CVTMI_EINVAL before any device work.  All scratch is reserved before the first row moves: on CVTMI_ENOMEM the index is
+ *            unchanged.  Memory is not given back; cvtmi_opq_reserve keeps its meaning.  The host entries return when the index is
+ *            in its new state.  The _dev entries (set and remap are device pointers) run on `stream` and WAIT on it once for the
+ *            8-byte kept count the host needs for cvtmi_opq_ntotal; cvtmi_opq_remove_videos_dev also waits for its set to reach
+ *            the host, where it is sorted (4 bytes per id).
+ *   Shards   On a row shard (cvtmi_opq_set_id_base) each rank removes from its own handle; id_base stays, so afterwards the ids
+ *            are no longer contiguous across ranks.  There is no collective form.
+ * The work is a mark (4 bytes per entry), a scan of per-tile counts and a move in chunks of "remove_chunk" rows
+ * (cvtmi_opq_set_param; scratch of one chunk, never a second copy of an array); rows before the first dropped entry are not moved. */
+int cvtmi_opq_remove_videos(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, int renumber, int64_t *removed, int64_t *remap);
+int cvtmi_opq_remove_videos_dev(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, int renumber, int64_t *removed, int64_t *remap,
+                                void *stream);
+int cvtmi_opq_remove_ids(cvtmi_opq_t h, const int64_t *ids, int64_t n_ids, int64_t *removed, int64_t *remap);
+int cvtmi_opq_remove_ids_dev(cvtmi_opq_t h, const int64_t *ids, int64_t n_ids, int64_t *removed, int64_t *remap, void *stream);
+
 /* Tuning / measurement hooks (no effect on results).
  *   "splits"   row splits per query group of the scan (0 = automatic)
  *   "qtile"    queries sharing one pass over the codes: 1, 2, 4 or 8 (0 = automatic)
@@ -375,7 +415,9 @@ int cvtmi_opq_last_range_plan(cvtmi_opq_t h, int64_t out[8]);
  *                 pass collects the rows below it into per-workgroup lists, one workgroup per query selects (exact fall-back inside the
  *                 kernel when a list overflows) -- four launches, rotation included, no partial lists and no merge
  *   "groups_a", "splits_b"  force that two-region shape: the first groups_a query groups use "splits" row
- *                 splits, the others splits_b (> splits); 0 = planner's choice */
+ *                 splits, the others splits_b (> splits); 0 = planner's choice
+ *   "remove_chunk"  rows cvtmi_opq_remove_* moves at a time (0 = default, 4 194 304): the scratch of a removal holds one chunk.
+ *                 Rounded UP to whole tiles of 256 rows (1 .. 256 give one tile); negative values fail with CVTMI_EINVAL */
 int cvtmi_opq_set_param(cvtmi_opq_t h, const char *name, int64_t value);
 /* With "profile" on: MEAN duration of the scan-kernel launches recorded since the previous call
  * (the 64 most recent are kept) and the algorithmic code bytes ONE launch reads
