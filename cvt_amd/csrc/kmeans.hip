@@ -317,8 +317,9 @@ int launch_kmeans_assign_split(const float *x, int64_t ld, int64_t n, int d, con
 // the final rounding to float: sums accumulated in ANY order differ from the index-order sum by at most
 // 2 (count) 2^-53 sum |x| (each of the <= count - 1 additions of either order rounds within 2^-53 of a partial sum that
 // is bounded by sum |x|).  So rows are scattered with double atomics in LDS (sum, sum of |x|, count), and where
-// float((S - E) / count) == float((S + E) / count) that float is the reference's centroid, proven; where it is not (and
-// for non-finite sums) the centroid is flagged and recomputed in index order by the wave-per-centroid kernel.
+// float((S - E) / count) and float((S + E) / count) are the same float (bit for bit: -0.0f and +0.0f are two) that float is the
+// reference's centroid, proven; where they are not (and for non-finite sums) the centroid is flagged and recomputed in index order
+// by the wave-per-centroid kernel.
 // k <= 512: the partial sums of a block of rows are kept in LDS (8 dimensions per workgroup column: k x 8 doubles twice),
 // one LDS atomic per element, and reach the global arrays once per workgroup
 constexpr int KM_LK = 512;   // centroids the LDS variant holds
@@ -375,7 +376,9 @@ __global__ __launch_bounds__(kBlock) void kmeans_finalize_kernel(const double *_
     if (m == 0) return;  // an empty cluster keeps its centroid
     const double S = sum[e], E = 2.0 * (double)m * 0x1p-53 * asum[e] * 1.0000001, dm = (double)m;
     const float lo = (float)__ddiv_rn(S - E, dm), hi = (float)__ddiv_rn(S + E, dm);
-    if (lo == hi) cent[e] = lo;  // proven: the index-order sum lies in [S - E, S + E], division and rounding are monotone
+    // proven: the index-order sum lies in [S - E, S + E], division and rounding are monotone.  The same float, not merely equal ones:
+    // around S = 0 (members that cancel) lo = -0.0f and hi = +0.0f compare equal and the index-order sum has one sign of the two
+    if (lo == hi && __float_as_uint(lo) == __float_as_uint(hi)) cent[e] = lo;
     else redo[c] = 1;            // (also NaN / inf): index order decides
 }
 
