@@ -647,6 +647,28 @@ class FlatIndex:
     def set_id_base(self, base):
         _check(lib().cvtmi_flat_set_id_base(self.h, C.c_int64(base)))
 
+    def remove_labels(self, labels, want_remap=False):
+        """Drop every row whose label (what search reports: id_base + row while labels are implicit) is in `labels`
+        (cvtmi_flat_remove_labels; int64, numpy or a torch device tensor).  The kept rows close up in their order and keep their
+        labels.  Returns the number of rows dropped, with want_remap (dropped, remap): remap[i] = new row of old row i, or -1."""
+        n0 = self.ntotal
+        removed = C.c_int64(0)
+        if _is_torch(labels):
+            import torch
+            assert labels.dtype == torch.int64 and labels.is_cuda
+            labels = labels.reshape(-1)
+            remap = torch.empty(n0, dtype=torch.int64, device=labels.device) if want_remap else None
+            _check(lib().cvtmi_flat_remove_labels_dev(self.h, _ptr(labels), C.c_int64(labels.shape[0]), C.byref(removed), _ptr(remap), _stream()))
+        else:
+            labels = _np(labels, np.int64).reshape(-1)
+            remap = np.empty(n0, dtype=np.int64) if want_remap else None
+            _check(lib().cvtmi_flat_remove_labels(self.h, _ptr(labels), C.c_int64(labels.shape[0]), C.byref(removed), _ptr(remap)))
+        return (removed.value, remap) if want_remap else removed.value
+
+    def set_param(self, name, value):
+        """cvtmi_flat_set_param: "remove_chunk" = rows the move of a removal works on at a time (0 = default)."""
+        _check(lib().cvtmi_flat_set_param(self.h, name.encode(), C.c_int64(value)))
+
     def search_sharded(self, comm, q, k):
         """Row-sharded exhaustive search: this handle holds the rank's row block (set_id_base = its first row)."""
         nq = q.shape[0]

@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "api_internal.h"
 
@@ -31,7 +32,7 @@ int cvtmi_flat_destroy(cvtmi_flat_t h)
     if (!h) return CVTMI_OK;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    for (DevBuf *b : { &h->data, &h->labels, &h->norms, &h->add_stage, &h->f_pack, &h->f_bias, &h->f_istats, &h->fs_bias, &h->fs_stats, &h->f_rows })
+    for (DevBuf *b : { &h->data, &h->labels, &h->norms, &h->add_stage, &h->rm_scratch, &h->f_pack, &h->f_bias, &h->f_istats, &h->fs_bias, &h->fs_stats, &h->f_rows })
         b->release();
     h->pool.destroy();
     delete h;
@@ -139,6 +140,127 @@ int cvtmi_flat_add_dev(cvtmi_flat_t h, const void *x, const int64_t *labels, int
     CHECK_H(h);
     FlatMutation mut(h, (hipStream_t)stream);
     return flat_add_common(h, x, labels, n, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+}
+
+// ---- removal: one stable compaction of the rows, labels and norms on the device (flat_remove.hip) ----
+// The set is a device array of labels.  Implicit labels: it is scattered into the bitmap as it is.  Explicit labels: `table` is the
+// sorted table of its distinct values (host memory: it is uploaded into the scratch).  Everything the call needs is reserved before
+// the first row moves; the host waits once, for the kept count, BEFORE the move: a call that drops nothing leaves the handle, its
+// derived copies and its implicit labels alone.
+static int flat_remove_common(cvtmi_flat_t h, const int64_t *set_dev, int64_t n_set, const int64_t *table, int64_t T, int64_t *removed,
+                              int64_t *remap_dev, hipStream_t st)
+{
+    if (removed) *removed = 0;
+    const int64_t n = h->n;
+    if (n == 0) return CVTMI_OK;
+    const bool blocked = flat_blocked(h->metric, h->D);
+    const bool has_norms = h->metric == CVTMI_METRIC_L2U8 && h->D % 32 == 0 && h->D <= 512;   // (as flat_add_common keeps them)
+    const FlatRmPlan p = flat_rm_plan(n, h->row_bytes, blocked, has_norms, h->identity ? 0 : T, h->p_rm_chunk);
+    CVTMI_TRY(h->rm_scratch.reserve(p.bytes));
+    void *S = h->rm_scratch.p;
+    if (h->identity) {
+        CVTMI_TRY(launch_rm_mark_ids(p.rm, S, set_dev, n_set, h->id_base, st));
+    } else {
+        if (T > 0) CVTMI_HIP(hipMemcpyAsync(static_cast<char *>(S) + p.off_table, table, (size_t)T * 8, hipMemcpyHostToDevice, st));
+        CVTMI_TRY(launch_flat_rm_mark_labels(p, S, h->labels.as<int64_t>(), st));
+    }
+    int64_t kept = 0;
+    CVTMI_HIP(hipMemcpyAsync(&kept, static_cast<char *>(S) + p.rm.off_total, sizeof kept, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    if (kept < 0 || kept > n) return fail(CVTMI_ESTATE, "cvtmi_flat_remove_labels: kept count %lld of %lld rows", (long long)kept, (long long)n);
+    if (kept == n) {
+        if (remap_dev) CVTMI_TRY(launch_rm_fill_remap(remap_dev, n, 1, st));
+        return CVTMI_OK;
+    }
+    if (h->identity) {   // kept rows keep their labels: id_base + old row becomes an array, as cvtmi_flat_add does for the first explicit label
+        CVTMI_TRY(h->labels.grow((size_t)std::max<int64_t>(n, 1024) * 8, 0, st));
+        CVTMI_TRY(launch_flat_rm_iota(h->labels.as<int64_t>(), n, h->id_base, st));
+        h->identity = false;
+    }
+    CVTMI_TRY(launch_flat_rm_move(p, S, h->data.p, h->labels.as<int64_t>(), has_norms ? h->norms.as<int32_t>() : nullptr, remap_dev, st));
+    h->n = kept;
+    // what the handle derives from its rows describes the kept rows only: the operand copies are rebuilt by the next search that
+    // needs them (never taken for a prefix: flat_prepare extends a copy only where 0 < f_pack_n < n) ...
+    h->f_pack_n = -1; h->f_rows_n = -1;
+    if (blocked && h->fs_bias.p && h->fs_stats.p) {   // ... bias and statistics of the stream are recomputed here; the stale rows of the last block are zeroed
+        CVTMI_HIP(hipMemsetAsync(h->fs_stats.p, 0, 16, st));
+        CVTMI_TRY(launch_flat_f32_bias(h->data.as<float>(), h->D, h->metric, 0, kept, h->fs_bias.as<float>(), h->fs_stats.as<uint32_t>(), st));
+        h->fs_stats_n = -1;
+    }
+    if (removed) *removed = n - kept;
+    return CVTMI_OK;
+}
+
+// arguments first, before anything touches the device
+static int flat_remove_check(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_flat_remove_labels: null handle");
+    if (n_labels < 0 || (n_labels > 0 && !labels)) return fail(CVTMI_EINVAL, "cvtmi_flat_remove_labels: bad arguments");
+    return CVTMI_OK;
+}
+
+// the distinct labels of the set, ascending
+static int flat_remove_table(const int64_t *labels, int64_t n_labels, std::vector<int64_t> &tab)
+{
+    try {
+        tab.assign(labels, labels + n_labels);
+    } catch (...) {
+        return fail(CVTMI_ENOMEM, "cvtmi_flat_remove_labels: out of host memory");
+    }
+    std::sort(tab.begin(), tab.end());
+    tab.erase(std::unique(tab.begin(), tab.end()), tab.end());
+    return CVTMI_OK;
+}
+
+int cvtmi_flat_remove_labels_dev(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, int64_t *removed, int64_t *remap, void *stream)
+{
+    CVTMI_TRY(flat_remove_check(h, labels, n_labels));
+    CHECK_H(h);
+    hipStream_t st = (hipStream_t)stream;
+    FlatMutation mut(h, st);
+    std::vector<int64_t> raw, tab;
+    if (!h->identity && n_labels > 0 && h->n > 0) {   // explicit labels: the set is sorted on the host, it comes down first (8 bytes per label)
+        try {
+            raw.resize((size_t)n_labels);
+        } catch (...) {
+            return fail(CVTMI_ENOMEM, "cvtmi_flat_remove_labels: out of host memory");
+        }
+        CVTMI_HIP(hipMemcpyAsync(raw.data(), labels, (size_t)n_labels * 8, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(stream_wait(st));
+        CVTMI_TRY(flat_remove_table(raw.data(), n_labels, tab));
+    }
+    return flat_remove_common(h, labels, n_labels, tab.data(), (int64_t)tab.size(), removed, remap, st);
+}
+
+int cvtmi_flat_remove_labels(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, int64_t *removed, int64_t *remap)
+{
+    CVTMI_TRY(flat_remove_check(h, labels, n_labels));
+    CHECK_H(h);
+    FlatMutation mut(h, nullptr);
+    const int64_t n0 = h->n;
+    std::vector<int64_t> tab;
+    Tmp ds, dm;
+    if (n_labels > 0 && n0 > 0) {
+        if (h->identity) CVTMI_TRY(ds.upload(labels, (size_t)n_labels * sizeof(int64_t)));
+        else CVTMI_TRY(flat_remove_table(labels, n_labels, tab));
+    }
+    if (remap && n0 > 0) CVTMI_TRY(dm.alloc((size_t)n0 * sizeof(int64_t)));
+    CVTMI_TRY(flat_remove_common(h, ds.as<int64_t>(), ds.p ? n_labels : 0, tab.data(), (int64_t)tab.size(), removed, dm.as<int64_t>(), nullptr));
+    if (dm.p) CVTMI_HIP(hipMemcpy(remap, dm.p, (size_t)n0 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    else CVTMI_HIP(stream_wait(nullptr));
+    return CVTMI_OK;
+}
+
+int cvtmi_flat_set_param(cvtmi_flat_t h, const char *name, int64_t value)
+{
+    if (!h || !name) return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: null");
+    if (!strcmp(name, "remove_chunk")) {
+        if (value < 0 || value > ((int64_t)1 << 32)) return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: remove_chunk must be 0 .. 2^32 rows");
+        std::unique_lock<std::shared_timed_mutex> lk(h->rw);
+        h->p_rm_chunk = value ? flat_rm_chunk_rows(value, h->row_bytes) : 0;   // whole tiles
+        return CVTMI_OK;
+    }
+    return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: unknown parameter '%s'", name);
 }
 
 int cvtmi_flat_ntotal(cvtmi_flat_t h, int64_t *n)

@@ -215,6 +215,8 @@ struct cvtmi_flat_s {
     size_t row_bytes = 0;
     DevBuf data, labels, norms;  // norms: int32 |x-128|^2 per row, uint8 metric with D % 32 == 0 (MFMA path)
     DevBuf add_stage;            // staging of host rows on their way into the blocked layout
+    DevBuf rm_scratch;           // removal (flat_remove.hip): bitmap, tile offsets, the table of removal labels, the chunk-sized row scratch
+    int64_t p_rm_chunk = 0;      // "remove_chunk": rows the move works on at a time (0 = the default)
     int64_t n = 0;
     int64_t id_base = 0;   // row r reports label id_base + r while labels are implicit (row shards, cvtmi_flat_set_id_base)
     bool identity = true;  // label == row

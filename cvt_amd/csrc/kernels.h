@@ -185,6 +185,26 @@ int launch_rm_mark_ids(const RmPlan &p, void *scratch, const int64_t *ids, int64
 int launch_rm_move(const RmPlan &p, void *scratch, uint8_t *codes, int32_t *lists, int32_t *videos, int renumber, int64_t *remap, hipStream_t st);
 int launch_rm_renumber(const RmPlan &p, void *scratch, int32_t *videos, hipStream_t st);   // the renumbering alone, in place
 int launch_rm_fill_remap(int64_t *remap, int64_t n, int identity, hipStream_t st);         // remap[i] = i, or -1
+int launch_rm_scan(const RmPlan &p, void *scratch, hipStream_t st);                        // tile counts at off_tile -> offsets; the kept count to off_total
+
+// ---- flat_remove.hip ----  stable compaction of the rows of a flat index with their labels and norms (cvtmi_flat_remove_labels)
+// The bitmap, the tile offsets and the scan are opq_remove.hip's (`rm`, an RmPlan without row scratch); behind them lie the sorted
+// table of distinct removal labels (int64; the caller copies T labels to off_table before the mark) and the chunk-sized scratch
+// of the rows (blocked fp32: one 64-row block more than the chunk, see flat_remove.hip), the labels and the norms.
+struct FlatRmPlan {
+    RmPlan rm;
+    int64_t T = 0;
+    size_t row_bytes = 0;
+    bool blocked = false;
+    size_t off_table = 0, off_rows = 0, off_labels = 0, off_norms = 0, bytes = 0;
+};
+int64_t flat_rm_chunk_rows(int64_t wanted, size_t row_bytes);   // "remove_chunk" of a flat handle: 0 = the rows of 64 MB; whole tiles
+FlatRmPlan flat_rm_plan(int64_t n, size_t row_bytes, bool blocked, bool has_norms, int64_t table_len, int64_t chunk_rows);
+// mark by explicit label + scan (n > 0): one lower bound per row in the table; afterwards the int64 at rm.off_total holds the kept count
+int launch_flat_rm_mark_labels(const FlatRmPlan &p, void *scratch, const int64_t *labels, hipStream_t st);
+// the chunked move behind a mark: rows (blocked: D / 4 float4 per row in 64-row blocks), labels [n], norms [n] or null, remap [n] or null
+int launch_flat_rm_move(const FlatRmPlan &p, void *scratch, void *rows, int64_t *labels, int32_t *norms, int64_t *remap, hipStream_t st);
+int launch_flat_rm_iota(int64_t *labels, int64_t n, int64_t base, hipStream_t st);   // labels[i] = base + i
 
 // ---- ivf_search.hip ----  k smallest (score, id) over the probed lists of every query (cvtmi_opq_search_ivf)
 // one workgroup per (query, group of G consecutive probe slots, piece of rows_per_piece rows of each list of the group)

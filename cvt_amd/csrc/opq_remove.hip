@@ -20,14 +20,9 @@
 // Every offset stays on the device; the host reads the kept total once.
 #include <algorithm>
 
-#include "kernels.h"
+#include "rm_common.h"
 
 namespace cvtmi {
-
-static_assert(kRmTile == 256, "a tile is 4 bitmap words: one per wave of its workgroup");
-constexpr int kRmWords = kRmTile / 64;     // bitmap words of a tile
-constexpr int kRmScanTiles = 2048;         // tiles one workgroup of the first scan level owns (8 per thread)
-constexpr int kRmPivots = 1024;            // pivots of the removal table kept in LDS
 
 // ---- the sorted table of distinct removal ids ----
 struct RmTable {
@@ -59,12 +54,6 @@ __device__ __forceinline__ int64_t rm_lower_bound(const RmTable &t, const int32_
     }
     *found = a < t.T && t.tab[a] == v;
     return a;
-}
-
-__device__ __forceinline__ unsigned long long rm_valid_mask(int64_t row0, int64_t n)   // rows row0 .. row0 + 63 that exist
-{
-    if (row0 >= n) return 0ull;
-    return n - row0 >= 64 ? ~0ull : ((1ull << (n - row0)) - 1ull);
 }
 
 // ---- mark ----
@@ -151,12 +140,6 @@ __global__ __launch_bounds__(256) void rm_scan_top_kernel(const uint32_t *__rest
     __syncthreads();
     int64_t run = part[threadIdx.x];
     for (int b = b0; b < b1; ++b) { boff[b] = run; run += bsum[b]; }
-}
-
-// new insertion index of the first kept row of tile t (t == ntiles: the kept total)
-__device__ __forceinline__ int64_t rm_tile_pos(const uint32_t *tile_off, const int64_t *boff, const int64_t *total, int64_t ntiles, int64_t t)
-{
-    return t < ntiles ? boff[t / kRmScanTiles] + tile_off[t] : total[0];
 }
 
 // ---- move ----
@@ -255,8 +238,6 @@ __global__ void rm_fill_remap_kernel(int64_t *__restrict__ remap, int64_t n, int
 }
 
 // ---- host side ----
-static size_t rm_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int64_t rm_chunk_rows(int64_t wanted)
 {
     if (wanted <= 0) wanted = kRmChunkDefault;
@@ -294,9 +275,7 @@ static RmTable rm_table(const RmPlan &p, void *scratch)
     return t;
 }
 
-template <class T> static T *rm_at(void *scratch, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(scratch) + off); }
-
-static int rm_scan(const RmPlan &p, void *scratch, hipStream_t st)
+int launch_rm_scan(const RmPlan &p, void *scratch, hipStream_t st)
 {
     hipLaunchKernelGGL(rm_scan_tiles_kernel, dim3((unsigned)p.nblk), dim3(256), 0, st, rm_at<uint32_t>(scratch, p.off_tile), p.ntiles,
                        rm_at<uint32_t>(scratch, p.off_bsum));
@@ -312,7 +291,7 @@ int launch_rm_mark_videos(const RmPlan &p, void *scratch, const int32_t *videos,
     hipLaunchKernelGGL(rm_mark_videos_kernel, dim3((unsigned)p.ntiles), dim3(256), 0, st, videos, p.n, rm_table(p, scratch),
                        rm_at<unsigned long long>(scratch, p.off_drop), rm_at<uint32_t>(scratch, p.off_tile));
     CVTMI_HIP(hipGetLastError());
-    return rm_scan(p, scratch, st);
+    return launch_rm_scan(p, scratch, st);
 }
 
 int launch_rm_mark_ids(const RmPlan &p, void *scratch, const int64_t *ids, int64_t n_ids, int64_t id_base, hipStream_t st)
@@ -326,7 +305,7 @@ int launch_rm_mark_ids(const RmPlan &p, void *scratch, const int64_t *ids, int64
     hipLaunchKernelGGL(rm_count_tiles_kernel, dim3((unsigned)((p.ntiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                        rm_at<unsigned long long>(scratch, p.off_drop), p.n, p.ntiles, rm_at<uint32_t>(scratch, p.off_tile));
     CVTMI_HIP(hipGetLastError());
-    return rm_scan(p, scratch, st);
+    return launch_rm_scan(p, scratch, st);
 }
 
 template <class U> static int rm_move_chunks(const RmPlan &p, RmMove a, const RmTable &t, int renumber, hipStream_t st)

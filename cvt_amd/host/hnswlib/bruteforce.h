@@ -6,6 +6,10 @@
 // Tie rule: the reference returns the k smallest (dist, label) pairs.  The device breaks ties by row, so
 // rows are uploaded in ascending LABEL order (a permutation only the device copy sees; data_ keeps the
 // reference's insertion order for saveIndex).
+//
+// removePoint: while every row of data_ is on the device the label is only recorded; the next search drops all recorded labels
+// with ONE cvtmi_flat_remove_labels call -- a stable compaction, so the device copy stays in ascending label order.  Anything
+// else (rows not yet uploaded, a rebuild already pending) re-sorts and re-uploads everything, as before.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -49,6 +53,7 @@ public:
     DISTFUNC<dist_t> fstdistfunc_;
     void *dist_func_param_;
     std::unordered_map<labeltype, size_t> dict_external_to_internal;
+    size_t device_rebuilds = 0;  // full uploads of the device copy so far (reset + sort by label + upload; the first upload counts)
 
     void addPoint(void *datapoint, labeltype label)
     {
@@ -69,8 +74,15 @@ public:
         dict_external_to_internal[label] = cur_c;
         memcpy(data_ + size_per_element_ * cur_c, data_ + size_per_element_ * (cur_element_count - 1), data_size_ + sizeof(labeltype));
         cur_element_count--;
+        // data_ is the reference's swap-remove; the device copy is in label order and only has to lose the row.  That holds while
+        // rows [0, synced_) are ALL rows: otherwise the row that moved into the hole is one the device has not seen
+        if (!rebuild_ && h_ && synced_ == cur_element_count + 1) {
+            pending_remove_.push_back((int64_t)cur_external);
+            synced_ = cur_element_count;
+        } else {
+            rebuild_ = true;  // the device copy is re-ordered from scratch on the next search
+        }
         dirty_ = true;
-        rebuild_ = true;  // a row moved: the device copy is re-ordered from scratch on the next search
     }
 
     std::priority_queue<std::pair<dist_t, labeltype> > searchKnn(void *query_data, size_t k)
@@ -130,7 +142,8 @@ private:
     std::mutex sync_mu_;
     bool rebuild_ = true;        // the device copy must be rebuilt (rows removed / loaded / labels not ascending)
     size_t synced_ = 0;          // rows [0, synced_) of data_ are on the device, in this order
-    labeltype synced_max_ = 0;   // the largest label among them
+    labeltype synced_max_ = 0;   // no label among them is larger (the largest, until it is removed)
+    std::vector<int64_t> pending_remove_;   // labels removePoint dropped from data_ that the device copy still holds
     int metric_;
 
     void bind(SpaceInterface<dist_t> *s)
@@ -155,7 +168,8 @@ private:
             throw std::runtime_error(std::string("cvtmi_flat_create: ") + cvtmi_last_error());
         // The device keeps rows in ascending label order (the (distance, label) tie rule of searchKnn's heap).  The common
         // case -- addPoint with ever larger labels, as brute_force.cpp does (labels = row numbers) -- only appends the new
-        // rows; anything else (removePoint, loadIndex, a label below one already uploaded) re-sorts and re-uploads everything.
+        // rows, after dropping the labels removePoint recorded; anything else (loadIndex, a label below one already uploaded, a
+        // removePoint while rows waited for their upload) re-sorts and re-uploads everything.
         if (!rebuild_ && synced_ <= cur_element_count) {
             bool ascending = true;
             labeltype prev = synced_max_;
@@ -165,6 +179,11 @@ private:
                 prev = lab;
             }
             if (ascending) {
+                if (!pending_remove_.empty()) {   // before any append: a removed label may come back with a new row
+                    if (cvtmi_flat_remove_labels(h_, pending_remove_.data(), (int64_t)pending_remove_.size(), NULL, NULL) != CVTMI_OK)
+                        throw std::runtime_error(std::string("cvtmi_flat_remove_labels: ") + cvtmi_last_error());
+                    pending_remove_.clear();
+                }
                 const size_t m = cur_element_count - synced_;
                 if (m) {
                     std::vector<char> rows(m * data_size_ + 1);
@@ -183,6 +202,8 @@ private:
             }
         }
         cvtmi_flat_reset(h_);
+        pending_remove_.clear();
+        ++device_rebuilds;
         const size_t n = cur_element_count;
         std::vector<size_t> order(n);
         for (size_t i = 0; i < n; ++i) order[i] = i;

@@ -563,6 +563,39 @@ int cvtmi_flat_add(cvtmi_flat_t h, const void *x, const int64_t *labels, int64_t
 int cvtmi_flat_add_dev(cvtmi_flat_t h, const void *x, const int64_t *labels, int64_t n, void *stream);
 int cvtmi_flat_ntotal(cvtmi_flat_t h, int64_t *n);
 int cvtmi_flat_reset(cvtmi_flat_t h);
+/* Removal: drop rows from the resident index on the device (BruteforceSearch::removePoint, brutoforce.hpp:58-70, for a whole set).
+ *   Set      A row is dropped when the label it reports in cvtmi_flat_search is in labels[n_labels]: id_base + row on a handle with
+ *            implicit labels, otherwise the label the row was added with.  The set may be unsorted, may hold duplicates and may
+ *            name labels that are not in the index (ignored); any int64 is a valid label.  If several rows carry the same explicit
+ *            label, all of them go.  The result never depends on the order or multiplicity of the set.
+ *   Result   The kept rows close up in their old order (a stable compaction), so the device's tie rule (distance, then row) keeps
+ *            meaning what it meant.  Kept rows keep their labels: on a handle with implicit labels the first call that drops
+ *            something first makes the labels an array holding id_base + old row (as cvtmi_flat_add does for the first explicit
+ *            label, but honouring id_base).  *removed (may be NULL) = rows dropped.  remap (may be NULL) has room for the OLD
+ *            cvtmi_flat_ntotal: remap[i] = new row of old row i, or -1 if it was dropped.  cvtmi_flat_ntotal reports the new count.
+ *            A later cvtmi_flat_add appends behind the kept rows; without labels it numbers its rows by position (the new row
+ *            number, id_base not added), as it does on any handle with explicit labels.
+ *   Equivalence  Afterwards cvtmi_flat_search, _search_dev and _search_sharded* answer bit for bit (distances and labels) as a new
+ *            handle of the same metric and width would that had been given only the kept rows, in their order, with their labels,
+ *            on every route a search can take.  Norms move with the rows; the score bias and the row statistics of the fp32 stream
+ *            are recomputed for the kept rows (a handle whose only non-finite row was removed takes the stream / threshold-filter
+ *            routes again); the operand copies of the filter routes are rebuilt by the first search that needs them.  A call that
+ *            drops nothing leaves the handle as it was, those copies and the implicit labels included (*removed = 0, remap the
+ *            identity).  A call that drops everything leaves an empty, usable index.
+ *   Calling  Mutating and exclusive, like cvtmi_flat_add.  NULL handle, a negative count, a NULL set with a positive count ->
+ *            CVTMI_EINVAL before any device work.  All scratch is reserved before the first row moves: on CVTMI_ENOMEM the index is
+ *            unchanged.  Memory is not given back.  The host entry returns when the index is in its new state.  The _dev entry (set
+ *            and remap are device pointers) runs on `stream` and WAITS on it once for the 8-byte kept count; on a handle with
+ *            explicit labels it also waits for its set to reach the host, where it is sorted (8 bytes per label).
+ *   Shards   On a row shard (cvtmi_flat_set_id_base) each rank removes from its own handle.  There is no collective form.
+ * The work is a mark (a bitmap of the dropped rows), a scan of per-tile counts and a move in chunks of "remove_chunk" rows
+ * (cvtmi_flat_set_param; scratch of one chunk, never a second copy of the rows); rows before the first dropped row are not moved. */
+int cvtmi_flat_remove_labels(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, int64_t *removed, int64_t *remap);
+int cvtmi_flat_remove_labels_dev(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, int64_t *removed, int64_t *remap, void *stream);
+/* Per-handle parameters (no effect on results).
+ *   "remove_chunk"  rows the move of cvtmi_flat_remove_labels works on at a time, rounded up to whole 256-row tiles;
+ *                   0 (default) = the rows of 64 MB. */
+int cvtmi_flat_set_param(cvtmi_flat_t h, const char *name, int64_t value);
 /* searchKnn (brutoforce.hpp:73-93) for nq queries: k smallest (distance, label), ascending.
  * dist is float[nq][k] for IP / L2F and int32_t[nq][k] for L2U8.  1 <= k <= CVTMI_K_MAX.  An index with fewer than k rows pads:
  * label -1, distance field 0x7f800000 -- +inf as a float, and for L2U8 the same bit pattern read as int32 (2139095040: larger than
