@@ -45,12 +45,12 @@ __global__ __launch_bounds__(PCA_THREADS) void pca_project_kernel(const float *_
     // the same for every p, so one mean float4 per chunk and thread
     const int c4 = (tid & 7) * 4, r0 = tid >> 3;
     float4 px[4], pe[NT], pm;  // raw loads of the chunk in flight; the arithmetic on them waits until stash()
-    float keep = 1.0f;
+    bool keep = true;
     auto fetch = [&](int c) {
         const int k = c * PCA_KC + c4;
         const bool live = k < din;  // din % 4 == 0: a float4 is inside or outside as a whole
-        const int kc = live ? k : 0;  // loads are unconditional (clamped address); dead values are zeroed below
-        keep = live ? 1.0f : 0.0f;
+        const int kc = live ? k : 0;  // loads are unconditional (clamped address); dead values are replaced by zeros below
+        keep = live;
         pm = *reinterpret_cast<const float4 *>(mean + kc);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
@@ -68,13 +68,16 @@ __global__ __launch_bounds__(PCA_THREADS) void pca_project_kernel(const float *_
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             float *d = buf + (p * 32 + r0) * PCA_LD + c4;
-            d[0] = px[p].x - pm.x; d[1] = px[p].y - pm.y; d[2] = px[p].z - pm.z; d[3] = px[p].w - pm.w;
+            // columns past din enter as exact zeros BY SELECTION on both operands: the clamped loads hold columns 0..3, and a non-finite
+            // value there times a zero would be NaN
+            d[0] = keep ? px[p].x - pm.x : 0.0f; d[1] = keep ? px[p].y - pm.y : 0.0f;
+            d[2] = keep ? px[p].z - pm.z : 0.0f; d[3] = keep ? px[p].w - pm.w : 0.0f;
         }
 #pragma unroll
         for (int p = 0; p < NT; ++p) {
             float *d = buf + (PCA_ROWS + p * 32 + r0) * PCA_LD + c4;
-            const float w = (p * 32 + r0) < dout ? keep : 0.0f;  // rows past dout and columns past din enter as exact zeros
-            d[0] = pe[p].x * w; d[1] = pe[p].y * w; d[2] = pe[p].z * w; d[3] = pe[p].w * w;
+            const bool w = keep && (p * 32 + r0) < dout;  // rows past dout and columns past din enter as exact zeros
+            d[0] = w ? pe[p].x : 0.0f; d[1] = w ? pe[p].y : 0.0f; d[2] = w ? pe[p].z : 0.0f; d[3] = w ? pe[p].w : 0.0f;
         }
     };
     f32x16 acc[NT];
@@ -105,7 +108,8 @@ __global__ __launch_bounds__(PCA_THREADS) void pca_project_kernel(const float *_
         for (int e = 0; e < 16; ++e) {
             double s = 0.0;
 #pragma unroll
-            for (int t = 0; t < NT; ++t) s += (double)acc[t][e] * (double)acc[t][e];  // pad columns hold exact zeros
+            for (int t = 0; t < NT; ++t)   // pad columns stay out: zero for a finite row, NaN (inf * 0) for one with an infinity
+                s += t * 32 + li < dout ? (double)acc[t][e] * (double)acc[t][e] : 0.0;
 #pragma unroll
             for (int o = 1; o < 32; o <<= 1) s += __shfl_xor(s, o, 64);  // stays inside the 32-lane half that owns the row
             // sqrtf, correctly rounded: the fp64 root of an fp32 value rounds to it (__fsqrt_rn is the 1-ulp native one)
