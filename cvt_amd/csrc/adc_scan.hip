@@ -21,6 +21,7 @@
 #include <atomic>
 
 #include "adc_scan16.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -1216,18 +1217,6 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16a_kernel(const ScanArg
 int scan_seed_enabled() { return tune_scan_seed.geti(); }
 
 // Row ids travel as 32-bit payloads: one launch covers at most 2^32-1 rows.
-static int cu_count()
-{
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 ScanPlan plan_scan(const OpqModelDev &m, int64_t n_rows, int64_t nq, int k, int want_qtile, int want_splits,
                    int want_variant)
 {
@@ -1265,7 +1254,7 @@ ScanPlan plan_scan(const OpqModelDev &m, int64_t n_rows, int64_t nq, int k, int 
     }
     if (qt == 8 && m.M == 16 && p.variant < 3) qt = 4;  // row-per-lane: 8 x 16 KB fp32 tables do not fit beside the buffers
     p.qtile = qt;
-    const int64_t groups = (nq + qt - 1) / qt;
+    const int64_t groups = blocks_for(nq, qt);
     int s = want_splits;
     if (s <= 0) {
         // Cost model fitted to tools/sweep_scan.py runs on 1 M rows (nq = 1250 ... 10000, splits 1-3) and
@@ -1274,7 +1263,7 @@ ScanPlan plan_scan(const OpqModelDev &m, int64_t n_rows, int64_t nq, int k, int 
         // (2 per CU); a partly filled last round is not as bad as its occupancy, because a workgroup alone on
         // its CU runs ~1.27x faster: at <= 50 % occupancy the round takes 0.78 of a full one.
         // Pick the S that minimises rounds(groups * S) * (FIX + rows / S), at least 16 K rows per workgroup.
-        const int64_t slots = 2 * (int64_t)cu_count();
+        const int64_t slots = 2 * (int64_t)device_cus();
         const double fix = 380000.0;
         const auto wg_cost = [&](int64_t S) { return fix + (double)n_rows / (double)S; };
         const auto rounds_of = [&](int64_t blocks) {
@@ -1320,7 +1309,7 @@ ScanPlan plan_scan(const OpqModelDev &m, int64_t n_rows, int64_t nq, int k, int 
     // the skewed kernels address a split's rows with 32-bit byte offsets (row * 16): at most 2^28 - 4096 rows per split
     if (p.variant >= 1) {
         const int64_t max_rows = (1LL << 28) - 4096;
-        const int64_t min_splits = (n_rows + max_rows - 1) / max_rows;
+        const int64_t min_splits = blocks_for(n_rows, max_rows);
         if (s < min_splits) { s = (int)min_splits; p.groups_a = 0; p.splits_b = 0; }
     }
     p.splits = s;
@@ -1333,10 +1322,7 @@ static int launch_t(const ScanArgs &a, hipStream_t st)
 {
     const int64_t blocks = (int64_t)a.groups * a.splits;
     if (blocks <= 0) return CVTMI_OK;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "adc_scan: grid too large (%lld)", (long long)blocks);
-    hipLaunchKernelGGL((adc_scan_kernel<M, QT>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("adc_scan_kernel", adc_scan_kernel<M, QT>, blocks, kBlock, 0, st, a);
 }
 
 template <int M>
@@ -1346,10 +1332,7 @@ static int launch_m(const ScanArgs &a, int qt, hipStream_t st)
         const int64_t blocks = (int64_t)a.groups * a.splits;
         if (qt != 1) return fail(CVTMI_EINVAL, "adc_scan: k=%d needs qtile 1", a.k);
         if (blocks <= 0) return CVTMI_OK;
-        if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "adc_scan: grid too large (%lld)", (long long)blocks);
-        hipLaunchKernelGGL((adc_scan_kernel<M, 1, kBigCap, kBigTrig>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
+        return launch("adc_scan_kernel", adc_scan_kernel<M, 1, kBigCap, kBigTrig>, blocks, kBlock, 0, st, a);
     }
     switch (qt) {
         case 1: return launch_t<M, 1>(a, st);
@@ -1392,22 +1375,14 @@ int launch_pad_codes(const uint8_t *codes, int M, uint8_t *codes16, int64_t row0
 {
     if (n <= row0) return CVTMI_OK;
     if (M < 1 || M > 16) return fail(CVTMI_EINVAL, "pad_codes: M=%d", M);
-    const int64_t blocks = (n - row0 + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "pad_codes: too many rows");
-    hipLaunchKernelGGL(pad_codes_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, codes, M, reinterpret_cast<uint4 *>(codes16), row0, n);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("pad_codes_kernel", pad_codes_kernel, blocks_for(n - row0, kBlock), kBlock, 0, st, codes, M, reinterpret_cast<uint4 *>(codes16), row0, n);
 }
 
 int launch_rotate_codes(const uint8_t *codes, uint8_t *codes_rot, int64_t row0, int64_t n, hipStream_t st)
 {
     if (n <= row0) return CVTMI_OK;
-    const int64_t blocks = (n - row0 + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "rotate_codes: too many rows");
-    hipLaunchKernelGGL(rotate_codes_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, reinterpret_cast<const uint4 *>(codes),
-                       reinterpret_cast<uint4 *>(codes_rot), row0, n);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("rotate_codes_kernel", rotate_codes_kernel, blocks_for(n - row0, kBlock), kBlock, 0, st, reinterpret_cast<const uint4 *>(codes),
+                  reinterpret_cast<uint4 *>(codes_rot), row0, n);
 }
 
 int launch_adc_scan(const OpqModelDev &m, const uint8_t *codes, int64_t n_rows, int64_t id_base, const float *q_rot,
@@ -1456,32 +1431,28 @@ int launch_adc_scan(const OpqModelDev &m, const uint8_t *codes, int64_t n_rows, 
         if (final_d && final_id && scan_in_place_queries(plan, m.M, nq) > 0) {   // (one region without splits: groups_a == groups, all in place)
             a.out_d = final_d; a.out_id = final_id;
         }
-        if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "adc_scan: grid too large (%lld)", (long long)blocks);
         if (gthr && a.stride > 1) {  // the row splits of a query share their filter threshold
             CVTMI_HIP(hipMemsetAsync(gthr, 0xff, (size_t)nq * sizeof(uint32_t), st));
             a.gthr = gthr;
         }
         if (plan.packed) return launch_adc_scan16p(a, plan.real_M, blocks, st);   // (codes = the model's own rows, codes_rot = their packed rotation)
-        const dim3 g((unsigned)blocks);
+        const int v = plan.variant;   // 3, 4: adc_scan16q with 1024 / 512 threads; else adc_scan16a
+        decltype(&adc_scan16q_kernel<1024, 1, true>) kern;
         if (codes_rot) {
-            if (plan.variant == 3) hipLaunchKernelGGL((adc_scan16q_kernel<1024, 1, true>), g, dim3(1024), 0, st, a);
-            else if (plan.variant == 4) hipLaunchKernelGGL((adc_scan16q_kernel<512, 2, true>), g, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((adc_scan16a_kernel<1024, 1, true>), g, dim3(1024), 0, st, a);
+            if (v == 3) kern = adc_scan16q_kernel<1024, 1, true>;
+            else if (v == 4) kern = adc_scan16q_kernel<512, 2, true>;
+            else kern = adc_scan16a_kernel<1024, 1, true>;
         } else {
-            if (plan.variant == 3) hipLaunchKernelGGL((adc_scan16q_kernel<1024, 1, false>), g, dim3(1024), 0, st, a);
-            else if (plan.variant == 4) hipLaunchKernelGGL((adc_scan16q_kernel<512, 2, false>), g, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((adc_scan16a_kernel<1024, 1, false>), g, dim3(1024), 0, st, a);
+            if (v == 3) kern = adc_scan16q_kernel<1024, 1, false>;
+            else if (v == 4) kern = adc_scan16q_kernel<512, 2, false>;
+            else kern = adc_scan16a_kernel<1024, 1, false>;
         }
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
+        return launch(v == 3 || v == 4 ? "adc_scan16q_kernel" : "adc_scan16a_kernel", kern, blocks, v == 4 ? 512 : 1024, 0, st, a);
     }
     if (plan.variant >= 1 && m.M == 16 && plan.qtile == 4) {
         const int64_t blocks = (int64_t)a.groups * a.splits;
-        if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "adc_scan: grid too large (%lld)", (long long)blocks);
-        if (plan.variant == 2) hipLaunchKernelGGL((adc_scan16_kernel<1024>), dim3((unsigned)blocks), dim3(1024), 0, st, a);
-        else hipLaunchKernelGGL((adc_scan16_kernel<512>), dim3((unsigned)blocks), dim3(512), 0, st, a);
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
+        const bool wide = plan.variant == 2;
+        return launch("adc_scan16_kernel", wide ? adc_scan16_kernel<1024> : adc_scan16_kernel<512>, blocks, wide ? 1024 : 512, 0, st, a);
     }
     switch (m.M) {
         case 16: return launch_m<16>(a, plan.qtile, st);

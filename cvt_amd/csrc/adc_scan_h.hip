@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "adc_scan16.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -1151,11 +1152,10 @@ int launch_adc_scan_small(const OpqModelDev &m, const uint8_t *codes, const uint
 {
     if (!scans_applies(m, n_rows, nq, k)) return fail(CVTMI_EUNSUPPORTED, "adc_scan16s: shape not covered");
     uint32_t *ctl = reinterpret_cast<uint32_t *>(scratch);
-    const unsigned ng = (unsigned)((nq + SQ_QT - 1) / SQ_QT);   // query groups: a grid row each in the two row passes
-    hipLaunchKernelGGL(scan16h_prep_kernel, dim3(ng), dim3(1024), 0, st, q, (int)nq, m.D, m.step, m.K, m.books, m.coarse, lut_g,
-                       reinterpret_cast<uint4 *>(qlut), reinterpret_cast<QuantParams *>(qp_g), lazy, rotate ? m.R : nullptr, rotate ? m.perm : nullptr,
-                       ctl, SS_WORDS);   // (a dense rotation: D a power of two <= 128, checked by the caller through scans_fuses_rotation)
-    CVTMI_HIP(hipGetLastError());
+    const int64_t ng = blocks_for(nq, SQ_QT);   // query groups: a grid row each in the two row passes
+    CVTMI_TRY(launch("scan16h_prep_kernel", scan16h_prep_kernel, ng, 1024, 0, st, q, (int)nq, m.D, m.step, m.K, m.books, m.coarse, lut_g,
+                     reinterpret_cast<uint4 *>(qlut), reinterpret_cast<QuantParams *>(qp_g), lazy, rotate ? m.R : nullptr, rotate ? m.perm : nullptr,
+                     ctl, SS_WORDS));   // (a dense rotation: D a power of two <= 128, checked by the caller through scans_fuses_rotation)
     ScanSArgs a;
     a.codes = codes; a.codes_rot = codes_rot; a.n_rows = n_rows; a.id_base = id_base;
     const int64_t grid = std::min<int64_t>(scanh_slots() / 2, (n_rows + 4095) / 4096);   // one workgroup per CU, at least 4096 rows each
@@ -1167,23 +1167,19 @@ int launch_adc_scan_small(const OpqModelDev &m, const uint8_t *codes, const uint
     a.wcnt = reinterpret_cast<uint32_t *>(sc);
     a.gcand = reinterpret_cast<unsigned long long *>(sc + (size_t)SS_GROUPS * scans_collect_max() * SQ_QT * 4);
     a.out_d = dist; a.out_id = ids; a.dbg = tune_scans_dbg.geti();   // timing experiments, results wrong when non-zero
-    const unsigned g = (unsigned)((n_rows + a.rows_per_wg - 1) / a.rows_per_wg);
+    const int64_t g = blocks_for(n_rows, a.rows_per_wg);
     a.G = (int)g;
     // the histogram pass: few workgroups (every bin they share costs a global atomic each: 256 of them on ~240 hot bins took 70 us),
     // each sampling every 4th chunk of a 1/32 slab
     const int64_t hg = std::min<int64_t>(32, (n_rows + 16383) / 16384);
     a.rows_per_hist_wg = ((n_rows + hg - 1) / hg + 255) / 256 * 256;
-    const unsigned gh = (unsigned)((n_rows + a.rows_per_hist_wg - 1) / a.rows_per_hist_wg);
-    if (codes_rot) {
-        hipLaunchKernelGGL((scan16s_hist_kernel<true>), dim3(gh, ng), dim3(1024), 0, st, a);
-        hipLaunchKernelGGL((scan16s_collect_kernel<true>), dim3(g, ng), dim3(1024), 0, st, a);
-    } else {
-        hipLaunchKernelGGL((scan16s_hist_kernel<false>), dim3(gh, ng), dim3(1024), 0, st, a);
-        hipLaunchKernelGGL((scan16s_collect_kernel<false>), dim3(g, ng), dim3(1024), 0, st, a);
-    }
-    hipLaunchKernelGGL(scan16s_select_kernel, dim3((unsigned)nq), dim3(1024), 0, st, a);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    const int64_t gh = blocks_for(n_rows, a.rows_per_hist_wg);
+    auto hist = scan16s_hist_kernel<true>;
+    auto collect = scan16s_collect_kernel<true>;
+    if (!codes_rot) { hist = scan16s_hist_kernel<false>; collect = scan16s_collect_kernel<false>; }
+    CVTMI_TRY(launch("scan16s_hist_kernel", hist, { gh, ng }, 1024, 0, st, a));
+    CVTMI_TRY(launch("scan16s_collect_kernel", collect, { g, ng }, 1024, 0, st, a));
+    return launch("scan16s_select_kernel", scan16s_select_kernel, nq, 1024, 0, st, a);
 }
 
 // =====================================================================================================================
@@ -1511,7 +1507,7 @@ __global__ __launch_bounds__(1024) void scan16k_select_kernel(const ScanSArgs a,
 // collect workgroups per query group and list capacity per (workgroup, query) of a big-k search
 static void scank_shape(int64_t n_rows, int64_t nq, int k, int *G, int *wcap)
 {
-    const int64_t groups = (nq + SQ_QT - 1) / SQ_QT;
+    const int64_t groups = blocks_for(nq, SQ_QT);
     int64_t g = (scanh_slots() / 2 + groups - 1) / groups;            // enough workgroups for one per CU
     g = std::max<int64_t>(1, std::min<int64_t>(g, std::min<int64_t>(64, (n_rows + 16383) / 16384)));
     *G = (int)g;
@@ -1550,26 +1546,22 @@ int launch_adc_scan_bigk(const OpqModelDev &m, const uint8_t *codes, const uint8
     sc += ((size_t)nq * 4 + 63) / 64 * 64;
     a.gcand = reinterpret_cast<unsigned long long *>(sc);
     CVTMI_HIP(hipMemsetAsync(flags, 0, (size_t)nq * 4, st));
-    hipLaunchKernelGGL(scan16h_prep_kernel, dim3((unsigned)groups), dim3(1024), 0, st, q_rot, (int)nq, m.D, m.step, m.K, m.books, m.coarse, lut_g,
-                       reinterpret_cast<uint4 *>(qlut), reinterpret_cast<QuantParams *>(qp_g), lazy, (const float *)nullptr, (const int32_t *)nullptr,
-                       ctl, SS_WORDS);
-    CVTMI_HIP(hipGetLastError());
+    CVTMI_TRY(launch("scan16h_prep_kernel", scan16h_prep_kernel, groups, 1024, 0, st, q_rot, (int)nq, m.D, m.step, m.K, m.books, m.coarse, lut_g,
+                     reinterpret_cast<uint4 *>(qlut), reinterpret_cast<QuantParams *>(qp_g), lazy, (const float *)nullptr, (const int32_t *)nullptr,
+                     ctl, SS_WORDS));
     a.codes = codes; a.codes_rot = codes_rot; a.n_rows = n_rows; a.id_base = id_base;
     a.rows_per_wg = ((n_rows + G - 1) / G + 255) / 256 * 256;   // whole groups of four chunks: the histogram's sample
     a.rows_per_hist_wg = a.rows_per_wg;
     a.nq = (int)nq; a.k = k; a.K = m.K; a.G = (int)((n_rows + a.rows_per_wg - 1) / a.rows_per_wg);
     a.qlut = reinterpret_cast<const uint4 *>(qlut); a.qp_g = reinterpret_cast<const QuantParams *>(qp_g); a.lut_g = lut_g;
     a.ctl = ctl; a.out_d = dist; a.out_id = ids; a.dbg = 0;
-    const dim3 grid((unsigned)a.G, (unsigned)groups);
-    if (codes_rot) {
-        hipLaunchKernelGGL((scan16k_hist_kernel<true>), grid, dim3(1024), 0, st, a);
-        hipLaunchKernelGGL((scan16k_collect_kernel<true>), grid, dim3(1024), 0, st, a, wcap);
-    } else {
-        hipLaunchKernelGGL((scan16k_hist_kernel<false>), grid, dim3(1024), 0, st, a);
-        hipLaunchKernelGGL((scan16k_collect_kernel<false>), grid, dim3(1024), 0, st, a, wcap);
-    }
-    hipLaunchKernelGGL(scan16k_select_kernel, dim3((unsigned)nq), dim3(1024), 0, st, a, wcap, flags);
-    CVTMI_HIP(hipGetLastError());
+    const Grid grid(a.G, groups);
+    auto hist = scan16k_hist_kernel<true>;
+    auto collect = scan16k_collect_kernel<true>;
+    if (!codes_rot) { hist = scan16k_hist_kernel<false>; collect = scan16k_collect_kernel<false>; }
+    CVTMI_TRY(launch("scan16k_hist_kernel", hist, grid, 1024, 0, st, a));
+    CVTMI_TRY(launch("scan16k_collect_kernel", collect, grid, 1024, 0, st, a, wcap));
+    CVTMI_TRY(launch("scan16k_select_kernel", scan16k_select_kernel, nq, 1024, 0, st, a, wcap, flags));
     *flags_out = flags;
     return CVTMI_OK;
 }
@@ -1581,23 +1573,13 @@ size_t scanh_gthr_bytes(int64_t nq) { return ((size_t)(nq + 3) / 4 * 4 + (size_t
 
 // Workgroup slots of the device: a constant of the process once read (every grid and scratch size of a search derives from this ONE
 // value; cvtmi_opq_scan_plan plans for another CU count through scanh_plan's own parameter, never through shared state).
-static int scanh_slots()
-{
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return 2 * cus;  // two 1024-thread workgroups per CU (LDS: 2 x 75 KB)
-}
+static int scanh_slots() { return 2 * device_cus(); }  // two 1024-thread workgroups per CU (LDS: 2 x 75 KB)
 
 // Builds the item table of one search.  splits > 0 forces (group, split) blocks with that many row splits.
 void scanh_plan(int64_t n_rows, int64_t nq, int splits, ScanHPlan &p, int cus)
 {
     constexpr int64_t TILE = 2048, MINT = 4, MAX_SEG = (1LL << 28) - 4096;  // rows: segment granule; 32-bit byte offsets inside a segment
-    const int64_t groups = (nq + SQ_QT - 1) / SQ_QT;
+    const int64_t groups = blocks_for(nq, SQ_QT);
     const int64_t slots = cus > 0 ? 2 * (int64_t)cus : scanh_slots();   // cus > 0: cvtmi_opq_scan_plan planning for a given CU count
     p.items.clear();
     p.multi.clear();
@@ -1649,7 +1631,7 @@ void scanh_plan(int64_t n_rows, int64_t nq, int splits, ScanHPlan &p, int cus)
         p.grid = (int)P;
     } else {
         int64_t S = splits > 0 ? splits : 1;
-        const int64_t min_splits = (n_rows + MAX_SEG - 1) / MAX_SEG;
+        const int64_t min_splits = blocks_for(n_rows, MAX_SEG);
         if (splits <= 0) {
             // Cost of cutting every group into `cand` row splits = the makespan of the persistent grid: workgroup w walks items w, w + P, ...;
             // CU c hosts workgroups c and c + slots / 2; an item costs its rows plus what it costs besides them (tables, seed, the candidates
@@ -1680,7 +1662,7 @@ void scanh_plan(int64_t n_rows, int64_t nq, int splits, ScanHPlan &p, int cus)
         if (S < min_splits) S = min_splits;
         // blocks of `cnt` groups from group g0 on, each cut into Sx row splits, appended in the order a grid of blocks would run them
         const auto add_blocks = [&](int64_t g0, int64_t cnt, int64_t Sx, int64_t first_slot, int64_t P) {
-            int64_t rps = (n_rows + Sx - 1) / Sx;
+            int64_t rps = blocks_for(n_rows, Sx);
             rps = ((rps + TILE - 1) / TILE) * TILE;
             for (int64_t b = 0; b < cnt * Sx; ++b) {
                 int64_t split, group;
@@ -1769,10 +1751,9 @@ int launch_adc_scan_h(const OpqModelDev &m, const uint8_t *codes, const uint8_t 
     if (k < 1 || k > 128) return fail(CVTMI_EUNSUPPORTED, "adc_scan16h: k=%d outside 1..128", k);
     if (n_rows > 0xfffffffeLL) return fail(CVTMI_EUNSUPPORTED, "adc_scan16h: more than 2^32-2 rows per shard");
     if (nq > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "adc_scan16h: nq too large");
-    const int64_t groups = (nq + SQ_QT - 1) / SQ_QT;
-    hipLaunchKernelGGL(scan16h_prep_kernel, dim3((unsigned)groups), dim3(1024), 0, st, q_rot, (int)nq, m.D, m.step, m.K, m.books, m.coarse,
-                       lut_g, reinterpret_cast<uint4 *>(qlut), reinterpret_cast<QuantParams *>(qp_g), lazy);
-    CVTMI_HIP(hipGetLastError());
+    const int64_t groups = blocks_for(nq, SQ_QT);
+    CVTMI_TRY(launch("scan16h_prep_kernel", scan16h_prep_kernel, groups, 1024, 0, st, q_rot, (int)nq, m.D, m.step, m.K, m.books, m.coarse,
+                     lut_g, reinterpret_cast<uint4 *>(qlut), reinterpret_cast<QuantParams *>(qp_g), lazy, nullptr, nullptr, nullptr, 0));   // (no fused rotation, nothing to clear)
     if (gthr && plan.stride > 1) CVTMI_HIP(hipMemsetAsync(gthr, 0xff, (size_t)nq * sizeof(uint32_t), st));
     // cvtmi_set_tuning("scanh_share_hist"): the segments of a query count their candidates in one histogram (bounds from the union)
     uint32_t *ghist = (gthr && plan.stride > 1 && tune_scanh_share_hist.geti()) ? gthr + (nq + 3) / 4 * 4 : nullptr;
@@ -1785,10 +1766,7 @@ int launch_adc_scan_h(const OpqModelDev &m, const uint8_t *codes, const uint8_t 
     a.spill = reinterpret_cast<unsigned long long *>(spill);
     a.gthr = (gthr && plan.stride > 1) ? gthr : nullptr;
     a.stride = plan.stride; a.part_d = part_d; a.part_id = part_id; a.out_d = out_d; a.out_id = out_id; a.seed = seed;
-    if (codes_rot) hipLaunchKernelGGL((adc_scan16h_kernel<true>), dim3((unsigned)plan.grid), dim3(1024), 0, st, a);
-    else hipLaunchKernelGGL((adc_scan16h_kernel<false>), dim3((unsigned)plan.grid), dim3(1024), 0, st, a);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("adc_scan16h_kernel", codes_rot ? adc_scan16h_kernel<true> : adc_scan16h_kernel<false>, plan.grid, 1024, 0, st, a);
 }
 
 }  // namespace cvtmi

@@ -15,6 +15,7 @@
 // lazy selection on the integer keys between checkpoints, candidates re-summed exactly from the fp32 tables in the reference's
 // m order (ExactFromLutBatchP) before they are ranked -- thresholds, kept sets and distances bit-identical to the reference's.
 #include "adc_scan16.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -503,14 +504,9 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16p_kernel(const ScanArg
 int launch_adc_scan16p(const ScanArgs &a, int M, int64_t blocks, hipStream_t st)
 {
     if (blocks <= 0) return CVTMI_OK;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "adc_scan16p: grid too large (%lld)", (long long)blocks);
     if (!a.codes_rot || !a.lut_g) return fail(CVTMI_EINVAL, "adc_scan16p: pre-rotated rows / table scratch missing");
-    const dim3 g((unsigned)blocks);
-    if (M == 8) hipLaunchKernelGGL((adc_scan16p_kernel<1024, 8>), g, dim3(1024), 0, st, a);
-    else if (M == 4) hipLaunchKernelGGL((adc_scan16p_kernel<1024, 4>), g, dim3(1024), 0, st, a);
-    else return fail(CVTMI_EUNSUPPORTED, "adc_scan16p: M=%d (8 or 4)", M);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    if (M != 8 && M != 4) return fail(CVTMI_EUNSUPPORTED, "adc_scan16p: M=%d (8 or 4)", M);
+    return launch("adc_scan16p_kernel", M == 8 ? adc_scan16p_kernel<1024, 8> : adc_scan16p_kernel<1024, 4>, blocks, 1024, 0, st, a);
 }
 
 // packed pre-rotation: the 16-byte group g (= 16 / M rows) keeps its rows where they are, each rotated left by (g & (M - 1)) bytes
@@ -545,14 +541,8 @@ int launch_rotate_codes_packed(const uint8_t *codes, int M, uint8_t *codes_rot, 
     if (M != 8 && M != 4) return fail(CVTMI_EINVAL, "rotate_codes_packed: M=%d", M);
     const int rpl = 16 / M;
     const int64_t g0 = row0 / rpl, g1 = (n + rpl - 1) / rpl;
-    const int64_t blocks = (g1 - g0 + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "rotate_codes_packed: too many rows");
-    if (M == 8) hipLaunchKernelGGL(rotate_codes_packed_kernel<8>, dim3((unsigned)blocks), dim3(kBlock), 0, st, reinterpret_cast<const uint4 *>(codes),
-                                   reinterpret_cast<uint4 *>(codes_rot), g0, g1);
-    else hipLaunchKernelGGL(rotate_codes_packed_kernel<4>, dim3((unsigned)blocks), dim3(kBlock), 0, st, reinterpret_cast<const uint4 *>(codes),
-                            reinterpret_cast<uint4 *>(codes_rot), g0, g1);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("rotate_codes_packed_kernel", M == 8 ? rotate_codes_packed_kernel<8> : rotate_codes_packed_kernel<4>, blocks_for(g1 - g0, kBlock), kBlock, 0, st,
+                  reinterpret_cast<const uint4 *>(codes), reinterpret_cast<uint4 *>(codes_rot), g0, g1);
 }
 
 }  // namespace cvtmi

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "api_internal.h"
+#include "launch.h"
 
 extern "C" {
 
@@ -70,8 +71,7 @@ static int flat_add_common(cvtmi_flat_t h, const void *x, const int64_t *labels,
         h->identity = false;
         CVTMI_TRY(h->labels.grow((size_t)std::max<int64_t>(total, 1024) * 8, 0, st));
         if (h->n) {
-            hipLaunchKernelGGL(iota_i64_kernel, dim3(1024), dim3(kBlock), 0, st, h->labels.as<int64_t>(), (int64_t)0, h->n);
-            CVTMI_HIP(hipGetLastError());
+            CVTMI_TRY(launch("iota_i64_kernel", iota_i64_kernel, 1024, kBlock, 0, st, h->labels.as<int64_t>(), (int64_t)0, h->n));
         }
     }
     if (!h->identity && (size_t)total * 8 > h->labels.cap)
@@ -100,8 +100,7 @@ static int flat_add_common(cvtmi_flat_t h, const void *x, const int64_t *labels,
     if (!h->identity) {
         if (labels) CVTMI_HIP(hipMemcpyAsync(h->labels.as<int64_t>() + h->n, labels, (size_t)n * 8, kind, st));
         else {
-            hipLaunchKernelGGL(iota_i64_kernel, dim3(1024), dim3(kBlock), 0, st, h->labels.as<int64_t>(), h->n, total);
-            CVTMI_HIP(hipGetLastError());
+            CVTMI_TRY(launch("iota_i64_kernel", iota_i64_kernel, 1024, kBlock, 0, st, h->labels.as<int64_t>(), h->n, total));
         }
     }
     if (h->metric == CVTMI_METRIC_L2U8 && h->D % 32 == 0 && h->D <= 512) {
@@ -384,10 +383,10 @@ static int flat_search_streamed(cvtmi_flat_t h, FlatScratch &S, const float *q, 
     (void)hipGetLastError();
     if (!flat_f32_stream_applies(h->metric, D, n, k)) return CVTMI_OK;   // (a width only the threshold filter takes)
     const int qmax = flat_f32_stream_qmax(D), qpriv = flat_f32_stream_private_max(D);
-    int64_t passes = (nq + qmax - 1) / qmax;
+    int64_t passes = blocks_for(nq, qmax);
     // just past one private-ring pass, two of them beat one pass of the shared ring (1 M x 128-d, 128 queries: 0.28 against 0.32 ms)
     if (nq > qpriv && nq <= 2 * qpriv) passes = 2;
-    const int64_t per = (nq + passes - 1) / passes;
+    const int64_t per = blocks_for(nq, passes);
     if (S.fs_scratch.reserve(flat_f32_stream_scratch(D, n, per)) != CVTMI_OK) return CVTMI_OK;   // no room: the exact path answers
     CVTMI_TRY(S.fs_redo.reserve((size_t)nq * 2 * sizeof(uint32_t)));   // redo flags, then list counters
     // round 6: the bf16 operand copy of the threshold filter, when the handle keeps one, is what a small batch streams (half the bytes)
@@ -579,6 +578,9 @@ static FlatRoute flat_route(const cvtmi_flat_s *h, const void *q, int64_t nq, in
     r.big_u8 = (tun.variant == 0 || (tun.variant == 2 && k > 128)) && h->metric == CVTMI_METRIC_L2U8 && aligned && h->norms.p && flat_u8_tfilter_applies(h->D, h->n, nq, k);
     return r;
 }
+
+// the grid rule of launch.h, for the CPU test that pins it (include/cvtmi.h)
+extern "C" int cvtmi_describe_launch_grid(int64_t x, int64_t y, int64_t z) { return check_grid("cvtmi_describe_launch_grid", Grid(x, y, z)); }
 
 // which pipeline a flat search would take under the current tuning values, for inspection and for the CPU tests that pin the
 // dispatch rules (include/cvtmi.h)

@@ -6,6 +6,7 @@
 #include <random>
 
 #include "api_internal.h"
+#include "launch.h"
 
 // ================================================================ HNSW search ==================
 // The graph is immutable once loaded and searchKnn is a pure read in the reference (hnswalg.h:688-728): searches on one handle run side
@@ -89,11 +90,7 @@ int cvtmi_hnsw_load(const void *file, int64_t bytes, int metric, int D, cvtmi_hn
     CVTMI_HIP(hipGetDevice(&dev));  // no device: fails here, there is no CPU path
     cvtmi_hnsw_s *h = new (std::nothrow) cvtmi_hnsw_s();
     if (!h) return fail(CVTMI_ENOMEM, "cvtmi_hnsw_load: out of host memory");
-    h->device = dev; h->metric = metric; h->D = D;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) h->cus = prop.multiProcessorCount;
-    }
+    h->device = dev; h->metric = metric; h->D = D; h->cus = device_cus();
     auto up = [&](DevBuf &b, const void *src, size_t nb) -> int {
         CVTMI_TRY(b.reserve(nb ? nb : 16));
         if (nb) CVTMI_HIP(hipMemcpy(b.p, src, nb, hipMemcpyHostToDevice));
@@ -156,11 +153,7 @@ static int hnsw_build_impl(const float *x, bool dev, int64_t n, int D, int metri
     CVTMI_HIP(hipGetDevice(&devn));
     cvtmi_hnsw_s *h = new (std::nothrow) cvtmi_hnsw_s();
     if (!h) return fail(CVTMI_ENOMEM, "cvtmi_hnsw_build: out of host memory");
-    h->device = devn; h->metric = metric; h->D = D;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, devn) == hipSuccess && prop.multiProcessorCount > 0) h->cus = prop.multiProcessorCount;
-    }
+    h->device = devn; h->metric = metric; h->D = D; h->cus = device_cus();
     const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     auto run = [&]() -> int {
         const size_t vb = (size_t)n * D * 4, l0b = (size_t)n * (maxM0 + 1) * 4, ub = (size_t)upper_words * 4;

@@ -6,6 +6,7 @@
 #include <thread>
 
 #include "api_internal.h"
+#include "launch.h"
 
 // the exclusive side: taken by the outermost of the (Serial-ordered) non-search calls of an OPQ handle; the stream first waits for
 // the searches that are still in flight on other streams, and the searches that follow wait for this call
@@ -233,11 +234,9 @@ __global__ void iota_i32_kernel(int32_t *p, int64_t begin, int64_t end, int32_t 
 static int fill_i32(int32_t *p, int64_t begin, int64_t end, int32_t value, int is_iota, hipStream_t st)
 {
     if (end <= begin) return CVTMI_OK;
-    int64_t blocks = (end - begin + kBlock - 1) / kBlock;
+    int64_t blocks = blocks_for(end - begin, kBlock);
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(iota_i32_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, p, begin, end, value, is_iota);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("iota_i32_kernel", iota_i32_kernel, blocks, kBlock, 0, st, p, begin, end, value, is_iota);
 }
 
 static int opq_add_common(cvtmi_opq_t h, const uint8_t *codes, const int32_t *list_id, const int32_t *video_id, int64_t n,

@@ -26,6 +26,7 @@
 #include "block_topk.h"
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -475,21 +476,14 @@ int launch_assign_filtered(const float *x, int64_t ld, int64_t n, int d, const f
     unsigned int *flag_cnt = cmax2 + 1;
     int32_t *flag_list = reinterpret_cast<int32_t *>(base + b_pack + b_nhc + b_misc);
     CVTMI_HIP(hipMemsetAsync(cmax2, 0, 8, st));
-    hipLaunchKernelGGL(assign_pack_kernel, dim3((unsigned)((ntiles * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, cent, k, d, ntiles,
-                       packA, nhcp, cmax2);
+    CVTMI_TRY(launch("assign_pack_kernel", assign_pack_kernel, blocks_for(ntiles * 64, kBlock), kBlock, 0, st, cent, k, d, ntiles, packA, nhcp, cmax2));
     constexpr int rows_per_block = 32 * (AF_THREADS / 64);
     const int64_t blocks = std::min<int64_t>((n + rows_per_block - 1) / rows_per_block, 256 * 4);
-#define CVTMI_AF(N)                                                                                                                \
-    case N:                                                                                                                        \
-        hipLaunchKernelGGL((assign_filter_kernel<N>), dim3((unsigned)blocks), dim3(AF_THREADS), 0, st, x, ld, n, packA, nhcp, cmax2, ntiles, \
-                           assign, changed, flag_list, flag_cnt);                                                                  \
-        break;
-    switch (nch) {
-        CVTMI_AF(2) CVTMI_AF(3) CVTMI_AF(4) CVTMI_AF(5) CVTMI_AF(6) CVTMI_AF(7) CVTMI_AF(8)
-        default: return fail(CVTMI_EUNSUPPORTED, "assign filter: d=%d", d);
-    }
-#undef CVTMI_AF
-    CVTMI_HIP(hipGetLastError());
+    static constexpr decltype(&assign_filter_kernel<2>) filter[] = {   // by 16-float chunks of a row: 2 .. 8
+        assign_filter_kernel<2>, assign_filter_kernel<3>, assign_filter_kernel<4>, assign_filter_kernel<5>,
+        assign_filter_kernel<6>, assign_filter_kernel<7>, assign_filter_kernel<8> };
+    if (nch < 2 || nch > 8) return fail(CVTMI_EUNSUPPORTED, "assign filter: d=%d", d);
+    CVTMI_TRY(launch("assign_filter_kernel", filter[nch - 2], blocks, AF_THREADS, 0, st, x, ld, n, packA, nhcp, cmax2, ntiles, assign, changed, flag_list, flag_cnt));
     unsigned int nf = 0;
     CVTMI_HIP(hipMemcpyAsync(&nf, flag_cnt, sizeof nf, hipMemcpyDeviceToHost, st));
     CVTMI_HIP(hipStreamSynchronize(st));
@@ -507,13 +501,12 @@ int launch_assign_filtered(const float *x, int64_t ld, int64_t n, int d, const f
     exact = reinterpret_cast<int32_t *>(tmp + b_rows);
     part_d = reinterpret_cast<float *>(tmp + b_rows + b_ex);
     part_i = reinterpret_cast<int32_t *>(tmp + b_rows + b_ex + b_part);
-    hipLaunchKernelGGL(assign_gather_rows_kernel, dim3((unsigned)(((int64_t)nf * d + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, x, ld, d,
-                       flag_list, (int)nf, rows);
-    int rc = launch_kmeans_assign_split(rows, d, nf, d, cent, k, exact, splits, part_d, part_i, st);
-    if (rc == CVTMI_OK) {
-        hipLaunchKernelGGL(assign_scatter_kernel, dim3((nf + kBlock - 1) / kBlock), dim3(kBlock), 0, st, flag_list, exact, (int)nf, assign, changed);
-        if (hipGetLastError() != hipSuccess) rc = fail(CVTMI_EHIP, "assign filter: scatter launch failed");
-    }
+    auto resolve = [&]() -> int {
+        CVTMI_TRY(launch("assign_gather_rows_kernel", assign_gather_rows_kernel, blocks_for((int64_t)nf * d, kBlock), kBlock, 0, st, x, ld, d, flag_list, (int)nf, rows));
+        CVTMI_TRY(launch_kmeans_assign_split(rows, d, nf, d, cent, k, exact, splits, part_d, part_i, st));
+        return launch("assign_scatter_kernel", assign_scatter_kernel, blocks_for(nf, kBlock), kBlock, 0, st, flag_list, exact, (int)nf, assign, changed);
+    };
+    const int rc = resolve();
     (void)hipStreamSynchronize(st);  // the temporaries die with this frame
     (void)hipFree(tmp);
     return rc;
@@ -542,26 +535,21 @@ int launch_coarse_probe_filtered(const float *q, int64_t nq, int d, const float 
     uint32_t *cmax2 = reinterpret_cast<uint32_t *>(base + b_pack + b_nhc);
     float *T = reinterpret_cast<float *>(base + b_pack + b_nhc + b_misc);
     CVTMI_HIP(hipMemsetAsync(cmax2, 0, 8, st));
-    hipLaunchKernelGGL(assign_pack_kernel, dim3((unsigned)((ntiles * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, cent, k, d, ntiles,
-                       packA, nhcp, cmax2);
+    CVTMI_TRY(launch("assign_pack_kernel", assign_pack_kernel, blocks_for(ntiles * 64, kBlock), kBlock, 0, st, cent, k, d, ntiles, packA, nhcp, cmax2));
     constexpr int rows_per_block = 32 * (AF_THREADS / 64);
+    static constexpr decltype(&probe_score_kernel<2>) scores[] = {   // by 16-float chunks of a query: 2 .. 8
+        probe_score_kernel<2>, probe_score_kernel<3>, probe_score_kernel<4>, probe_score_kernel<5>,
+        probe_score_kernel<6>, probe_score_kernel<7>, probe_score_kernel<8> };
+    if (nch < 2 || nch > 8) return fail(CVTMI_EUNSUPPORTED, "probe filter: d=%d", d);
+    const auto score = scores[nch - 2];
     for (int64_t a = 0; a < nq; a += chunk) {
         const int64_t m = std::min(chunk, nq - a);
         const int64_t blocks = std::min<int64_t>((m + rows_per_block - 1) / rows_per_block, 256 * 4);
         // centroid-tile ranges per query block: enough workgroups for two per CU, at least 8 tiles (256 centroids) each
-        const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ntiles / 8, 32), (512 + blocks - 1) / blocks));
-#define CVTMI_PS(N)                                                                                                                   \
-    case N:                                                                                                                           \
-        hipLaunchKernelGGL((probe_score_kernel<N>), dim3((unsigned)blocks, gy), dim3(AF_THREADS), 0, st, q + a * d, (int64_t)d, m, packA, nhcp, ntiles, T, ldT); \
-        break;
-        switch (nch) {
-            CVTMI_PS(2) CVTMI_PS(3) CVTMI_PS(4) CVTMI_PS(5) CVTMI_PS(6) CVTMI_PS(7) CVTMI_PS(8)
-            default: return fail(CVTMI_EUNSUPPORTED, "probe filter: d=%d", d);
-        }
-#undef CVTMI_PS
-        hipLaunchKernelGGL(probe_select_kernel, dim3((unsigned)m), dim3(kBlock), (size_t)d * sizeof(float), st, T, ldT, q + a * d, d, cent, k,
-                           cmax2, nprobe, probe + a * nprobe);
-        CVTMI_HIP(hipGetLastError());
+        const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ntiles / 8, 32), (512 + blocks - 1) / blocks));
+        CVTMI_TRY(launch("probe_score_kernel", score, { blocks, gy }, AF_THREADS, 0, st, q + a * d, (int64_t)d, m, packA, nhcp, ntiles, T, ldT));
+        CVTMI_TRY(launch("probe_select_kernel", probe_select_kernel, m, kBlock, (size_t)d * sizeof(float), st, T, ldT, q + a * d, d, cent, k, cmax2, nprobe,
+                         probe + a * nprobe));
     }
     CVTMI_HIP(hipStreamSynchronize(st));  // the shared scratch is free for the next caller when the lock is dropped
     return CVTMI_OK;

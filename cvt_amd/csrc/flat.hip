@@ -20,6 +20,7 @@
 #include "block_topk.h"
 #include "kernels.h"
 #include "dist_f32.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -249,10 +250,8 @@ int launch_flat_block(const float *src, int64_t n, int D, int64_t row0, float *d
     if (n <= 0) return CVTMI_OK;
     int64_t blocks = (n * (D / 4) + kBlock - 1) / kBlock;
     if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL(flat_block_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, reinterpret_cast<const float4 *>(src), n, D / 4,
-                       row0, reinterpret_cast<float4 *>(dst));
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("flat_block_kernel", flat_block_kernel, blocks, kBlock, 0, st, reinterpret_cast<const float4 *>(src), n, D / 4, row0,
+                  reinterpret_cast<float4 *>(dst));
 }
 
 // the inverse, for the threshold filter's exact finish (round 6): rows [row0 / 64 * 64, n) of the blocked layout -> row-major dst.  A workgroup moves 16
@@ -280,10 +279,8 @@ int launch_flat_unblock(const float *blocked, int64_t row0, int64_t n, int D, fl
     if (b1 <= b0) return CVTMI_OK;
     const int64_t blocks = (b1 - b0) * ((D / 4 + 15) / 16);
     if (blocks > 0x7fffffffLL) return fail(CVTMI_EINVAL, "flat_unblock: too many blocks");
-    hipLaunchKernelGGL(flat_unblock_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, reinterpret_cast<const float4 *>(blocked), b0, n, D / 4,
-                       reinterpret_cast<float4 *>(dst));
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("flat_unblock_kernel", flat_unblock_kernel, blocks, kBlock, 0, st, reinterpret_cast<const float4 *>(blocked), b0, n, D / 4,
+                  reinterpret_cast<float4 *>(dst));
 }
 
 // uint8 rows.  VEC: rows are 16-byte aligned multiples of 16 (D % 16 == 0) -> dwordx4 loads + dot4
@@ -696,13 +693,9 @@ int launch_flat_u8_norms(const uint8_t *x, int64_t n, int D, int32_t *norms, hip
     const int lpr = D >> 4;
     if (D % 32 == 0 && D <= 1024 && (lpr & (lpr - 1)) == 0 && ((uintptr_t)x & 15) == 0) {
         const int64_t threads = n * lpr;
-        hipLaunchKernelGGL(flat_u8_norms_coalesced_kernel, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                           st, x, n, D, norms);
-    } else {
-        hipLaunchKernelGGL(flat_u8_norms_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, x, n, D, norms);
+        return launch("flat_u8_norms_coalesced_kernel", flat_u8_norms_coalesced_kernel, blocks_for(threads, kBlock), kBlock, 0, st, x, n, D, norms);
     }
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("flat_u8_norms_kernel", flat_u8_norms_kernel, blocks_for(n, kBlock), kBlock, 0, st, x, n, D, norms);
 }
 
 struct FlatMfmaArgs {
@@ -1230,12 +1223,24 @@ int flat_u8_mfma_qtile(int D, int k, int64_t nq)
 int flat_u8_mfma_splits(int64_t n, int64_t nq, int qt)
 {
     if (qt <= 32) return flat_plan_splits(n, nq, qt);
-    const int64_t groups = (nq + qt - 1) / qt;
-    int64_t s = (512 + groups - 1) / groups;
+    const int64_t groups = blocks_for(nq, qt);
+    int64_t s = blocks_for(512, groups);
     const int64_t max_by_rows = n / 8192 > 1 ? n / 8192 : 1;
     if (s > max_by_rows) s = max_by_rows;
     if (s >= 8) s = (s / 8) * 8;  // a row split per XCD: the query groups of a split share its L2
     return (int)(s < 1 ? 1 : s);
+}
+
+// the row-tile kernel of NW waves under cvtmi_set_tuning("flat_u8_opt"): the 8-wave kernel for D <= 512 has the forms 0 .. 3, the
+// others form 0 alone (their other forms are built and never taken)
+template <int NW, int CAP, int DMAX>
+static decltype(&flat_u8_rowtile_kernel<NW, CAP, DMAX, 0>) flat_u8_rowtile_for(int opt)
+{
+    if (NW == 8 && DMAX == 512 && opt == 0) return flat_u8_rowtile_kernel<NW, CAP, DMAX, 0>;
+    if (NW == 8 && DMAX == 512 && opt == 1) return flat_u8_rowtile_kernel<NW, CAP, DMAX, 1>;
+    if (NW == 8 && DMAX == 512 && opt == 2) return flat_u8_rowtile_kernel<NW, CAP, DMAX, 2>;
+    if (NW == 8 && DMAX == 512) return flat_u8_rowtile_kernel<NW, CAP, DMAX, 3>;
+    return flat_u8_rowtile_kernel<NW, CAP, DMAX, 0>;
 }
 
 int launch_flat_u8_mfma(int D, const uint8_t *data, const int32_t *norms, int64_t n, const uint8_t *q, int64_t nq, int k,
@@ -1245,60 +1250,37 @@ int launch_flat_u8_mfma(int D, const uint8_t *data, const int32_t *norms, int64_
     if (!qt) return fail(CVTMI_EUNSUPPORTED, "flat_u8_mfma: shape not covered");
     FlatMfmaArgs a;
     a.data = data; a.norms = norms; a.n = n; a.q = q; a.nq = (int)nq; a.D = D; a.k = k; a.splits = splits;
-    int64_t rps = (n + splits - 1) / splits;
+    int64_t rps = blocks_for(n, splits);
     rps = ((rps + 127) / 128) * 128;
     if (rps < 128) rps = 128;
     a.rows_per_split = rps;
     a.part_d = part_d; a.part_id = part_id; a.gthr = gthr;
     a.nslot = (qt > 32 && k <= 16 && splits >= 2 * k) ? k : 0;
     a.gslot = gthr ? gthr + nq : nullptr;
-    const int64_t groups = (nq + qt - 1) / qt;
+    const int64_t groups = blocks_for(nq, qt);
     const int64_t blocks = groups * splits;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "flat_u8_mfma: grid too large");
     if (qt > 32) {
         if (!gthr) return fail(CVTMI_EINVAL, "flat_u8_mfma: threshold scratch missing");
         CVTMI_HIP(hipMemsetAsync(gthr, 0xff, (size_t)nq * (1 + 16) * sizeof(uint32_t), st));  // k-th bests + up to 16 slots per query
     }
     if (qt == 32) {
         const size_t lds = (size_t)qt * (D + 16);
-#define CVTMI_FM(QB, CAP, TRIG, DMAX)                                                                                   \
-    do {                                                                                                                \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)flat_u8_mfma_kernel<QB, CAP, TRIG, DMAX>,                           \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-        hipLaunchKernelGGL((flat_u8_mfma_kernel<QB, CAP, TRIG, DMAX>), dim3((unsigned)blocks), dim3(kBlock), lds, st, a); \
-    } while (0)
-        if (D <= 128) CVTMI_FM(1, 208, 176, 128); else CVTMI_FM(1, 208, 176, 512);
-#undef CVTMI_FM
-    } else {
-        const size_t lds = (size_t)2 * 32 * (D + 16);
-        const int u8_opt = tune_flat_u8_opt.geti();
-#define CVTMI_RT1(NW, CAP, DMAX, OPT)                                                                                   \
-    do {                                                                                                                \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)flat_u8_rowtile_kernel<NW, CAP, DMAX, OPT>,                         \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-        hipLaunchKernelGGL((flat_u8_rowtile_kernel<NW, CAP, DMAX, OPT>), dim3((unsigned)blocks), dim3(64 * NW), lds, st, a); \
-    } while (0)
-#define CVTMI_RT(NW, CAP, DMAX)                                                                                         \
-    do {                                                                                                                \
-        if (NW == 8 && DMAX == 512 && u8_opt == 0) CVTMI_RT1(NW, CAP, DMAX, 0);                                         \
-        else if (NW == 8 && DMAX == 512 && u8_opt == 1) CVTMI_RT1(NW, CAP, DMAX, 1);                                    \
-        else if (NW == 8 && DMAX == 512 && u8_opt == 2) CVTMI_RT1(NW, CAP, DMAX, 2);                                    \
-        else if (NW == 8 && DMAX == 512) CVTMI_RT1(NW, CAP, DMAX, 3);                                                   \
-        else CVTMI_RT1(NW, CAP, DMAX, 0);                                                                               \
-    } while (0)
-        // CAP by k: k <= 24 -> 56, k <= 80 -> 112 (CAP - k >= 32: a compacted buffer takes a whole tile)
-        if (k <= 24) {
-            if (qt == 256) { if (D <= 128) CVTMI_RT(8, 56, 128); else CVTMI_RT(8, 56, 512); }
-            else if (qt == 128) { if (D <= 128) CVTMI_RT(4, 56, 128); else CVTMI_RT(4, 56, 512); }
-            else { if (D <= 128) CVTMI_RT(2, 56, 128); else CVTMI_RT(2, 56, 512); }
-        } else {  // k <= 80, 128 queries
-            if (D <= 128) CVTMI_RT(4, 112, 128); else CVTMI_RT(4, 112, 512);
-        }
-#undef CVTMI_RT
-#undef CVTMI_RT1
+        return launch_lds("flat_u8_mfma_kernel", D <= 128 ? flat_u8_mfma_kernel<1, 208, 176, 128> : flat_u8_mfma_kernel<1, 208, 176, 512>, blocks, kBlock, lds, st, a);
     }
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    const size_t lds = (size_t)2 * 32 * (D + 16);
+    const int opt = tune_flat_u8_opt.geti();
+    const bool narrow = D <= 128;
+    decltype(&flat_u8_rowtile_kernel<8, 56, 128, 0>) kern;
+    int nw = 4;
+    // CAP by k: k <= 24 -> 56, k <= 80 -> 112 (CAP - k >= 32: a compacted buffer takes a whole tile)
+    if (k <= 24) {
+        if (qt == 256) { nw = 8; kern = narrow ? flat_u8_rowtile_for<8, 56, 128>(opt) : flat_u8_rowtile_for<8, 56, 512>(opt); }
+        else if (qt == 128) kern = narrow ? flat_u8_rowtile_for<4, 56, 128>(opt) : flat_u8_rowtile_for<4, 56, 512>(opt);
+        else { nw = 2; kern = narrow ? flat_u8_rowtile_for<2, 56, 128>(opt) : flat_u8_rowtile_for<2, 56, 512>(opt); }
+    } else {  // k <= 80, 128 queries
+        kern = narrow ? flat_u8_rowtile_for<4, 112, 128>(opt) : flat_u8_rowtile_for<4, 112, 512>(opt);
+    }
+    return launch_lds("flat_u8_rowtile_kernel", kern, blocks, 64 * nw, lds, st, a);
 }
 
 __global__ __launch_bounds__(kBlock) void gather_labels_kernel(int64_t *ids, int64_t count, const int64_t *labels)
@@ -1313,10 +1295,7 @@ __global__ __launch_bounds__(kBlock) void gather_labels_kernel(int64_t *ids, int
 int launch_gather_labels(int64_t *ids, int64_t count, const int64_t *labels, hipStream_t st)
 {
     if (count <= 0) return CVTMI_OK;
-    hipLaunchKernelGGL(gather_labels_kernel, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, ids,
-                       count, labels);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("gather_labels_kernel", gather_labels_kernel, blocks_for(count, kBlock), kBlock, 0, st, ids, count, labels);
 }
 
 __global__ __launch_bounds__(kBlock) void offset_labels_kernel(int64_t *ids, int64_t count, int64_t base)
@@ -1327,9 +1306,7 @@ __global__ __launch_bounds__(kBlock) void offset_labels_kernel(int64_t *ids, int
 int launch_offset_labels(int64_t *ids, int64_t count, int64_t base, hipStream_t st)
 {
     if (count <= 0) return CVTMI_OK;
-    hipLaunchKernelGGL(offset_labels_kernel, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, ids, count, base);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("offset_labels_kernel", offset_labels_kernel, blocks_for(count, kBlock), kBlock, 0, st, ids, count, base);
 }
 
 // *out = the non-zero words of flags[0 .. count) (one workgroup: the redo flags of one search)
@@ -1346,9 +1323,7 @@ __global__ __launch_bounds__(kBlock) void count_nonzero_kernel(const uint32_t *f
 }
 int launch_count_nonzero(const uint32_t *flags, int64_t count, uint32_t *out, hipStream_t st)
 {
-    hipLaunchKernelGGL(count_nonzero_kernel, dim3(1), dim3(kBlock), 0, st, flags, count, out);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("count_nonzero_kernel", count_nonzero_kernel, 1, kBlock, 0, st, flags, count, out);
 }
 
 constexpr int STREAM_SLICES = 64;
@@ -1364,8 +1339,7 @@ int launch_flat_u8_mstream_finish(int D, const uint8_t *data, int64_t n, const u
     StreamFinishArgs fa = {};
     fa.n = n; fa.gmin = wmin; fa.G = G; fa.S = S; fa.rpi_log2 = 5; fa.k = k; fa.part_d = part_d; fa.part_id = part_id;
     fa.tmin = tmin; fa.nqp = nqp; fa.tile_group = tile_group; fa.X = data; fa.Q = q; fa.D = D;
-    hipLaunchKernelGGL(flat_u8_stream_finish_kernel, dim3((unsigned)(nq * S)), dim3(kBlock), 0, st, fa);
-    CVTMI_HIP(hipGetLastError());
+    CVTMI_TRY(launch("flat_u8_stream_finish_kernel", flat_u8_stream_finish_kernel, nq * S, kBlock, 0, st, fa));
     return launch_topk_merge(part_d, part_id, nq, S, k, out_d, out_rows, st);
 }
 int flat_u8_stream_slices() { return STREAM_SLICES; }
@@ -1377,7 +1351,7 @@ int flat_plan_splits(int64_t n, int64_t nq, int qtile)
     // 8 workgroups of 256 threads fit a CU: 2048 run at a time on 256 CUs.  One round of long workgroups beats
     // two rounds of short ones (tools/bench_flat_f32.py: 2250 workgroups took as long as 2 x their own length),
     // so the row splits fill the machine once and no more: the largest split count with groups * splits <= 2048.
-    const int64_t groups = (nq + qtile - 1) / qtile;
+    const int64_t groups = blocks_for(nq, qtile);
     const int64_t slots = 2048;
     int64_t need = slots / groups;
     int64_t max_by_rows = n / 2048;
@@ -1389,23 +1363,18 @@ int flat_plan_splits(int64_t n, int64_t nq, int qtile)
 }
 
 template <bool IP, int LANES>
-static int launch_f32(const FlatArgs &a, int qtile, unsigned blocks, size_t lds, hipStream_t st)
+static int launch_f32(const FlatArgs &a, int qtile, int64_t blocks, size_t lds, hipStream_t st)
 {
-    if (a.k > 128) {  // one query per workgroup, the large selection buffer (kernels.h: kBigK)
-        if constexpr (LANES >= 4) hipLaunchKernelGGL((flat_f32_sq_kernel<IP, LANES, 1, kBigCap, kBigTrig>), dim3(blocks), dim3(kBlock), 0, st, a);
-        else hipLaunchKernelGGL((flat_f32_kernel<IP, LANES, 1, kBigCap, kBigTrig>), dim3(blocks), dim3(kBlock), lds, st, a);
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
-    }
-    if constexpr (LANES >= 4) {  // queries in SGPRs (rows are 16-byte aligned: D % 4 == 0)
-        if (qtile == 4) hipLaunchKernelGGL((flat_f32_sq_kernel<IP, LANES, 4>), dim3(blocks), dim3(kBlock), 0, st, a);
-        else hipLaunchKernelGGL((flat_f32_sq_kernel<IP, LANES, 1>), dim3(blocks), dim3(kBlock), 0, st, a);
+    const bool big = a.k > 128;   // one query per workgroup, the large selection buffer (kernels.h: kBigK)
+    if constexpr (LANES >= 4) {   // queries in SGPRs (rows are 16-byte aligned: D % 4 == 0)
+        auto kern = flat_f32_sq_kernel<IP, LANES, 1, kBigCap, kBigTrig>;
+        if (!big) kern = qtile == 4 ? flat_f32_sq_kernel<IP, LANES, 4> : flat_f32_sq_kernel<IP, LANES, 1>;
+        return launch("flat_f32_sq_kernel", kern, blocks, kBlock, 0, st, a);
     } else {
-        if (qtile == 4) hipLaunchKernelGGL((flat_f32_kernel<IP, LANES, 4>), dim3(blocks), dim3(kBlock), lds, st, a);
-        else hipLaunchKernelGGL((flat_f32_kernel<IP, LANES, 1>), dim3(blocks), dim3(kBlock), lds, st, a);
+        auto kern = flat_f32_kernel<IP, LANES, 1, kBigCap, kBigTrig>;
+        if (!big) kern = qtile == 4 ? flat_f32_kernel<IP, LANES, 4> : flat_f32_kernel<IP, LANES, 1>;
+        return launch("flat_f32_kernel", kern, blocks, kBlock, lds, st, a);
     }
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
 }
 
 int launch_flat_search(int metric, int D, const void *data, int64_t n, const void *q, int64_t nq, int k, int qtile,
@@ -1419,39 +1388,31 @@ int launch_flat_search(int metric, int D, const void *data, int64_t n, const voi
     if (D < 1 || D > 4096) return fail(CVTMI_EUNSUPPORTED, "flat_search: D=%d outside 1..4096", D);
     FlatArgs a;
     a.data = data; a.n = n; a.q = q; a.nq = (int)nq; a.D = D; a.k = k; a.splits = splits;
-    int64_t rps = (n + splits - 1) / splits;
+    int64_t rps = blocks_for(n, splits);
     const int64_t tile_rows = (int64_t)kBlock * FLAT_R;
     rps = ((rps + tile_rows - 1) / tile_rows) * tile_rows;
     if (rps < tile_rows) rps = tile_rows;
     a.rows_per_split = rps;
     a.part_d = part_d; a.part_id = part_id;
     a.only_if = only_if;
-    const int64_t groups = (nq + qtile - 1) / qtile;
+    const int64_t groups = blocks_for(nq, qtile);
     const int64_t blocks = groups * splits;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "flat_search: grid too large");
     const size_t lds_f = (size_t)qtile * D * sizeof(float);
     switch (metric) {
         case CVTMI_METRIC_IP:
-            if (D % 4 == 0) return launch_f32<true, 4>(a, qtile, (unsigned)blocks, lds_f, st);
-            return launch_f32<true, 1>(a, qtile, (unsigned)blocks, lds_f, st);
+            if (D % 4 == 0) return launch_f32<true, 4>(a, qtile, blocks, lds_f, st);
+            return launch_f32<true, 1>(a, qtile, blocks, lds_f, st);
         case CVTMI_METRIC_L2F:
-            if (D % 16 == 0) return launch_f32<false, 8>(a, qtile, (unsigned)blocks, lds_f, st);
-            if (D % 4 == 0) return launch_f32<false, 4>(a, qtile, (unsigned)blocks, lds_f, st);
-            return launch_f32<false, 1>(a, qtile, (unsigned)blocks, lds_f, st);
+            if (D % 16 == 0) return launch_f32<false, 8>(a, qtile, blocks, lds_f, st);
+            if (D % 4 == 0) return launch_f32<false, 4>(a, qtile, blocks, lds_f, st);
+            return launch_f32<false, 1>(a, qtile, blocks, lds_f, st);
         case CVTMI_METRIC_L2U8: {
             const size_t lds_u = (size_t)qtile * ((D >> 2) + 1) * sizeof(uint32_t);
-            if (k > 128) {
-                if (D % 16 == 0) hipLaunchKernelGGL((flat_u8_kernel<true, 1, kBigCap, kBigTrig>), dim3((unsigned)blocks), dim3(kBlock), lds_u, st, a);
-                else hipLaunchKernelGGL((flat_u8_kernel<false, 1, kBigCap, kBigTrig>), dim3((unsigned)blocks), dim3(kBlock), lds_u, st, a);
-            } else if (D % 16 == 0) {
-                if (qtile == 4) hipLaunchKernelGGL((flat_u8_kernel<true, 4>), dim3((unsigned)blocks), dim3(kBlock), lds_u, st, a);
-                else hipLaunchKernelGGL((flat_u8_kernel<true, 1>), dim3((unsigned)blocks), dim3(kBlock), lds_u, st, a);
-            } else {
-                if (qtile == 4) hipLaunchKernelGGL((flat_u8_kernel<false, 4>), dim3((unsigned)blocks), dim3(kBlock), lds_u, st, a);
-                else hipLaunchKernelGGL((flat_u8_kernel<false, 1>), dim3((unsigned)blocks), dim3(kBlock), lds_u, st, a);
-            }
-            CVTMI_HIP(hipGetLastError());
-            return CVTMI_OK;
+            decltype(&flat_u8_kernel<true, 1>) kern;   // <true>: rows of whole 16-byte pieces
+            if (k > 128) kern = D % 16 == 0 ? flat_u8_kernel<true, 1, kBigCap, kBigTrig> : flat_u8_kernel<false, 1, kBigCap, kBigTrig>;
+            else if (D % 16 == 0) kern = qtile == 4 ? flat_u8_kernel<true, 4> : flat_u8_kernel<true, 1>;
+            else kern = qtile == 4 ? flat_u8_kernel<false, 4> : flat_u8_kernel<false, 1>;
+            return launch("flat_u8_kernel", kern, blocks, kBlock, lds_u, st, a);
         }
         default: break;
     }

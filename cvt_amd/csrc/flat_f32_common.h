@@ -1,8 +1,6 @@
 // flat_f32_common.h -- helpers shared by the fp32 flat-search kernels (flat_f32_stream.hip: the stream over the rows;
 // flat_f32_tfilter.hip: large batches as a threshold filter).  gfx950 only.
 #pragma once
-#include <atomic>
-
 #include "common.h"
 
 namespace cvtmi {
@@ -151,18 +149,6 @@ __device__ __forceinline__ float fs_qlow(const float *q, int D)
         }
     }
     return fs_wave_sum(s_);
-}
-
-// (host) the dynamic-LDS attribute of a kernel, once per device
-static int fs_set_lds(const void *fn, size_t lds, std::atomic<bool> (&done)[16])
-{
-    int dev = 0;
-    CVTMI_HIP(hipGetDevice(&dev));
-    if (dev >= 16 || !done[dev].load(std::memory_order_acquire)) {   // the attribute is per device (several host threads may search at once: setting it twice is harmless)
-        CVTMI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev < 16) done[dev].store(true, std::memory_order_release);
-    }
-    return CVTMI_OK;
 }
 
 }  // namespace

@@ -33,11 +33,11 @@
 #include <algorithm>
 #include <type_traits>
 
-#include <atomic>
 
 #include "common.h"
 #include "flat_f32_common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -923,10 +923,8 @@ int launch_flat_f32_bias(float *X, int D, int metric, int64_t row0, int64_t row1
 {
     const int64_t row_pad = (row1 + 63) / 64 * 64;
     if (row_pad <= row0) return CVTMI_OK;
-    hipLaunchKernelGGL(flat_f32_bias_kernel, dim3((unsigned)((row_pad - row0 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, X, D,
-                       metric == CVTMI_METRIC_L2F ? 1 : 0, row0, row1, row_pad, bias, stats);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("flat_f32_bias_kernel", flat_f32_bias_kernel, blocks_for(row_pad - row0, kBlock), kBlock, 0, st, X, D, metric == CVTMI_METRIC_L2F ? 1 : 0,
+                  row0, row1, row_pad, bias, stats);
 }
 
 struct FsStreamArgs {
@@ -935,13 +933,10 @@ struct FsStreamArgs {
 template <int NCH, int QB>
 static int fs_launch_packed_qb(const FsStreamArgs &a, const void *pack, hipStream_t st)
 {
-    static std::atomic<bool> attr_set[16] = {};
+    static LdsOnce attr_set = {};
     const size_t lds = (size_t)4 * FsGeom<NCH, true>::WAVE_LDS;
-    CVTMI_TRY(fs_set_lds((const void *)flat_f32_mstream_kernel<NCH, QB, true>, lds, attr_set));
-    hipLaunchKernelGGL((flat_f32_mstream_kernel<NCH, QB, true>), dim3(FS_BLOCKS), dim3(256), lds, st, reinterpret_cast<const float *>(pack), a.bias, a.n_tiles, a.q, a.nq,
-                       a.G, a.NG, a.gb, a.wm, a.redo, a.cnt, fs_nt(false, QB) ? 1 : 0);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch_lds_once("flat_f32_mstream_kernel", flat_f32_mstream_kernel<NCH, QB, true>, attr_set, lds, FS_BLOCKS, 256, lds, st,
+                           reinterpret_cast<const float *>(pack), a.bias, a.n_tiles, a.q, a.nq, a.G, a.NG, a.gb, a.wm, a.redo, a.cnt, fs_nt(false, QB) ? 1 : 0);
 }
 template <int NCH>
 static int fs_launch_packed(int qb, const FsStreamArgs &a, const void *pack, hipStream_t st)
@@ -955,22 +950,19 @@ static int fs_launch_packed(int qb, const FsStreamArgs &a, const void *pack, hip
 template <int NCH, int QB, bool SHARED>
 static int fs_launch_stream(const FsStreamArgs &a, hipStream_t st)
 {
-    static std::atomic<bool> attr_set[16] = {};
+    static LdsOnce attr_set = {};
     if constexpr (SHARED && NCH % 4 != 0) {
         return fail(CVTMI_EINVAL, "flat_f32_stream: shared ring at D=%d", 16 * NCH);
     } else if constexpr (SHARED) {
         const size_t lds = FssGeom<NCH, 4>::LDS;
-        CVTMI_TRY(fs_set_lds((const void *)flat_f32_mshare_kernel<NCH, QB, 4, 4>, lds, attr_set));
-        hipLaunchKernelGGL((flat_f32_mshare_kernel<NCH, QB, 4, 4>), dim3(FSS_STREAMS), dim3(256), lds, st, a.X, a.bias, a.n_tiles, a.q, a.nq, a.G, a.NG,
-                           a.gb, a.wm, a.redo, a.cnt, tune_flat_f32_dbg.geti() | (fs_nt(true, QB) ? 16 : 0));   // "flat_f32_dbg": timing experiments (results wrong when non-zero)
+        return launch_lds_once("flat_f32_mshare_kernel", flat_f32_mshare_kernel<NCH, QB, 4, 4>, attr_set, lds, FSS_STREAMS, 256, lds, st, a.X, a.bias, a.n_tiles, a.q, a.nq,
+                               a.G, a.NG, a.gb, a.wm, a.redo, a.cnt,
+                               tune_flat_f32_dbg.geti() | (fs_nt(true, QB) ? 16 : 0));   // "flat_f32_dbg": timing experiments (results wrong when non-zero)
     } else {
         const size_t lds = (size_t)4 * FsGeom<NCH>::WAVE_LDS;
-        CVTMI_TRY(fs_set_lds((const void *)flat_f32_mstream_kernel<NCH, QB>, lds, attr_set));
-        hipLaunchKernelGGL((flat_f32_mstream_kernel<NCH, QB>), dim3(FS_BLOCKS), dim3(256), lds, st, a.X, a.bias, a.n_tiles, a.q, a.nq, a.G, a.NG,
-                           a.gb, a.wm, a.redo, a.cnt, fs_nt(false, QB) ? 1 : 0);
+        return launch_lds_once("flat_f32_mstream_kernel", flat_f32_mstream_kernel<NCH, QB>, attr_set, lds, FS_BLOCKS, 256, lds, st, a.X, a.bias, a.n_tiles, a.q, a.nq,
+                               a.G, a.NG, a.gb, a.wm, a.redo, a.cnt, fs_nt(false, QB) ? 1 : 0);
     }
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
 }
 template <int NCH, bool SHARED>
 static int fs_launch_qb(int qb, const FsStreamArgs &a, hipStream_t st)
@@ -984,6 +976,14 @@ static int fs_launch_qb(int qb, const FsStreamArgs &a, hipStream_t st)
     if (qb == 2) return fs_launch_stream<NCH, 2, SHARED>(a, st);
     if (qb == 1) return fs_launch_stream<NCH, 1, SHARED>(a, st);
     return fail(CVTMI_EINVAL, "flat_f32_stream: %d query blocks per wave at D=%d", qb, 16 * NCH);
+}
+
+// rows of 16 NCH floats: the bf16 operand copy, the shared ring or one stream per wave
+template <int NCH>
+static int fs_launch_any(bool packed, bool shared, int qb, const FsStreamArgs &a, const void *pack, hipStream_t st)
+{
+    if (packed) return fs_launch_packed<NCH>(qb, a, pack, st);
+    return shared ? fs_launch_qb<NCH, true>(qb, a, st) : fs_launch_qb<NCH, false>(qb, a, st);
 }
 
 // one pass: nq <= flat_f32_stream_qmax(D) queries against rows [0, n); results for queries whose redo flag stays 0.
@@ -1006,13 +1006,15 @@ int launch_flat_f32_stream(int metric, int D, const float *X, const float *bias,
     const int qb = shared ? (int)((nq + 127) / 128) : (int)((nq + 31) / 32);
     // round 6: up to 32 queries over the bf16 operand copy of the rows when the handle keeps one (half the bytes, one product per term)
     const bool packed = pack != nullptr && pstats != nullptr && !shared && qb <= 3 && tune_flat_f32_packed.geti() != 0;   // "flat_f32_packed": 1 = small batches stream the bf16 operand copy when there is one
-#define CVTMI_FS(NCH_) \
-    case NCH_: CVTMI_TRY(packed ? fs_launch_packed<NCH_>(qb, sa, pack, st) : shared ? (fs_launch_qb<NCH_, true>(qb, sa, st)) : (fs_launch_qb<NCH_, false>(qb, sa, st))); break;
     switch (D / 16) {
-        CVTMI_FS(2) CVTMI_FS(4) CVTMI_FS(6) CVTMI_FS(8) CVTMI_FS(12) CVTMI_FS(16)
+        case 2: CVTMI_TRY(fs_launch_any<2>(packed, shared, qb, sa, pack, st)); break;
+        case 4: CVTMI_TRY(fs_launch_any<4>(packed, shared, qb, sa, pack, st)); break;
+        case 6: CVTMI_TRY(fs_launch_any<6>(packed, shared, qb, sa, pack, st)); break;
+        case 8: CVTMI_TRY(fs_launch_any<8>(packed, shared, qb, sa, pack, st)); break;
+        case 12: CVTMI_TRY(fs_launch_any<12>(packed, shared, qb, sa, pack, st)); break;
+        case 16: CVTMI_TRY(fs_launch_any<16>(packed, shared, qb, sa, pack, st)); break;
         default: return fail(CVTMI_EUNSUPPORTED, "flat_f32_stream: D=%d", D);
     }
-#undef CVTMI_FS
     FsFinishArgs fa;
     fa.X = X; fa.Xr = Xrows; fa.n = n; fa.D = D; fa.Q = q; fa.nq = nq; fa.k = k; fa.gb = gb; fa.wm = wm; fa.G = G; fa.NG = NG; fa.stats = stats;
     fa.pstats = packed ? pstats : nullptr;
@@ -1021,16 +1023,11 @@ int launch_flat_f32_stream(int metric, int D, const float *X, const float *bias,
     // slices per query: one batch of loads per thread (2048 entries per slice) while that keeps the grid near one round of workgroups
     const int64_t E = (int64_t)NG * streams * 32;
     fa.S = (int)std::min<int64_t>(std::max<int64_t>(1, 1024 / nq), std::max<int64_t>(1, E / 2048));
-    const unsigned cgrid = (unsigned)(nq * fa.S);
-    if (metric == CVTMI_METRIC_IP) {
-        hipLaunchKernelGGL((flat_f32_stream_collect_kernel<true, 4>), dim3(cgrid), dim3(kBlock), 0, st, fa);
-        hipLaunchKernelGGL((flat_f32_stream_finish_kernel<true, 4>), dim3((unsigned)nq), dim3(kBlock), 0, st, fa);
-    } else {
-        hipLaunchKernelGGL((flat_f32_stream_collect_kernel<false, 8>), dim3(cgrid), dim3(kBlock), 0, st, fa);
-        hipLaunchKernelGGL((flat_f32_stream_finish_kernel<false, 8>), dim3((unsigned)nq), dim3(kBlock), 0, st, fa);
-    }
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    auto collect = flat_f32_stream_collect_kernel<true, 4>;
+    auto finish = flat_f32_stream_finish_kernel<true, 4>;
+    if (metric != CVTMI_METRIC_IP) { collect = flat_f32_stream_collect_kernel<false, 8>; finish = flat_f32_stream_finish_kernel<false, 8>; }
+    CVTMI_TRY(launch("flat_f32_stream_collect_kernel", collect, nq * fa.S, kBlock, 0, st, fa));
+    return launch("flat_f32_stream_finish_kernel", finish, nq, kBlock, 0, st, fa);
 }
 
 }  // namespace cvtmi

@@ -49,12 +49,12 @@
 #include <algorithm>
 #include <bitset>
 #include <cmath>
-#include <atomic>
 #include <vector>
 
 #include "common.h"
 #include "flat_f32_common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -966,16 +966,10 @@ size_t flat_f32_tfilter_scratch(int64_t nq, int k)
 template <int NCH, int NPROD, int RT, int NW = FT_WAVES, int KH = 1>
 static int ft_launch(bool maxmode, const FtArgs &a, size_t lds, hipStream_t st)
 {
-    static std::atomic<bool> attr_a[16] = {}, attr_b[16] = {};
-    if (maxmode) {
-        CVTMI_TRY(fs_set_lds((const void *)flat_f32_tfilter_kernel<NCH, NPROD, RT, true, NW, KH>, 163840, attr_a));
-        hipLaunchKernelGGL((flat_f32_tfilter_kernel<NCH, NPROD, RT, true, NW, KH>), dim3(FT_GRID), dim3(64 * NW), lds, st, a);
-    } else {
-        CVTMI_TRY(fs_set_lds((const void *)flat_f32_tfilter_kernel<NCH, NPROD, RT, false, NW, KH>, 163840, attr_b));
-        hipLaunchKernelGGL((flat_f32_tfilter_kernel<NCH, NPROD, RT, false, NW, KH>), dim3(FT_GRID), dim3(64 * NW), lds, st, a);
-    }
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    static LdsOnce attr_a = {}, attr_b = {};
+    if (maxmode)
+        return launch_lds_once("flat_f32_tfilter_kernel", flat_f32_tfilter_kernel<NCH, NPROD, RT, true, NW, KH>, attr_a, 163840, FT_GRID, 64 * NW, lds, st, a);
+    return launch_lds_once("flat_f32_tfilter_kernel", flat_f32_tfilter_kernel<NCH, NPROD, RT, false, NW, KH>, attr_b, 163840, FT_GRID, 64 * NW, lds, st, a);
 }
 static int ft_launch_any(int D, int nprod, bool maxmode, const FtArgs &a, size_t lds, hipStream_t st)
 {
@@ -1049,65 +1043,53 @@ int launch_flat_f32_tfilter(int metric, int D, const float *X, const float *Xrow
         a.t1 = n_tiles;
         a.n_sample = ft_n_sample(D, n, k, nprod, chunks);
         CVTMI_TRY(ft_launch_any(D, nprod, true, a, lds, st));
-        const unsigned tg = (unsigned)((m + 3) / 4);
         const float loosen = (a.dbg & 32) ? 0.02f : 0.0f;
-        if (metric == CVTMI_METRIC_IP) {
-            if (big) hipLaunchKernelGGL((ft_theta_kernel<true, FT_SLOTS_BIG / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, fixed, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
-            else hipLaunchKernelGGL((ft_theta_kernel<true, FT_SLOTS / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, fixed, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
-        } else {
-            if (big) hipLaunchKernelGGL((ft_theta_kernel<false, FT_SLOTS_BIG / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, fixed, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
-            else hipLaunchKernelGGL((ft_theta_kernel<false, FT_SLOTS / 64>), dim3(tg), dim3(256), 0, st, smax, a.Q, (int)m, D, k, nprod, fixed, stats, pstats, loosen, thr, qbnd, redo + a0, cnt);
-        }
+        decltype(&ft_theta_kernel<true, FT_SLOTS / 64>) theta;
+        if (metric == CVTMI_METRIC_IP) theta = big ? ft_theta_kernel<true, FT_SLOTS_BIG / 64> : ft_theta_kernel<true, FT_SLOTS / 64>;
+        else theta = big ? ft_theta_kernel<false, FT_SLOTS_BIG / 64> : ft_theta_kernel<false, FT_SLOTS / 64>;
+        CVTMI_TRY(launch("ft_theta_kernel", theta, blocks_for(m, 4), 256, 0, st, smax, a.Q, (int)m, D, k, nprod, fixed, stats, pstats, loosen, thr, qbnd, redo + a0, cnt));
         a.t1 = n_tiles; a.n_sample = 0;
         CVTMI_TRY(ft_launch_any(D, nprod, false, a, lds, st));
         if (a.dbg & 8) continue;   // timing experiments: the filter passes alone (results stale)
         const bool retry = tune_flat_f32_tfilter_retry.geti() != 0 && !big;
         const size_t bucket_lds = (size_t)FT_STAGE * (sizeof(uint2) + sizeof(uint16_t));
-        {
-            static std::atomic<bool> attr_k[16] = {};
-            CVTMI_TRY(fs_set_lds((const void *)ft_bucket_kernel, bucket_lds, attr_k));
-        }
+        static LdsOnce attr_k = {};
         const int rcap = std::min<int>(qcap, (int)((m + 31) / 32 * 32));   // queries one second attempt takes (a single chunk)
         const bool wide = !big && D >= 256 && tune_flat_f32_tfilter_wide_band.geti() != 0;   // (narrow rows: the exact kernels' turn costs less than this launch on every call)
-        auto finish = [&](int second) {
+        const int sums = metric == CVTMI_METRIC_IP ? 0 : D % 16 == 0 ? 1 : 2;   // (the reference's L2 sums in 8 lanes when D % 16 == 0, in 4 lanes otherwise: space_l2.h:40-151)
+        auto finish = [&](int second) -> int {
             if (big || second == 2) {   // k = 129 .. 2048: the candidates' keys in LDS, a bitonic sort of the exact distances (2: the second chance of the other form's wide bands)
                 const int cstride = big ? FT_CAP_BIG : FT_CAP, only2 = big ? 0 : 1;
-                const unsigned bgrid = big ? (unsigned)m : (unsigned)std::min<int64_t>(m, 256);
+                const int64_t bgrid = big ? m : std::min<int64_t>(m, 256);
                 const size_t lds_b = (size_t)FT_CAP_BIG * sizeof(uint32_t);
-                static std::atomic<bool> attr_f[3][16] = {};
-                if (metric == CVTMI_METRIC_IP) {
-                    (void)fs_set_lds((const void *)ft_finish_big_kernel<true, 4>, lds_b, attr_f[0]);
-                    hipLaunchKernelGGL((ft_finish_big_kernel<true, 4>), dim3(bgrid), dim3(1024), lds_b, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, (int)m, cstride, only2, bcount, blist, rm, fixed);
-                } else if (D % 16 == 0) {
-                    (void)fs_set_lds((const void *)ft_finish_big_kernel<false, 8>, lds_b, attr_f[1]);
-                    hipLaunchKernelGGL((ft_finish_big_kernel<false, 8>), dim3(bgrid), dim3(1024), lds_b, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, (int)m, cstride, only2, bcount, blist, rm, fixed);
-                } else {
-                    (void)fs_set_lds((const void *)ft_finish_big_kernel<false, 4>, lds_b, attr_f[2]);
-                    hipLaunchKernelGGL((ft_finish_big_kernel<false, 4>), dim3(bgrid), dim3(1024), lds_b, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, (int)m, cstride, only2, bcount, blist, rm, fixed);
-                }
-                return;
+                static LdsOnce attr_f[3] = {};
+                decltype(&ft_finish_big_kernel<true, 4>) kern;
+                if (sums == 0) kern = ft_finish_big_kernel<true, 4>;
+                else if (sums == 1) kern = ft_finish_big_kernel<false, 8>;
+                else kern = ft_finish_big_kernel<false, 4>;
+                return launch_lds_once("ft_finish_big_kernel", kern, attr_f[sums], lds_b, bgrid, 1024, lds_b, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k,
+                                       out_i + a0 * k, redo + a0, (int)m, cstride, only2, bcount, blist, rm, fixed);
             }
-            const unsigned grid = second ? (unsigned)rcap : (unsigned)m;
-            uint32_t *rl = retry ? rlist : nullptr;
-            if (metric == CVTMI_METRIC_IP)
-                hipLaunchKernelGGL((ft_finish_kernel<true, 4>), dim3(grid), dim3(256), 0, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, rcount, rl, rcap, second, (int)m, wide ? bcount : nullptr, blist, rm, fixed);
-            else if (D % 16 == 0)   // (the reference's L2 sums in 8 lanes when D % 16 == 0, in 4 lanes otherwise: space_l2.h:40-151)
-                hipLaunchKernelGGL((ft_finish_kernel<false, 8>), dim3(grid), dim3(256), 0, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, rcount, rl, rcap, second, (int)m, wide ? bcount : nullptr, blist, rm, fixed);
-            else
-                hipLaunchKernelGGL((ft_finish_kernel<false, 4>), dim3(grid), dim3(256), 0, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, rcount, rl, rcap, second, (int)m, wide ? bcount : nullptr, blist, rm, fixed);
+            decltype(&ft_finish_kernel<true, 4>) kern;
+            if (sums == 0) kern = ft_finish_kernel<true, 4>;
+            else if (sums == 1) kern = ft_finish_kernel<false, 8>;
+            else kern = ft_finish_kernel<false, 4>;
+            return launch("ft_finish_kernel", kern, second ? rcap : m, 256, 0, st, Xe, n, D, a.Q, k, thr, qbnd, cnt, cand, out_d + a0 * k, out_i + a0 * k, redo + a0, rcount,
+                          retry ? rlist : nullptr, rcap, second, (int)m, wide ? bcount : nullptr, blist, rm, fixed);
         };
-        hipLaunchKernelGGL(ft_bucket_kernel, dim3(FT_GRID), dim3(FT_BUCKET_T), bucket_lds, st, rec, wcnt, cap, thr, cnt, cand, chunks, qper, (int)m, redo + a0, nw, nullptr, nullptr, fcap);
-        finish(0);
+        CVTMI_TRY(launch_lds_once("ft_bucket_kernel", ft_bucket_kernel, attr_k, bucket_lds, FT_GRID, FT_BUCKET_T, bucket_lds, st, rec, wcnt, cap, thr, cnt, cand, chunks, qper,
+                                  (int)m, redo + a0, nw, nullptr, nullptr, fcap));
+        CVTMI_TRY(finish(0));
         if (retry) {   // the queries whose lists ran over, under the thresholds their own candidates give (nothing listed: three empty launches)
             FtArgs b = a;
             b.qlist = rlist; b.qcount = rcount; b.chunks = 1; b.qper = rcap;
             const size_t lds2 = (size_t)(rcap / 32) * nch * nt * 1024 + FT_SLACK + (size_t)rcap * 2 * sizeof(float);
             CVTMI_TRY(ft_launch_any(D, nprod, false, b, lds2, st));
-            hipLaunchKernelGGL(ft_bucket_kernel, dim3(FT_GRID), dim3(FT_BUCKET_T), bucket_lds, st, rec, wcnt, cap, thr, cnt, cand, 1, rcap, (int)m, redo + a0, nw, rlist, rcount, fcap);
-            finish(1);
+            CVTMI_TRY(launch_lds_once("ft_bucket_kernel", ft_bucket_kernel, attr_k, bucket_lds, FT_GRID, FT_BUCKET_T, bucket_lds, st, rec, wcnt, cap, thr, cnt, cand, 1, rcap,
+                                      (int)m, redo + a0, nw, rlist, rcount, fcap));
+            CVTMI_TRY(finish(1));
         }
-        if (wide) finish(2);
-        CVTMI_HIP(hipGetLastError());
+        if (wide) CVTMI_TRY(finish(2));
         if (getenv("CVTMI_FT_DEBUG")) {   // counts of the pass (synchronises)
             CVTMI_HIP(hipStreamSynchronize(st));
             std::vector<uint32_t> hc(m), hw(FT_GRID * FT_WAVES), hr(m);

@@ -24,9 +24,9 @@
 // (D + 4) u 2Q and |q|^2 (D + 1) u Q in distance units, i.e. ~200 uQ in T units.  thr_q is lowered by 2048 uQ = 2^-13 Q.
 #include <algorithm>
 
-#include <atomic>
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -1261,7 +1261,7 @@ bool flat_u8_mstream_applies(int D, int64_t n, int64_t nq, int k)
 int64_t flat_u8_mstream_groups(int64_t n)
 {
     const int64_t waves = (int64_t)MSTREAM_BLOCKS * 4, tiles = (n + 31) / 32;
-    const int64_t per_wave = (tiles + waves - 1) / waves;
+    const int64_t per_wave = blocks_for(tiles, waves);
     return (per_wave + MS_GROUP - 1) / MS_GROUP * waves;
 }
 int flat_u8_mstream_group() { return MS_GROUP; }
@@ -1273,31 +1273,27 @@ size_t flat_u8_mstream_scratch(int64_t n, int64_t nq, int *nqp, int *waves)
     if (waves) *waves = MSTREAM_BLOCKS * 4;
     return ((size_t)flat_u8_mstream_groups(n) * 32 * qb + (size_t)nq * MSTREAM_BLOCKS * 4) * sizeof(int32_t);
 }
+template <int KS>
+static decltype(&flat_u8_mstream_kernel<KS, 1>) flat_u8_mstream_for(int qb)
+{
+    if (qb == 1) return flat_u8_mstream_kernel<KS, 1>;
+    if (qb == 2) return flat_u8_mstream_kernel<KS, 2>;
+    return flat_u8_mstream_kernel<KS, 4>;
+}
 int launch_flat_u8_mstream(int D, const uint8_t *data, const int32_t *norms, int64_t n, const uint8_t *q, int64_t nq, int32_t *tmin,
                            int32_t *wmin, hipStream_t st)
 {
     const int qb = nq <= 32 ? 1 : (nq <= 64 ? 2 : 4);
-#define CVTMI_MS(KS_, QB_)                                                                                                         \
-    do {                                                                                                                          \
-        constexpr int NB_ = 32 / (KS_) >= 2 ? 32 / (KS_) : 2;                                                                     \
-        const size_t lds = (size_t)4 * NB_ * ((KS_) * (1024 + MS_PAD) + 256);                                                     \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)flat_u8_mstream_kernel<KS_, QB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((flat_u8_mstream_kernel<KS_, QB_>), dim3(MSTREAM_BLOCKS), dim3(256), lds, st, data, norms, n, q, (int)nq, tmin, wmin); \
-    } while (0)
-#define CVTMI_MSQ(KS_)                                                                                                             \
-    do {                                                                                                                          \
-        if (qb == 1) CVTMI_MS(KS_, 1); else if (qb == 2) CVTMI_MS(KS_, 2); else CVTMI_MS(KS_, 4);                                   \
-    } while (0)
+    decltype(&flat_u8_mstream_kernel<4, 1>) kern;
     switch (D) {
-        case 128: CVTMI_MSQ(4); break;
-        case 256: CVTMI_MSQ(8); break;
-        case 512: CVTMI_MSQ(16); break;
+        case 128: kern = flat_u8_mstream_for<4>(qb); break;
+        case 256: kern = flat_u8_mstream_for<8>(qb); break;
+        case 512: kern = flat_u8_mstream_for<16>(qb); break;
         default: return fail(CVTMI_EUNSUPPORTED, "flat_u8_mstream: D=%d", D);
     }
-#undef CVTMI_MSQ
-#undef CVTMI_MS
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    const int ks = D / 32, nb = 32 / ks >= 2 ? 32 / ks : 2;
+    const size_t lds = (size_t)4 * nb * (ks * (1024 + MS_PAD) + 256);
+    return launch_lds("flat_u8_mstream_kernel", kern, MSTREAM_BLOCKS, 256, lds, st, data, norms, n, q, (int)nq, tmin, wmin);
 }
 
 bool flat_u8_filter_applies(int D, int64_t n, int64_t nq, int k)
@@ -1311,9 +1307,7 @@ int launch_flat_u8_pack(const uint8_t *X, int64_t n, int D, uint4 *pack, hipStre
 {
     const int64_t ntiles = (n + 31) / 32, tile0 = row0 / 32, total = (ntiles - tile0) * (D / 32) * 64;
     if (total <= 0) return CVTMI_OK;
-    hipLaunchKernelGGL(flat_u8_pack_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, X, n, D, tile0, ntiles, pack);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("flat_u8_pack_kernel", flat_u8_pack_kernel, blocks_for(total, kBlock), kBlock, 0, st, X, n, D, tile0, ntiles, pack);
 }
 
 // rows [row_begin, n) against all queries; thresholds = the sample's k-th best; *pair_cnt zeroed by the caller
@@ -1327,7 +1321,7 @@ int launch_flat_u8_filter(const uint8_t *q, int64_t nq, int D, const uint4 *pack
         const bool two = gfilter == 2;   // two 4-wave workgroups per CU: measured 15 % slower than one 8-wave workgroup (16 matrix instructions per barrier)
         const bool wide4 = gfilter == 4 && D >= 128;   // one wave per SIMD, 96-128 queries per wave (flat_u8_gfilter_wide_kernel): measured equal at nq = 4096, 10 % slower at nq = 1000
         const int qpb = wide4 ? (D == 512 ? 384 : 512) : (two ? 128 : 256);
-        const int64_t qblocks = (nq + qpb - 1) / qpb;
+        const int64_t qblocks = blocks_for(nq, qpb);
         const int64_t want = two ? 512 : 256;                                     // workgroups resident at a time
         // row splits: a multiple of 8 (one split per XCD at a time), chosen so that rounds(grid / resident) x tiles per split is smallest --
         // qblocks x splits rarely lands on a multiple of the resident count, and a 3 % overhang used to cost a whole second round
@@ -1341,71 +1335,49 @@ int launch_flat_u8_filter(const uint8_t *q, int64_t nq, int D, const uint4 *pack
             if (cost < best_cost) { best_cost = cost; tps = t; }
             if (t == 64) break;
         }
-        const int64_t splits = (tiles + tps - 1) / tps;
+        const int64_t splits = blocks_for(tiles, tps);
         const int64_t splits8 = (splits + 7) / 8 * 8;
-        if (splits8 * qblocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "flat u8 filter: nq too large");
-        const dim3 g((unsigned)(splits8 * qblocks));
-#define CVTMI_GF(N, NW, G, NB)                                                                                                    \
-    do {                                                                                                                         \
-        const size_t lds = (size_t)(NB) * (G) * (N) * 64 * sizeof(uint4);                                                        \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)flat_u8_gfilter_kernel<N, NW, G, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((flat_u8_gfilter_kernel<N, NW, G, NB>), g, dim3(64 * (NW)), lds, st, q, nq, pack, norms, n, sample_d, k, tile_begin, tile_end, \
-                           tps, pair_cap, pair_cnt, pairs, (int)qblocks, dbg);                                                   \
-    } while (0)
-#define CVTMI_GW(N, AQ, NB)                                                                                                      \
-    do {                                                                                                                         \
-        const size_t lds = (size_t)(NB) * (N) * 64 * sizeof(uint4);                                                              \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)flat_u8_gfilter_wide_kernel<N, AQ, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((flat_u8_gfilter_wide_kernel<N, AQ, NB>), g, dim3(256), lds, st, q, nq, pack, norms, n, sample_d, k, tile_begin, tile_end, \
-                           tps, pair_cap, pair_cnt, pairs, (int)qblocks, dbg);                                                   \
-    } while (0)
+        const int64_t grid = splits8 * qblocks;
+        const int ks = D / 32;
         if (wide4) {
-            switch (D / 32) {
-                case 4: CVTMI_GW(4, 4, 4); break;
-                case 8: CVTMI_GW(8, 4, 4); break;
-                default: CVTMI_GW(16, 3, 4); break;   // 3 x 64 operand registers (an 8-slot ring measured the same as 4: the DMA is not latency-bound): the fourth query set does not fit beside two accumulator sets
-            }
-            CVTMI_HIP(hipGetLastError());
-            return CVTMI_OK;
+            // D = 512: 3 x 64 operand registers (an 8-slot ring measured the same as 4: the DMA is not latency-bound): the fourth query set does not fit beside two accumulator sets
+            int N = 4;
+            auto kern = flat_u8_gfilter_wide_kernel<4, 4, 4>;
+            if (ks == 8) { N = 8; kern = flat_u8_gfilter_wide_kernel<8, 4, 4>; }
+            else if (ks != 4) { N = 16; kern = flat_u8_gfilter_wide_kernel<16, 3, 4>; }
+            return launch_lds("flat_u8_gfilter_wide_kernel", kern, grid, 256, (size_t)4 * N * 64 * sizeof(uint4), st, q, nq, pack, norms, n, sample_d, k, tile_begin, tile_end,
+                              tps, pair_cap, pair_cnt, pairs, (int)qblocks, dbg);
         }
-#undef CVTMI_GW
-        switch (D / 32) {
-            case 2: CVTMI_GF(2, 8, 4, 3); break;
-            case 4: if (two) CVTMI_GF(4, 4, 2, 3); else CVTMI_GF(4, 8, 2, 3); break;
-            case 8: if (two) CVTMI_GF(8, 4, 2, 3); else CVTMI_GF(8, 8, 2, 3); break;
-            case 16: if (two) CVTMI_GF(16, 4, 2, 2); else CVTMI_GF(16, 8, 2, 3); break;   // 4 waves: ring of 2 groups, two workgroups fit a CU's LDS
+        decltype(&flat_u8_gfilter_kernel<2, 8, 4, 3>) kern;   // <K steps, waves, tile groups, ring slots>
+        int nw = two ? 4 : 8, ring = 2 * 3;                   // waves, groups x slots
+        switch (ks) {
+            case 2: kern = flat_u8_gfilter_kernel<2, 8, 4, 3>; nw = 8; ring = 4 * 3; break;
+            case 4: kern = two ? flat_u8_gfilter_kernel<4, 4, 2, 3> : flat_u8_gfilter_kernel<4, 8, 2, 3>; break;
+            case 8: kern = two ? flat_u8_gfilter_kernel<8, 4, 2, 3> : flat_u8_gfilter_kernel<8, 8, 2, 3>; break;
+            case 16:   // 4 waves: ring of 2 groups, two workgroups fit a CU's LDS
+                kern = two ? flat_u8_gfilter_kernel<16, 4, 2, 2> : flat_u8_gfilter_kernel<16, 8, 2, 3>;
+                if (two) ring = 2 * 2;
+                break;
             default: return fail(CVTMI_EUNSUPPORTED, "flat u8 pipelined filter: D=%d (64, 128, 256 or 512)", D);
         }
-#undef CVTMI_GF
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
+        return launch_lds("flat_u8_gfilter_kernel", kern, grid, 64 * nw, (size_t)ring * ks * 64 * sizeof(uint4), st, q, nq, pack, norms, n, sample_d, k, tile_begin, tile_end, tps,
+                          pair_cap, pair_cnt, pairs, (int)qblocks, dbg);
     }
     const bool wide = nq >= 1024;  // 16 waves: 512 queries per workgroup
     const int qpb = wide ? 512 : 256;
-    const int64_t qblocks = (nq + qpb - 1) / qpb;
+    const int64_t qblocks = blocks_for(nq, qpb);
     int64_t splits = std::max<int64_t>(1, (256 * 2 + qblocks - 1) / qblocks);
     int64_t tps = std::max<int64_t>(16, (tile_end - tile_begin + splits - 1) / splits);
     splits = (tile_end - tile_begin + tps - 1) / tps;
     const int64_t splits8 = (splits + 7) / 8 * 8;
-    if (splits8 * qblocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "flat u8 filter: nq too large");
-    const dim3 g((unsigned)(splits8 * qblocks));
-#define CVTMI_FU(N)                                                                                                              \
-    do {                                                                                                                         \
-        if (wide)                                                                                                                \
-            hipLaunchKernelGGL((flat_u8_filter_kernel<N, 1024, 1>), g, dim3(1024), 0, st, q, nq, D, pack, norms, n, sample_d, k, tile_begin,   \
-                               tile_end, tps, pair_cap, pair_cnt, pairs, (int)qblocks);                                          \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((flat_u8_filter_kernel<N, 512, 1>), g, dim3(512), 0, st, q, nq, D, pack, norms, n, sample_d, k, tile_begin,   \
-                               tile_end, tps, pair_cap, pair_cnt, pairs, (int)qblocks);                                          \
-    } while (0)
     const int ks = D / 32;
-    if (ks <= 2) CVTMI_FU(2);
-    else if (ks <= 4) CVTMI_FU(4);
-    else if (ks <= 8) CVTMI_FU(8);
-    else CVTMI_FU(16);
-#undef CVTMI_FU
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    decltype(&flat_u8_filter_kernel<2, 1024, 1>) kern;
+    if (ks <= 2) kern = wide ? flat_u8_filter_kernel<2, 1024, 1> : flat_u8_filter_kernel<2, 512, 1>;
+    else if (ks <= 4) kern = wide ? flat_u8_filter_kernel<4, 1024, 1> : flat_u8_filter_kernel<4, 512, 1>;
+    else if (ks <= 8) kern = wide ? flat_u8_filter_kernel<8, 1024, 1> : flat_u8_filter_kernel<8, 512, 1>;
+    else kern = wide ? flat_u8_filter_kernel<16, 1024, 1> : flat_u8_filter_kernel<16, 512, 1>;
+    return launch("flat_u8_filter_kernel", kern, splits8 * qblocks, wide ? 1024 : 512, 0, st, q, nq, D, pack, norms, n, sample_d, k, tile_begin, tile_end, tps, pair_cap,
+                  pair_cnt, pairs, (int)qblocks);
 }
 
 int launch_flat_u8_finish(int64_t nq, const uint32_t *pair_cnt, uint32_t pair_cap, const uint4 *pairs, int cap, int k, const float *sample_d,
@@ -1413,11 +1385,8 @@ int launch_flat_u8_finish(int64_t nq, const uint32_t *pair_cnt, uint32_t pair_ca
                           uint32_t *overflow, hipStream_t st)
 {
     if (cap + k > 4096) return fail(CVTMI_EUNSUPPORTED, "flat u8 finish: cap=%d k=%d", cap, k);
-    hipLaunchKernelGGL(flat_scatter_kernel, dim3(256 * 8), dim3(kBlock), 0, st, pair_cnt, pair_cap, pairs, cap, cand_cnt, cand_d, cand_row, overflow);
-    hipLaunchKernelGGL(flat_u8_finish_kernel, dim3((unsigned)nq), dim3(kBlock), 0, st, cand_cnt, cand_d, cand_row, cap, k, sample_d, sample_i, out_d,
-                       out_i, overflow);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    CVTMI_TRY(launch("flat_scatter_kernel", flat_scatter_kernel, 256 * 8, kBlock, 0, st, pair_cnt, pair_cap, pairs, cap, cand_cnt, cand_d, cand_row, overflow));
+    return launch("flat_u8_finish_kernel", flat_u8_finish_kernel, nq, kBlock, 0, st, cand_cnt, cand_d, cand_row, cap, k, sample_d, sample_i, out_d, out_i, overflow);
 }
 
 bool flat_filter_applies(int metric, int D, int64_t n, int64_t nq, int k)
@@ -1434,19 +1403,15 @@ int launch_flat_pack(const float *X, int64_t n, int D, int nch, int metric, uint
     const int64_t ntiles = (n + 31) / 32, tile0 = row0 / 32;
     if (row0 == 0) CVTMI_HIP(hipMemsetAsync(stats, 0, 12, st));
     if (tile0 >= ntiles) return CVTMI_OK;
-    hipLaunchKernelGGL(flat_pack_kernel, dim3((unsigned)(((ntiles - tile0) * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, X, n, D, nch,
-                       metric == CVTMI_METRIC_L2F ? 1 : 0, tile0, ntiles, pack, bias, stats);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("flat_pack_kernel", flat_pack_kernel, blocks_for((ntiles - tile0) * 64, kBlock), kBlock, 0, st, X, n, D, nch, metric == CVTMI_METRIC_L2F ? 1 : 0,
+                  tile0, ntiles, pack, bias, stats);
 }
 
 int launch_flat_thr(const float *q, int64_t nq, int D, int metric, const float *sample_d, int k, uint32_t *stats, float *thr,
                     float *margin, hipStream_t st)
 {
-    hipLaunchKernelGGL(flat_thr_kernel, dim3((unsigned)((nq + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, q, nq, D,
-                       metric == CVTMI_METRIC_L2F ? 1 : 0, sample_d, k, stats, thr, margin);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("flat_thr_kernel", flat_thr_kernel, blocks_for(nq, kBlock), kBlock, 0, st, q, nq, D, metric == CVTMI_METRIC_L2F ? 1 : 0, sample_d, k, stats, thr,
+                  margin);
 }
 
 // rows [row_begin, n) (row_begin % 32 == 0) against all queries; *pair_cnt must be zeroed by the caller
@@ -1460,19 +1425,11 @@ int launch_flat_filter(const float *q, int64_t nq, int D, const uint4 *pack, con
     int64_t tps = std::max<int64_t>(16, (tile_end - tile_begin + splits - 1) / splits);
     splits = (tile_end - tile_begin + tps - 1) / tps;
     const int64_t splits8 = (splits + 7) / 8 * 8;  // empty splits return at once
-    if (splits8 * qblocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "flat filter: nq too large");
-    const dim3 g((unsigned)(splits8 * qblocks)), b(FF_THREADS);
-#define CVTMI_FF(N)                                                                                                               \
-    case N:                                                                                                                       \
-        hipLaunchKernelGGL((flat_filter_kernel<N>), g, b, 0, st, q, nq, pack, bias, thr, tile_begin, tile_end, tps, pair_cap, pair_cnt, pairs, (int)qblocks); \
-        break;
-    switch (D / 16) {
-        CVTMI_FF(2) CVTMI_FF(3) CVTMI_FF(4) CVTMI_FF(5) CVTMI_FF(6) CVTMI_FF(7) CVTMI_FF(8)
-        default: return fail(CVTMI_EUNSUPPORTED, "flat filter: D=%d", D);
-    }
-#undef CVTMI_FF
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    static constexpr decltype(&flat_filter_kernel<2>) kernels[] = {   // by 16-float chunks of a row: 2 .. 8
+        flat_filter_kernel<2>, flat_filter_kernel<3>, flat_filter_kernel<4>, flat_filter_kernel<5>, flat_filter_kernel<6>, flat_filter_kernel<7>, flat_filter_kernel<8> };
+    if (D / 16 < 2 || D / 16 > 8) return fail(CVTMI_EUNSUPPORTED, "flat filter: D=%d", D);
+    return launch("flat_filter_kernel", kernels[D / 16 - 2], splits8 * qblocks, FF_THREADS, 0, st, q, nq, pack, bias, thr, tile_begin, tile_end, tps, pair_cap, pair_cnt, pairs,
+                  (int)qblocks);
 }
 
 // cand_cnt [nq] must be zeroed by the caller; *overflow > cap afterwards: a list ran over, the results are not to be used
@@ -1482,15 +1439,9 @@ int launch_flat_finish(int metric, const float *X, int64_t n, int D, const float
                        hipStream_t st)
 {
     if (cap > FIN_CAND || k > 128) return fail(CVTMI_EUNSUPPORTED, "flat finish: cap=%d k=%d", cap, k);
-    hipLaunchKernelGGL(flat_scatter_kernel, dim3(256 * 8), dim3(kBlock), 0, st, pair_cnt, pair_cap, pairs, cap, cand_cnt, cand_t, cand_row, overflow);
-    if (metric == CVTMI_METRIC_IP)
-        hipLaunchKernelGGL((flat_finish_kernel<true, 4>), dim3((unsigned)nq), dim3(kBlock), 0, st, X, n, D, q, cand_cnt, cand_t, cand_row, cap, k,
-                           margin, sample_d, sample_i, out_d, out_i, overflow);
-    else
-        hipLaunchKernelGGL((flat_finish_kernel<false, 8>), dim3((unsigned)nq), dim3(kBlock), 0, st, X, n, D, q, cand_cnt, cand_t, cand_row, cap, k,
-                           margin, sample_d, sample_i, out_d, out_i, overflow);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    CVTMI_TRY(launch("flat_scatter_kernel", flat_scatter_kernel, 256 * 8, kBlock, 0, st, pair_cnt, pair_cap, pairs, cap, cand_cnt, cand_t, cand_row, overflow));
+    return launch("flat_finish_kernel", metric == CVTMI_METRIC_IP ? flat_finish_kernel<true, 4> : flat_finish_kernel<false, 8>, nq, kBlock, 0, st, X, n, D, q, cand_cnt, cand_t,
+                  cand_row, cap, k, margin, sample_d, sample_i, out_d, out_i, overflow);
 }
 
 }  // namespace cvtmi

@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "rm_common.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -231,16 +232,9 @@ int launch_flat_rm_mark_labels(const FlatRmPlan &p, void *scratch, const int64_t
     t.T = p.T;
     t.stride = std::max<int64_t>(1, (p.T + kRmPivots - 1) / kRmPivots);
     t.np = (int)((p.T + t.stride - 1) / t.stride);
-    hipLaunchKernelGGL(flat_rm_mark_labels_kernel, dim3((unsigned)p.rm.ntiles), dim3(256), 0, st, labels, p.rm.n, t,
-                       rm_at<unsigned long long>(scratch, p.rm.off_drop), rm_at<uint32_t>(scratch, p.rm.off_tile));
-    CVTMI_HIP(hipGetLastError());
+    CVTMI_TRY(launch("flat_rm_mark_labels_kernel", flat_rm_mark_labels_kernel, p.rm.ntiles, 256, 0, st, labels, p.rm.n, t, rm_at<unsigned long long>(scratch, p.rm.off_drop),
+                     rm_at<uint32_t>(scratch, p.rm.off_tile)));
     return launch_rm_scan(p.rm, scratch, st);
-}
-
-template <class U> static void flat_rm_chunk_rows_launch(unsigned grid, const FlatRmMove &a, hipStream_t st)
-{
-    hipLaunchKernelGGL(flat_rm_gather_rows_kernel<U>, dim3(grid), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(flat_rm_copy_rows_kernel<U>, dim3(grid), dim3(256), 0, st, a);
 }
 
 int launch_flat_rm_move(const FlatRmPlan &p, void *scratch, void *rows, int64_t *labels, int32_t *norms, int64_t *remap, hipStream_t st)
@@ -257,31 +251,28 @@ int launch_flat_rm_move(const FlatRmPlan &p, void *scratch, void *rows, int64_t 
     const size_t rb = p.row_bytes;
     const int unit = p.blocked ? 16 : (rb % 16 == 0 ? 16 : rb % 8 == 0 ? 8 : rb % 4 == 0 ? 4 : rb % 2 == 0 ? 2 : 1);
     a.upr = (int)(rb / unit);
+    auto gather = flat_rm_gather_blocked_kernel, copy = flat_rm_copy_blocked_kernel;
+    if (p.blocked) ;
+    else if (unit == 16) { gather = flat_rm_gather_rows_kernel<uint4>; copy = flat_rm_copy_rows_kernel<uint4>; }
+    else if (unit == 8) { gather = flat_rm_gather_rows_kernel<uint2>; copy = flat_rm_copy_rows_kernel<uint2>; }
+    else if (unit == 4) { gather = flat_rm_gather_rows_kernel<uint32_t>; copy = flat_rm_copy_rows_kernel<uint32_t>; }
+    else if (unit == 2) { gather = flat_rm_gather_rows_kernel<uint16_t>; copy = flat_rm_copy_rows_kernel<uint16_t>; }
+    else { gather = flat_rm_gather_rows_kernel<uint8_t>; copy = flat_rm_copy_rows_kernel<uint8_t>; }
     const int64_t tiles_per_chunk = p.rm.chunk / kRmTile;
     for (int64_t t0 = 0; t0 < p.rm.ntiles; t0 += tiles_per_chunk) {
         a.tile0 = t0;
-        const unsigned grid = (unsigned)std::min(tiles_per_chunk, p.rm.ntiles - t0);
-        if (p.blocked) {
-            hipLaunchKernelGGL(flat_rm_gather_blocked_kernel, dim3(grid), dim3(256), 0, st, a);
-            hipLaunchKernelGGL(flat_rm_copy_blocked_kernel, dim3(grid), dim3(256), 0, st, a);
-        }
-        else if (unit == 16) flat_rm_chunk_rows_launch<uint4>(grid, a, st);
-        else if (unit == 8) flat_rm_chunk_rows_launch<uint2>(grid, a, st);
-        else if (unit == 4) flat_rm_chunk_rows_launch<uint32_t>(grid, a, st);
-        else if (unit == 2) flat_rm_chunk_rows_launch<uint16_t>(grid, a, st);
-        else flat_rm_chunk_rows_launch<uint8_t>(grid, a, st);
+        const int64_t grid = std::min(tiles_per_chunk, p.rm.ntiles - t0);
+        CVTMI_TRY(launch(p.blocked ? "flat_rm_gather_blocked_kernel" : "flat_rm_gather_rows_kernel", gather, grid, 256, 0, st, a));
+        CVTMI_TRY(launch(p.blocked ? "flat_rm_copy_blocked_kernel" : "flat_rm_copy_rows_kernel", copy, grid, 256, 0, st, a));
     }
-    CVTMI_HIP(hipGetLastError());
     return CVTMI_OK;
 }
 
 int launch_flat_rm_iota(int64_t *labels, int64_t n, int64_t base, hipStream_t st)
 {
     if (n <= 0) return CVTMI_OK;
-    const int64_t blocks = std::min<int64_t>((n + kBlock - 1) / kBlock, 4096);
-    hipLaunchKernelGGL(flat_rm_iota_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, labels, n, base);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    const int64_t blocks = std::min<int64_t>(blocks_for(n, kBlock), 4096);
+    return launch("flat_rm_iota_kernel", flat_rm_iota_kernel, blocks, kBlock, 0, st, labels, n, base);
 }
 
 }  // namespace cvtmi

@@ -20,13 +20,13 @@
 // on this metric) and lets the round-5 paths answer the flagged queries, or the whole call.  Distances come out as int32 bits in the
 // float array, as from every uint8 path.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdlib>
 
 #include "common.h"
 #include "flat_f32_common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -432,16 +432,32 @@ __global__ __launch_bounds__(1024) void ut_finish_kernel(int64_t n, int k, const
 template <int KS, int RT>
 static int ut_launch(bool maxmode, const UtArgs &a, size_t lds, hipStream_t st)
 {
-    static std::atomic<bool> attr_a[16] = {}, attr_b[16] = {};
-    if (maxmode) {
-        CVTMI_TRY(fs_set_lds((const void *)flat_u8_tfilter_kernel<KS, RT, true>, 163840, attr_a));
-        hipLaunchKernelGGL((flat_u8_tfilter_kernel<KS, RT, true>), dim3(UT_GRID), dim3(64 * UT_WAVES), lds, st, a);
-    } else {
-        CVTMI_TRY(fs_set_lds((const void *)flat_u8_tfilter_kernel<KS, RT, false>, 163840, attr_b));
-        hipLaunchKernelGGL((flat_u8_tfilter_kernel<KS, RT, false>), dim3(UT_GRID), dim3(64 * UT_WAVES), lds, st, a);
+    static LdsOnce attr_a = {}, attr_b = {};
+    if (maxmode) return launch_lds_once("flat_u8_tfilter_kernel", flat_u8_tfilter_kernel<KS, RT, true>, attr_a, 163840, UT_GRID, 64 * UT_WAVES, lds, st, a);
+    return launch_lds_once("flat_u8_tfilter_kernel", flat_u8_tfilter_kernel<KS, RT, false>, attr_b, 163840, UT_GRID, 64 * UT_WAVES, lds, st, a);
+}
+
+// by the K steps of a row (D / 32) and the row tiles a wave holds
+static int ut_launch_any(int ks, bool maxmode, const UtArgs &a, size_t lds, hipStream_t st)
+{
+    switch (ks) {
+        case 16: return ut_launch<16, 2>(maxmode, a, lds, st);
+        case 15: return ut_launch<15, 2>(maxmode, a, lds, st);
+        case 14: return ut_launch<14, 2>(maxmode, a, lds, st);
+        case 13: return ut_launch<13, 2>(maxmode, a, lds, st);
+        case 12: return ut_launch<12, 2>(maxmode, a, lds, st);
+        case 11: return ut_launch<11, 3>(maxmode, a, lds, st);
+        case 10: return ut_launch<10, 3>(maxmode, a, lds, st);
+        case 9: return ut_launch<9, 3>(maxmode, a, lds, st);
+        case 8: return ut_launch<8, 3>(maxmode, a, lds, st);
+        case 7: return ut_launch<7, 3>(maxmode, a, lds, st);
+        case 6: return ut_launch<6, 3>(maxmode, a, lds, st);
+        case 5: return ut_launch<5, 3>(maxmode, a, lds, st);
+        case 4: return ut_launch<4, 3>(maxmode, a, lds, st);
+        case 3: return ut_launch<3, 4>(maxmode, a, lds, st);
+        case 2: return ut_launch<2, 4>(maxmode, a, lds, st);
+        default: return ut_launch<1, 4>(maxmode, a, lds, st);
     }
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
 }
 
 }  // namespace
@@ -550,25 +566,17 @@ int launch_flat_u8_tfilter(int D, const void *pack, const int32_t *norms, int64_
             a.n_sample = std::min<int64_t>(all_groups, std::max<int64_t>(1, (want + streams - 1) / streams) * streams);   // (never a smaller sample than asked for)
         }
         const size_t lds = (size_t)(qper / 32) * ks * 1024 + (size_t)qper * sizeof(int) + (size_t)UT_WAVES * rt * 32 * sizeof(int) + 3072;
-#define CVTMI_UT(MAXM) \
-        (ks == 16 ? ut_launch<16, 2>(MAXM, a, lds, st) : ks == 15 ? ut_launch<15, 2>(MAXM, a, lds, st) : ks == 14 ? ut_launch<14, 2>(MAXM, a, lds, st) : \
-         ks == 13 ? ut_launch<13, 2>(MAXM, a, lds, st) : ks == 12 ? ut_launch<12, 2>(MAXM, a, lds, st) : ks == 11 ? ut_launch<11, 3>(MAXM, a, lds, st) : \
-         ks == 10 ? ut_launch<10, 3>(MAXM, a, lds, st) : ks == 9 ? ut_launch<9, 3>(MAXM, a, lds, st) : ks == 8 ? ut_launch<8, 3>(MAXM, a, lds, st) : \
-         ks == 7 ? ut_launch<7, 3>(MAXM, a, lds, st) : ks == 6 ? ut_launch<6, 3>(MAXM, a, lds, st) : ks == 5 ? ut_launch<5, 3>(MAXM, a, lds, st) : \
-         ks == 4 ? ut_launch<4, 3>(MAXM, a, lds, st) : ks == 3 ? ut_launch<3, 4>(MAXM, a, lds, st) : ks == 2 ? ut_launch<2, 4>(MAXM, a, lds, st) : ut_launch<1, 4>(MAXM, a, lds, st))
-        CVTMI_TRY(CVTMI_UT(true));
+        CVTMI_TRY(ut_launch_any(ks, true, a, lds, st));
         // (merged keys while that leaves eight per neighbour wanted)
-        if (k * 8 <= UT_SLOTS / 4 / chunks) hipLaunchKernelGGL(ut_theta_kernel<UT_SLOTS / 256>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, smax, a.Q, (int)m, D, k, thr, qqv, flags + 1 + a0, cnt, flags);
-        else hipLaunchKernelGGL(ut_theta_kernel<UT_SLOTS / 64>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, smax, a.Q, (int)m, D, k, thr, qqv, flags + 1 + a0, cnt, flags);
-        CVTMI_TRY(CVTMI_UT(false));
-#undef CVTMI_UT
+        CVTMI_TRY(launch("ut_theta_kernel", k * 8 <= UT_SLOTS / 4 / chunks ? ut_theta_kernel<UT_SLOTS / 256> : ut_theta_kernel<UT_SLOTS / 64>, blocks_for(m, 4), 256, 0, st, smax,
+                         a.Q, (int)m, D, k, thr, qqv, flags + 1 + a0, cnt, flags));
+        CVTMI_TRY(ut_launch_any(ks, false, a, lds, st));
         const size_t bucket_lds = (size_t)UT_STAGE * (sizeof(uint2) + sizeof(uint16_t)), fin_lds = (size_t)UT_CAP * sizeof(uint32_t);
-        static std::atomic<bool> attr_k[16] = {}, attr_f[16] = {};
-        CVTMI_TRY(fs_set_lds((const void *)ut_bucket_kernel, bucket_lds, attr_k));
-        CVTMI_TRY(fs_set_lds((const void *)ut_finish_kernel, fin_lds, attr_f));
-        hipLaunchKernelGGL(ut_bucket_kernel, dim3(UT_GRID), dim3(1024), bucket_lds, st, rec, wcnt, cap, thr, qqv, norms, cnt, cand, chunks, qper, (int)m, flags);
-        hipLaunchKernelGGL(ut_finish_kernel, dim3((unsigned)m), dim3(1024), fin_lds, st, n, k, cnt, cand, out_d + a0 * k, out_i + a0 * k, flags + 1 + a0, flags);
-        CVTMI_HIP(hipGetLastError());
+        static LdsOnce attr_k = {}, attr_f = {};
+        CVTMI_TRY(launch_lds_once("ut_bucket_kernel", ut_bucket_kernel, attr_k, bucket_lds, UT_GRID, 1024, bucket_lds, st, rec, wcnt, cap, thr, qqv, norms, cnt, cand, chunks, qper,
+                                  (int)m, flags));
+        CVTMI_TRY(launch_lds_once("ut_finish_kernel", ut_finish_kernel, attr_f, fin_lds, m, 1024, fin_lds, st, n, k, cnt, cand, out_d + a0 * k, out_i + a0 * k, flags + 1 + a0,
+                                  flags));
     }
     return CVTMI_OK;
 }

@@ -17,6 +17,7 @@
 #include "dist_f32.h"
 #include "hnsw_heap.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -350,16 +351,12 @@ int launch_hnsw_search(const HnswDevGraph &g, int metric, const float *q, int64_
     const size_t lds = (size_t)hnsw_lds_bytes(g.D, ef > k ? ef : k);
     const bool ip = metric == CVTMI_METRIC_IP;
     const int lanes = (g.D % 4 != 0) ? 1 : (ip ? 4 : (g.D % 16 == 0 ? 8 : 4));
-#define CVTMI_HN(IPV, L)                                                                                                                   \
-    do {                                                                                                                                   \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)hnsw_search_kernel<DistF32<IPV, L> >, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((hnsw_search_kernel<DistF32<IPV, L> >), dim3((unsigned)slots), dim3(64), lds, st, a);                            \
-    } while (0)
-    if (ip) { if (lanes == 4) CVTMI_HN(true, 4); else CVTMI_HN(true, 1); }
-    else { if (lanes == 8) CVTMI_HN(false, 8); else if (lanes == 4) CVTMI_HN(false, 4); else CVTMI_HN(false, 1); }
-#undef CVTMI_HN
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    decltype(&hnsw_search_kernel<DistF32<true, 4> >) kern;
+    if (ip) { if (lanes == 4) kern = hnsw_search_kernel<DistF32<true, 4> >; else kern = hnsw_search_kernel<DistF32<true, 1> >; }
+    else if (lanes == 8) kern = hnsw_search_kernel<DistF32<false, 8> >;
+    else if (lanes == 4) kern = hnsw_search_kernel<DistF32<false, 4> >;
+    else kern = hnsw_search_kernel<DistF32<false, 1> >;
+    return launch_lds("hnsw_search_kernel", kern, slots, 64, lds, st, a);
 }
 
 // same traversal, distances = ADC over the nodes' PQ codes (codes [n][M] in internal-id order, lut [nq][M][K])
@@ -374,15 +371,7 @@ int launch_hnsw_search_adc(const HnswDevGraph &g, const float *lut, const uint8_
     // state_floats: what the caller sized the slots for (hnsw_adc_state_floats, read ONCE per search: M K = tables in LDS, 0 = in the scratch)
     const bool lds_tables = state_floats != 0;
     const size_t lds = (size_t)hnsw_lds_bytes(state_floats, ef > k ? ef : k);
-    if (lds_tables) {
-        CVTMI_HIP(hipFuncSetAttribute((const void *)hnsw_search_kernel<DistADC<true> >, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((hnsw_search_kernel<DistADC<true> >), dim3((unsigned)slots), dim3(64), lds, st, a);
-    } else {
-        CVTMI_HIP(hipFuncSetAttribute((const void *)hnsw_search_kernel<DistADC<false> >, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((hnsw_search_kernel<DistADC<false> >), dim3((unsigned)slots), dim3(64), lds, st, a);
-    }
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch_lds("hnsw_search_kernel", lds_tables ? hnsw_search_kernel<DistADC<true> > : hnsw_search_kernel<DistADC<false> >, slots, 64, lds, st, a);
 }
 
 // Exact re-rank of an ADC result list: ids [nq][R] internal ids (-1 = padding) -> out_d [nq][R] = the fp32 distance of the
@@ -406,15 +395,14 @@ int launch_hnsw_rerank(const HnswDevGraph &g, int metric, const float *q, int64_
 {
     const int64_t total = nq * R;
     if (total <= 0) return CVTMI_OK;
-    const unsigned blocks = (unsigned)((total + kBlock - 1) / kBlock);
     const bool ip = metric == CVTMI_METRIC_IP;
     const int lanes = (g.D % 4 != 0) ? 1 : (ip ? 4 : (g.D % 16 == 0 ? 8 : 4));  // as launch_hnsw_search picks them
-#define CVTMI_RR(IPV, L) hipLaunchKernelGGL((hnsw_rerank_kernel<IPV, L>), dim3(blocks), dim3(kBlock), 0, st, g.vec, g.D, q, ids, total, R, out_d)
-    if (ip) { if (lanes == 4) CVTMI_RR(true, 4); else CVTMI_RR(true, 1); }
-    else { if (lanes == 8) CVTMI_RR(false, 8); else if (lanes == 4) CVTMI_RR(false, 4); else CVTMI_RR(false, 1); }
-#undef CVTMI_RR
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    decltype(&hnsw_rerank_kernel<true, 4>) kern;
+    if (ip) { if (lanes == 4) kern = hnsw_rerank_kernel<true, 4>; else kern = hnsw_rerank_kernel<true, 1>; }
+    else if (lanes == 8) kern = hnsw_rerank_kernel<false, 8>;
+    else if (lanes == 4) kern = hnsw_rerank_kernel<false, 4>;
+    else kern = hnsw_rerank_kernel<false, 1>;
+    return launch("hnsw_rerank_kernel", kern, blocks_for(total, kBlock), kBlock, 0, st, g.vec, g.D, q, ids, total, R, out_d);
 }
 
 // LDS bytes of one query slot: query state (floats) + top queue (ef + 1) + the LDS part of the candidate queue

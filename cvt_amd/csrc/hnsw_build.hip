@@ -23,6 +23,7 @@
 #include "hnsw_heap.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -516,24 +517,22 @@ int launch_hnsw_build(const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, 
         CVTMI_HIP(hipEventRecord(e, st));
         return CVTMI_OK;
     };
-#define CVTMI_HB_ALL(KERNEL, GRID, LDS)                                                                                                   \
-    do {                                                                                                                                   \
-        if (ip) { if (lanes == 4) hipLaunchKernelGGL((KERNEL<true, 4>), GRID, dim3(64), LDS, st, a);                                       \
-                  else hipLaunchKernelGGL((KERNEL<true, 1>), GRID, dim3(64), LDS, st, a); }                                                \
-        else { if (lanes == 8) hipLaunchKernelGGL((KERNEL<false, 8>), GRID, dim3(64), LDS, st, a);                                         \
-               else if (lanes == 4) hipLaunchKernelGGL((KERNEL<false, 4>), GRID, dim3(64), LDS, st, a);                                    \
-               else hipLaunchKernelGGL((KERNEL<false, 1>), GRID, dim3(64), LDS, st, a); }                                                  \
-    } while (0)
-#define CVTMI_HB_LDS(KERNEL, LDS)                                                                                                         \
-    do {                                                                                                                                   \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)KERNEL<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)));            \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)KERNEL<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)));            \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)KERNEL<false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)));           \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)KERNEL<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)));           \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)KERNEL<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)));           \
-    } while (0)
-    CVTMI_HB_LDS(hnsw_build_search_kernel, lds_search);
-    CVTMI_HB_LDS(hnsw_build_select_kernel, sel_lds);
+    // the <IP, LANES> instance of the three kernel families that suits the index
+    static constexpr decltype(&hnsw_build_search_kernel<true, 4>) search_k[5] = {
+        hnsw_build_search_kernel<true, 4>, hnsw_build_search_kernel<true, 1>, hnsw_build_search_kernel<false, 8>, hnsw_build_search_kernel<false, 4>,
+        hnsw_build_search_kernel<false, 1> };
+    static constexpr decltype(&hnsw_build_select_kernel<true, 4>) select_k[5] = {
+        hnsw_build_select_kernel<true, 4>, hnsw_build_select_kernel<true, 1>, hnsw_build_select_kernel<false, 8>, hnsw_build_select_kernel<false, 4>,
+        hnsw_build_select_kernel<false, 1> };
+    static constexpr decltype(&hnsw_build_link_kernel<true, 4>) link_k[5] = {
+        hnsw_build_link_kernel<true, 4>, hnsw_build_link_kernel<true, 1>, hnsw_build_link_kernel<false, 8>, hnsw_build_link_kernel<false, 4>,
+        hnsw_build_link_kernel<false, 1> };
+    const int form = ip ? (lanes == 4 ? 0 : 1) : (lanes == 8 ? 2 : lanes == 4 ? 3 : 4);
+    const auto search = search_k[form];
+    const auto select = select_k[form];
+    const auto link = link_k[form];
+    CVTMI_TRY(set_max_lds("hnsw_build_search_kernel", search, lds_search));
+    CVTMI_TRY(set_max_lds("hnsw_build_select_kernel", select, sel_lds));
     const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
     CVTMI_TRY(mark());
     for (const HbBatch &B : batches) {
@@ -544,23 +543,20 @@ int launch_hnsw_build(const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, 
         a.words = (B.s + 31) / 32 + 1;
         const int64_t slots = (int64_t)cus * per_cu < a.rows ? (int64_t)cus * per_cu : a.rows;
         const int64_t np = (int64_t)B.ntask * M;
-        const unsigned pb = (unsigned)((np + 255) / 256);
+        const int64_t pb = blocks_for(np, 256);
         CVTMI_HIP(hipMemsetAsync(ctr.p, 0, sizeof(HbCounters), st));
-        CVTMI_HB_ALL(hnsw_build_search_kernel, dim3((unsigned)slots), lds_search);
+        CVTMI_TRY(launch("hnsw_build_search_kernel", search, slots, 64, lds_search, st, a));
         CVTMI_TRY(mark());
         const int64_t sel_grid = B.ntask < (int64_t)cus * 32 ? B.ntask : (int64_t)cus * 32;
-        CVTMI_HB_ALL(hnsw_build_select_kernel, dim3((unsigned)sel_grid), sel_lds);
+        CVTMI_TRY(launch("hnsw_build_select_kernel", select, sel_grid, 64, sel_lds, st, a));
         CVTMI_TRY(mark());
-        hipLaunchKernelGGL(hnsw_build_count_kernel, dim3(pb), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(hnsw_build_reserve_kernel, dim3(pb), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(hnsw_build_scatter_kernel, dim3(pb), dim3(256), 0, st, a);
+        CVTMI_TRY(launch("hnsw_build_count_kernel", hnsw_build_count_kernel, pb, 256, 0, st, a));
+        CVTMI_TRY(launch("hnsw_build_reserve_kernel", hnsw_build_reserve_kernel, pb, 256, 0, st, a));
+        CVTMI_TRY(launch("hnsw_build_scatter_kernel", hnsw_build_scatter_kernel, pb, 256, 0, st, a));
         const int64_t link_grid = np < (int64_t)cus * 16 ? np : (int64_t)cus * 16;
-        CVTMI_HB_ALL(hnsw_build_link_kernel, dim3((unsigned)(link_grid > 0 ? link_grid : 1)), 0);
+        CVTMI_TRY(launch("hnsw_build_link_kernel", link, link_grid > 0 ? link_grid : 1, 64, 0, st, a));
         CVTMI_TRY(mark());
     }
-#undef CVTMI_HB_ALL
-#undef CVTMI_HB_LDS
-    CVTMI_HIP(hipGetLastError());
     CVTMI_HIP(hipStreamSynchronize(st));
     int e = 0;
     CVTMI_HIP(hipMemcpy(&e, err.p, 4, hipMemcpyDeviceToHost));

@@ -20,6 +20,7 @@
 
 #include "ivf_table.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -257,7 +258,6 @@ static int ivf_range_args(IvfRangeArgs &a, size_t &lds, const OpqModelDev &m, co
     if (m.K > 256) return fail(CVTMI_EUNSUPPORTED, "range_search_ivf: K=%d > 256", m.K);
     if (m.M > 16) return fail(CVTMI_EUNSUPPORTED, "range_search_ivf: M=%d > 16", m.M);
     if (nprobe < 1 || nprobe > 128) return fail(CVTMI_EUNSUPPORTED, "range_search_ivf: nprobe=%d outside 1..128", nprobe);
-    if (nq * p.grid.parts() > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "range_search_ivf: grid too large");
     lds = ((size_t)((m.D + 3) & ~3) + (size_t)m.M * 256) * sizeof(float);
     if (lds + 64 > ((size_t)64 << 10)) return fail(CVTMI_EUNSUPPORTED, "range_search_ivf: D=%d does not fit the workgroup's LDS", m.D);
     a = IvfRangeArgs{};
@@ -280,15 +280,10 @@ int launch_ivf_range_count(const OpqModelDev &m, const float *q_rot, int64_t nq,
     size_t lds = 0;
     CVTMI_TRY(ivf_range_args(a, lds, m, q_rot, nq, nprobe, list_off, codes, radius, p, b, lims));
     const int parts = p.grid.parts();
-    hipLaunchKernelGGL(ivf_range_order_kernel, dim3((unsigned)nq), dim3(128), 0, st, probe, nprobe, b.order);
-    CVTMI_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ivf_range_scan_kernel, dim3((unsigned)(nq * parts)), dim3(kBlock), lds, st, a);
-    CVTMI_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ivf_range_part_offsets_kernel, dim3((unsigned)nq), dim3(kBlock), 0, st, b.part_cnt, parts, b.part_off, lims);
-    CVTMI_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ivf_range_lims_kernel, dim3(1), dim3(kBlock), 0, st, lims, nq);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    CVTMI_TRY(launch("ivf_range_order_kernel", ivf_range_order_kernel, nq, 128, 0, st, probe, nprobe, b.order));
+    CVTMI_TRY(launch("ivf_range_scan_kernel", ivf_range_scan_kernel, nq * parts, kBlock, lds, st, a));
+    CVTMI_TRY(launch("ivf_range_part_offsets_kernel", ivf_range_part_offsets_kernel, nq, kBlock, 0, st, b.part_cnt, parts, b.part_off, lims));
+    return launch("ivf_range_lims_kernel", ivf_range_lims_kernel, 1, kBlock, 0, st, lims, nq);
 }
 
 int launch_ivf_range_fill(const OpqModelDev &m, const float *q_rot, int64_t nq, int nprobe, const int64_t *list_off, const uint8_t *codes,
@@ -301,14 +296,9 @@ int launch_ivf_range_fill(const OpqModelDev &m, const float *q_rot, int64_t nq, 
     CVTMI_TRY(ivf_range_args(a, lds, m, q_rot, nq, nprobe, list_off, codes, radius, p, b, const_cast<int64_t *>(lims)));
     a.entry = entry; a.videos = videos; a.id_base = id_base; a.cap = cap;
     a.dist = dist; a.ids = ids; a.video = video;
-    const unsigned blocks = (unsigned)(nq * p.grid.parts());
-    if (p.spill > 0) {
-        hipLaunchKernelGGL(ivf_range_fill_kernel, dim3(blocks), dim3(kBlock), 0, st, a);
-        CVTMI_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(ivf_range_rescan_kernel, dim3(blocks), dim3(kBlock), lds, st, a);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    const int64_t blocks = nq * p.grid.parts();
+    if (p.spill > 0) CVTMI_TRY(launch("ivf_range_fill_kernel", ivf_range_fill_kernel, blocks, kBlock, 0, st, a));
+    return launch("ivf_range_rescan_kernel", ivf_range_rescan_kernel, blocks, kBlock, lds, st, a);
 }
 
 }  // namespace cvtmi

@@ -26,6 +26,7 @@
 #include "block_topk.h"
 #include "ivf_table.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -163,18 +164,6 @@ __global__ __launch_bounds__(kBlock) void ivf_merge_kernel(const unsigned long l
     }
 }
 
-static int ivf_cu_count()
-{
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 // Grid rules (pure host logic).  Wanted: at least two workgroups per CU.
 //   1  nq alone gives that: G = nprobe, one workgroup per query walks all its lists whole -- no partial lists, no merge;
 //   2  otherwise the probe slots of a query are cut into groups of G (down to one list per workgroup);
@@ -184,7 +173,7 @@ static int ivf_cu_count()
 IvfPlan plan_ivf_search(int64_t nq, int nprobe, int k, int64_t longest, size_t part_cap, int cus)
 {
     IvfPlan p;
-    if (cus <= 0) cus = ivf_cu_count();
+    if (cus <= 0) cus = device_cus();
     const int64_t want = 2 * (int64_t)cus;
     if (nq < 1) nq = 1;
     int groups = (int)std::min<int64_t>(nprobe, (want + nq - 1) / nq);
@@ -234,26 +223,18 @@ int launch_ivf_search(const OpqModelDev &m, const float *q_rot, int64_t nq, int 
     if (k < 1 || k > kBigK) return fail(CVTMI_EUNSUPPORTED, "search_ivf: k=%d outside 1..%d", k, kBigK);
     const int parts = p.parts();
     const int64_t blocks = nq * parts;
-    if (blocks > 0x7fffffff || (int64_t)parts * k > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "search_ivf: grid too large");
+    if ((int64_t)parts * k > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "search_ivf: grid too large");
     if (parts > 1 && !part) return fail(CVTMI_EINVAL, "search_ivf: no room for partial lists");
     unsigned long long *pw = parts > 1 ? static_cast<unsigned long long *>(part) : nullptr;
     const size_t lds = ((size_t)((m.D + 3) & ~3) + (size_t)m.M * 256) * sizeof(float);
     if (lds + (k <= 128 ? sizeof(TopKShared<1, IVF_CAP>) : sizeof(TopKShared<1, kBigCap>)) > ((size_t)64 << 10))
         return fail(CVTMI_EUNSUPPORTED, "search_ivf: D=%d does not fit the workgroup's LDS", m.D);
-    if (k <= 128)
-        hipLaunchKernelGGL((ivf_search_kernel<IVF_CAP, IVF_TRIG>), dim3((unsigned)blocks), dim3(kBlock), lds, st, q_rot, m.D, m.M, m.K, m.step, m.coarse,
-                           m.books, nprobe, probe, list_off, codes, entry, k, p.G, p.groups, p.pieces, p.rows_per_piece, id_base, out_d, out_id, pw);
-    else
-        hipLaunchKernelGGL((ivf_search_kernel<kBigCap, kBigTrig>), dim3((unsigned)blocks), dim3(kBlock), lds, st, q_rot, m.D, m.M, m.K, m.step, m.coarse,
-                           m.books, nprobe, probe, list_off, codes, entry, k, p.G, p.groups, p.pieces, p.rows_per_piece, id_base, out_d, out_id, pw);
-    CVTMI_HIP(hipGetLastError());
-    if (parts > 1) {
-        if (k <= 128)
-            hipLaunchKernelGGL((ivf_merge_kernel<IVF_CAP, IVF_TRIG>), dim3((unsigned)nq), dim3(kBlock), 0, st, pw, parts * k, k, id_base, out_d, out_id);
-        else
-            hipLaunchKernelGGL((ivf_merge_kernel<kBigCap, kBigTrig>), dim3((unsigned)nq), dim3(kBlock), 0, st, pw, parts * k, k, id_base, out_d, out_id);
-        CVTMI_HIP(hipGetLastError());
-    }
+    const bool small = k <= 128;   // the selection buffer of block_topk.h that holds k
+    CVTMI_TRY(launch("ivf_search_kernel", small ? ivf_search_kernel<IVF_CAP, IVF_TRIG> : ivf_search_kernel<kBigCap, kBigTrig>, blocks, kBlock, lds, st, q_rot, m.D, m.M, m.K,
+                     m.step, m.coarse, m.books, nprobe, probe, list_off, codes, entry, k, p.G, p.groups, p.pieces, p.rows_per_piece, id_base, out_d, out_id, pw));
+    if (parts > 1)
+        CVTMI_TRY(launch("ivf_merge_kernel", small ? ivf_merge_kernel<IVF_CAP, IVF_TRIG> : ivf_merge_kernel<kBigCap, kBigTrig>, nq, kBlock, 0, st, pw, parts * k, k, id_base, out_d,
+                         out_id));
     return CVTMI_OK;
 }
 

@@ -329,9 +329,6 @@ int launch_flat_u8_mstream(int D, const uint8_t *data, const int32_t *norms, int
 int launch_flat_u8_mstream_finish(int D, const uint8_t *data, int64_t n, const uint8_t *q, int64_t nq, int k, const int32_t *wmin, int G,
                                   const int32_t *tmin, int nqp, int tile_group, float *part_d, int64_t *part_id, float *out_d, int64_t *out_rows, hipStream_t st);
 int flat_u8_stream_slices();
-size_t flat_u8_stream_scratch(int64_t n, int64_t nq, int *slices, int64_t *ld);
-int launch_flat_u8_stream(int D, const uint8_t *data, const int32_t *norms, int64_t n, const uint8_t *q, int64_t nq, int k, float *scratch,
-                          float *part_d, int64_t *part_id, float *out_d, int64_t *out_rows, hipStream_t st);
 bool flat_u8_gfilter_shape(int D);
 int launch_gather_labels(int64_t *ids, int64_t count, const int64_t *labels, hipStream_t st);
 // ids[i] = ids[i] >= 0 ? ids[i] + base : -1

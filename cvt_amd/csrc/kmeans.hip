@@ -19,6 +19,7 @@
 #include <mutex>
 #include "host_util.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -222,6 +223,16 @@ __global__ __launch_bounds__(kBlock) void kmeans_residual_kernel(const float *__
     }
 }
 
+// the register kernel for rows of d <= 128 floats
+static decltype(&kmeans_assign_reg_kernel<8>) kmeans_assign_reg_for(int d)
+{
+    if (d <= 8) return kmeans_assign_reg_kernel<8>;
+    if (d <= 16) return kmeans_assign_reg_kernel<16>;
+    if (d <= 32) return kmeans_assign_reg_kernel<32>;
+    if (d <= 64) return kmeans_assign_reg_kernel<64>;
+    return kmeans_assign_reg_kernel<128>;
+}
+
 int launch_kmeans_assign(const float *x, int64_t ld, int64_t n, int d, const float *cent, int k, int32_t *assign,
                          unsigned long long *changed, hipStream_t st)
 {
@@ -265,17 +276,9 @@ int launch_kmeans_assign_exact(const float *x, int64_t ld, int64_t n, int d, con
                                unsigned long long *changed, hipStream_t st)
 {
     if (n <= 0) return CVTMI_OK;
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "kmeans: n too large");
-    const dim3 g((unsigned)blocks), b(kBlock);
-    if (d <= 8) hipLaunchKernelGGL(kmeans_assign_reg_kernel<8>, g, b, 0, st, x, ld, n, d, cent, k, assign, changed, 0, nullptr, nullptr);
-    else if (d <= 16) hipLaunchKernelGGL(kmeans_assign_reg_kernel<16>, g, b, 0, st, x, ld, n, d, cent, k, assign, changed, 0, nullptr, nullptr);
-    else if (d <= 32) hipLaunchKernelGGL(kmeans_assign_reg_kernel<32>, g, b, 0, st, x, ld, n, d, cent, k, assign, changed, 0, nullptr, nullptr);
-    else if (d <= 64) hipLaunchKernelGGL(kmeans_assign_reg_kernel<64>, g, b, 0, st, x, ld, n, d, cent, k, assign, changed, 0, nullptr, nullptr);
-    else if (d <= 128) hipLaunchKernelGGL(kmeans_assign_reg_kernel<128>, g, b, 0, st, x, ld, n, d, cent, k, assign, changed, 0, nullptr, nullptr);
-    else hipLaunchKernelGGL(kmeans_assign_kernel, g, b, 0, st, x, ld, n, d, cent, k, assign, changed);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    const int64_t blocks = blocks_for(n, kBlock);
+    if (d <= 128) return launch("kmeans_assign_reg_kernel", kmeans_assign_reg_for(d), blocks, kBlock, 0, st, x, ld, n, d, cent, k, assign, changed, 0, nullptr, nullptr);
+    return launch("kmeans_assign_kernel", kmeans_assign_kernel, blocks, kBlock, 0, st, x, ld, n, d, cent, k, assign, changed);
 }
 
 // few rows against many centroids (the rows the matrix-core filter of assign_mfma.hip could not decide): the centroid
@@ -301,15 +304,9 @@ int launch_kmeans_assign_split(const float *x, int64_t ld, int64_t n, int d, con
     if (d > 128) return fail(CVTMI_EUNSUPPORTED, "kmeans_assign_split: d=%d > 128", d);
     const int csplit = ((k + splits - 1) / splits + KM_CT - 1) / KM_CT * KM_CT;
     splits = (k + csplit - 1) / csplit;
-    const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)splits), b(kBlock);
-    if (d <= 8) hipLaunchKernelGGL(kmeans_assign_reg_kernel<8>, g, b, 0, st, x, ld, n, d, cent, k, assign, nullptr, csplit, part_d, part_i);
-    else if (d <= 16) hipLaunchKernelGGL(kmeans_assign_reg_kernel<16>, g, b, 0, st, x, ld, n, d, cent, k, assign, nullptr, csplit, part_d, part_i);
-    else if (d <= 32) hipLaunchKernelGGL(kmeans_assign_reg_kernel<32>, g, b, 0, st, x, ld, n, d, cent, k, assign, nullptr, csplit, part_d, part_i);
-    else if (d <= 64) hipLaunchKernelGGL(kmeans_assign_reg_kernel<64>, g, b, 0, st, x, ld, n, d, cent, k, assign, nullptr, csplit, part_d, part_i);
-    else hipLaunchKernelGGL(kmeans_assign_reg_kernel<128>, g, b, 0, st, x, ld, n, d, cent, k, assign, nullptr, csplit, part_d, part_i);
-    hipLaunchKernelGGL(kmeans_assign_fold_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), b, 0, st, part_d, part_i, n, splits, assign);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    CVTMI_TRY(launch("kmeans_assign_reg_kernel", kmeans_assign_reg_for(d), { blocks_for(n, kBlock), splits }, kBlock, 0, st, x, ld, n, d, cent, k, assign, nullptr,
+                     csplit, part_d, part_i));
+    return launch("kmeans_assign_fold_kernel", kmeans_assign_fold_kernel, blocks_for(n, kBlock), kBlock, 0, st, part_d, part_i, n, splits, assign);
 }
 
 // ---- update, fast path -------------------------------------------------------------------------------------
@@ -444,45 +441,37 @@ int launch_kmeans_update(const float *x, int64_t ld, int64_t n, int d, const int
         int *redo = reinterpret_cast<int *>(cnt + k);
         CVTMI_HIP(hipMemsetAsync(scratch, 0, need, st));
         const int64_t rpb = std::max<int64_t>(2048, (n + 255) / 256);
-        const dim3 g((unsigned)((n + rpb - 1) / rpb), (unsigned)((d + KM_DG - 1) / KM_DG));
         const size_t lds = (size_t)k * KM_DG * 16 + (size_t)k * 4;
-        CVTMI_HIP(hipFuncSetAttribute((const void *)kmeans_scatter_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kmeans_scatter_lds_kernel, g, dim3(kBlock), lds, st, x, ld, n, d, assign, k, rpb, sum, asum, cnt);
-        hipLaunchKernelGGL(kmeans_finalize_kernel, dim3((unsigned)((kd + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, sum, asum, cnt, k, d, cent, redo);
-        hipLaunchKernelGGL(kmeans_update_flagged_kernel, dim3((unsigned)((k + wpb - 1) / wpb)), dim3(kBlock), 0, st, x, ld, n, d, assign, k, redo, cent);
-        const hipError_t le = hipGetLastError();
-        CVTMI_HIP(hipFreeAsync(scratch, st));
-        CVTMI_HIP(le);
-        return CVTMI_OK;
+        auto chain = [&]() -> int {
+            CVTMI_TRY(launch_lds("kmeans_scatter_lds_kernel", kmeans_scatter_lds_kernel, { blocks_for(n, rpb), blocks_for(d, KM_DG) }, kBlock, lds, st, x, ld, n, d,
+                                 assign, k, rpb, sum, asum, cnt));
+            CVTMI_TRY(launch("kmeans_finalize_kernel", kmeans_finalize_kernel, blocks_for((int64_t)kd, kBlock), kBlock, 0, st, sum, asum, cnt, k, d, cent, redo));
+            return launch("kmeans_update_flagged_kernel", kmeans_update_flagged_kernel, blocks_for(k, wpb), kBlock, 0, st, x, ld, n, d, assign, k, redo, cent);
+        };
+        const int rc = chain();
+        CVTMI_HIP(hipFreeAsync(scratch, st));   // after the chain whatever its outcome
+        return rc;
     }
-    hipLaunchKernelGGL(kmeans_update_kernel, dim3((unsigned)((k + wpb - 1) / wpb)), dim3(kBlock), 0, st, x, ld, n, d, assign, k, cent);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("kmeans_update_kernel", kmeans_update_kernel, blocks_for(k, wpb), kBlock, 0, st, x, ld, n, d, assign, k, cent);
 }
 
 int launch_kmeans_gather(const float *x, int64_t ld, int d, const int64_t *rows, int k, float *cent, hipStream_t st)
 {
     const int64_t total = (int64_t)k * d;
-    hipLaunchKernelGGL(kmeans_gather_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, x, ld, d, rows, k, cent);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("kmeans_gather_kernel", kmeans_gather_kernel, blocks_for(total, kBlock), kBlock, 0, st, x, ld, d, rows, k, cent);
 }
 
 int launch_kmeans_fill(int32_t *p, int64_t n, int32_t v, hipStream_t st)
 {
     if (n <= 0) return CVTMI_OK;
-    hipLaunchKernelGGL(kmeans_fill_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, p, n, v);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("kmeans_fill_kernel", kmeans_fill_kernel, blocks_for(n, kBlock), kBlock, 0, st, p, n, v);
 }
 
 int launch_kmeans_residual(const float *x, int64_t n, int d, const float *cent, const int32_t *assign, float *res,
                            hipStream_t st)
 {
     if (n <= 0) return CVTMI_OK;
-    hipLaunchKernelGGL(kmeans_residual_kernel, dim3(2048), dim3(kBlock), 0, st, x, n, d, cent, assign, res);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("kmeans_residual_kernel", kmeans_residual_kernel, 2048, kBlock, 0, st, x, n, d, cent, assign, res);
 }
 
 }  // namespace cvtmi

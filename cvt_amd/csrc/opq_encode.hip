@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -81,12 +82,7 @@ int launch_coarse_assign(const OpqModelDev &m, const float *x_rot, int64_t n, in
     // the k-means assignment kernel is this computation (same arithmetic, same first-minimum rule); for D <= 128
     // it keeps the row in registers and packs two centroids per instruction (kmeans.hip)
     if (m.D <= 128) return launch_kmeans_assign(x_rot, m.D, n, m.D, m.coarse, m.coarseK, list_id, nullptr, st);
-    const int64_t blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "coarse_assign: n too large");
-    hipLaunchKernelGGL(coarse_assign_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, x_rot, n, m.D, m.coarse,
-                       m.coarseK, list_id);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("coarse_assign_kernel", coarse_assign_kernel, blocks_for(n, kBlock), kBlock, 0, st, x_rot, n, m.D, m.coarse, m.coarseK, list_id);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -566,19 +562,6 @@ __global__ __launch_bounds__(kBlock) void pq_encode_generic_kernel(const float *
     }
 }
 
-static int encm_cus()
-{
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
-    }
-    return cus;
-}
-
 static size_t encm_lds(const OpqModelDev &m) { return ((size_t)m.M * 256 * m.step + (size_t)m.M * 256 + m.M) * sizeof(float); }
 static bool encm_ok(const OpqModelDev &m, const float *x_rot)
 {
@@ -617,43 +600,25 @@ int launch_pq_encode(const OpqModelDev &m, const float *x_rot, int64_t n, const 
     if (mfma_ok && (variant == 2 || (variant == 0 && n >= ENCM_MIN_ROWS))) {
         constexpr int waves = ENCM_THREADS / 64;
         const int64_t nbatch = (n + 31) / 32;
-        const int64_t blocks = std::min<int64_t>(encm_cus(), (nbatch + waves - 1) / waves);
-        if (perm) {
-            CVTMI_HIP(hipFuncSetAttribute((const void *)pq_encode_mfma_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mfma));
-            hipLaunchKernelGGL((pq_encode_mfma_kernel<8, true>), dim3((unsigned)blocks), dim3(ENCM_THREADS), lds_mfma, st, x_rot, n, m.D, m.M,
-                               m.coarse, list_id, m.books, codes, single_list_out, perm);
-        } else if (m.step == 8) {
-            CVTMI_HIP(hipFuncSetAttribute((const void *)pq_encode_mfma_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mfma));
-            hipLaunchKernelGGL((pq_encode_mfma_kernel<8>), dim3((unsigned)blocks), dim3(ENCM_THREADS), lds_mfma, st, x_rot, n, m.D, m.M,
-                               m.coarse, list_id, m.books, codes, single_list_out, nullptr);
-        } else {
-            CVTMI_HIP(hipFuncSetAttribute((const void *)pq_encode_mfma_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mfma));
-            hipLaunchKernelGGL((pq_encode_mfma_kernel<16>), dim3((unsigned)blocks), dim3(ENCM_THREADS), lds_mfma, st, x_rot, n, m.D, m.M,
-                               m.coarse, list_id, m.books, codes, single_list_out, nullptr);
-        }
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
+        const int64_t blocks = std::min<int64_t>(device_cus(), blocks_for(nbatch, waves));
+        auto kern = pq_encode_mfma_kernel<8, true>;   // <step, rows through the permutation>
+        if (!perm) kern = m.step == 8 ? pq_encode_mfma_kernel<8> : pq_encode_mfma_kernel<16>;
+        return launch_lds("pq_encode_mfma_kernel", kern, blocks, ENCM_THREADS, lds_mfma, st, x_rot, n, m.D, m.M, m.coarse, list_id, m.books, codes, single_list_out, perm);
     }
     const int64_t rows_per_block = (int64_t)kBlock * ENC_V;
-    const int64_t blocks = (n + rows_per_block - 1) / rows_per_block;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "pq_encode: n too large");
-#define CVTMI_ENC(S)                                                                                               \
-    case S:                                                                                                        \
-        hipLaunchKernelGGL((pq_encode_kernel<S>), dim3((unsigned)blocks), dim3(kBlock), 0, st, x_rot, n, m.D, m.M, \
-                           m.K, m.coarse, list_id, m.books, codes);                                                \
-        break;
+    const int64_t blocks = blocks_for(n, rows_per_block);
+    decltype(&pq_encode_kernel<2>) kern;   // by the floats of a sub-vector
     switch (m.step) {
-        CVTMI_ENC(2) CVTMI_ENC(4) CVTMI_ENC(8) CVTMI_ENC(16) CVTMI_ENC(32)
-        default: {
-            const int64_t gb = (n + kBlock - 1) / kBlock;
-            if (gb > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "pq_encode: n too large");
-            hipLaunchKernelGGL(pq_encode_generic_kernel, dim3((unsigned)gb), dim3(kBlock), 0, st, x_rot, n, m.D, m.M,
-                               m.K, m.step, m.coarse, list_id, m.books, codes);
-        }
+        case 2: kern = pq_encode_kernel<2>; break;
+        case 4: kern = pq_encode_kernel<4>; break;
+        case 8: kern = pq_encode_kernel<8>; break;
+        case 16: kern = pq_encode_kernel<16>; break;
+        case 32: kern = pq_encode_kernel<32>; break;
+        default:
+            return launch("pq_encode_generic_kernel", pq_encode_generic_kernel, blocks_for(n, kBlock), kBlock, 0, st, x_rot, n, m.D, m.M, m.K, m.step, m.coarse, list_id, m.books,
+                          codes);
     }
-#undef CVTMI_ENC
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("pq_encode_kernel", kern, blocks, kBlock, 0, st, x_rot, n, m.D, m.M, m.K, m.coarse, list_id, m.books, codes);
 }
 
 #ifdef CVTMI_ENC_STATS
@@ -756,18 +721,13 @@ int launch_lut(const OpqModelDev &m, const float *q_rot, int64_t nq, const int32
     if (nq > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "lut: nq too large");
     if ((m.step == 8 || m.step == 16 || m.step == 32) && nq >= 64 && (((uintptr_t)m.books) & 15) == 0) {
         constexpr int QB = 4;
-        const dim3 g((unsigned)((nq + QB - 1) / QB));
         const size_t lds = (size_t)QB * m.D * sizeof(float);
-        if (m.step == 8) hipLaunchKernelGGL((lut8_kernel<QB, 8>), g, dim3(kBlock), lds, st, q_rot, nq, m.D, m.M, m.K, m.coarse, list_id, m.books, lut, ld, tables);
-        else if (m.step == 16) hipLaunchKernelGGL((lut8_kernel<QB, 16>), g, dim3(kBlock), lds, st, q_rot, nq, m.D, m.M, m.K, m.coarse, list_id, m.books, lut, ld, tables);
-        else hipLaunchKernelGGL((lut8_kernel<QB, 32>), g, dim3(kBlock), lds, st, q_rot, nq, m.D, m.M, m.K, m.coarse, list_id, m.books, lut, ld, tables);
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
+        auto kern = lut8_kernel<QB, 8>;
+        if (m.step == 16) kern = lut8_kernel<QB, 16>;
+        else if (m.step != 8) kern = lut8_kernel<QB, 32>;
+        return launch("lut8_kernel", kern, blocks_for(nq, QB), kBlock, lds, st, q_rot, nq, m.D, m.M, m.K, m.coarse, list_id, m.books, lut, ld, tables);
     }
-    hipLaunchKernelGGL(lut_kernel, dim3((unsigned)nq), dim3(kBlock), (size_t)m.D * sizeof(float), st, q_rot, m.D, m.M,
-                       m.K, m.step, m.coarse, list_id, m.books, lut, ld, tables);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("lut_kernel", lut_kernel, nq, kBlock, (size_t)m.D * sizeof(float), st, q_rot, m.D, m.M, m.K, m.step, m.coarse, list_id, m.books, lut, ld, tables);
 }
 
 }  // namespace cvtmi

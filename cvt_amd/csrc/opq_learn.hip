@@ -21,6 +21,7 @@
 #include "host_util.h"
 #include "kernels.h"
 #include "../../include/cvtmi.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -190,7 +191,7 @@ int cvtmi_opq_learn_rotation_dev(const float *x, int64_t n, int D, int M, int K,
     if (n < K) return fail(CVTMI_EINVAL, "cvtmi_opq_learn_rotation: fewer rows (%lld) than centroids (%d)", (long long)n, K);
     hipStream_t st = (hipStream_t)stream;
     const int step = D / M;
-    const int64_t nblocks = (n + XTY_BLOCK - 1) / XTY_BLOCK;
+    const int64_t nblocks = blocks_for(n, XTY_BLOCK);
     Tmp xr, y, assign, part, Cd;
     CVTMI_TRY(xr.alloc((size_t)n * D * sizeof(float)));
     CVTMI_TRY(y.alloc((size_t)n * D * sizeof(float)));
@@ -208,17 +209,14 @@ int cvtmi_opq_learn_rotation_dev(const float *x, int64_t n, int D, int M, int K,
             CVTMI_TRY(cvtmi_kmeans_dev(xr.as<float>() + m * step, D, n, step, K, niter, seed, books + (size_t)m * K * step,
                                        assign.as<int32_t>() + (size_t)m * n, nullptr, stream));
         if (t == outer) break;
-        const unsigned rb = (unsigned)std::min<int64_t>((n * D + kBlock - 1) / kBlock, 65535);
-        hipLaunchKernelGGL(opq_reconstruct_kernel, dim3(rb), dim3(kBlock), 0, st, books, assign.as<int32_t>(), n, D, M, K, y.as<float>());
-        switch (D / 16) {
-        case 2: hipLaunchKernelGGL((opq_xty_kernel<2>), dim3((unsigned)nblocks), dim3(256), 0, st, x, y.as<float>(), n, part.as<double>()); break;
-        case 4: hipLaunchKernelGGL((opq_xty_kernel<4>), dim3((unsigned)nblocks), dim3(256), 0, st, x, y.as<float>(), n, part.as<double>()); break;
-        case 6: hipLaunchKernelGGL((opq_xty_kernel<6>), dim3((unsigned)nblocks), dim3(256), 0, st, x, y.as<float>(), n, part.as<double>()); break;
-        default: hipLaunchKernelGGL((opq_xty_kernel<8>), dim3((unsigned)nblocks), dim3(256), 0, st, x, y.as<float>(), n, part.as<double>()); break;
-        }
-        hipLaunchKernelGGL(opq_xty_reduce_kernel, dim3((unsigned)((D * D + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, part.as<double>(), nblocks, D * D,
-                           Cd.as<double>());
-        CVTMI_HIP(hipGetLastError());
+        const int64_t rb = std::min<int64_t>(blocks_for(n * D, kBlock), 65535);
+        CVTMI_TRY(launch("opq_reconstruct_kernel", opq_reconstruct_kernel, rb, kBlock, 0, st, books, assign.as<int32_t>(), n, D, M, K, y.as<float>()));
+        auto xty = opq_xty_kernel<2>;   // by 16-float chunks of a row
+        if (D / 16 == 4) xty = opq_xty_kernel<4>;
+        else if (D / 16 == 6) xty = opq_xty_kernel<6>;
+        else if (D / 16 != 2) xty = opq_xty_kernel<8>;
+        CVTMI_TRY(launch("opq_xty_kernel", xty, nblocks, 256, 0, st, x, y.as<float>(), n, part.as<double>()));
+        CVTMI_TRY(launch("opq_xty_reduce_kernel", opq_xty_reduce_kernel, blocks_for(D * D, kBlock), kBlock, 0, st, part.as<double>(), nblocks, D * D, Cd.as<double>()));
         CVTMI_HIP(hipMemcpyAsync(Ch.data(), Cd.p, Ch.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         CVTMI_HIP(stream_wait(st));
         (void)procrustes_host(Ch.data(), D, Rh.data());   // a degenerate step keeps R

@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "rm_common.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -277,20 +278,16 @@ static RmTable rm_table(const RmPlan &p, void *scratch)
 
 int launch_rm_scan(const RmPlan &p, void *scratch, hipStream_t st)
 {
-    hipLaunchKernelGGL(rm_scan_tiles_kernel, dim3((unsigned)p.nblk), dim3(256), 0, st, rm_at<uint32_t>(scratch, p.off_tile), p.ntiles,
-                       rm_at<uint32_t>(scratch, p.off_bsum));
-    hipLaunchKernelGGL(rm_scan_top_kernel, dim3(1), dim3(256), 0, st, rm_at<uint32_t>(scratch, p.off_bsum), p.nblk, rm_at<int64_t>(scratch, p.off_boff),
-                       rm_at<int64_t>(scratch, p.off_total));
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    CVTMI_TRY(launch("rm_scan_tiles_kernel", rm_scan_tiles_kernel, p.nblk, 256, 0, st, rm_at<uint32_t>(scratch, p.off_tile), p.ntiles, rm_at<uint32_t>(scratch, p.off_bsum)));
+    return launch("rm_scan_top_kernel", rm_scan_top_kernel, 1, 256, 0, st, rm_at<uint32_t>(scratch, p.off_bsum), p.nblk, rm_at<int64_t>(scratch, p.off_boff),
+                  rm_at<int64_t>(scratch, p.off_total));
 }
 
 int launch_rm_mark_videos(const RmPlan &p, void *scratch, const int32_t *videos, hipStream_t st)
 {
     if (p.n <= 0) return fail(CVTMI_EINVAL, "opq remove: empty index");
-    hipLaunchKernelGGL(rm_mark_videos_kernel, dim3((unsigned)p.ntiles), dim3(256), 0, st, videos, p.n, rm_table(p, scratch),
-                       rm_at<unsigned long long>(scratch, p.off_drop), rm_at<uint32_t>(scratch, p.off_tile));
-    CVTMI_HIP(hipGetLastError());
+    CVTMI_TRY(launch("rm_mark_videos_kernel", rm_mark_videos_kernel, p.ntiles, 256, 0, st, videos, p.n, rm_table(p, scratch), rm_at<unsigned long long>(scratch, p.off_drop),
+                     rm_at<uint32_t>(scratch, p.off_tile)));
     return launch_rm_scan(p, scratch, st);
 }
 
@@ -299,12 +296,11 @@ int launch_rm_mark_ids(const RmPlan &p, void *scratch, const int64_t *ids, int64
     if (p.n <= 0) return fail(CVTMI_EINVAL, "opq remove: empty index");
     CVTMI_HIP(hipMemsetAsync(rm_at<char>(scratch, p.off_drop), 0, (size_t)p.ntiles * kRmWords * 8, st));
     if (n_ids > 0) {
-        const int64_t blocks = std::min<int64_t>((n_ids + kBlock - 1) / kBlock, 4096);
-        hipLaunchKernelGGL(rm_scatter_ids_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, ids, n_ids, id_base, p.n, rm_at<uint32_t>(scratch, p.off_drop));
+        const int64_t blocks = std::min<int64_t>(blocks_for(n_ids, kBlock), 4096);
+        CVTMI_TRY(launch("rm_scatter_ids_kernel", rm_scatter_ids_kernel, blocks, kBlock, 0, st, ids, n_ids, id_base, p.n, rm_at<uint32_t>(scratch, p.off_drop)));
     }
-    hipLaunchKernelGGL(rm_count_tiles_kernel, dim3((unsigned)((p.ntiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       rm_at<unsigned long long>(scratch, p.off_drop), p.n, p.ntiles, rm_at<uint32_t>(scratch, p.off_tile));
-    CVTMI_HIP(hipGetLastError());
+    CVTMI_TRY(launch("rm_count_tiles_kernel", rm_count_tiles_kernel, blocks_for(p.ntiles, kBlock), kBlock, 0, st, rm_at<unsigned long long>(scratch, p.off_drop), p.n, p.ntiles,
+                     rm_at<uint32_t>(scratch, p.off_tile)));
     return launch_rm_scan(p, scratch, st);
 }
 
@@ -313,11 +309,10 @@ template <class U> static int rm_move_chunks(const RmPlan &p, RmMove a, const Rm
     const int64_t tiles_per_chunk = p.chunk / kRmTile;
     for (int64_t t0 = 0; t0 < p.ntiles; t0 += tiles_per_chunk) {
         a.tile0 = t0;
-        const unsigned grid = (unsigned)std::min(tiles_per_chunk, p.ntiles - t0);
-        hipLaunchKernelGGL(rm_gather_kernel<U>, dim3(grid), dim3(256), 0, st, a, t, renumber);
-        hipLaunchKernelGGL(rm_copy_kernel<U>, dim3(grid), dim3(256), 0, st, a);
+        const int64_t grid = std::min(tiles_per_chunk, p.ntiles - t0);
+        CVTMI_TRY(launch("rm_gather_kernel", rm_gather_kernel<U>, grid, 256, 0, st, a, t, renumber));
+        CVTMI_TRY(launch("rm_copy_kernel", rm_copy_kernel<U>, grid, 256, 0, st, a));
     }
-    CVTMI_HIP(hipGetLastError());
     return CVTMI_OK;
 }
 
@@ -342,19 +337,15 @@ int launch_rm_move(const RmPlan &p, void *scratch, uint8_t *codes, int32_t *list
 int launch_rm_renumber(const RmPlan &p, void *scratch, int32_t *videos, hipStream_t st)
 {
     if (p.n <= 0 || p.T <= 0) return CVTMI_OK;
-    const int64_t blocks = std::min<int64_t>((p.n + 255) / 256, 4096);
-    hipLaunchKernelGGL(rm_renumber_kernel, dim3((unsigned)blocks), dim3(256), 0, st, videos, p.n, rm_table(p, scratch));
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    const int64_t blocks = std::min<int64_t>(blocks_for(p.n, 256), 4096);
+    return launch("rm_renumber_kernel", rm_renumber_kernel, blocks, 256, 0, st, videos, p.n, rm_table(p, scratch));
 }
 
 int launch_rm_fill_remap(int64_t *remap, int64_t n, int identity, hipStream_t st)
 {
     if (n <= 0) return CVTMI_OK;
-    const int64_t blocks = std::min<int64_t>((n + kBlock - 1) / kBlock, 4096);
-    hipLaunchKernelGGL(rm_fill_remap_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, remap, n, identity);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    const int64_t blocks = std::min<int64_t>(blocks_for(n, kBlock), 4096);
+    return launch("rm_fill_remap_kernel", rm_fill_remap_kernel, blocks, kBlock, 0, st, remap, n, identity);
 }
 
 }  // namespace cvtmi

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "div_rn.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -137,23 +138,12 @@ int launch_pca_project(const float *mean, const float *E, int din, int dout, con
     if ((((uintptr_t)x) | ((uintptr_t)E) | ((uintptr_t)mean)) & 15) return fail(CVTMI_EINVAL, "pca_project: pointers must be 16-byte aligned");
     if (n == 0) return CVTMI_OK;
     const int nt = (dout + 31) / 32;
-    const int64_t blocks = (n + PCA_ROWS - 1) / PCA_ROWS;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "pca_project: %lld rows in one call", (long long)n);
+    const int64_t blocks = blocks_for(n, PCA_ROWS);
     const size_t lds = (size_t)2 * (PCA_ROWS + 32 * nt) * PCA_LD * sizeof(float);
-#define CVTMI_PCA_CASE(T)                                                                                                   \
-    case T:                                                                                                                 \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)pca_project_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((pca_project_kernel<T>), dim3((unsigned)blocks), dim3(PCA_THREADS), lds, st, mean, E, din, dout, x, n, \
-                           l2norm, y);                                                                                      \
-        break;
-    switch (nt) {
-        CVTMI_PCA_CASE(1) CVTMI_PCA_CASE(2) CVTMI_PCA_CASE(3) CVTMI_PCA_CASE(4)
-        CVTMI_PCA_CASE(5) CVTMI_PCA_CASE(6) CVTMI_PCA_CASE(7) CVTMI_PCA_CASE(8)
-        default: return fail(CVTMI_EUNSUPPORTED, "pca_project: dout=%d", dout);
-    }
-#undef CVTMI_PCA_CASE
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    static constexpr decltype(&pca_project_kernel<1>) kernels[] = {   // by 32-column tiles of the output: 1 .. 8
+        pca_project_kernel<1>, pca_project_kernel<2>, pca_project_kernel<3>, pca_project_kernel<4>,
+        pca_project_kernel<5>, pca_project_kernel<6>, pca_project_kernel<7>, pca_project_kernel<8> };
+    return launch_lds("pca_project_kernel", kernels[nt - 1], blocks, PCA_THREADS, lds, st, mean, E, din, dout, x, n, l2norm, y);
 }
 
 }  // namespace cvtmi

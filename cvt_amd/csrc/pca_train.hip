@@ -27,6 +27,7 @@
 #include <string>
 
 #include "host_util.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -58,7 +59,7 @@ Plan make_plan(int64_t n, int din)
     const int nt = (din + PT_TILE - 1) / PT_TILE;
     p.tiles = nt * (nt + 1) / 2;
     const int64_t want = (PT_COV_TARGET + p.tiles - 1) / p.tiles;
-    int64_t rows = (n + want - 1) / want;
+    int64_t rows = blocks_for(n, want);
     rows = std::max<int64_t>(PT_COV_MIN_ROWS, (rows + PT_KC - 1) / PT_KC * PT_KC);
     p.cov_rows = rows;
     p.cov_blocks = (n + rows - 1) / rows;
@@ -356,16 +357,11 @@ int covariance(const float *x, int64_t n, int din, float *mean, double *cov, hip
     CVTMI_TRY(mpart.alloc((size_t)p.mean_blocks * din * sizeof(double)));
     CVTMI_TRY(cpart.alloc((size_t)p.cov_blocks * p.tiles * PT_TILE * PT_TILE * sizeof(double)));
     const int cgroups = (din / 4 + PT_THREADS - 1) / PT_THREADS;
-    hipLaunchKernelGGL(pca_colsum_kernel, dim3((unsigned)p.mean_blocks, cgroups), dim3(PT_THREADS), 0, st, x, n, din, p.mean_rows,
-                       mpart.as<double>());
-    hipLaunchKernelGGL(pca_mean_kernel, dim3((din + PT_THREADS - 1) / PT_THREADS), dim3(PT_THREADS), 0, st, mpart.as<double>(),
-                       p.mean_blocks, din, n, mean);
-    hipLaunchKernelGGL(pca_cov_kernel, dim3((unsigned)p.tiles, (unsigned)p.cov_blocks), dim3(PT_THREADS), 0, st, x, n, din, mean,
-                       p.cov_rows, cpart.as<double>());
+    CVTMI_TRY(launch("pca_colsum_kernel", pca_colsum_kernel, { p.mean_blocks, cgroups }, PT_THREADS, 0, st, x, n, din, p.mean_rows, mpart.as<double>()));
+    CVTMI_TRY(launch("pca_mean_kernel", pca_mean_kernel, blocks_for(din, PT_THREADS), PT_THREADS, 0, st, mpart.as<double>(), p.mean_blocks, din, n, mean));
+    CVTMI_TRY(launch("pca_cov_kernel", pca_cov_kernel, { p.tiles, p.cov_blocks }, PT_THREADS, 0, st, x, n, din, mean, p.cov_rows, cpart.as<double>()));
     const int64_t el = (int64_t)din * din;
-    hipLaunchKernelGGL(pca_cov_reduce_kernel, dim3((unsigned)((el + PT_THREADS - 1) / PT_THREADS)), dim3(PT_THREADS), 0, st,
-                       cpart.as<double>(), p.cov_blocks, p.tiles, din, n, cov);
-    CVTMI_HIP(hipGetLastError());
+    CVTMI_TRY(launch("pca_cov_reduce_kernel", pca_cov_reduce_kernel, blocks_for(el, PT_THREADS), PT_THREADS, 0, st, cpart.as<double>(), p.cov_blocks, p.tiles, din, n, cov));
     CVTMI_HIP(hipStreamSynchronize(st));
     return CVTMI_OK;
 }
@@ -416,8 +412,7 @@ int train(const float *x, int64_t n, int din, int dout, float *mean, float *vect
     CVTMI_HIP(hipMemcpyAsync(&info, dinfo.p, sizeof info, hipMemcpyDeviceToHost, st));
     CVTMI_HIP(hipStreamSynchronize(st));
     if (info != 0) return fail(CVTMI_EHIP, "pca_train: rocsolver_dsyevd did not converge (info = %d)", (int)info);
-    hipLaunchKernelGGL(pca_finish_kernel, dim3(dout), dim3(PT_THREADS), 0, st, dcov.as<double>(), dw.as<double>(), din, vectors, values);
-    CVTMI_HIP(hipGetLastError());
+    CVTMI_TRY(launch("pca_finish_kernel", pca_finish_kernel, dout, PT_THREADS, 0, st, dcov.as<double>(), dw.as<double>(), din, vectors, values));
     CVTMI_HIP(hipStreamSynchronize(st));
     return CVTMI_OK;
 }

@@ -13,6 +13,7 @@
 
 #include "block_topk.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -218,31 +219,19 @@ int launch_coarse_probe(const OpqModelDev &m, const float *q_rot, int64_t nq, in
         splits = (m.coarseK + chunk - 1) / chunk;
         uint32_t *pk = reinterpret_cast<uint32_t *>(scratch);
         int32_t *pid = reinterpret_cast<int32_t *>(pk + (size_t)nq * splits * nprobe);
-        hipLaunchKernelGGL(coarse_probe_split_kernel, dim3((unsigned)splits, (unsigned)nq), dim3(kBlock), (size_t)m.D * sizeof(float), st, q_rot, m.D, m.coarse,
-                           m.coarseK, nprobe, chunk, pk, pid);
-        hipLaunchKernelGGL(coarse_probe_merge_kernel, dim3((unsigned)nq), dim3(kBlock), 0, st, pk, pid, splits, nprobe, probe);
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
+        CVTMI_TRY(launch("coarse_probe_split_kernel", coarse_probe_split_kernel, { splits, nq }, kBlock, (size_t)m.D * sizeof(float), st, q_rot, m.D, m.coarse, m.coarseK, nprobe,
+                         chunk, pk, pid));
+        return launch("coarse_probe_merge_kernel", coarse_probe_merge_kernel, nq, kBlock, 0, st, pk, pid, splits, nprobe, probe);
     }
     if (variant != 1 && coarse_probe_filter_applies(q_rot, variant == 2 ? std::max<int64_t>(nq, 256) : nq, m.D, m.coarse, m.coarseK, nprobe))
         return launch_coarse_probe_filtered(q_rot, nq, m.D, m.coarse, m.coarseK, nprobe, probe, st);
     if (nq >= 64 && nprobe <= 128 && m.D <= 256) {
         const size_t lds = ((size_t)CPT_Q * m.D + (size_t)m.D * (CPT_TILE + 1)) * sizeof(float);
-        const int64_t blocks = (nq + CPT_Q - 1) / CPT_Q;
-        if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "query_video: nq too large");
-        CVTMI_HIP(hipFuncSetAttribute((const void *)coarse_probe_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(coarse_probe_tile_kernel, dim3((unsigned)blocks), dim3(kBlock), lds, st, q_rot, nq, m.D, m.coarse, m.coarseK,
-                           nprobe, probe);
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
+        return launch_lds("coarse_probe_tile_kernel", coarse_probe_tile_kernel, blocks_for(nq, CPT_Q), kBlock, lds, st, q_rot, nq, m.D, m.coarse, m.coarseK, nprobe, probe);
     }
     if (nq <= 0) return CVTMI_OK;
     if (nprobe < 1 || nprobe > 128) return fail(CVTMI_EUNSUPPORTED, "query_video: nprobe=%d outside 1..128", nprobe);
-    if (nq > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "query_video: nq too large");
-    hipLaunchKernelGGL(coarse_probe_kernel, dim3((unsigned)nq), dim3(kBlock), (size_t)m.D * sizeof(float), st, q_rot, m.D,
-                       m.coarse, m.coarseK, nprobe, probe);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("coarse_probe_kernel", coarse_probe_kernel, nq, kBlock, (size_t)m.D * sizeof(float), st, q_rot, m.D, m.coarse, m.coarseK, nprobe, probe);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -381,19 +370,13 @@ int launch_csr_build(const int32_t *lists, const int32_t *videos, const uint8_t 
     CVTMI_HIP(hipMemsetAsync(st64, 0, 8, st));
     CVTMI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(vst), 0x7fffffff, 1, st));        // min video id
     CVTMI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(vst + 1), (int)0x80000000u, 1, st));   // max video id
-    if (n > 0) {
-        hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(64), 0, st, lists, n, L, hist);
-        CVTMI_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(csr_prefix_kernel, dim3((L + kBlock - 1) / kBlock), dim3(kBlock), 0, st, hist, nb, L, total);
-    hipLaunchKernelGGL(csr_offsets_kernel, dim3(1), dim3(1024), 0, st, total, L, list_off, st64);
-    CVTMI_HIP(hipGetLastError());
+    if (n > 0) CVTMI_TRY(launch("csr_count_kernel", csr_count_kernel, nb, 64, 0, st, lists, n, L, hist));
+    CVTMI_TRY(launch("csr_prefix_kernel", csr_prefix_kernel, blocks_for(L, kBlock), kBlock, 0, st, hist, nb, L, total));
+    CVTMI_TRY(launch("csr_offsets_kernel", csr_offsets_kernel, 1, 1024, 0, st, total, L, list_off, st64));
     if (n > 0) {
         int key_bits = 1;
         while ((1 << key_bits) < L) ++key_bits;
-        hipLaunchKernelGGL(csr_scatter_kernel, dim3(nb), dim3(64), 0, st, lists, videos, codes, n, L, M, key_bits, hist, list_off,
-                           out_codes, out_videos, vst, out_entry);
-        CVTMI_HIP(hipGetLastError());
+        CVTMI_TRY(launch("csr_scatter_kernel", csr_scatter_kernel, nb, 64, 0, st, lists, videos, codes, n, L, M, key_bits, hist, list_off, out_codes, out_videos, vst, out_entry));
     }
     return CVTMI_OK;
 }
@@ -475,20 +458,17 @@ int launch_query_video(const OpqModelDev &m, const float *q_rot, int64_t nq, int
     if (nq <= 0 || img_num <= 0) return CVTMI_OK;
     if (m.K > 256) return fail(CVTMI_EUNSUPPORTED, "query_video: K=%d > 256", m.K);
     const int64_t total = nq * img_num;
-    int64_t fb = (total + kBlock - 1) / kBlock;
+    int64_t fb = blocks_for(total, kBlock);
     if (fb > 4096) fb = 4096;
-    hipLaunchKernelGGL(fill_u32_kernel, dim3((unsigned)fb), dim3(kBlock), 0, st,
-                       reinterpret_cast<uint32_t *>(match_score), total, 0x3f800000u /* 1.0f = threhold */);
+    CVTMI_TRY(launch("fill_u32_kernel", fill_u32_kernel, fb, kBlock, 0, st, reinterpret_cast<uint32_t *>(match_score), total, 0x3f800000u /* 1.0f = threhold */));
     if (longest_list <= 0) return CVTMI_OK;
     const int rows_per_piece = 4096;
-    const int64_t pieces = (longest_list + rows_per_piece - 1) / rows_per_piece;
+    const int64_t pieces = blocks_for(longest_list, rows_per_piece);
     const int64_t blocks = nq * nprobe * pieces;
-    if (blocks > 0x7fffffff || pieces > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "query_video: grid too large");
+    if (pieces > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "query_video: grid too large");
     const size_t lds = ((size_t)m.D + (size_t)m.M * 256) * sizeof(float);
-    hipLaunchKernelGGL(query_video_kernel, dim3((unsigned)blocks), dim3(kBlock), lds, st, q_rot, m.D, m.M, m.K, m.step,
-                       m.coarse, m.books, nprobe, probe, list_off, codes, video_id, img_num, match_score, (int)pieces, rows_per_piece);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("query_video_kernel", query_video_kernel, blocks, kBlock, lds, st, q_rot, m.D, m.M, m.K, m.step, m.coarse, m.books, nprobe, probe, list_off, codes, video_id,
+                  img_num, match_score, (int)pieces, rows_per_piece);
 }
 
 }  // namespace cvtmi

@@ -16,6 +16,7 @@
 // 32 rows x D outputs = NT accumulators of 32x32 (16 VGPRs each), holds its 32 x D slab of X in
 // registers (loaded straight from HBM) and issues NT MFMAs per k-pair with B read from LDS.
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -55,15 +56,12 @@ __global__ __launch_bounds__(kBlock) void permute_wide_kernel(const int32_t *__r
 int launch_permute(const int32_t *perm, int D, const float *x, int64_t n, float *y, hipStream_t st)
 {
     if (n <= 0) return CVTMI_OK;
-    const unsigned grid = 256 * 8;
-    if ((D & 3) == 0 && D / 4 <= kBlock && ((uintptr_t)y & 15) == 0)
-        hipLaunchKernelGGL(permute_kernel<4>, dim3(grid), dim3(kBlock), 0, st, perm, D, x, n, y);
-    else if (D <= kBlock)
-        hipLaunchKernelGGL(permute_kernel<1>, dim3(grid), dim3(kBlock), 0, st, perm, D, x, n, y);
-    else
-        hipLaunchKernelGGL(permute_wide_kernel, dim3(grid), dim3(kBlock), 0, st, perm, D, x, n, y);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    const char *what = "permute_kernel";
+    auto kern = permute_kernel<4>;
+    if ((D & 3) == 0 && D / 4 <= kBlock && ((uintptr_t)y & 15) == 0) ;
+    else if (D <= kBlock) kern = permute_kernel<1>;
+    else { kern = permute_wide_kernel; what = "permute_wide_kernel"; }
+    return launch(what, kern, 256 * 8, kBlock, 0, st, perm, D, x, n, y);
 }
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
@@ -194,19 +192,8 @@ int launch_rotate_gemm(const float *R, int D, const float *x, int64_t n, float *
     const int64_t n_slabs = (n + 31) / 32;
     int64_t blocks = (n_slabs + 7) / 8;
     if (blocks > 256) blocks = 256;  // one persistent 8-wave workgroup per CU
-#define CVTMI_ROT(T)                                                                                              \
-    case T:                                                                                                       \
-        CVTMI_HIP(hipFuncSetAttribute((const void *)rotate_gemm_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      (int)lds));                                                                 \
-        hipLaunchKernelGGL((rotate_gemm_kernel<T>), dim3((unsigned)blocks), dim3(ROT_THREADS), lds, st, R, x, n, y); \
-        break;
-    switch (NT) {
-        CVTMI_ROT(1) CVTMI_ROT(2) CVTMI_ROT(3) CVTMI_ROT(4)
-        default: return fail(CVTMI_EUNSUPPORTED, "rotate_gemm: D=%d", D);
-    }
-#undef CVTMI_ROT
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    static constexpr decltype(&rotate_gemm_kernel<1>) kernels[] = { rotate_gemm_kernel<1>, rotate_gemm_kernel<2>, rotate_gemm_kernel<3>, rotate_gemm_kernel<4> };
+    return launch_lds("rotate_gemm_kernel", kernels[NT - 1], blocks, ROT_THREADS, lds, st, R, x, n, y);   // (D = 32 NT)
 }
 
 }  // namespace cvtmi

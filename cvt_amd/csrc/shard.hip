@@ -34,6 +34,7 @@
 #include "host_util.h"
 #include "kernels.h"
 #include "shard.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -294,9 +295,8 @@ int comm_exchange_merge(cvtmi_comm_t c, int64_t nq, int k, int status, float *di
                                          (int64_t)(slot / sizeof(float)), (int64_t)(slot / sizeof(int64_t)), nq, c->world, k, dist, ids, st));
     if (deferred) {
         const int64_t count = nq * k;
-        hipLaunchKernelGGL(comm_status_fold_kernel, dim3((unsigned)std::min<int64_t>(256, (count + 255) / 256)), dim3(256), 0, st, c->gather.as<uint8_t>(), slot,
-                           c->world, c->d_sticky, dist, ids, count);
-        CVTMI_HIP(hipGetLastError());
+        CVTMI_TRY(launch("comm_status_fold_kernel", comm_status_fold_kernel, std::min<int64_t>(256, blocks_for(count, 256)), 256, 0, st, c->gather.as<uint8_t>(), slot, c->world,
+                         c->d_sticky, dist, ids, count));
     }
     if (earlier != CVTMI_OK) return fail(CVTMI_ECOMM, "%s", earlier_msg.c_str());
     return CVTMI_OK;

@@ -30,6 +30,7 @@
 
 #include "div_rn.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -247,13 +248,11 @@ static int launch_sq8_tile(const Sq8Args &a, hipStream_t st)
 {
     const size_t lds = (size_t)SQ_ROWS * ((a.d >> 2) + 1) * sizeof(float4);
     // set on every call: the attribute belongs to the (function, device) pair, and a process may hold handles on several devices
-    CVTMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sq8_tile_kernel<TRAIN>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 129 * 16));
-    const int64_t n_tiles = (a.n + SQ_ROWS - 1) / SQ_ROWS;
+    CVTMI_TRY(set_max_lds("sq8_tile_kernel", sq8_tile_kernel<TRAIN>, 64 * 129 * 16));
+    const int64_t n_tiles = blocks_for(a.n, SQ_ROWS);
     int64_t blocks = lds > 72 * 1024 ? 256 : 512;  // one or two workgroups per CU
     if (blocks > n_tiles) blocks = n_tiles;
-    hipLaunchKernelGGL(sq8_tile_kernel<TRAIN>, dim3((unsigned)blocks), dim3(SQ_NT), lds, st, a);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("sq8_tile_kernel", sq8_tile_kernel<TRAIN>, blocks, SQ_NT, lds, st, a);
 }
 
 // ---- two-pass kernels for the other row widths ----------------------------------------------------
@@ -293,11 +292,7 @@ __global__ __launch_bounds__(kBlock) void sq8_rownorm_kernel(const float *__rest
 int launch_sq8_rownorm(const float *x, int64_t n, int d, float *den, hipStream_t st)
 {
     if (n <= 0) return CVTMI_OK;
-    const int64_t blocks = (n + NORM_ROWS - 1) / NORM_ROWS;
-    if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "sq8: n too large");
-    hipLaunchKernelGGL(sq8_rownorm_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, x, n, d, den);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("sq8_rownorm_kernel", sq8_rownorm_kernel, blocks_for(n, NORM_ROWS), kBlock, 0, st, x, n, d, den);
 }
 
 constexpr int EW_ROWS = 16;  // rows per workgroup of the element-wise kernels
@@ -328,12 +323,9 @@ int launch_sq8_encode(const float *vmin, const float *vdiff, int d, float *x, in
                       int write_back, uint8_t *codes, hipStream_t st)
 {
     if (n <= 0) return CVTMI_OK;
-    int64_t blocks = (n + EW_ROWS - 1) / EW_ROWS;
+    int64_t blocks = blocks_for(n, EW_ROWS);
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(sq8_encode_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, vmin, vdiff, d, x, n, den,
-                       write_back, codes);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("sq8_encode_kernel", sq8_encode_kernel, blocks, kBlock, 0, st, vmin, vdiff, d, x, n, den, write_back, codes);
 }
 
 static int launch_sq8_encode_wave(const float *vmin, const float *vdiff, int d, float *x, int64_t n, int l2norm, int write_back,
@@ -501,19 +493,14 @@ int launch_sq8_decode(const float *vmin, const float *vdiff, int d, const uint8_
         int rs = (256 + slabs - 1) / slabs;                    // one workgroup per CU
         if ((int64_t)rs * 2048 > n) rs = (int)std::max<int64_t>(1, n / 2048);
         const size_t lds = 4 * 256 * 32 * sizeof(float);
-        CVTMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sq8_decode_lut_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(sq8_decode_lut_kernel, dim3((unsigned)(slabs * rs)), dim3(DEC_NT), lds, st, vmin, vdiff, d, codes, n, x, rs, mode);
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
+        return launch_lds("sq8_decode_lut_kernel", sq8_decode_lut_kernel, slabs * rs, DEC_NT, lds, st, vmin, vdiff, d, codes, n, x, rs, mode);
     }
-    int64_t blocks = (n + EW_ROWS - 1) / EW_ROWS;
+    int64_t blocks = blocks_for(n, EW_ROWS);
     if (blocks > 256 * 16) blocks = 256 * 16;
     const bool vec = (d & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)codes & 3) == 0 &&
                      ((uintptr_t)vmin & 15) == 0 && ((uintptr_t)vdiff & 15) == 0;
-    if (vec) hipLaunchKernelGGL(sq8_decode_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, vmin, vdiff, d, codes, n, x, mode);
-    else hipLaunchKernelGGL(sq8_decode_any_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, vmin, vdiff, d, codes, n, x, mode);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    if (vec) return launch("sq8_decode_kernel", sq8_decode_kernel, blocks, kBlock, 0, st, vmin, vdiff, d, codes, n, x, mode);
+    return launch("sq8_decode_any_kernel", sq8_decode_any_kernel, blocks, kBlock, 0, st, vmin, vdiff, d, codes, n, x, mode);
 }
 
 // ---- train: per-dimension min / max over (normalised) rows; min and max are order-independent ----
@@ -1380,58 +1367,47 @@ __global__ __launch_bounds__(kBlock) void sq8_zero_sign_kernel(const float *__re
 // workgroups per CU of the wave-per-row training kernel.  A wave keeps RB rows in flight that lie (waves in the grid) rows apart: with a
 // power-of-two grid those streams are a power-of-two distance apart and fall on the same HBM channels -- measured on 2 M x 512-d:
 // 8 per CU 4.62-4.67 TB/s, 4: 4.38, 16: 4.89, 3: 5.04, 24: 5.09 (tools: cvtmi_set_tuning("sq8_wave_blocks"))
+// the filter kernel for rows of 256 NF floats (NF = 1, 2, 3, 4, 6, 8)
 template <bool NORM>
-static void launch_sq8_train_wave_f_n(int NF, unsigned blocks, hipStream_t st, const float *x, int64_t n, uint32_t *kmin, uint32_t *kmax, int seeded, int flags)
+static decltype(&sq8_train_wave_f_kernel<1, NORM>) sq8_train_wave_f_of(int NF)
 {
     switch (NF) {
-        case 1: hipLaunchKernelGGL((sq8_train_wave_f_kernel<1, NORM>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax, seeded, flags); break;
-        case 2: hipLaunchKernelGGL((sq8_train_wave_f_kernel<2, NORM>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax, seeded, flags); break;
-        case 3: hipLaunchKernelGGL((sq8_train_wave_f_kernel<3, NORM>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax, seeded, flags); break;
-        case 4: hipLaunchKernelGGL((sq8_train_wave_f_kernel<4, NORM>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax, seeded, flags); break;
-        case 6: hipLaunchKernelGGL((sq8_train_wave_f_kernel<6, NORM>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax, seeded, flags); break;
-        default: hipLaunchKernelGGL((sq8_train_wave_f_kernel<8, NORM>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax, seeded, flags); break;
+        case 1: return sq8_train_wave_f_kernel<1, NORM>;
+        case 2: return sq8_train_wave_f_kernel<2, NORM>;
+        case 3: return sq8_train_wave_f_kernel<3, NORM>;
+        case 4: return sq8_train_wave_f_kernel<4, NORM>;
+        case 6: return sq8_train_wave_f_kernel<6, NORM>;
+        default: return sq8_train_wave_f_kernel<8, NORM>;
     }
 }
-static void launch_sq8_train_wave_f(int NF, bool norm, unsigned blocks, hipStream_t st, const float *x, int64_t n, uint32_t *kmin, uint32_t *kmax, int seeded,
-                                    int flags)
+static decltype(&sq8_train_wave_f_kernel<1, true>) sq8_train_wave_f_for(int NF, bool norm)
 {
-    if (norm) launch_sq8_train_wave_f_n<true>(NF, blocks, st, x, n, kmin, kmax, seeded, flags);
-    else launch_sq8_train_wave_f_n<false>(NF, blocks, st, x, n, kmin, kmax, seeded, flags);
+    return norm ? sq8_train_wave_f_of<true>(NF) : sq8_train_wave_f_of<false>(NF);
 }
-static unsigned sq8_group_blocks(int64_t n, int d)
+static int64_t sq8_group_blocks(int64_t n, int d)
 {
     const int64_t groups = (n * d + 255) / 256, per_wg = kBlock / 64;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + per_wg - 1) / per_wg, 256 * tune_sq8_wave_blocks.geti()));
+    return std::max<int64_t>(1, std::min<int64_t>(blocks_for(groups, per_wg), 256 * tune_sq8_wave_blocks.geti()));
 }
-static void launch_sq8_train_group(int d, bool norm, unsigned blocks, hipStream_t st, const float *x, int64_t n, uint32_t *kmin, uint32_t *kmax, int seeded)
+// 64-d / 128-d rows: 16 / 32 lanes per row
+static decltype(&sq8_train_group_f_kernel<16, true>) sq8_train_group_for(int d, bool norm)
 {
-    if (d == 64) {
-        if (norm) hipLaunchKernelGGL((sq8_train_group_f_kernel<16, true>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax, seeded);
-        else hipLaunchKernelGGL((sq8_train_group_f_kernel<16, false>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax, seeded);
-    } else {
-        if (norm) hipLaunchKernelGGL((sq8_train_group_f_kernel<32, true>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax, seeded);
-        else hipLaunchKernelGGL((sq8_train_group_f_kernel<32, false>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax, seeded);
-    }
+    if (d == 64) return norm ? sq8_train_group_f_kernel<16, true> : sq8_train_group_f_kernel<16, false>;
+    return norm ? sq8_train_group_f_kernel<32, true> : sq8_train_group_f_kernel<32, false>;
 }
 static int launch_sq8_encode_group(const float *vmin, const float *vdiff, int d, float *x, int64_t n, int l2norm, int write_back, uint8_t *codes, hipStream_t st)
 {
-    const unsigned blocks = sq8_group_blocks(n, d);
-    if (d == 64) {
-        if (l2norm) hipLaunchKernelGGL((sq8_encode_group_f_kernel<16, true>), dim3(blocks), dim3(kBlock), 0, st, vmin, vdiff, x, n, write_back, codes);
-        else hipLaunchKernelGGL((sq8_encode_group_f_kernel<16, false>), dim3(blocks), dim3(kBlock), 0, st, vmin, vdiff, x, n, 0, codes);
-    } else {
-        if (l2norm) hipLaunchKernelGGL((sq8_encode_group_f_kernel<32, true>), dim3(blocks), dim3(kBlock), 0, st, vmin, vdiff, x, n, write_back, codes);
-        else hipLaunchKernelGGL((sq8_encode_group_f_kernel<32, false>), dim3(blocks), dim3(kBlock), 0, st, vmin, vdiff, x, n, 0, codes);
-    }
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    decltype(&sq8_encode_group_f_kernel<16, true>) kern;
+    if (d == 64) kern = l2norm ? sq8_encode_group_f_kernel<16, true> : sq8_encode_group_f_kernel<16, false>;
+    else kern = l2norm ? sq8_encode_group_f_kernel<32, true> : sq8_encode_group_f_kernel<32, false>;
+    return launch("sq8_encode_group_f_kernel", kern, sq8_group_blocks(n, d), kBlock, 0, st, vmin, vdiff, x, n, l2norm ? write_back : 0, codes);
 }
 // den_scratch: n floats, only used for row widths the tile kernel does not take
 int launch_sq8_train(const float *x, int64_t n, int d, int l2norm, float *den_scratch, uint32_t *kmin, uint32_t *kmax,
                      float *vmin, float *vdiff, hipStream_t st)
 {
-    const unsigned db = (unsigned)((d + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(sq8_train_init_kernel, dim3(db), dim3(kBlock), 0, st, kmin, kmax, d);
+    const int64_t db = blocks_for(d, kBlock);
+    CVTMI_TRY(launch("sq8_train_init_kernel", sq8_train_init_kernel, db, kBlock, 0, st, kmin, kmax, d));
     if (n > 0) {
         // the wave-per-row kernels: normalised rows of 256 / 512 floats as before; round 5: through the filter kernel also rows of 768 ...
         // 2048 floats, and those without normalisation (the tile kernel stops at 512-d; the generic kernels ran at 0.8 / 3.3 TB/s)
@@ -1439,23 +1415,26 @@ int launch_sq8_train(const float *x, int64_t n, int d, int l2norm, float *den_sc
         if (sq8_filter_on() && sq8_group_width(d) && (((uintptr_t)x) & 15) == 0 && n >= 4096) {
             // 64-d / 128-d rows (round 6): several rows per wave, sample pass + seeded pass like the wide rows
             const int64_t ns = n >= 8 * SQ8_SAMPLE_ROWS ? SQ8_SAMPLE_ROWS : 0;
-            if (ns) launch_sq8_train_group(d, l2norm != 0, sq8_group_blocks(ns / 16, d), st, x, ns, kmin, kmax, 0);
-            launch_sq8_train_group(d, l2norm != 0, sq8_group_blocks(n - ns, d), st, x + ns * d, n - ns, kmin, kmax, ns ? 1 : 0);
+            const auto kern = sq8_train_group_for(d, l2norm != 0);
+            if (ns) CVTMI_TRY(launch("sq8_train_group_f_kernel", kern, sq8_group_blocks(ns / 16, d), kBlock, 0, st, x, ns, kmin, kmax, 0));
+            CVTMI_TRY(launch("sq8_train_group_f_kernel", kern, sq8_group_blocks(n - ns, d), kBlock, 0, st, x + ns * d, n - ns, kmin, kmax, ns ? 1 : 0));
         } else if ((wave_f || (l2norm && (d == 256 || d == 512))) && (((uintptr_t)x) & 15) == 0 && n >= (wave_f && d > 512 ? 1 : 4096)) {
             // whole rows per wave, no LDS tile (the tile kernel's phases serialise behind its barriers: 3.3 TB/s at d = 512)
             const int64_t rows_per_wg = kBlock / 64;
-            const unsigned blocks = (unsigned)std::min<int64_t>((n + rows_per_wg - 1) / rows_per_wg, 256 * tune_sq8_wave_blocks.geti());
+            const int64_t blocks = std::min<int64_t>(blocks_for(n, rows_per_wg), 256 * tune_sq8_wave_blocks.geti());
             if (wave_f) {
                 // sample pass over the first rows (its extremes seed every wave of the main pass: "new extreme" is rare from the start),
                 // then the rest; both through the filter kernel, the sample unseeded
                 const int64_t ns = n >= 8 * SQ8_SAMPLE_ROWS ? SQ8_SAMPLE_ROWS : 0;
                 const float *xr = x + ns * d;
-                const unsigned sblocks = (unsigned)((ns / 16 + rows_per_wg - 1) / rows_per_wg);   // 16 rows per wave of the sample
+                const int64_t sblocks = blocks_for(ns / 16, rows_per_wg);   // 16 rows per wave of the sample
                 const int fl = tune_sq8_flags.geti();
-                if (ns) launch_sq8_train_wave_f(d / 256, l2norm != 0, sblocks, st, x, ns, kmin, kmax, 0, fl);
-                launch_sq8_train_wave_f(d / 256, l2norm != 0, blocks, st, xr, n - ns, kmin, kmax, ns ? 1 : 0, fl);
-            } else if (d == 512) hipLaunchKernelGGL((sq8_train_wave_kernel<2>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax);
-            else hipLaunchKernelGGL((sq8_train_wave_kernel<1>), dim3(blocks), dim3(kBlock), 0, st, x, n, kmin, kmax);
+                const auto kern = sq8_train_wave_f_for(d / 256, l2norm != 0);
+                if (ns) CVTMI_TRY(launch("sq8_train_wave_f_kernel", kern, sblocks, kBlock, 0, st, x, ns, kmin, kmax, 0, fl));
+                CVTMI_TRY(launch("sq8_train_wave_f_kernel", kern, blocks, kBlock, 0, st, xr, n - ns, kmin, kmax, ns ? 1 : 0, fl));
+            } else {
+                CVTMI_TRY(launch("sq8_train_wave_kernel", d == 512 ? sq8_train_wave_kernel<2> : sq8_train_wave_kernel<1>, blocks, kBlock, 0, st, x, n, kmin, kmax));
+            }
         } else if (sq8_tile_ok(d, x, nullptr, nullptr, nullptr)) {
             Sq8Args a{};
             a.x = const_cast<float *>(x); a.kmin = kmin; a.kmax = kmax; a.n = n; a.d = d; a.l2norm = l2norm;
@@ -1465,20 +1444,16 @@ int launch_sq8_train(const float *x, int64_t n, int d, int l2norm, float *den_sc
                 if (!den_scratch) return fail(CVTMI_EINVAL, "sq8_train: norm scratch missing");
                 CVTMI_TRY(launch_sq8_rownorm(x, n, d, den_scratch, st));
             }
-            const int64_t blocks = (n + TRAIN_ROWS - 1) / TRAIN_ROWS;
-            if (blocks > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "sq8_train: n too large");
-            hipLaunchKernelGGL(sq8_train_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, x, n, d,
-                               l2norm ? den_scratch : nullptr, kmin, kmax);
+            CVTMI_TRY(launch("sq8_train_kernel", sq8_train_kernel, blocks_for(n, TRAIN_ROWS), kBlock, 0, st, x, n, d, l2norm ? den_scratch : nullptr, kmin, kmax));
         }
     }
-    hipLaunchKernelGGL(sq8_train_finish_kernel, dim3(db), dim3(kBlock), 0, st, kmin, kmax, d, vmin, vdiff);
+    CVTMI_TRY(launch("sq8_train_finish_kernel", sq8_train_finish_kernel, db, kBlock, 0, st, kmin, kmax, d, vmin, vdiff));
     if (n > 0 && n < 0xffffffffLL) {   // the sign of a zero minimum (see sq8_zero_first_kernel); kmax is free again: first[d]
         CVTMI_HIP(hipMemsetAsync(kmax, 0xff, (size_t)d * sizeof(uint32_t), st));
-        const unsigned zb = (unsigned)std::min<int64_t>((n + kBlock - 1) / kBlock, 1024);
-        hipLaunchKernelGGL(sq8_zero_first_kernel, dim3(zb), dim3(kBlock), 0, st, x, n, d, l2norm, vmin, kmax);
-        hipLaunchKernelGGL(sq8_zero_sign_kernel, dim3(db), dim3(kBlock), 0, st, x, d, kmax, vmin);
+        const int64_t zb = std::min<int64_t>(blocks_for(n, kBlock), 1024);
+        CVTMI_TRY(launch("sq8_zero_first_kernel", sq8_zero_first_kernel, zb, kBlock, 0, st, x, n, d, l2norm, vmin, kmax));
+        CVTMI_TRY(launch("sq8_zero_sign_kernel", sq8_zero_sign_kernel, db, kBlock, 0, st, x, d, kmax, vmin));
     }
-    CVTMI_HIP(hipGetLastError());
     return CVTMI_OK;
 }
 
@@ -1486,35 +1461,19 @@ static int launch_sq8_encode_wave(const float *vmin, const float *vdiff, int d, 
                                   uint8_t *codes, hipStream_t st)
 {
     const int64_t rows_per_wg = kBlock / 64;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + rows_per_wg - 1) / rows_per_wg, 256 * tune_sq8_wave_blocks.geti());
+    const int64_t blocks = std::min<int64_t>(blocks_for(n, rows_per_wg), 256 * tune_sq8_wave_blocks.geti());
     if (sq8_filter_on()) {
-        const int fl = tune_sq8_flags.geti();
-#define CVTMI_SQ8_ENC(NF_)                                                                                                                                    \
-        do {                                                                                                                                                  \
-            if (l2norm) hipLaunchKernelGGL((sq8_encode_wave_f_kernel<NF_, true>), dim3(blocks), dim3(kBlock), 0, st, vmin, vdiff, x, n, write_back, codes, fl); \
-            else hipLaunchKernelGGL((sq8_encode_wave_f_kernel<NF_, false>), dim3(blocks), dim3(kBlock), 0, st, vmin, vdiff, x, n, 0, codes, fl);                 \
-        } while (0)
-        switch (d / 256) {
-            case 1: CVTMI_SQ8_ENC(1); break;
-            case 2: CVTMI_SQ8_ENC(2); break;
-            case 3: CVTMI_SQ8_ENC(3); break;
-            case 4: CVTMI_SQ8_ENC(4); break;
-            case 6: CVTMI_SQ8_ENC(6); break;
-            default: CVTMI_SQ8_ENC(8); break;
-        }
-#undef CVTMI_SQ8_ENC
-        CVTMI_HIP(hipGetLastError());
-        return CVTMI_OK;
+        static constexpr decltype(&sq8_encode_wave_f_kernel<1, true>) kernels[6][2] = {   // rows of 256 NF floats (NF = 1, 2, 3, 4, 6, 8) x { normalised, not }
+            { sq8_encode_wave_f_kernel<1, true>, sq8_encode_wave_f_kernel<1, false> }, { sq8_encode_wave_f_kernel<2, true>, sq8_encode_wave_f_kernel<2, false> },
+            { sq8_encode_wave_f_kernel<3, true>, sq8_encode_wave_f_kernel<3, false> }, { sq8_encode_wave_f_kernel<4, true>, sq8_encode_wave_f_kernel<4, false> },
+            { sq8_encode_wave_f_kernel<6, true>, sq8_encode_wave_f_kernel<6, false> }, { sq8_encode_wave_f_kernel<8, true>, sq8_encode_wave_f_kernel<8, false> } };
+        const int nf = d / 256, row = nf >= 1 && nf <= 4 ? nf - 1 : nf == 6 ? 4 : 5;
+        return launch("sq8_encode_wave_f_kernel", kernels[row][l2norm ? 0 : 1], blocks, kBlock, 0, st, vmin, vdiff, x, n, l2norm ? write_back : 0, codes, tune_sq8_flags.geti());
     }
-    if (d == 512) {
-        if (l2norm) hipLaunchKernelGGL((sq8_encode_wave_kernel<2, true>), dim3(blocks), dim3(kBlock), 0, st, vmin, vdiff, x, n, write_back, codes);
-        else hipLaunchKernelGGL((sq8_encode_wave_kernel<2, false>), dim3(blocks), dim3(kBlock), 0, st, vmin, vdiff, x, n, write_back, codes);
-    } else {
-        if (l2norm) hipLaunchKernelGGL((sq8_encode_wave_kernel<1, true>), dim3(blocks), dim3(kBlock), 0, st, vmin, vdiff, x, n, write_back, codes);
-        else hipLaunchKernelGGL((sq8_encode_wave_kernel<1, false>), dim3(blocks), dim3(kBlock), 0, st, vmin, vdiff, x, n, write_back, codes);
-    }
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    decltype(&sq8_encode_wave_kernel<1, true>) kern;
+    if (d == 512) kern = l2norm ? sq8_encode_wave_kernel<2, true> : sq8_encode_wave_kernel<2, false>;
+    else kern = l2norm ? sq8_encode_wave_kernel<1, true> : sq8_encode_wave_kernel<1, false>;
+    return launch("sq8_encode_wave_kernel", kern, blocks, kBlock, 0, st, vmin, vdiff, x, n, write_back, codes);
 }
 
 }  // namespace cvtmi

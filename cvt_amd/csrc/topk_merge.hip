@@ -14,6 +14,7 @@
 // keyed as 0x7ffffffe (KEY_MAX marks "not a candidate").  Ties under that order, NaNs included, go by position.
 #include "block_topk.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -85,14 +86,8 @@ int launch_topk_merge_gathered(const float *in_d, const int64_t *in_id, int64_t 
     if (nq <= 0) return CVTMI_OK;
     if (k < 1 || k > kBigK) return fail(CVTMI_EUNSUPPORTED, "topk: k=%d outside 1..%d", k, kBigK);
     if (L < 1 || (int64_t)L * k > 0x7fffffff || nq > 0x7fffffff) return fail(CVTMI_EINVAL, "topk_merge: bad list count %d", L);
-    if (k > MERGE_TRIG / 2)
-        hipLaunchKernelGGL((topk_merge_kernel<true, kBigCap, kBigTrig>), dim3((unsigned)nq), dim3(kBlock), 0, st, in_d, in_id, L * k, k, out_d, out_id,
-                           stride_d, stride_id, (const uint32_t *)nullptr);
-    else
-        hipLaunchKernelGGL(topk_merge_kernel<true>, dim3((unsigned)nq), dim3(kBlock), 0, st, in_d, in_id, L * k, k, out_d, out_id, stride_d,
-                           stride_id, (const uint32_t *)nullptr);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("topk_merge_kernel", k > MERGE_TRIG / 2 ? topk_merge_kernel<true, kBigCap, kBigTrig> : topk_merge_kernel<true>, nq, kBlock, 0, st, in_d, in_id, L * k, k, out_d,
+                  out_id, stride_d, stride_id, nullptr);
 }
 
 int launch_topk_merge(const float *in_d, const int64_t *in_id, int64_t nq, int L, int k, float *out_d, int64_t *out_id,
@@ -109,15 +104,8 @@ int launch_topk_select(const float *in_d, const int64_t *in_id, int64_t nq, int6
     if (nq <= 0) return CVTMI_OK;
     if (k < 1 || k > kBigK) return fail(CVTMI_EUNSUPPORTED, "topk: k=%d outside 1..%d", k, kBigK);
     if (n_cand < 0 || n_cand > 0x7fffffff) return fail(CVTMI_EINVAL, "topk: bad candidate count");
-    if (nq > 0x7fffffff) return fail(CVTMI_EUNSUPPORTED, "topk: nq too large");
-    if (k > MERGE_TRIG / 2)
-        hipLaunchKernelGGL((topk_merge_kernel<false, kBigCap, kBigTrig>), dim3((unsigned)nq), dim3(kBlock), 0, st, in_d, in_id, (int)n_cand, k, out_d,
-                           out_id, (int64_t)0, (int64_t)0, only_if);
-    else
-        hipLaunchKernelGGL(topk_merge_kernel<false>, dim3((unsigned)nq), dim3(kBlock), 0, st, in_d, in_id, (int)n_cand, k, out_d, out_id,
-                           (int64_t)0, (int64_t)0, only_if);
-    CVTMI_HIP(hipGetLastError());
-    return CVTMI_OK;
+    return launch("topk_merge_kernel", k > MERGE_TRIG / 2 ? topk_merge_kernel<false, kBigCap, kBigTrig> : topk_merge_kernel<false>, nq, kBlock, 0, st, in_d, in_id, (int)n_cand, k,
+                  out_d, out_id, 0, 0, only_if);
 }
 
 }  // namespace cvtmi

@@ -447,6 +447,11 @@ int cvtmi_opq_describe_dispatch(int D, int M, int K, int64_t n_rows, int64_t nq,
  * to 128 queries; all zero: the exact / row-tile kernels. */
 int cvtmi_flat_describe_dispatch(int metric, int D, int64_t n_rows, int64_t nq, int k, int out[4]);
 
+/* The status every kernel launch of the library gives a grid of x * y * z workgroups before it launches (pure host logic, nothing is
+ * launched): CVTMI_OK for 1 <= x <= 0x7fffffff and 1 <= y, z <= 65535, else CVTMI_EUNSUPPORTED with the offending count in
+ * cvtmi_last_error().  What tests/test_launch.py pins the rule with. */
+int cvtmi_describe_launch_grid(int64_t x, int64_t y, int64_t z);
+
 /* Page-locked host memory.  The host-pointer entries move their arrays through pinned staging areas (one extra host copy each way);
  * arrays that already ARE page-locked -- from here, or the caller's own hipHostMalloc / hipHostRegister -- need none: page-locked
  * queries go to the copy engine as they are, and page-locked RESULT arrays of cvtmi_opq_search are written by the kernels themselves
