@@ -666,8 +666,53 @@ class FlatIndex:
         return (removed.value, remap) if want_remap else removed.value
 
     def set_param(self, name, value):
-        """cvtmi_flat_set_param: "remove_chunk" = rows the move of a removal works on at a time (0 = default)."""
+        """cvtmi_flat_set_param: "remove_chunk" = rows the move of a removal works on at a time (0 = default); "range_part_rows" = rows
+        per part of a range search (0 = default); "range_spill" = hits a (query, part) may park before the sizes are known (-1 = default)."""
         _check(lib().cvtmi_flat_set_param(self.h, name.encode(), C.c_int64(value)))
+
+    def range_search(self, q, radius, out=None):
+        """Range search (cvtmi_flat_range_search): every row whose distance to a query is < radius, in ascending row order.  Returns
+        (lims [nq + 1] int64, distances (float32; int32 for the uint8 metric), labels): the hits of query f are [lims[f], lims[f + 1]).
+        Without `out` a count-only call sizes the arrays and a second call fills them (torch input: the first one is waited for).
+        With out = (lims, dist, labels) ONE call runs with the capacity of `dist`: numpy raises CvtmiError (code ESPACE) when the hits
+        do not fit; torch never waits -- read lims[-1] after synchronising, the arrays are untouched when it is larger than their
+        length."""
+        nq = q.shape[0]
+        dev = _is_torch(q)
+        if not dev:
+            q = _np(q, self._dt())
+        dist_dt = "int32" if self.metric == 2 else "float32"
+
+        def call(cap, lims, d, i):
+            args = (self.h, _ptr(q), C.c_int64(nq), C.c_double(float(radius)), C.c_int64(cap), _ptr(lims), _ptr(d), _ptr(i))
+            if dev:
+                return lib().cvtmi_flat_range_search_dev(*args, _stream())
+            return lib().cvtmi_flat_range_search(*args)
+
+        def empty(n, dt):
+            if dev:
+                import torch
+                return torch.empty(n, dtype=getattr(torch, dt), device=q.device)
+            return np.empty(n, dtype=dt)
+
+        if out is not None:
+            lims, d, i = out
+            assert lims.shape[0] == nq + 1 and i.shape[0] == d.shape[0]
+            _check(call(d.shape[0], lims, d, i))
+            return out
+        lims = empty(nq + 1, "int64")
+        _check(call(0, lims, None, None))
+        total = int(lims[nq])
+        d, i = empty(total, dist_dt), empty(total, "int64")
+        if total:
+            _check(call(total, lims, d, i))
+        return lims, d, i
+
+    def last_range_plan(self):
+        """plan of the last range_search on this handle (cvtmi_flat_last_range_plan)"""
+        o = (C.c_int64 * 6)()
+        _check(lib().cvtmi_flat_last_range_plan(self.h, o))
+        return dict(qt=o[0], parts=o[1], rows_per_part=o[2], spill=o[3], spill_bytes=o[4], form=o[5])
 
     def search_sharded(self, comm, q, k):
         """Row-sharded exhaustive search: this handle holds the rank's row block (set_id_base = its first row)."""

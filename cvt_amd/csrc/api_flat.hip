@@ -1,5 +1,7 @@
 // api_flat.hip -- the flat (exhaustive fp32 / uint8) handle of the C ABI (include/cvtmi.h): add / reset, the exact search over a row
 // range, the pipeline drivers, the dispatch between them (flat_route, flat_prepare), the search entries and their sharded forms.
+#include <float.h>
+#include <math.h>
 #include <string.h>
 
 #include <algorithm>
@@ -257,6 +259,18 @@ int cvtmi_flat_set_param(cvtmi_flat_t h, const char *name, int64_t value)
         if (value < 0 || value > ((int64_t)1 << 32)) return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: remove_chunk must be 0 .. 2^32 rows");
         std::unique_lock<std::shared_timed_mutex> lk(h->rw);
         h->p_rm_chunk = value ? flat_rm_chunk_rows(value, h->row_bytes) : 0;   // whole tiles
+        return CVTMI_OK;
+    }
+    if (!strcmp(name, "range_part_rows")) {
+        if (value < 0 || value > ((int64_t)1 << 32)) return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: range_part_rows must be 0 .. 2^32 rows");
+        std::unique_lock<std::shared_timed_mutex> lk(h->rw);
+        h->p_range_part_rows = blocks_for(value, kBlock) * kBlock;   // whole tiles
+        return CVTMI_OK;
+    }
+    if (!strcmp(name, "range_spill")) {
+        if (value < -1) return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: range_spill must be -1 (the default) or a record count");
+        std::unique_lock<std::shared_timed_mutex> lk(h->rw);
+        h->p_range_spill = value;
         return CVTMI_OK;
     }
     return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: unknown parameter '%s'", name);
@@ -734,6 +748,140 @@ int cvtmi_flat_search_dev(cvtmi_flat_t h, const void *q, int64_t nq, int k, void
     FlatLease lease;
     CVTMI_TRY(lease.open(h, st, false));
     return flat_search_leased(h, *lease.s, q, nq, k, dist, labels, st, tun);
+}
+
+// ---- range search: every row under a distance radius (flat_range.hip) ----
+// A search like the others: `rw` shared, a leased scratch set, nothing of the handle changes.  A call is a count (scan, offsets: lims
+// is complete on the device) and, where the caller gave room, a fill (fill + rescan, both predicated on the device on
+// lims[nq] <= cap).
+struct FlatRangeCall {
+    FlatRangePlan plan;
+    FlatRangeBufs bufs;
+    FlatRangeRows rows;
+    uint32_t thr = 0;
+    int64_t *lims_scratch = nullptr;   // nq + 1 words behind the carved areas (the host entry's device lims)
+};
+
+// the radius as the kernels compare against it: fp32 the smallest float t >= radius (d < t in fp32 is d < radius in real numbers),
+// uint8 T = ceil(radius) in [0, 2^31] (2^31: every row -- no distance reaches it)
+static uint32_t flat_range_threshold(int metric, double radius)
+{
+    if (metric == CVTMI_METRIC_L2U8) {
+        if (!(radius > 0.0)) return 0u;
+        if (radius >= 2147483648.0) return 0x80000000u;
+        return (uint32_t)std::min(ceil(radius), 2147483647.0);
+    }
+    float t;
+    if (radius > (double)FLT_MAX) t = INFINITY;
+    else if (radius < -(double)FLT_MAX) t = radius == -(double)INFINITY ? -INFINITY : -FLT_MAX;
+    else {
+        t = (float)radius;
+        if ((double)t < radius) t = nextafterf(t, INFINITY);
+    }
+    return __builtin_bit_cast(uint32_t, t);
+}
+
+// arguments first, before anything touches the device
+static int flat_range_check(cvtmi_flat_t h, const void *q, int64_t nq, double radius, int64_t cap, const int64_t *lims, const void *dist,
+                            const int64_t *labels)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_flat_range_search: null handle");
+    if (!q || !lims || nq < 0 || cap < 0) return fail(CVTMI_EINVAL, "cvtmi_flat_range_search: bad arguments");
+    if (cap > 0 && (!dist || !labels)) return fail(CVTMI_EINVAL, "cvtmi_flat_range_search: cap=%lld without result arrays", (long long)cap);
+    if (radius != radius) return fail(CVTMI_EINVAL, "cvtmi_flat_range_search: the radius is NaN");
+    if (nq > INT32_MAX) return fail(CVTMI_EUNSUPPORTED, "cvtmi_flat_range_search: nq=%lld above 2^31-1", (long long)nq);
+    return CVTMI_OK;
+}
+
+// plan and scratch (all of it, before the first kernel), then the count.  The caller holds `rw` shared and the lease; h->n > 0, nq > 0
+static int flat_range_count_leased(cvtmi_flat_t h, FlatScratch &S, const void *q, int64_t nq, double radius, bool spill, int64_t *lims,
+                                   FlatRangeCall &c, hipStream_t st)
+{
+    const bool has_norms = h->metric == CVTMI_METRIC_L2U8 && h->D % 32 == 0 && h->D <= 512 && h->norms.p;   // (as flat_add_common keeps them)
+    c.plan = plan_flat_range(h->metric, h->D, has_norms, h->n, nq, h->p_range_part_rows, spill ? h->p_range_spill : 0);
+    c.thr = flat_range_threshold(h->metric, radius);
+    c.rows.metric = h->metric; c.rows.D = h->D; c.rows.data = h->data.p; c.rows.norms = has_norms ? h->norms.as<int32_t>() : nullptr;
+    c.rows.n = h->n; c.rows.labels = h->identity ? nullptr : h->labels.as<int64_t>(); c.rows.id_base = h->id_base;
+    const size_t carved = flat_range_carve(nullptr, c.plan, nq, nullptr);
+    CVTMI_TRY(S.s_range.reserve(carved + ((size_t)nq + 1) * sizeof(int64_t)));
+    flat_range_carve(S.s_range.p, c.plan, nq, &c.bufs);
+    c.lims_scratch = reinterpret_cast<int64_t *>(S.s_range.as<char>() + carved);
+    {
+        std::lock_guard<std::mutex> g(h->pool.mu);
+        const int64_t v[6] = { c.plan.qt, c.plan.parts, c.plan.rows_per_part, c.plan.spill, (int64_t)c.plan.spill_bytes, c.plan.form };
+        for (int i = 0; i < 6; ++i) h->range_last[i] = v[i];
+    }
+    return launch_flat_range_count(c.rows, q, nq, c.thr, c.plan, c.bufs, lims ? lims : c.lims_scratch, st);
+}
+
+int cvtmi_flat_range_search_dev(cvtmi_flat_t h, const void *q, int64_t nq, double radius, int64_t cap, int64_t *lims, void *dist, int64_t *labels,
+                                void *stream)
+{
+    CVTMI_TRY(flat_range_check(h, q, nq, radius, cap, lims, dist, labels));
+    CVTMI_TRY(use_device(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (nq == 0) {
+        CVTMI_HIP(hipMemsetAsync(lims, 0, sizeof(int64_t), st));
+        return CVTMI_OK;
+    }
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    FlatLease lease;
+    CVTMI_TRY(lease.open(h, st, false));
+    if (h->n == 0) {   // an empty index: no hits
+        CVTMI_HIP(hipMemsetAsync(lims, 0, ((size_t)nq + 1) * sizeof(int64_t), st));
+        return CVTMI_OK;
+    }
+    FlatRangeCall c;
+    CVTMI_TRY(flat_range_count_leased(h, *lease.s, q, nq, radius, cap > 0, lims, c, st));
+    if (cap == 0) return CVTMI_OK;   // a count-only call
+    return launch_flat_range_fill(c.rows, q, nq, c.thr, c.plan, c.bufs, lims, cap, dist, labels, st);
+}
+
+// host pointers: the queries go up and lims comes back through the leased set's staging buffers -- the one wait the call needs to
+// know whether the result fits; then the two arrays, sized by lims[nq]
+int cvtmi_flat_range_search(cvtmi_flat_t h, const void *q, int64_t nq, double radius, int64_t cap, int64_t *lims, void *dist, int64_t *labels)
+{
+    CVTMI_TRY(flat_range_check(h, q, nq, radius, cap, lims, dist, labels));
+    CVTMI_TRY(use_device(h->device));
+    lims[0] = 0;
+    if (nq == 0) return CVTMI_OK;
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    if (h->n == 0) {   // an empty index: no hits
+        memset(lims, 0, ((size_t)nq + 1) * sizeof(int64_t));
+        return CVTMI_OK;
+    }
+    FlatLease lease;
+    CVTMI_TRY(lease.open(h, nullptr, true));
+    FlatScratch &S = *lease.s;
+    hipStream_t st = lease.st;
+    const size_t qb = (size_t)nq * h->row_bytes;
+    CVTMI_TRY(S.io_q.reserve(qb));
+    CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
+    FlatRangeCall c;
+    CVTMI_TRY(flat_range_count_leased(h, S, S.io_q.p, nq, radius, cap > 0, nullptr, c, st));
+    CVTMI_HIP(hipMemcpyAsync(lims, c.lims_scratch, ((size_t)nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    const int64_t total = lims[nq];
+    if (cap == 0 && !dist && !labels) return CVTMI_OK;   // a count-only call: lims is the answer
+    if (total > cap)
+        return fail(CVTMI_ESPACE, "cvtmi_flat_range_search: %lld hits, room for %lld (lims holds the sizes)", (long long)total, (long long)cap);
+    if (total == 0) return CVTMI_OK;
+    const size_t db = (size_t)total * 4, ib = (size_t)total * sizeof(int64_t);
+    CVTMI_TRY(S.io_d.reserve(db));
+    CVTMI_TRY(S.io_i.reserve(ib));
+    CVTMI_TRY(launch_flat_range_fill(c.rows, S.io_q.p, nq, c.thr, c.plan, c.bufs, c.lims_scratch, total, S.io_d.p, S.io_i.as<int64_t>(), st));
+    CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(hipMemcpyAsync(labels, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    return CVTMI_OK;
+}
+
+int cvtmi_flat_last_range_plan(cvtmi_flat_t h, int64_t out[6])
+{
+    if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_flat_last_range_plan: null");
+    std::lock_guard<std::mutex> g(h->pool.mu);
+    for (int i = 0; i < 6; ++i) out[i] = h->range_last[i];
+    return CVTMI_OK;
 }
 
 int cvtmi_flat_set_id_base(cvtmi_flat_t h, int64_t base)

@@ -194,12 +194,13 @@ struct FlatScratch : ScratchBase {
     DevBuf f_stats, f_thr, f_marg, f_cnt, f_cand, f_sd, f_si, f_sd2, f_si2, f_seld, f_seli;   // matrix-core filter pipelines
     DevBuf fs_redo, fs_scratch;                                                                // fp32 stream
     DevBuf redo_count;                                                                         // "flat_count_redo": the count of the flags
+    DevBuf s_range;                 // range search (flat_range.hip): part counts and offsets, spill area; host entry: lims behind them
     DevBuf io_q, io_d, io_i;                                                                   // staging of the host-pointer entry
     PinBuf io_pin;                  // small calls: [queries | distances | labels] in page-locked memory the kernels write into
     void release_all()
     {
         for (DevBuf *b : { &s_part_d, &s_part_id, &s_gthr, &s_stage, &f_stats, &f_thr, &f_marg, &f_cnt, &f_cand, &f_sd, &f_si, &f_sd2,
-                           &f_si2, &f_seld, &f_seli, &fs_redo, &fs_scratch, &redo_count, &io_q, &io_d, &io_i })
+                           &f_si2, &f_seld, &f_seli, &fs_redo, &fs_scratch, &redo_count, &s_range, &io_q, &io_d, &io_i })
             b->release();
         io_pin.release();
         release_lease_state();
@@ -217,6 +218,9 @@ struct cvtmi_flat_s {
     DevBuf add_stage;            // staging of host rows on their way into the blocked layout
     DevBuf rm_scratch;           // removal (flat_remove.hip): bitmap, tile offsets, the table of removal labels, the chunk-sized row scratch
     int64_t p_rm_chunk = 0;      // "remove_chunk": rows the move works on at a time (0 = the default)
+    int64_t p_range_part_rows = 0;   // "range_part_rows": rows per part of a range search (0 = the default)
+    int64_t p_range_spill = -1;      // "range_spill": spill records per (query, part) (-1 = the default)
+    int64_t range_last[6] = {};      // plan of the last range search (cvtmi_flat_last_range_plan), written under pool.mu
     int64_t n = 0;
     int64_t id_base = 0;   // row r reports label id_base + r while labels are implicit (row shards, cvtmi_flat_set_id_base)
     bool identity = true;  // label == row

@@ -61,6 +61,58 @@ __device__ __forceinline__ void dist_f32_row(const float *__restrict__ row, cons
     }
 }
 
+// The same distances for R rows of the 64-row blocked layout (flat_block_kernel: float4 c of a row lies 64 float4 behind its
+// float4 c - 1) with the queries behind uniform constant-address-space pointers, i.e. in SGPRs, as flat_f32_sq_kernel reads them.
+// Per lane and query the operations and their order are dist_f32_row's, hence the same bits.  LANES = 4 or 8, D % LANES == 0.
+typedef const __attribute__((address_space(4))) float dist_cfloat;
+template <bool IP, int LANES, int QT, int R>
+__device__ __forceinline__ void dist_f32_blocked(const float4 *const (&rowp)[R], dist_cfloat *const (&qp)[QT], int D, float (&out)[R][QT])
+{
+    static_assert(LANES == 4 || LANES == 8, "the blocked layout holds whole float4");
+    float acc[R][QT][LANES];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int q = 0; q < QT; ++q)
+#pragma unroll
+            for (int l = 0; l < LANES; ++l) acc[r][q][l] = 0.0f;
+#pragma unroll 16 / LANES
+    for (int i = 0; i < D; i += LANES) {
+        float xv[R][LANES];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int l4 = 0; l4 < LANES / 4; ++l4) {
+                const float4 v = rowp[r][(int64_t)((i >> 2) + l4) * 64];
+                xv[r][4 * l4 + 0] = v.x; xv[r][4 * l4 + 1] = v.y; xv[r][4 * l4 + 2] = v.z; xv[r][4 * l4 + 3] = v.w;
+            }
+#pragma unroll
+        for (int q = 0; q < QT; ++q) {
+#pragma unroll
+            for (int l = 0; l < LANES; ++l) {
+                const float qv = qp[q][i + l];  // uniform address: scalar load
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if constexpr (IP) {
+                        acc[r][q][l] = __fadd_rn(acc[r][q][l], __fmul_rn(qv, xv[r][l]));
+                    } else {
+                        const float t = __fsub_rn(qv, xv[r][l]);
+                        acc[r][q][l] = __fadd_rn(acc[r][q][l], __fmul_rn(t, t));
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int q = 0; q < QT; ++q) {
+            float s = acc[r][q][0];
+#pragma unroll
+            for (int l = 1; l < LANES; ++l) s = __fadd_rn(s, acc[r][q][l]);
+            out[r][q] = IP ? __fsub_rn(1.0f, s) : s;
+        }
+}
 
 }  // namespace cvtmi
 #endif

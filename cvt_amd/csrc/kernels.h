@@ -245,6 +245,41 @@ int launch_ivf_range_fill(const OpqModelDev &m, const float *q_rot, int64_t nq, 
                           const uint32_t *entry, const int32_t *videos, float radius, int64_t id_base, const IvfRangePlan &p,
                           const IvfRangeBufs &b, const int64_t *lims, int64_t cap, float *dist, int64_t *ids, int32_t *video, hipStream_t st);
 
+// ---- flat_range.hip ----  every row of a flat index with distance < radius (cvtmi_flat_range_search)
+constexpr int64_t kFlatRangeSpill = 512;                       // spill records per (query, part) unless "range_spill" says otherwise
+constexpr size_t kFlatRangeSpillBytes = (size_t)256 << 20;     // the spill area never grows past this: the records shrink to fit
+struct FlatRangePlan {
+    int qt = 1, parts = 1;       // queries per workgroup, parts of the rows per query group
+    int form = 0;                // 0 fp32 row-major (queries in LDS), 1 fp32 blocked (queries in SGPRs), 2 uint8 bytes, 3 uint8 16-byte pieces, 4 ... with the handle's norms
+    int64_t rows_per_part = 256; // whole 256-row tiles
+    int64_t spill = 0;           // records a (query, part) may leave in its segment of the spill area
+    size_t spill_bytes = 0;
+};
+// pure host logic; part_rows = 0: the default parts; spill < 0: the default records, 0 = a count-only call / every part walks twice
+FlatRangePlan plan_flat_range(int metric, int D, bool has_norms, int64_t n, int64_t nq, int64_t part_rows, int64_t spill);
+struct FlatRangeBufs {
+    uint32_t *part_cnt = nullptr, *part_off = nullptr;   // [nq][parts] hits of a part, and where they start inside the query's
+    unsigned long long *spill = nullptr;                  // [nq][parts][plan.spill] (distance bits << 32 | row)
+};
+// bytes of scratch the plan needs; with base != null the three areas are laid out in it
+size_t flat_range_carve(void *base, const FlatRangePlan &p, int64_t nq, FlatRangeBufs *b);
+// the rows of the handle as the kernels read them (labels null: id_base + row)
+struct FlatRangeRows {
+    int metric = 0, D = 0;
+    const void *data = nullptr;
+    const int32_t *norms = nullptr;
+    int64_t n = 0;
+    const int64_t *labels = nullptr;
+    int64_t id_base = 0;
+};
+// thr: fp32 metrics the bits of the smallest float >= radius, uint8 the integer bound (a row hits when distance < thr).
+// scan, offsets: lims[nq + 1] (device) is complete when these have run
+int launch_flat_range_count(const FlatRangeRows &x, const void *q, int64_t nq, uint32_t thr, const FlatRangePlan &p, const FlatRangeBufs &b,
+                            int64_t *lims, hipStream_t st);
+// fill and rescan behind a count with the same arguments; both do nothing unless lims[nq] <= cap (checked on the device)
+int launch_flat_range_fill(const FlatRangeRows &x, const void *q, int64_t nq, uint32_t thr, const FlatRangePlan &p, const FlatRangeBufs &b,
+                           const int64_t *lims, int64_t cap, void *dist, int64_t *labels, hipStream_t st);
+
 // ---- flat.hip ----
 int flat_plan_splits(int64_t n, int64_t nq, int qtile);
 int flat_qtile(int64_t nq);

@@ -106,6 +106,28 @@ public:
             throw std::runtime_error(std::string("cvtmi_flat_search: ") + cvtmi_last_error());
     }
 
+    // every row with distance < radius (not in the reference: cvtmi_flat_range_search), as (distance, label) in the order of the
+    // device rows, which sync_device keeps in ascending label order
+    std::vector<std::pair<dist_t, labeltype> > searchRange(const void *query, dist_t radius)
+    {
+        sync_device();
+        static_assert(sizeof(dist_t) == 4, "distances are 32-bit (float or int)");
+        std::vector<std::pair<dist_t, labeltype> > hits;
+        int64_t lims[2] = { 0, 0 };
+        std::vector<dist_t> d(16);
+        std::vector<int64_t> l(16);
+        for (;;) {   // a second round only when the hits outgrow the arrays
+            const int rc = cvtmi_flat_range_search(h_, query, 1, (double)radius, (int64_t)d.size(), lims, d.data(), l.data());
+            if (rc == CVTMI_OK) break;
+            if (rc != CVTMI_ESPACE) throw std::runtime_error(std::string("cvtmi_flat_range_search: ") + cvtmi_last_error());
+            d.resize((size_t)lims[1]);
+            l.resize((size_t)lims[1]);
+        }
+        hits.reserve((size_t)lims[1]);
+        for (int64_t i = 0; i < lims[1]; ++i) hits.push_back(std::pair<dist_t, labeltype>(d[i], (labeltype)l[i]));
+        return hits;
+    }
+
     // index.bin: size_t max, size_t per_elem, size_t count, raw rows (brutoforce.hpp:95-106)
     void saveIndex(const std::string &location)
     {

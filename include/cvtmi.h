@@ -598,8 +598,14 @@ int cvtmi_flat_reset(cvtmi_flat_t h);
 int cvtmi_flat_remove_labels(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, int64_t *removed, int64_t *remap);
 int cvtmi_flat_remove_labels_dev(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, int64_t *removed, int64_t *remap, void *stream);
 /* Per-handle parameters (no effect on results).
- *   "remove_chunk"  rows the move of cvtmi_flat_remove_labels works on at a time, rounded up to whole 256-row tiles;
- *                   0 (default) = the rows of 64 MB. */
+ *   "remove_chunk"     rows the move of cvtmi_flat_remove_labels works on at a time, rounded up to whole 256-row tiles;
+ *                      0 (default) = the rows of 64 MB.
+ *   "range_part_rows"  rows a workgroup of cvtmi_flat_range_search walks, rounded up to whole 256-row tiles; 0 (default) = the
+ *                      parts that fill the device once.
+ *   "range_spill"      hits C a (query, part) of cvtmi_flat_range_search may park in the leased scratch set while the sizes are not
+ *                      known yet; a part that meets more walks its rows a second time once they are.  0 = every part with a hit
+ *                      does; a huge value = none: C is cut down to the rows of a part and so that the area, nq x parts x C x 8
+ *                      bytes, stays within 256 MB.  -1 (default) = 512. */
 int cvtmi_flat_set_param(cvtmi_flat_t h, const char *name, int64_t value);
 /* searchKnn (brutoforce.hpp:73-93) for nq queries: k smallest (distance, label), ascending.
  * dist is float[nq][k] for IP / L2F and int32_t[nq][k] for L2U8.  1 <= k <= CVTMI_K_MAX.  An index with fewer than k rows pads:
@@ -608,6 +614,47 @@ int cvtmi_flat_set_param(cvtmi_flat_t h, const char *name, int64_t value);
 int cvtmi_flat_search(cvtmi_flat_t h, const void *q, int64_t nq, int k, void *dist, int64_t *labels);
 int cvtmi_flat_search_dev(cvtmi_flat_t h, const void *q, int64_t nq, int k, void *dist, int64_t *labels,
                           void *stream);
+/* Range search: for every query, EVERY row of the index whose distance is under `radius` -- the test the reference's retrieval loop
+ * makes behind a top-5 (hnsw_sifts_retrieval/makeSearch.cpp:52-61), without the 5.  q holds nq rows of the index's own type.
+ *   Distance the one cvtmi_flat_search reports for that (query, row), bit for bit: IP is 1 - sum in the 4-lane order; L2F sums in 8
+ *            lanes for D % 16 == 0, in 4 lanes for D % 4 == 0 and in the scalar loop otherwise; L2U8 is the exact int32 sum over
+ *            D / 4 * 4 bytes (the D % 4 tail is dropped, as L2SqrI does).  dist holds 4-byte fields: float for IP and L2F, int32 for
+ *            L2U8.
+ *   Hit      distance < radius as real numbers, strict.  radius is a double, so that an integer radius above 2^24 is exact for L2U8.
+ *            fp32 metrics: the host turns radius into the smallest float t >= radius and the kernels test d < t in fp32 -- the same
+ *            predicate.  L2U8: the host turns radius into T = ceil(radius) clamped to [0, 2^31-1] (2^31 or more: every row) and the
+ *            kernels test d < T in integers.  NaN distances never hit; a +inf distance never hits, not even for radius = +inf.
+ *            radius = -inf or radius <= 0 yields no hit for the L2 metrics; for IP it yields whatever is below it (IP distances
+ *            can be negative, -inf included).  A NaN radius fails with CVTMI_EINVAL.
+ *   Order    the hits of a query come in ascending row order -- insertion order, as left by removals -- whatever the grid, the
+ *            stream or the run: no atomic decides where a hit lands.
+ *   Labels   each hit carries the label cvtmi_flat_search would report: id_base + row while labels are implicit, otherwise the
+ *            stored label.  Duplicate explicit labels simply repeat.
+ *   Outputs  lims[nq + 1] (int64): lims[0] = 0, lims[f + 1] - lims[f] = hits of query f.  For hit i of the batch dist[i] = its
+ *            distance and labels[i] = its label.
+ *   Capacity cap = hits the caller's arrays hold.  lims is always written in full and exactly; dist / labels are written only if
+ *            lims[nq] <= cap and are left untouched otherwise.  cap == 0 with NULL dist / labels is the count-only call.
+ * Host entry: CVTMI_OK after writing the results (a count-only call: after writing lims), or CVTMI_ESPACE with lims valid and the
+ * arrays untouched.  Device entry: enqueues on `stream` and never waits for the device; the fill is predicated ON the device on
+ * lims[nq] <= cap, the call returns CVTMI_OK and the caller reads lims[nq] after synchronising.
+ * Checked before any device work: NULL h / q / lims, nq < 0, cap < 0, NULL dist or labels with cap > 0, a NaN radius ->
+ * CVTMI_EINVAL; nq > INT32_MAX -> CVTMI_EUNSUPPORTED.  nq == 0 writes lims[0] = 0 and nothing else; an empty index writes all-zero
+ * lims.
+ * Concurrency: a range search is a search.  It runs side by side with the other searches of the handle, each on a scratch set of its
+ * own, and waits behind cvtmi_flat_add / _remove_labels / _reset like them.
+ * Shards: there is no sharded form.  Each rank answers for its own rows, and cvtmi_flat_set_id_base makes the labels global; the
+ * caller concatenates.
+ * The rows are read once as the handle holds them (no second copy): one workgroup per (group of queries, part of the rows) counts
+ * the hits and parks up to C per (query, part) ("range_spill"), two scans turn the counts into lims, and a fill places the parked
+ * hits; only parts with more than C hits are walked a second time ("range_part_rows", "range_spill": cvtmi_flat_set_param). */
+int cvtmi_flat_range_search(cvtmi_flat_t h, const void *q, int64_t nq, double radius, int64_t cap,
+                            int64_t *lims, void *dist, int64_t *labels);
+int cvtmi_flat_range_search_dev(cvtmi_flat_t h, const void *q, int64_t nq, double radius, int64_t cap,
+                                int64_t *lims, void *dist, int64_t *labels, void *stream);
+/* The plan of the handle's last range search: out = { queries per workgroup QT, parts per query group, rows per part, spill records
+ * per (query, part) C, spill bytes, kernel form }.  Forms: 0 fp32 row-major rows, queries in LDS; 1 fp32 blocked rows, queries in
+ * SGPRs; 2 uint8 single bytes; 3 uint8 16-byte pieces; 4 uint8 16-byte pieces with the handle's norms.  A count-only call plans C = 0. */
+int cvtmi_flat_last_range_plan(cvtmi_flat_t h, int64_t out[6]);
 /* Measurement hook: how the last search was answered -- *filtered = 0 the exact kernels; 1 the sample + matrix-core filter
  * pipeline (fp32 metrics, 32 <= D <= 128, D % 16 == 0, >= 131072 rows: exact search of a leading sample, bf16 matrix-core
  * products decide which other rows need an exact distance); 2 the fp32 stream (D in {32, 64, 96, 128, 192, 256}, >= 32768 rows:
