@@ -310,6 +310,24 @@ class OpqIndex:
                                           _ptr(d), _ptr(i)))
         return d, i
 
+    def search_refine(self, flat, q, k, R, nprobe=0, rotate=True):
+        """ADC candidates, exact finish (cvtmi_opq_search_refine): the R best entries of search_ivf(nprobe) -- nprobe = 0: of search,
+        which needs coarseK == 1 -- reranked against the FlatIndex `flat` (the same rows, fp32) with the raw queries:
+        (exact distances [nq][k] float32, the flat index's labels [nq][k] int64).  The candidate lists never leave the device."""
+        nq = q.shape[0]
+        if _is_torch(q):
+            import torch
+            d = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+            i = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+            _check(lib().cvtmi_opq_search_refine_dev(self.h, flat.h, _ptr(q), C.c_int64(nq), C.c_int(1 if rotate else 0), C.c_int(nprobe),
+                                                     C.c_int(k), C.c_int(R), _ptr(d), _ptr(i), _stream()))
+            return d, i
+        q = _np(q, np.float32)
+        d = np.empty((nq, k), dtype=np.float32); i = np.empty((nq, k), dtype=np.int64)
+        _check(lib().cvtmi_opq_search_refine(self.h, flat.h, _ptr(q), C.c_int64(nq), C.c_int(1 if rotate else 0), C.c_int(nprobe), C.c_int(k),
+                                             C.c_int(R), _ptr(d), _ptr(i)))
+        return d, i
+
     def last_ivf_plan(self):
         """grid of the last search_ivf on this handle (cvtmi_opq_last_ivf_plan)"""
         o = (C.c_int64 * 8)()
@@ -713,6 +731,35 @@ class FlatIndex:
         o = (C.c_int64 * 6)()
         _check(lib().cvtmi_flat_last_range_plan(self.h, o))
         return dict(qt=o[0], parts=o[1], rows_per_part=o[2], spill=o[3], spill_bytes=o[4], form=o[5])
+
+    def rerank(self, q, cand, k, cand_base=0):
+        """Exact top k among candidate rows (cvtmi_flat_rerank): cand is int64 [nq][R], entry j of query f names row
+        cand[f][j] - cand_base; anything outside the index (the -1 padding of the searches, another shard's ids) is skipped and a row
+        named twice counts once.  Returns (distances [nq][k] float32 / int32 for the uint8 metric, labels [nq][k] int64) in ascending
+        (distance, row) order, padded like search.  numpy in, numpy out; torch device tensors run on torch's current stream."""
+        nq, R = cand.shape
+        assert q.shape[0] == nq
+        if _is_torch(q):
+            import torch
+            assert _is_torch(cand) and cand.dtype == torch.int64
+            d = torch.empty((nq, k), dtype=torch.int32 if self.metric == 2 else torch.float32, device=q.device)
+            i = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+            _check(lib().cvtmi_flat_rerank_dev(self.h, _ptr(q), C.c_int64(nq), _ptr(cand), C.c_int(R), C.c_int64(cand_base), C.c_int(k),
+                                               _ptr(d), _ptr(i), _stream()))
+            return d, i
+        q = _np(q, self._dt())
+        cand = _np(cand, np.int64)
+        d = np.empty((nq, k), dtype=np.int32 if self.metric == 2 else np.float32)
+        i = np.empty((nq, k), dtype=np.int64)
+        _check(lib().cvtmi_flat_rerank(self.h, _ptr(q), C.c_int64(nq), _ptr(cand), C.c_int(R), C.c_int64(cand_base), C.c_int(k), _ptr(d), _ptr(i)))
+        return d, i
+
+    def last_rerank(self):
+        """(row source, lanes per distance, workgroups, LDS bytes per workgroup) of the last rerank on this handle
+        (cvtmi_flat_last_rerank); row source 0 = row-major primary rows, 1 = blocked rows, 2 = the row-major copy."""
+        o = (C.c_int64 * 4)()
+        _check(lib().cvtmi_flat_last_rerank(self.h, o))
+        return o[0], o[1], o[2], o[3]
 
     def search_sharded(self, comm, q, k):
         """Row-sharded exhaustive search: this handle holds the rank's row block (set_id_base = its first row)."""

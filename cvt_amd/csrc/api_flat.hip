@@ -273,6 +273,12 @@ int cvtmi_flat_set_param(cvtmi_flat_t h, const char *name, int64_t value)
         h->p_range_spill = value;
         return CVTMI_OK;
     }
+    if (!strcmp(name, "rerank_rows_copy")) {
+        if (value != 0 && value != 1) return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: rerank_rows_copy must be 0 or 1");
+        std::unique_lock<std::shared_timed_mutex> lk(h->rw);
+        h->p_rerank_rows_copy = value;
+        return CVTMI_OK;
+    }
     return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: unknown parameter '%s'", name);
 }
 
@@ -615,6 +621,28 @@ extern "C" int cvtmi_flat_describe_dispatch(int metric, int D, int64_t n_rows, i
     return CVTMI_OK;
 }
 
+// The row-major copy f_rows of blocked fp32 rows, brought up to the handle's n rows: only the rows appended since it was made are
+// unblocked, the buffer grows by halves.  The caller holds the handle exclusively (FlatMutation on st); the stream is drained before
+// the copy counts as current.  No room: CVTMI_OK with f_rows_failed set -- the readers gather from the blocked rows.  Shared by
+// flat_prepare (the threshold filter's exact finish) and flat_rerank_prepare ("rerank_rows_copy")
+static int flat_rows_copy_build(cvtmi_flat_t h, hipStream_t st)
+{
+    const int64_t n = h->n;
+    int64_t row0 = (h->f_rows.p && h->f_rows_n > 0 && h->f_rows_n < n) ? h->f_rows_n : 0;
+    h->f_rows_n = -1;
+    const size_t need_b = (size_t)n * h->D * sizeof(float);
+    bool ok = true;
+    if (row0 > 0 && need_b > h->f_rows.cap &&
+        h->f_rows.grow(std::max(need_b, h->f_rows.cap + h->f_rows.cap / 2), (size_t)row0 * h->D * sizeof(float), st) != CVTMI_OK) { (void)hipGetLastError(); row0 = 0; }
+    if (row0 == 0 && h->f_rows.reserve(need_b) != CVTMI_OK) { (void)hipGetLastError(); ok = false; h->f_rows_failed = true; }   // no room: the finish gathers from the blocked rows
+    if (ok) {
+        CVTMI_TRY(launch_flat_unblock(h->data.as<float>(), row0, n, h->D, h->f_rows.as<float>(), st));
+        CVTMI_HIP(stream_wait(st));
+        h->f_rows_n = n;
+    }
+    return CVTMI_OK;
+}
+
 // The lazily built parts of the index a route needs -- the host copy of the row statistics (fp32 stream), the operand copies of
 // the filter pipelines -- are built under the EXCLUSIVE lock, once per index state, and the stream is drained before the lock
 // is given back.  Called before the search takes its shared lock.
@@ -674,20 +702,7 @@ static int flat_prepare(cvtmi_flat_t h, const void *q, int64_t nq, int k, hipStr
             h->f_pack_n = n;
             h->f_pack_nch = want_nch;
         }
-        if (need_rm && h->f_rows_n != n && !need_fs) {   // row-major copy for the exact finish: the rows appended since it was made, the buffer grows by halves
-            int64_t row0 = (h->f_rows.p && h->f_rows_n > 0 && h->f_rows_n < n) ? h->f_rows_n : 0;
-            h->f_rows_n = -1;
-            const size_t need_b = (size_t)n * h->D * sizeof(float);
-            bool ok = true;
-            if (row0 > 0 && need_b > h->f_rows.cap &&
-                h->f_rows.grow(std::max(need_b, h->f_rows.cap + h->f_rows.cap / 2), (size_t)row0 * h->D * sizeof(float), st) != CVTMI_OK) { (void)hipGetLastError(); row0 = 0; }
-            if (row0 == 0 && h->f_rows.reserve(need_b) != CVTMI_OK) { (void)hipGetLastError(); ok = false; h->f_rows_failed = true; }   // no room: the finish gathers from the blocked rows
-            if (ok) {
-                CVTMI_TRY(launch_flat_unblock(h->data.as<float>(), row0, n, h->D, h->f_rows.as<float>(), st));
-                CVTMI_HIP(stream_wait(st));
-                h->f_rows_n = n;
-            }
-        }
+        if (need_rm && h->f_rows_n != n && !need_fs) CVTMI_TRY(flat_rows_copy_build(h, st));
         if (need_u8 && h->f_pack_n != n) {    // operand-ordered copy of the rows (x - 128 as int8)
             // rows appended since the copy was made: only their tiles are packed (from the last, partly filled one on), the buffer grows by halves
             int64_t row0 = (h->f_pack.p && h->f_pack_n > 0 && h->f_pack_n < n) ? h->f_pack_n / 32 * 32 : 0;
@@ -1011,6 +1026,103 @@ int cvtmi_flat_search(cvtmi_flat_t h, const void *q, int64_t nq, int k, void *di
     CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
     CVTMI_HIP(hipMemcpyAsync(labels, S.io_i.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
     CVTMI_HIP(stream_wait(st));
+    return CVTMI_OK;
+}
+
+}  // extern "C"
+
+// ---- rerank: the exact top k among the candidate rows the caller names (flat_rerank.hip) ----
+// A search like the others: `rw` shared, a leased scratch set, nothing of the handle changes -- but for "rerank_rows_copy" = 1, where
+// the first call that finds no current row-major copy of blocked rows builds it under the exclusive lock first, as flat_prepare does.
+static int flat_rerank_prepare(cvtmi_flat_t h, hipStream_t st)
+{
+    {
+        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+        if (!h->p_rerank_rows_copy || !flat_blocked(h->metric, h->D) || h->n == 0 || h->f_rows_n == h->n || h->f_rows_failed) return CVTMI_OK;
+    }
+    FlatMutation mut(h, st);
+    if (h->n > 0 && h->f_rows_n != h->n && !h->f_rows_failed) CVTMI_TRY(flat_rows_copy_build(h, st));
+    return CVTMI_OK;
+}
+
+// arguments first, before anything touches the device
+static int flat_rerank_check(cvtmi_flat_t h, const void *q, int64_t nq, const int64_t *cand, int R, int k, const void *dist, const int64_t *labels)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_flat_rerank: null handle");
+    if (nq < 0 || (nq > 0 && (!q || !cand || !dist || !labels))) return fail(CVTMI_EINVAL, "cvtmi_flat_rerank: bad arguments");
+    if (k < 1 || k > CVTMI_K_MAX) return fail(CVTMI_EINVAL, "cvtmi_flat_rerank: k=%d outside 1..%d", k, CVTMI_K_MAX);
+    if (R < 1 || R > CVTMI_RERANK_MAX) return fail(CVTMI_EINVAL, "cvtmi_flat_rerank: R=%d outside 1..%d", R, CVTMI_RERANK_MAX);
+    return CVTMI_OK;
+}
+
+// the launch, on a leased scratch set's stream or the caller's, under the shared lock
+static int flat_rerank_leased(cvtmi_flat_t h, const void *q, int64_t nq, const int64_t *cand, int R, int64_t cand_base, bool skip_minus_one, int k,
+                              void *dist, int64_t *labels, hipStream_t st)
+{
+    if (h->n >= ((int64_t)1 << 32)) return fail(CVTMI_EUNSUPPORTED, "cvtmi_flat_rerank: %lld rows: rows travel as 32-bit words", (long long)h->n);
+    const bool blocked = flat_blocked(h->metric, h->D);
+    const bool copy = blocked && h->f_rows.p && h->f_rows_n == h->n;   // (a stale copy -- rows added since -- is not read)
+    const int src = !blocked ? 0 : (copy ? 2 : 1);
+    int64_t info[4];
+    CVTMI_TRY(launch_flat_rerank(h->metric, h->D, copy ? h->f_rows.p : h->data.p, src, h->n, h->identity ? nullptr : h->labels.as<int64_t>(), h->id_base, q, nq, cand,
+                                 R, cand_base, skip_minus_one, k, dist, labels, info, st));
+    std::lock_guard<std::mutex> g(h->pool.mu);
+    for (int i = 0; i < 4; ++i) h->rerank_last[i] = info[i];
+    return CVTMI_OK;
+}
+
+int cvtmi::flat_rerank_on_stream(cvtmi_flat_t h, const void *q, int64_t nq, const int64_t *cand, int R, int64_t cand_base, bool skip_minus_one, int k,
+                                 void *dist, int64_t *labels, hipStream_t st)
+{
+    CVTMI_TRY(flat_rerank_prepare(h, st));
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    FlatLease lease;
+    CVTMI_TRY(lease.open(h, st, false));
+    return flat_rerank_leased(h, q, nq, cand, R, cand_base, skip_minus_one, k, dist, labels, st);
+}
+
+extern "C" {
+
+int cvtmi_flat_rerank_dev(cvtmi_flat_t h, const void *q, int64_t nq, const int64_t *cand, int R, int64_t cand_base, int k, void *dist,
+                          int64_t *labels, void *stream)
+{
+    CVTMI_TRY(flat_rerank_check(h, q, nq, cand, R, k, dist, labels));
+    CVTMI_TRY(use_device(h->device));
+    if (nq == 0) return CVTMI_OK;
+    return flat_rerank_on_stream(h, q, nq, cand, R, cand_base, false, k, dist, labels, (hipStream_t)stream);
+}
+
+// host pointers: queries and candidate lists up, the two result arrays down, through the leased set's staging buffers and its stream
+int cvtmi_flat_rerank(cvtmi_flat_t h, const void *q, int64_t nq, const int64_t *cand, int R, int64_t cand_base, int k, void *dist, int64_t *labels)
+{
+    CVTMI_TRY(flat_rerank_check(h, q, nq, cand, R, k, dist, labels));
+    CVTMI_TRY(use_device(h->device));
+    if (nq == 0) return CVTMI_OK;
+    CVTMI_TRY(flat_rerank_prepare(h, nullptr));
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    FlatLease lease;
+    CVTMI_TRY(lease.open(h, nullptr, true));
+    FlatScratch &S = *lease.s;
+    hipStream_t st = lease.st;
+    const size_t qb = (size_t)nq * h->row_bytes, cb = (size_t)nq * R * sizeof(int64_t), db = (size_t)nq * k * 4, ib = (size_t)nq * k * sizeof(int64_t);
+    CVTMI_TRY(S.io_q.reserve(qb));
+    CVTMI_TRY(S.io_c.reserve(cb));
+    CVTMI_TRY(S.io_d.reserve(db));
+    CVTMI_TRY(S.io_i.reserve(ib));
+    CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
+    CVTMI_HIP(hipMemcpyAsync(S.io_c.p, cand, cb, hipMemcpyHostToDevice, st));
+    CVTMI_TRY(flat_rerank_leased(h, S.io_q.p, nq, S.io_c.as<int64_t>(), R, cand_base, false, k, S.io_d.p, S.io_i.as<int64_t>(), st));
+    CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(hipMemcpyAsync(labels, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    return CVTMI_OK;
+}
+
+int cvtmi_flat_last_rerank(cvtmi_flat_t h, int64_t out[4])
+{
+    if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_flat_last_rerank: null");
+    std::lock_guard<std::mutex> g(h->pool.mu);
+    for (int i = 0; i < 4; ++i) out[i] = h->rerank_last[i];
     return CVTMI_OK;
 }
 

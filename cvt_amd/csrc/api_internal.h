@@ -122,6 +122,7 @@ struct OpqScratch : ScratchBase {
     DevBuf s_qrot, s_part_d, s_part_id, s_lut, s_gthr, s_qlut, s_qp, s_spill, s_items, s_probe;
     DevBuf s_ivf;              // partial lists of an IVF search (ivf_search.hip)
     DevBuf s_range;            // range search (ivf_range.hip): probe order, part counts and offsets, spill area; host entry: lims behind them
+    DevBuf s_ref_d, s_ref_i;   // cvtmi_opq_search_refine: the [nq][R] candidate lists between the scan and the rerank
     ScanHPlan hplan;                       // the item table s_items holds ...
     int64_t hplan_n = -1, hplan_nq = -1;   // ... and the (rows, queries, forced splits, planner settings) it was built for
     int hplan_splits = 0, hplan_key = 0;
@@ -130,7 +131,7 @@ struct OpqScratch : ScratchBase {
     PinBuf io_pin;             // its pinned staging area
     void release_all()
     {
-        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &s_range, &io_q, &io_d, &io_i, &io_v }) b->release();
+        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &s_range, &s_ref_d, &s_ref_i, &io_q, &io_d, &io_i, &io_v }) b->release();
         io_pin.release();
         release_lease_state();
     }
@@ -196,11 +197,12 @@ struct FlatScratch : ScratchBase {
     DevBuf redo_count;                                                                         // "flat_count_redo": the count of the flags
     DevBuf s_range;                 // range search (flat_range.hip): part counts and offsets, spill area; host entry: lims behind them
     DevBuf io_q, io_d, io_i;                                                                   // staging of the host-pointer entry
+    DevBuf io_c;                    // ... and the candidate lists of cvtmi_flat_rerank
     PinBuf io_pin;                  // small calls: [queries | distances | labels] in page-locked memory the kernels write into
     void release_all()
     {
         for (DevBuf *b : { &s_part_d, &s_part_id, &s_gthr, &s_stage, &f_stats, &f_thr, &f_marg, &f_cnt, &f_cand, &f_sd, &f_si, &f_sd2,
-                           &f_si2, &f_seld, &f_seli, &fs_redo, &fs_scratch, &redo_count, &s_range, &io_q, &io_d, &io_i })
+                           &f_si2, &f_seld, &f_seli, &fs_redo, &fs_scratch, &redo_count, &s_range, &io_q, &io_d, &io_i, &io_c })
             b->release();
         io_pin.release();
         release_lease_state();
@@ -221,6 +223,8 @@ struct cvtmi_flat_s {
     int64_t p_range_part_rows = 0;   // "range_part_rows": rows per part of a range search (0 = the default)
     int64_t p_range_spill = -1;      // "range_spill": spill records per (query, part) (-1 = the default)
     int64_t range_last[6] = {};      // plan of the last range search (cvtmi_flat_last_range_plan), written under pool.mu
+    int64_t p_rerank_rows_copy = 0;  // "rerank_rows_copy": 1 = a rerank builds / extends the row-major copy f_rows it would otherwise do without
+    int64_t rerank_last[4] = {};     // the last rerank (cvtmi_flat_last_rerank), written under pool.mu
     int64_t n = 0;
     int64_t id_base = 0;   // row r reports label id_base + r while labels are implicit (row shards, cvtmi_flat_set_id_base)
     bool identity = true;  // label == row
@@ -278,6 +282,9 @@ extern std::atomic<int> g_scanh_key;   // bumped by a REPLAN tuning key (api.hip
 
 int use_device(int dev);
 int opq_rotate_impl(cvtmi_opq_t h, const float *x, int64_t n, float *y, hipStream_t st);   // api_opq.hip
+// api_flat.hip: cvtmi_flat_rerank_dev behind its argument checks (device pointers, stream st); skip_minus_one: a candidate of -1 is padding
+int flat_rerank_on_stream(cvtmi_flat_t h, const void *q, int64_t nq, const int64_t *cand, int R, int64_t cand_base, bool skip_minus_one, int k,
+                          void *dist, int64_t *labels, hipStream_t st);
 int sharded_local_failure(cvtmi_comm_t c);
 using ShardLocalSearch = std::function<int(int, const void *, float *, int64_t *)>;
 int sharded_all(cvtmi_comm_t *comms, int ndev, const void *q, size_t q_bytes, int64_t nq, int k, void *dist, int64_t *ids,

@@ -1127,6 +1127,80 @@ int cvtmi_opq_ivf_plan(int64_t nq, int nprobe, int k, int64_t longest_list, int 
     return CVTMI_OK;
 }
 
+// ---- refine: R ADC candidates per query (IVF lists, or the exhaustive scan for nprobe == 0), exact finish against a flat index ----
+// The candidate lists stay in the leased set (s_ref_d, s_ref_i).  Lock order: THIS handle's shared lock (and lease) first, the flat
+// handle's -- its preparation under the exclusive lock included -- inside it; nothing takes the two the other way round.
+static int opq_refine_check(cvtmi_opq_t h, cvtmi_flat_t flat, const float *q, int64_t nq, int *nprobe, int k, int R, const float *dist, const int64_t *labels)
+{
+    if (!h || !flat) return fail(CVTMI_EINVAL, "cvtmi_opq_search_refine: null handle");
+    if (nq < 0 || (nq > 0 && (!q || !dist || !labels))) return fail(CVTMI_EINVAL, "cvtmi_opq_search_refine: bad arguments");
+    if (k < 1 || R < k || R > CVTMI_K_MAX) return fail(CVTMI_EINVAL, "cvtmi_opq_search_refine: 1 <= k <= R <= %d does not hold for k=%d R=%d", CVTMI_K_MAX, k, R);
+    if (*nprobe < 0) return fail(CVTMI_EINVAL, "cvtmi_opq_search_refine: nprobe=%d", *nprobe);
+    if (*nprobe == 0 && h->m.coarseK != 1) return fail(CVTMI_EINVAL, "cvtmi_opq_search_refine: nprobe == 0 is the exhaustive scan, which needs coarseK == 1");
+    if (flat->metric != CVTMI_METRIC_IP && flat->metric != CVTMI_METRIC_L2F) return fail(CVTMI_EINVAL, "cvtmi_opq_search_refine: the flat index must hold fp32 rows");
+    if (flat->D != h->m.D) return fail(CVTMI_EINVAL, "cvtmi_opq_search_refine: flat D=%d, model D=%d", flat->D, h->m.D);
+    if (flat->n != h->n) return fail(CVTMI_EINVAL, "cvtmi_opq_search_refine: %lld flat rows, %lld entries", (long long)flat->n, (long long)h->n);
+    if (flat->device != h->device) return fail(CVTMI_EINVAL, "cvtmi_opq_search_refine: the handles live on different devices");
+    if (*nprobe >= 1) {
+        float probe_d = 0.0f;   // (the IVF search's own limits; its outputs are the leased lists)
+        int64_t probe_i = 0;
+        CVTMI_TRY(opq_search_ivf_check(h, q ? q : &probe_d, nq, nprobe, R, &probe_d, &probe_i));
+    }
+    return CVTMI_OK;
+}
+
+// candidates into the leased lists, rerank into (dist, labels): device pointers, stream st; the caller holds h->rw shared
+static int opq_refine_leased(cvtmi_opq_t h, cvtmi_flat_t flat, OpqScratch &S, const float *q, int64_t nq, int rotate, int nprobe, int k, int R,
+                             float *dist, int64_t *labels, hipStream_t st)
+{
+    CVTMI_TRY(S.s_ref_d.reserve((size_t)nq * R * sizeof(float)));
+    CVTMI_TRY(S.s_ref_i.reserve((size_t)nq * R * sizeof(int64_t)));
+    if (nprobe >= 1) CVTMI_TRY(opq_search_ivf_leased(h, S, q, nq, rotate, nprobe, R, S.s_ref_d.as<float>(), S.s_ref_i.as<int64_t>(), st));
+    else CVTMI_TRY(opq_search_leased(h, S, q, nq, rotate, R, S.s_ref_d.as<float>(), S.s_ref_i.as<int64_t>(), st));
+    return flat_rerank_on_stream(flat, q, nq, S.s_ref_i.as<int64_t>(), R, h->id_base, true, k, dist, labels, st);
+}
+
+static int opq_refine_common(cvtmi_opq_t h, cvtmi_flat_t flat, const float *q, int64_t nq, int rotate, int nprobe, int k, int R, float *dist,
+                             int64_t *labels, hipStream_t stream, bool host)
+{
+    CVTMI_TRY(opq_refine_check(h, flat, q, nq, &nprobe, k, R, dist, labels));
+    CVTMI_TRY(use_device(h->device));
+    if (nq == 0) return CVTMI_OK;
+    for (int attempt = 0;; ++attempt) {   // (as cvtmi_opq_search_ivf: an append between the preparation and the shared lock sends it round again)
+        if (nprobe >= 1) CVTMI_TRY(opq_ivf_prepare(h, stream));
+        else CVTMI_TRY(opq_prepare(h, nq, R, stream));
+        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+        if (nprobe >= 1 && !(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
+        OpqLease lease;
+        CVTMI_TRY(lease.open(h, stream, host));
+        if (!host) return opq_refine_leased(h, flat, *lease.s, q, nq, rotate, nprobe, k, R, dist, labels, stream);
+        OpqScratch &S = *lease.s;
+        hipStream_t st = lease.st;
+        const size_t qb = (size_t)nq * h->m.D * sizeof(float), db = (size_t)nq * k * sizeof(float), ib = (size_t)nq * k * sizeof(int64_t);
+        CVTMI_TRY(S.io_q.reserve(qb));
+        CVTMI_TRY(S.io_d.reserve(db));
+        CVTMI_TRY(S.io_i.reserve(ib));
+        CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
+        CVTMI_TRY(opq_refine_leased(h, flat, S, S.io_q.as<float>(), nq, rotate, nprobe, k, R, S.io_d.as<float>(), S.io_i.as<int64_t>(), st));
+        CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(hipMemcpyAsync(labels, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(stream_wait(st));
+        return CVTMI_OK;
+    }
+}
+
+int cvtmi_opq_search_refine_dev(cvtmi_opq_t h, cvtmi_flat_t flat, const float *q, int64_t nq, int rotate, int nprobe, int k, int R, float *dist,
+                                int64_t *labels, void *stream)
+{
+    return opq_refine_common(h, flat, q, nq, rotate, nprobe, k, R, dist, labels, (hipStream_t)stream, false);
+}
+
+int cvtmi_opq_search_refine(cvtmi_opq_t h, cvtmi_flat_t flat, const float *q, int64_t nq, int rotate, int nprobe, int k, int R, float *dist,
+                            int64_t *labels)
+{
+    return opq_refine_common(h, flat, q, nq, rotate, nprobe, k, R, dist, labels, nullptr, true);
+}
+
 // ---- range search: every entry of the probed lists under a score radius (ivf_range.hip) ----
 // Concurrency and preparation are the IVF search's.  A call is a count (probe order, scan, offsets: lims is complete on the device)
 // and, where the caller gave room, a fill (fill + rescan, both predicated on the device on lims[nq] <= cap).

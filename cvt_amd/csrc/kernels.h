@@ -280,6 +280,14 @@ int launch_flat_range_count(const FlatRangeRows &x, const void *q, int64_t nq, u
 int launch_flat_range_fill(const FlatRangeRows &x, const void *q, int64_t nq, uint32_t thr, const FlatRangePlan &p, const FlatRangeBufs &b,
                            const int64_t *lims, int64_t cap, void *dist, int64_t *labels, hipStream_t st);
 
+// ---- flat_rerank.hip ----  the exact top k among candidate rows the caller names (cvtmi_flat_rerank), one fused launch
+// src: 0 row-major primary rows (uint8, fp32 with D % 4 != 0), 1 blocked fp32 rows, 2 the row-major fp32 copy of blocked rows -- the same
+// bits from all three.  labels null: id_base + row.  skip_minus_one: a candidate of -1 is padding whatever cand_base says
+// (cvtmi_opq_search_refine).  info (may be null) = { src, lanes per distance (0 for uint8), workgroups, LDS bytes per workgroup }
+int launch_flat_rerank(int metric, int D, const void *data, int src, int64_t n, const int64_t *labels, int64_t id_base, const void *q,
+                       int64_t nq, const int64_t *cand, int R, int64_t cand_base, bool skip_minus_one, int k, void *dist, int64_t *out_labels,
+                       int64_t info[4], hipStream_t st);
+
 // ---- flat.hip ----
 int flat_plan_splits(int64_t n, int64_t nq, int qtile);
 int flat_qtile(int64_t nq);

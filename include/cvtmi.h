@@ -605,7 +605,9 @@ int cvtmi_flat_remove_labels_dev(cvtmi_flat_t h, const int64_t *labels, int64_t 
  *   "range_spill"      hits C a (query, part) of cvtmi_flat_range_search may park in the leased scratch set while the sizes are not
  *                      known yet; a part that meets more walks its rows a second time once they are.  0 = every part with a hit
  *                      does; a huge value = none: C is cut down to the rows of a part and so that the area, nq x parts x C x 8
- *                      bytes, stays within 256 MB.  -1 (default) = 512. */
+ *                      bytes, stays within 256 MB.  -1 (default) = 512.
+ *   "rerank_rows_copy" 0 (default) / 1: whether cvtmi_flat_rerank may build a row-major copy of blocked fp32 rows -- a second copy
+ *                      of the table in device memory against eight times the gather traffic (see cvtmi_flat_rerank). */
 int cvtmi_flat_set_param(cvtmi_flat_t h, const char *name, int64_t value);
 /* searchKnn (brutoforce.hpp:73-93) for nq queries: k smallest (distance, label), ascending.
  * dist is float[nq][k] for IP / L2F and int32_t[nq][k] for L2U8.  1 <= k <= CVTMI_K_MAX.  An index with fewer than k rows pads:
@@ -655,6 +657,62 @@ int cvtmi_flat_range_search_dev(cvtmi_flat_t h, const void *q, int64_t nq, doubl
  * per (query, part) C, spill bytes, kernel form }.  Forms: 0 fp32 row-major rows, queries in LDS; 1 fp32 blocked rows, queries in
  * SGPRs; 2 uint8 single bytes; 3 uint8 16-byte pieces; 4 uint8 16-byte pieces with the handle's norms.  A count-only call plans C = 0. */
 int cvtmi_flat_last_range_plan(cvtmi_flat_t h, int64_t out[6]);
+/* Rerank: the exact top k among the candidate rows the caller names -- the exact finish behind any candidate generator (the IVF or
+ * exhaustive ADC searches, HNSW-ADC, the lists of a shard, a metadata filter), the counterpart of faiss's IndexRefineFlat.  q holds nq
+ * rows of the index's own type, cand is int64[nq][R].
+ *   Candidates  entry j of query f names row cand[f][j] - cand_base; it is valid when cand_base <= cand[f][j] < cand_base + ntotal,
+ *            evaluated without signed overflow (INT64_MIN, INT64_MAX and any cand_base are safe).  Everything else is skipped
+ *            silently: the -1 padding of the searches, ids another shard owns.  A row named several times counts once; the result
+ *            never depends on the order or the multiplicity of a query's candidates.
+ *   Distance the one cvtmi_flat_search reports for that (query, row), bit for bit: IP is 1 - sum in the 4-lane order; L2F sums in 8
+ *            lanes for D % 16 == 0, in 4 lanes for D % 4 == 0 and in the scalar loop otherwise; L2U8 is the exact int32 sum over
+ *            D / 4 * 4 bytes.  dist holds 4-byte fields: float for IP and L2F, int32 for L2U8.
+ *   Order    ascending (distance, row), the device tie rule of cvtmi_flat_search.  Floats compare as in cvtmi_topk_select:
+ *            -0.0 == +0.0, NaN by its key.  A NaN distance is a real candidate: a query holding a NaN returns min(k, distinct valid
+ *            rows) distinct rows, all with NaN distances, in an unspecified order.  Short lists pad with label -1 and distance field
+ *            0x7f800000, as cvtmi_flat_search pads.
+ *   Labels   what cvtmi_flat_search would report for the row: id_base + row while labels are implicit, otherwise the stored label.
+ *   In short for NaN-free data, query f gets exactly what cvtmi_flat_search(k) returns on a fresh handle that holds only f's distinct
+ *            valid rows, in ascending row order, with the labels they report.
+ *   Limits   1 <= k <= CVTMI_K_MAX, 1 <= R <= CVTMI_RERANK_MAX; k may exceed R (the list then pads).  ntotal >= 2^32 fails with
+ *            CVTMI_EUNSUPPORTED.
+ * Checked before any device work: NULL h, or NULL q / cand / dist / labels with nq > 0, nq < 0, k or R out of range -> CVTMI_EINVAL.
+ * nq == 0 does nothing; an empty index pads everything.
+ * Concurrency: a rerank is a search.  It takes the shared lock and a scratch set of its own, runs beside the other searches of the
+ * handle and waits behind cvtmi_flat_add / _remove_labels / _reset like them.  The `_dev` entry enqueues on `stream` and never waits
+ * for the device (but for the one call that builds the copy below).
+ * One launch: a workgroup per query scores the valid candidates out of LDS tiles of their rows, sorts the (distance, row) pairs in LDS,
+ * drops equal neighbours and writes k of them; no [nq][R] array passes through device memory.
+ * Row source.  fp32 rows with D % 4 == 0 live in 64-row blocks: a gathered row costs EIGHT times its bytes there (16 useful bytes of
+ * every 128-byte line).  cvtmi_flat_set_param(h, "rerank_rows_copy", v):
+ *   0 (default)  read the row-major copy of the rows only if the handle already has a current one (the fp32 threshold filter builds
+ *                it: "flat_f32_rows_copy"); otherwise gather from the blocked rows;
+ *   1            the first rerank that needs it builds or extends that copy, under the exclusive lock, before it takes its shared
+ *                lock.  The price is a SECOND copy of the table in device memory, against eight times the gather traffic without
+ *                it.  If the allocation fails the blocked rows are read.
+ * Every source gives the same bits.  No effect on uint8 rows or on fp32 rows with D % 4 != 0: those are row-major as they are. */
+#define CVTMI_RERANK_MAX 4096
+int cvtmi_flat_rerank(cvtmi_flat_t h, const void *q, int64_t nq, const int64_t *cand, int R, int64_t cand_base,
+                      int k, void *dist, int64_t *labels);
+int cvtmi_flat_rerank_dev(cvtmi_flat_t h, const void *q, int64_t nq, const int64_t *cand, int R, int64_t cand_base,
+                          int k, void *dist, int64_t *labels, void *stream);
+/* The handle's last rerank: out = { row source, lanes per distance (1 / 4 / 8; 0 for uint8), workgroups, LDS bytes per workgroup }.
+ * Row source: 0 = row-major primary rows (uint8, or fp32 with D % 4 != 0), 1 = blocked rows, 2 = the row-major copy. */
+int cvtmi_flat_last_rerank(cvtmi_flat_t h, int64_t out[4]);
+/* ADC candidates, exact finish: R candidates per query from the OPQ index -- what cvtmi_opq_search_ivf(nprobe, R) returns for
+ * nprobe >= 1, what cvtmi_opq_search(R) returns for nprobe == 0 (which needs coarseK == 1) -- reranked against `flat` as
+ * cvtmi_flat_rerank does, with cand_base = the OPQ handle's id_base and the RAW queries (rotate only steers the scan).  dist and
+ * labels receive the exact distances and the FLAT index's labels: the result equals that composition of the two public calls, bit for
+ * bit.  The padding of a short scan list is never a candidate (with an OPQ id_base in [-ntotal, -1] the entry whose id is -1 reads as
+ * padding).  The candidate lists stay in the scratch set the OPQ handle leases and never reach the host.
+ * Requirements, checked before any device work, else CVTMI_EINVAL: flat is IP or L2F, its D is the model's, both hold the same number
+ * of rows and live on the same device, 1 <= k <= R <= CVTMI_K_MAX, nprobe >= 0, nprobe == 0 only with coarseK == 1, no NULL handle,
+ * nq >= 0, and no NULL q / dist / labels with nq > 0.  nq == 0 does nothing.
+ * The call holds the OPQ handle's shared lock first and takes the flat handle's inside it. */
+int cvtmi_opq_search_refine(cvtmi_opq_t h, cvtmi_flat_t flat, const float *q, int64_t nq, int rotate, int nprobe,
+                            int k, int R, float *dist, int64_t *labels);
+int cvtmi_opq_search_refine_dev(cvtmi_opq_t h, cvtmi_flat_t flat, const float *q, int64_t nq, int rotate, int nprobe,
+                                int k, int R, float *dist, int64_t *labels, void *stream);
 /* Measurement hook: how the last search was answered -- *filtered = 0 the exact kernels; 1 the sample + matrix-core filter
  * pipeline (fp32 metrics, 32 <= D <= 128, D % 16 == 0, >= 131072 rows: exact search of a leading sample, bf16 matrix-core
  * products decide which other rows need an exact distance); 2 the fp32 stream (D in {32, 64, 96, 128, 192, 256}, >= 32768 rows:
