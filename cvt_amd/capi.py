@@ -685,7 +685,9 @@ class FlatIndex:
 
     def set_param(self, name, value):
         """cvtmi_flat_set_param: "remove_chunk" = rows the move of a removal works on at a time (0 = default); "range_part_rows" = rows
-        per part of a range search (0 = default); "range_spill" = hits a (query, part) may park before the sizes are known (-1 = default)."""
+        per part of a range search (0 = default); "range_spill" = hits a (query, part) may park before the sizes are known (-1 = default);
+        "rerank_rows_copy" = 1 lets a rerank build the row-major copy of blocked rows; "masked_parts" = parts per query group of a masked
+        search (0 = the plan, 1 .. 1024)."""
         _check(lib().cvtmi_flat_set_param(self.h, name.encode(), C.c_int64(value)))
 
     def range_search(self, q, radius, out=None):
@@ -759,6 +761,75 @@ class FlatIndex:
         (cvtmi_flat_last_rerank); row source 0 = row-major primary rows, 1 = blocked rows, 2 = the row-major copy."""
         o = (C.c_int64 * 4)()
         _check(lib().cvtmi_flat_last_rerank(self.h, o))
+        return o[0], o[1], o[2], o[3]
+
+    def _mask_words(self, mask, dev):
+        """`mask` as uint64 words: words stay as they are, a bool array of length ntotal is packed little-endian (bit r & 63 of word
+        r >> 6 = row r)."""
+        if _is_torch(mask):
+            import torch
+            if mask.dtype == torch.bool:
+                pad = (-mask.shape[0]) % 64
+                bits = torch.nn.functional.pad(mask.reshape(-1).to(torch.int64), (0, pad)).reshape(-1, 64)
+                # (bit 63 wraps into the sign of the int64 word: the same 64 bits)
+                return (bits << torch.arange(64, device=mask.device, dtype=torch.int64)).sum(dim=1).contiguous()
+            assert mask.dtype in (torch.int64, torch.uint64) and mask.is_cuda == dev
+            return mask.reshape(-1).contiguous()
+        mask = np.asarray(mask)
+        if mask.dtype == np.bool_:
+            assert mask.ndim == 1 and mask.shape[0] == self.ntotal, "a bool mask has one entry per row"
+            packed = np.packbits(mask, bitorder="little")
+            words = np.zeros((mask.shape[0] + 63) // 64 * 8, dtype=np.uint8)
+            words[:packed.shape[0]] = packed
+            return words.view("<u8").astype(np.uint64, copy=False)
+        assert mask.dtype == np.uint64, "a mask is np.uint64 words or a bool array of length ntotal"
+        return np.ascontiguousarray(mask.reshape(-1))
+
+    def search_masked(self, q, k, mask):
+        """The k nearest rows among those `mask` allows (cvtmi_flat_search_masked).  mask: np.uint64 words, bit r & 63 of word r >> 6
+        allowing ROW r (at least ceil(ntotal / 64) words; bits past ntotal are ignored), or a bool array of length ntotal; one mask
+        serves every query.  Returns (distances [nq][k] float32 / int32 for the uint8 metric, labels [nq][k] int64) in ascending
+        (distance, row) order, padded like search when fewer than k rows are allowed.  numpy in, numpy out; torch device tensors
+        (mask: int64 / uint64 words or bool) run on torch's current stream."""
+        nq = q.shape[0]
+        if _is_torch(q):
+            import torch
+            words = self._mask_words(mask, True)
+            assert _is_torch(words) and words.is_cuda
+            d = torch.empty((nq, k), dtype=torch.int32 if self.metric == 2 else torch.float32, device=q.device)
+            i = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+            _check(lib().cvtmi_flat_search_masked_dev(self.h, _ptr(q), C.c_int64(nq), C.c_int(k), _ptr(words), C.c_int64(words.shape[0]),
+                                                      _ptr(d), _ptr(i), _stream()))
+            return d, i
+        q = _np(q, self._dt())
+        words = self._mask_words(mask, False)
+        d = np.empty((nq, k), dtype=np.int32 if self.metric == 2 else np.float32)
+        i = np.empty((nq, k), dtype=np.int64)
+        _check(lib().cvtmi_flat_search_masked(self.h, _ptr(q), C.c_int64(nq), C.c_int(k), _ptr(words), C.c_int64(words.shape[0]), _ptr(d), _ptr(i)))
+        return d, i
+
+    def mask_from_labels(self, labels, words=None):
+        """The mask of the rows whose reported label is in `labels` (cvtmi_flat_mask_labels; int64, numpy or a torch device tensor):
+        `words` uint64 words (default ceil(ntotal / 64)), every bit past ntotal cleared.  Invert or combine masks with plain word
+        operations (~m, a & b)."""
+        n_words = (self.ntotal + 63) // 64 if words is None else int(words)
+        if _is_torch(labels):
+            import torch
+            assert labels.dtype == torch.int64 and labels.is_cuda
+            labels = labels.reshape(-1)
+            mask = torch.empty(n_words, dtype=torch.int64, device=labels.device)
+            _check(lib().cvtmi_flat_mask_labels_dev(self.h, _ptr(labels), C.c_int64(labels.shape[0]), _ptr(mask), C.c_int64(n_words), _stream()))
+            return mask
+        labels = _np(labels, np.int64).reshape(-1)
+        mask = np.empty(n_words, dtype=np.uint64)
+        _check(lib().cvtmi_flat_mask_labels(self.h, _ptr(labels), C.c_int64(labels.shape[0]), _ptr(mask), C.c_int64(n_words)))
+        return mask
+
+    def last_masked(self):
+        """(queries per workgroup, parts per query group, bytes of the row list, kernel form) of the last search_masked on this handle
+        (cvtmi_flat_last_masked); form 0 = fp32 row-major rows, 1 = fp32 blocked rows, 2 = uint8 single bytes, 3 = uint8 16-byte pieces."""
+        o = (C.c_int64 * 4)()
+        _check(lib().cvtmi_flat_last_masked(self.h, o))
         return o[0], o[1], o[2], o[3]
 
     def search_sharded(self, comm, q, k):

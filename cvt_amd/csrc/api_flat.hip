@@ -9,6 +9,7 @@
 
 #include "api_internal.h"
 #include "launch.h"
+#include "rm_common.h"
 
 extern "C" {
 
@@ -277,6 +278,12 @@ int cvtmi_flat_set_param(cvtmi_flat_t h, const char *name, int64_t value)
         if (value != 0 && value != 1) return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: rerank_rows_copy must be 0 or 1");
         std::unique_lock<std::shared_timed_mutex> lk(h->rw);
         h->p_rerank_rows_copy = value;
+        return CVTMI_OK;
+    }
+    if (!strcmp(name, "masked_parts")) {
+        if (value < 0 || value > 1024) return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: masked_parts must be 0 (the plan) or 1 .. 1024 parts");
+        std::unique_lock<std::shared_timed_mutex> lk(h->rw);
+        h->p_masked_parts = value;
         return CVTMI_OK;
     }
     return fail(CVTMI_EINVAL, "cvtmi_flat_set_param: unknown parameter '%s'", name);
@@ -1123,6 +1130,212 @@ int cvtmi_flat_last_rerank(cvtmi_flat_t h, int64_t out[4])
     if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_flat_last_rerank: null");
     std::lock_guard<std::mutex> g(h->pool.mu);
     for (int i = 0; i < 4; ++i) out[i] = h->rerank_last[i];
+    return CVTMI_OK;
+}
+
+}  // extern "C"
+
+// ---- masked search: the k nearest rows among those a bitmap allows (flat_masked.hip) ----
+// A search like the others: `rw` shared, a leased scratch set, nothing of the handle changes.  The mask becomes a row list in the
+// leased set, the exact kernels walk the list, the parts merge, rows become labels; nothing of it reaches the host.
+static int flat_masked_check(cvtmi_flat_t h, const void *q, int64_t nq, int k, const uint64_t *mask, int64_t mask_words, const void *dist,
+                             const int64_t *labels)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_flat_search_masked: null handle");
+    if (nq < 0 || mask_words < 0 || (nq > 0 && (!q || !mask || !dist || !labels))) return fail(CVTMI_EINVAL, "cvtmi_flat_search_masked: bad arguments");
+    if (k < 1 || k > CVTMI_K_MAX) return fail(CVTMI_EINVAL, "cvtmi_flat_search_masked: k=%d outside 1..%d", k, CVTMI_K_MAX);
+    if (nq > INT32_MAX) return fail(CVTMI_EUNSUPPORTED, "cvtmi_flat_search_masked: nq=%lld above 2^31-1", (long long)nq);
+    return CVTMI_OK;
+}
+
+// under the shared lock: the mask covers the rows there are now
+static int flat_mask_covers(cvtmi_flat_t h, int64_t mask_words, const char *who)
+{
+    if (h->n >= ((int64_t)1 << 32)) return fail(CVTMI_EUNSUPPORTED, "%s: %lld rows: rows travel as 32-bit words", who, (long long)h->n);
+    if (mask_words < (h->n + 63) / 64)
+        return fail(CVTMI_EINVAL, "%s: %lld mask words for %lld rows (%lld needed)", who, (long long)mask_words, (long long)h->n, (long long)((h->n + 63) / 64));
+    return CVTMI_OK;
+}
+
+// the launches, on a leased scratch set, under the shared lock; h->n > 0, nq > 0; all pointers are device pointers
+static int flat_masked_leased(cvtmi_flat_t h, FlatScratch &S, const void *q, int64_t nq, int k, const uint64_t *mask, void *dist, int64_t *labels,
+                              hipStream_t st)
+{
+    const int64_t n = h->n;
+    const int qt = k > 128 ? 1 : flat_qtile(nq);   // k > 128: one query per workgroup (kernels.h: kBigK)
+    // planned for the worst case, a mask that allows every row: the host never learns how many it allows
+    int parts = h->p_masked_parts ? (int)h->p_masked_parts : flat_plan_splits(n, nq, qt);
+    const int64_t room = std::max<int64_t>(1, (int64_t)(1LL << 30) / std::max<int64_t>(1, nq * (int64_t)k * 12));   // at most ~1 GB of partial lists
+    if (parts > room) parts = (int)room;
+    const RmPlan p = rm_plan(n, 0, 0, 0);
+    const size_t off_list = p.off_table, list_bytes = (size_t)n * sizeof(uint32_t);   // (nothing of the plan behind its scan areas is used)
+    CVTMI_TRY(S.s_masked.reserve(off_list + list_bytes));
+    float *pd = reinterpret_cast<float *>(dist);
+    int64_t *pi = labels;
+    if (parts > 1) {
+        const size_t cnt = (size_t)nq * parts * k;
+        CVTMI_TRY(S.s_part_d.reserve(cnt * sizeof(float)));
+        CVTMI_TRY(S.s_part_id.reserve(cnt * sizeof(int64_t)));
+        pd = S.s_part_d.as<float>();
+        pi = S.s_part_id.as<int64_t>();
+    }
+    {
+        std::lock_guard<std::mutex> g(h->pool.mu);
+        const int64_t v[4] = { qt, parts, (int64_t)list_bytes, flat_masked_form(h->metric, h->D) };
+        for (int i = 0; i < 4; ++i) h->masked_last[i] = v[i];
+    }
+    uint32_t *list = rm_at<uint32_t>(S.s_masked.p, off_list);
+    CVTMI_TRY(launch_flat_masked_list(p, S.s_masked.p, mask, list, st));
+    CVTMI_TRY(launch_flat_masked_search(h->metric, h->D, h->data.p, n, q, nq, k, qt, parts, list, rm_at<int64_t>(S.s_masked.p, p.off_total), pd, pi, st));
+    if (parts > 1) CVTMI_TRY(launch_topk_merge(pd, pi, nq, parts, k, reinterpret_cast<float *>(dist), labels, st));
+    if (!h->identity) CVTMI_TRY(launch_gather_labels(labels, nq * k, h->labels.as<int64_t>(), st));
+    else if (h->id_base != 0) CVTMI_TRY(launch_offset_labels(labels, nq * k, h->id_base, st));
+    return CVTMI_OK;
+}
+
+// ---- the bitmap of a label set: the mark step of the removal, on a leased scratch set (the handle does not change) ----
+static int flat_mask_labels_check(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, const uint64_t *mask, int64_t mask_words)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_flat_mask_labels: null handle");
+    if (n_labels < 0 || mask_words < 0 || (n_labels > 0 && !labels) || (mask_words > 0 && !mask)) return fail(CVTMI_EINVAL, "cvtmi_flat_mask_labels: bad arguments");
+    return CVTMI_OK;
+}
+
+// set_dev: the labels on the device (implicit labels); table: their distinct values, ascending, in host memory (explicit labels).
+// Under the shared lock; mask is a device pointer of mask_words words
+static int flat_mask_labels_leased(cvtmi_flat_t h, FlatScratch &S, const int64_t *set_dev, int64_t n_set, const int64_t *table, int64_t T, uint64_t *mask,
+                                   int64_t mask_words, hipStream_t st)
+{
+    if (mask_words == 0) return CVTMI_OK;
+    if (h->n == 0 || n_set == 0) {
+        CVTMI_HIP(hipMemsetAsync(mask, 0, (size_t)mask_words * 8, st));
+        return CVTMI_OK;
+    }
+    FlatRmPlan p;   // the mark's areas alone: no row moves, so no chunk scratch
+    p.rm = rm_plan(h->n, 0, 0, 0);
+    p.T = h->identity ? 0 : T;
+    p.off_table = p.rm.off_table;
+    p.bytes = p.off_table + rm_align((size_t)std::max<int64_t>(p.T, 1) * 8);
+    CVTMI_TRY(S.s_masked.reserve(p.bytes));
+    void *W = S.s_masked.p;
+    if (h->identity) {
+        CVTMI_TRY(launch_rm_mark_ids(p.rm, W, set_dev, n_set, h->id_base, st));
+    } else {
+        CVTMI_HIP(hipMemcpyAsync(static_cast<char *>(W) + p.off_table, table, (size_t)T * 8, hipMemcpyHostToDevice, st));
+        CVTMI_TRY(launch_flat_rm_mark_labels(p, W, h->labels.as<int64_t>(), st));
+    }
+    return launch_flat_masked_copy(p.rm, W, mask, mask_words, st);
+}
+
+extern "C" {
+
+int cvtmi_flat_search_masked_dev(cvtmi_flat_t h, const void *q, int64_t nq, int k, const uint64_t *mask, int64_t mask_words, void *dist, int64_t *labels,
+                                 void *stream)
+{
+    CVTMI_TRY(flat_masked_check(h, q, nq, k, mask, mask_words, dist, labels));
+    CVTMI_TRY(use_device(h->device));
+    if (nq == 0) return CVTMI_OK;
+    hipStream_t st = (hipStream_t)stream;
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    CVTMI_TRY(flat_mask_covers(h, mask_words, "cvtmi_flat_search_masked"));
+    FlatLease lease;
+    CVTMI_TRY(lease.open(h, st, false));
+    if (h->n == 0) return launch_flat_masked_pad(dist, labels, nq * k, st);   // an empty index pads everything
+    return flat_masked_leased(h, *lease.s, q, nq, k, mask, dist, labels, st);
+}
+
+// host pointers: queries and mask words up, the two result arrays down, through the leased set's staging buffers and its stream
+int cvtmi_flat_search_masked(cvtmi_flat_t h, const void *q, int64_t nq, int k, const uint64_t *mask, int64_t mask_words, void *dist, int64_t *labels)
+{
+    CVTMI_TRY(flat_masked_check(h, q, nq, k, mask, mask_words, dist, labels));
+    CVTMI_TRY(use_device(h->device));
+    if (nq == 0) return CVTMI_OK;
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    CVTMI_TRY(flat_mask_covers(h, mask_words, "cvtmi_flat_search_masked"));
+    if (h->n == 0) {   // an empty index pads everything
+        for (int64_t i = 0; i < nq * k; ++i) { reinterpret_cast<uint32_t *>(dist)[i] = 0x7f800000u; labels[i] = -1; }
+        return CVTMI_OK;
+    }
+    FlatLease lease;
+    CVTMI_TRY(lease.open(h, nullptr, true));
+    FlatScratch &S = *lease.s;
+    hipStream_t st = lease.st;
+    const size_t qb = (size_t)nq * h->row_bytes, mb = (size_t)((h->n + 63) / 64) * 8, db = (size_t)nq * k * 4, ib = (size_t)nq * k * sizeof(int64_t);
+    CVTMI_TRY(S.io_q.reserve(qb));
+    CVTMI_TRY(S.io_m.reserve(mb));
+    CVTMI_TRY(S.io_d.reserve(db));
+    CVTMI_TRY(S.io_i.reserve(ib));
+    CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
+    CVTMI_HIP(hipMemcpyAsync(S.io_m.p, mask, mb, hipMemcpyHostToDevice, st));   // (the words behind the rows are never read)
+    CVTMI_TRY(flat_masked_leased(h, S, S.io_q.p, nq, k, S.io_m.as<uint64_t>(), S.io_d.p, S.io_i.as<int64_t>(), st));
+    CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(hipMemcpyAsync(labels, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    return CVTMI_OK;
+}
+
+int cvtmi_flat_last_masked(cvtmi_flat_t h, int64_t out[4])
+{
+    if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_flat_last_masked: null");
+    std::lock_guard<std::mutex> g(h->pool.mu);
+    for (int i = 0; i < 4; ++i) out[i] = h->masked_last[i];
+    return CVTMI_OK;
+}
+
+int cvtmi_flat_mask_labels_dev(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, uint64_t *mask, int64_t mask_words, void *stream)
+{
+    CVTMI_TRY(flat_mask_labels_check(h, labels, n_labels, mask, mask_words));
+    CVTMI_TRY(use_device(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    CVTMI_TRY(flat_mask_covers(h, mask_words, "cvtmi_flat_mask_labels"));
+    FlatLease lease;
+    CVTMI_TRY(lease.open(h, st, false));
+    std::vector<int64_t> raw, tab;
+    if (!h->identity && n_labels > 0 && h->n > 0 && mask_words > 0) {   // explicit labels: the set is sorted on the host, it comes down first (8 bytes per label)
+        try {
+            raw.resize((size_t)n_labels);
+        } catch (...) {
+            return fail(CVTMI_ENOMEM, "cvtmi_flat_mask_labels: out of host memory");
+        }
+        CVTMI_HIP(hipMemcpyAsync(raw.data(), labels, (size_t)n_labels * 8, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(stream_wait(st));
+        CVTMI_TRY(flat_remove_table(raw.data(), n_labels, tab));
+    }
+    CVTMI_TRY(flat_mask_labels_leased(h, *lease.s, labels, n_labels, tab.data(), (int64_t)tab.size(), mask, mask_words, st));
+    if (!tab.empty()) CVTMI_HIP(stream_wait(st));   // (the table leaves host memory that ends with this call)
+    return CVTMI_OK;
+}
+
+int cvtmi_flat_mask_labels(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, uint64_t *mask, int64_t mask_words)
+{
+    CVTMI_TRY(flat_mask_labels_check(h, labels, n_labels, mask, mask_words));
+    CVTMI_TRY(use_device(h->device));
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    CVTMI_TRY(flat_mask_covers(h, mask_words, "cvtmi_flat_mask_labels"));
+    if (mask_words == 0) return CVTMI_OK;
+    if (h->n == 0 || n_labels == 0) {
+        memset(mask, 0, (size_t)mask_words * 8);
+        return CVTMI_OK;
+    }
+    FlatLease lease;
+    CVTMI_TRY(lease.open(h, nullptr, true));
+    FlatScratch &S = *lease.s;
+    hipStream_t st = lease.st;
+    // only the words that can hold a row pass through the device; the caller's words behind them are cleared here
+    const int64_t words = (h->n + 63) / 64;
+    std::vector<int64_t> tab;
+    if (h->identity) {
+        CVTMI_TRY(S.io_c.reserve((size_t)n_labels * 8));
+        CVTMI_HIP(hipMemcpyAsync(S.io_c.p, labels, (size_t)n_labels * 8, hipMemcpyHostToDevice, st));
+    } else {
+        CVTMI_TRY(flat_remove_table(labels, n_labels, tab));
+    }
+    CVTMI_TRY(S.io_m.reserve((size_t)words * 8));
+    CVTMI_TRY(flat_mask_labels_leased(h, S, S.io_c.as<int64_t>(), n_labels, tab.data(), (int64_t)tab.size(), S.io_m.as<uint64_t>(), words, st));
+    CVTMI_HIP(hipMemcpyAsync(mask, S.io_m.p, (size_t)words * 8, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    memset(mask + words, 0, (size_t)(mask_words - words) * 8);
     return CVTMI_OK;
 }
 

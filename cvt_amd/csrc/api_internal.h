@@ -198,11 +198,13 @@ struct FlatScratch : ScratchBase {
     DevBuf s_range;                 // range search (flat_range.hip): part counts and offsets, spill area; host entry: lims behind them
     DevBuf io_q, io_d, io_i;                                                                   // staging of the host-pointer entry
     DevBuf io_c;                    // ... and the candidate lists of cvtmi_flat_rerank
+    DevBuf s_masked;                // masked search (flat_masked.hip): tile offsets, scan levels, the row list; mask_labels: the marked bitmap and its table
+    DevBuf io_m;                    // ... and the mask words / the label set of the host-pointer entries
     PinBuf io_pin;                  // small calls: [queries | distances | labels] in page-locked memory the kernels write into
     void release_all()
     {
         for (DevBuf *b : { &s_part_d, &s_part_id, &s_gthr, &s_stage, &f_stats, &f_thr, &f_marg, &f_cnt, &f_cand, &f_sd, &f_si, &f_sd2,
-                           &f_si2, &f_seld, &f_seli, &fs_redo, &fs_scratch, &redo_count, &s_range, &io_q, &io_d, &io_i, &io_c })
+                           &f_si2, &f_seld, &f_seli, &fs_redo, &fs_scratch, &redo_count, &s_range, &io_q, &io_d, &io_i, &io_c, &s_masked, &io_m })
             b->release();
         io_pin.release();
         release_lease_state();
@@ -225,6 +227,8 @@ struct cvtmi_flat_s {
     int64_t range_last[6] = {};      // plan of the last range search (cvtmi_flat_last_range_plan), written under pool.mu
     int64_t p_rerank_rows_copy = 0;  // "rerank_rows_copy": 1 = a rerank builds / extends the row-major copy f_rows it would otherwise do without
     int64_t rerank_last[4] = {};     // the last rerank (cvtmi_flat_last_rerank), written under pool.mu
+    int64_t p_masked_parts = 0;      // "masked_parts": parts per query group of a masked search (0 = the plan)
+    int64_t masked_last[4] = {};     // the last masked search (cvtmi_flat_last_masked), written under pool.mu
     int64_t n = 0;
     int64_t id_base = 0;   // row r reports label id_base + r while labels are implicit (row shards, cvtmi_flat_set_id_base)
     bool identity = true;  // label == row

@@ -288,6 +288,20 @@ int launch_flat_rerank(int metric, int D, const void *data, int src, int64_t n, 
                        int64_t nq, const int64_t *cand, int R, int64_t cand_base, bool skip_minus_one, int k, void *dist, int64_t *out_labels,
                        int64_t info[4], hipStream_t st);
 
+// ---- flat_masked.hip ----  the k nearest rows among those a bitmap allows (cvtmi_flat_search_masked)
+// p = rm_plan(n, 0, 0, 0): only its tile offsets, scan levels and total are used (the scratch up to p.off_table).  mask: bit r & 63 of
+// word r >> 6 allows row r, ceil(n / 64) words are read.  Afterwards list holds the allowed rows, ascending (room for n entries), and
+// the int64 at p.off_total their number
+int launch_flat_masked_list(const RmPlan &p, void *scratch, const uint64_t *mask, uint32_t *list, hipStream_t st);
+// mask[0 .. mask_words) = the bitmap a mark left at p.off_drop (launch_rm_mark_ids, launch_flat_rm_mark_labels), zeros behind its words
+int launch_flat_masked_copy(const RmPlan &p, const void *scratch, uint64_t *mask, int64_t mask_words, hipStream_t st);
+int flat_masked_form(int metric, int D);   // 0 fp32 row-major rows, queries in LDS; 1 fp32 blocked rows, queries in SGPRs; 2 uint8 single bytes; 3 uint8 16-byte pieces
+// qt queries per workgroup (1 or 4; 1 for k > 128), `parts` workgroups per query group dividing the LIST in whole 512-entry tiles by
+// the device-side length *len; part_d / part_id: [nq][parts][k] (with parts == 1 they may be the result arrays); ids are rows
+int launch_flat_masked_search(int metric, int D, const void *data, int64_t n, const void *q, int64_t nq, int k, int qt, int parts,
+                              const uint32_t *list, const int64_t *len, float *part_d, int64_t *part_id, hipStream_t st);
+int launch_flat_masked_pad(void *dist, int64_t *labels, int64_t count, hipStream_t st);   // every distance field 0x7f800000, every label -1
+
 // ---- flat.hip ----
 int flat_plan_splits(int64_t n, int64_t nq, int qtile);
 int flat_qtile(int64_t nq);

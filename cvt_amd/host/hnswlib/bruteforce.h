@@ -22,6 +22,13 @@
 #include "../../../include/cvtmi.h"
 
 namespace hnswlib {
+// current hnswlib's filter (hnswlib.h: BaseFilterFunctor), an extension here: the reference's searchKnn takes none.  true = the label
+// may be returned
+struct BaseFilterFunctor {
+    virtual bool operator()(labeltype) { return true; }
+    virtual ~BaseFilterFunctor() {}
+};
+
 template <typename dist_t> class BruteforceSearch : public AlgorithmInterface<dist_t> {
 public:
     BruteforceSearch(SpaceInterface<dist_t> *s) : data_(NULL), maxelements_(0), cur_element_count(0), h_(NULL), dirty_(true)
@@ -104,6 +111,40 @@ public:
         static_assert(sizeof(dist_t) == 4, "distances are 32-bit (float or int)");
         if (cvtmi_flat_search(h_, queries, (int64_t)nq, (int)k, dist, labels) != CVTMI_OK)
             throw std::runtime_error(std::string("cvtmi_flat_search: ") + cvtmi_last_error());
+    }
+
+    // searchKnn among the labels the functor allows (current hnswlib's signature; not in the reference).  NULL = the unfiltered call
+    std::priority_queue<std::pair<dist_t, labeltype> > searchKnn(void *query_data, size_t k, BaseFilterFunctor *isIdAllowed)
+    {
+        if (!isIdAllowed) return searchKnn(query_data, k);
+        std::priority_queue<std::pair<dist_t, labeltype> > top;
+        if (k == 0) return top;
+        std::vector<dist_t> d(k);
+        std::vector<int64_t> l(k);
+        searchKnnBatch(query_data, 1, k, d.data(), l.data(), isIdAllowed);
+        for (size_t i = 0; i < k; ++i)
+            if (l[i] >= 0) top.push(std::pair<dist_t, labeltype>(d[i], (labeltype)l[i]));
+        return top;
+    }
+
+    // nq queries under one filter: the functor is evaluated once per resident label on the host, the allowed labels become the row
+    // mask of the device copy (cvtmi_flat_mask_labels) and cvtmi_flat_search_masked answers
+    void searchKnnBatch(const void *queries, size_t nq, size_t k, dist_t *dist, int64_t *labels, BaseFilterFunctor *isIdAllowed)
+    {
+        if (!isIdAllowed) return searchKnnBatch(queries, nq, k, dist, labels);
+        sync_device();
+        static_assert(sizeof(dist_t) == 4, "distances are 32-bit (float or int)");
+        std::vector<int64_t> allowed;
+        for (size_t i = 0; i < cur_element_count; ++i) {
+            const labeltype lab = *((const labeltype *)(data_ + size_per_element_ * i + data_size_));
+            if ((*isIdAllowed)(lab)) allowed.push_back((int64_t)lab);
+        }
+        std::vector<uint64_t> mask((cur_element_count + 63) / 64);
+        if (cvtmi_flat_mask_labels(h_, allowed.data(), (int64_t)allowed.size(), mask.data(), (int64_t)mask.size()) != CVTMI_OK)
+            throw std::runtime_error(std::string("cvtmi_flat_mask_labels: ") + cvtmi_last_error());
+        static const uint64_t none = 0;   // (an empty index has no mask words, and the call still wants a pointer)
+        if (cvtmi_flat_search_masked(h_, queries, (int64_t)nq, (int)k, mask.empty() ? &none : mask.data(), (int64_t)mask.size(), dist, labels) != CVTMI_OK)
+            throw std::runtime_error(std::string("cvtmi_flat_search_masked: ") + cvtmi_last_error());
     }
 
     // every row with distance < radius (not in the reference: cvtmi_flat_range_search), as (distance, label) in the order of the

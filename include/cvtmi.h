@@ -607,7 +607,9 @@ int cvtmi_flat_remove_labels_dev(cvtmi_flat_t h, const int64_t *labels, int64_t 
  *                      does; a huge value = none: C is cut down to the rows of a part and so that the area, nq x parts x C x 8
  *                      bytes, stays within 256 MB.  -1 (default) = 512.
  *   "rerank_rows_copy" 0 (default) / 1: whether cvtmi_flat_rerank may build a row-major copy of blocked fp32 rows -- a second copy
- *                      of the table in device memory against eight times the gather traffic (see cvtmi_flat_rerank). */
+ *                      of the table in device memory against eight times the gather traffic (see cvtmi_flat_rerank).
+ *   "masked_parts"     workgroups per query group of cvtmi_flat_search_masked, each walking an equal share of the allowed rows:
+ *                      0 (default) = the plan for a mask that allows every row, 1 .. 1024 = that many parts. */
 int cvtmi_flat_set_param(cvtmi_flat_t h, const char *name, int64_t value);
 /* searchKnn (brutoforce.hpp:73-93) for nq queries: k smallest (distance, label), ascending.
  * dist is float[nq][k] for IP / L2F and int32_t[nq][k] for L2U8.  1 <= k <= CVTMI_K_MAX.  An index with fewer than k rows pads:
@@ -713,6 +715,56 @@ int cvtmi_opq_search_refine(cvtmi_opq_t h, cvtmi_flat_t flat, const float *q, in
                             int k, int R, float *dist, int64_t *labels);
 int cvtmi_opq_search_refine_dev(cvtmi_opq_t h, cvtmi_flat_t flat, const float *q, int64_t nq, int rotate, int nprobe,
                                 int k, int R, float *dist, int64_t *labels, void *stream);
+/* Masked search: the k nearest rows among those a bitmap allows -- search under a filter (tenant, date range, not yet seen, the ids a
+ * relational query returned), the counterpart of faiss's IDSelector and of hnswlib's searchKnn(query, k, BaseFilterFunctor *).  q holds
+ * nq rows of the index's own type, mask is uint64[mask_words].
+ *   Mask     bit r & 63 of word r >> 6 allows ROW r.  A row is a position, in insertion order, as removals left it -- the addressing of
+ *            cvtmi_flat_rerank's candidates with cand_base = 0.  One mask serves all nq queries of the call.
+ *            mask_words >= ceil(ntotal / 64), checked under the handle's lock: fewer fails with CVTMI_EINVAL (a mask built before a
+ *            cvtmi_flat_add is too short, not silently wrong).  Bits at positions >= ntotal are ignored whatever they hold, and words
+ *            behind ceil(ntotal / 64) are never read: a caller may pass all-ones words.
+ *   Distance the one cvtmi_flat_search reports for that (query, row), bit for bit: IP is 1 - sum in the 4-lane order; L2F sums in 8
+ *            lanes for D % 16 == 0, in 4 lanes for D % 4 == 0 and in the scalar loop otherwise; L2U8 is the exact int32 sum over
+ *            D / 4 * 4 bytes.  dist holds 4-byte fields: float for IP and L2F, int32 for L2U8.
+ *   Order    ascending (distance, row), the device tie rule of cvtmi_flat_search.  Floats compare as in cvtmi_topk_select:
+ *            -0.0 == +0.0, NaN by its key.  A NaN distance is a real candidate, ordered by its key: a query holding a NaN returns
+ *            min(k, allowed rows) distinct allowed rows, all with NaN distances.  With fewer than k allowed rows the list pads with
+ *            label -1 and distance field 0x7f800000, as cvtmi_flat_search pads.
+ *   Labels   what cvtmi_flat_search would report for the row: id_base + row while labels are implicit, otherwise the stored label.
+ *   In short for NaN-free data the result equals cvtmi_flat_search(k) on a fresh handle that holds only the allowed rows, in their
+ *            order, with the labels they report.
+ *   Limits   1 <= k <= CVTMI_K_MAX; nq <= INT32_MAX (more fails with CVTMI_EUNSUPPORTED); ntotal < 2^32.
+ * Checked before any device work: NULL h, or NULL q / mask / dist / labels with nq > 0, nq < 0, mask_words < 0, k out of range ->
+ * CVTMI_EINVAL.  nq == 0 does nothing; an empty index or an all-zero mask pads everything.
+ * Concurrency: a masked search is a search.  It takes the shared lock and a scratch set of its own, runs beside the other searches of
+ * the handle and waits behind cvtmi_flat_add / _remove_labels / _reset like them.  The `_dev` entry enqueues on `stream` and never waits
+ * for the device; mask, queries and outputs are device pointers there.
+ * Shards: there is no collective form.  Each rank passes the mask of its own rows (cvtmi_flat_set_id_base makes the labels global)
+ * and the caller merges the lists with cvtmi_topk_merge.
+ * One form for every density: the mask is compacted on the device into an ascending list of the allowed rows (per-tile popcounts, a
+ * scan, no atomics; 4 bytes per row at most, in the leased scratch set; the host never learns its length), and the exact kernels of
+ * cvtmi_flat_search walk the LIST, one lane per allowed row.  The parts of a query group divide the list, not the rows, so the work
+ * is even however the mask clusters; the grid is planned for the worst case ("masked_parts": cvtmi_flat_set_param).  An all-ones
+ * mask reads what the exact search reads plus 4 bytes per row; a sparse mask reads the allowed rows only. */
+int cvtmi_flat_search_masked(cvtmi_flat_t h, const void *q, int64_t nq, int k, const uint64_t *mask, int64_t mask_words,
+                             void *dist, int64_t *labels);
+int cvtmi_flat_search_masked_dev(cvtmi_flat_t h, const void *q, int64_t nq, int k, const uint64_t *mask, int64_t mask_words,
+                                 void *dist, int64_t *labels, void *stream);
+/* The mask of a label set: writes all mask_words words -- the bit of every row whose reported label (id_base + row while labels are
+ * implicit, the stored label otherwise) is in labels[n_labels] is set, every other bit is cleared, those at positions >= ntotal
+ * included.  The set follows the rules of cvtmi_flat_remove_labels: unsorted, duplicates, foreign labels and any int64 are fine, and
+ * several rows sharing a label are all set.  n_labels == 0 clears the mask.  mask_words >= ceil(ntotal / 64), else CVTMI_EINVAL; NULL
+ * h, a negative count, a NULL set with n_labels > 0 or a NULL mask with mask_words > 0 -> CVTMI_EINVAL before any device work.
+ * Non-mutating: the shared lock and a leased scratch set, like a search; the work is the mark step of cvtmi_flat_remove_labels.  The
+ * _dev entry (set and mask are device pointers) runs on `stream`; on a handle with explicit labels it waits for its set to reach the
+ * host, where it is sorted (8 bytes per label).  The caller inverts or combines masks with plain word operations. */
+int cvtmi_flat_mask_labels(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, uint64_t *mask, int64_t mask_words);
+int cvtmi_flat_mask_labels_dev(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, uint64_t *mask, int64_t mask_words,
+                               void *stream);
+/* The handle's last masked search: out = { queries per workgroup, parts per query group, bytes of the row list, kernel form }.
+ * Forms: 0 fp32 row-major rows with queries in LDS; 1 fp32 blocked rows with queries in SGPRs; 2 uint8 single bytes; 3 uint8 16-byte
+ * pieces. */
+int cvtmi_flat_last_masked(cvtmi_flat_t h, int64_t out[4]);
 /* Measurement hook: how the last search was answered -- *filtered = 0 the exact kernels; 1 the sample + matrix-core filter
  * pipeline (fp32 metrics, 32 <= D <= 128, D % 16 == 0, >= 131072 rows: exact search of a leading sample, bf16 matrix-core
  * products decide which other rows need an exact distance); 2 the fp32 stream (D in {32, 64, 96, 128, 192, 256}, >= 32768 rows:
