@@ -334,6 +334,81 @@ class OpqIndex:
         _check(lib().cvtmi_opq_last_ivf_plan(self.h, o))
         return dict(rule=o[0], G=o[1], groups=o[2], pieces=o[3], rows_per_piece=o[4], parts=o[5], part_bytes=o[6], entry_bytes=o[7])
 
+    def _mask_words(self, mask, dev):
+        """`mask` as uint64 words (bit i & 63 of word i >> 6 = insertion index i), as FlatIndex._mask_words: words stay as they are
+        (np.uint64 for the host entry, a torch int64 / uint64 device tensor for the device entry), a bool array of length ntotal
+        is packed little-endian."""
+        if _is_torch(mask):
+            import torch
+            if mask.dtype == torch.bool:
+                pad = (-mask.shape[0]) % 64
+                bits = torch.nn.functional.pad(mask.reshape(-1).to(torch.int64), (0, pad)).reshape(-1, 64)
+                # (bit 63 wraps into the sign of the int64 word: the same 64 bits)
+                return (bits << torch.arange(64, device=mask.device, dtype=torch.int64)).sum(dim=1).contiguous()
+            assert mask.dtype in (torch.int64, torch.uint64) and mask.is_cuda == dev
+            return mask.reshape(-1).contiguous()
+        mask = np.asarray(mask)
+        if mask.dtype == np.bool_:
+            assert mask.ndim == 1 and mask.shape[0] == self.ntotal, "a bool mask has one entry per insertion index"
+            packed = np.packbits(mask, bitorder="little")
+            words = np.zeros((mask.shape[0] + 63) // 64 * 8, dtype=np.uint8)
+            words[:packed.shape[0]] = packed
+            return words.view("<u8").astype(np.uint64, copy=False)
+        assert mask.dtype == np.uint64, "a mask is np.uint64 words or a bool array of length ntotal"
+        return np.ascontiguousarray(mask.reshape(-1))
+
+    def search_ivf_masked(self, q, nprobe, k, mask, rotate=True, out=None):
+        """search_ivf among the entries `mask` allows (cvtmi_opq_search_ivf_masked).  mask: uint64 words, bit i & 63 of word i >> 6
+        allowing the entry with INSERTION INDEX i (id - id_base; at least ceil(ntotal / 64) words, bits past ntotal are ignored),
+        or a bool array of length ntotal; one mask serves every query.  numpy in (np.uint64 words), numpy out; torch device tensors (int64 / uint64 words) run on
+        torch's current stream.  Returns (distances [nq][k] float32, ids [nq][k] int64), padded with (+inf, -1)."""
+        nq = q.shape[0]
+        if _is_torch(q):
+            import torch
+            words = self._mask_words(mask, True)
+            if out is None:
+                d = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+                i = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+            else:
+                d, i = out
+            _check(lib().cvtmi_opq_search_ivf_masked_dev(self.h, _ptr(q), C.c_int64(nq), C.c_int(1 if rotate else 0), C.c_int(nprobe),
+                                                         C.c_int(k), _ptr(words), C.c_int64(words.shape[0]), _ptr(d), _ptr(i), _stream()))
+            return d, i
+        q = _np(q, np.float32)
+        words = self._mask_words(mask, False)
+        if out is None:
+            d = np.empty((nq, k), dtype=np.float32); i = np.empty((nq, k), dtype=np.int64)
+        else:
+            d, i = out
+            assert d.dtype == np.float32 and i.dtype == np.int64 and d.shape == (nq, k) and i.shape == (nq, k)
+            assert d.flags.c_contiguous and i.flags.c_contiguous
+        _check(lib().cvtmi_opq_search_ivf_masked(self.h, _ptr(q), C.c_int64(nq), C.c_int(1 if rotate else 0), C.c_int(nprobe), C.c_int(k),
+                                                 _ptr(words), C.c_int64(words.shape[0]), _ptr(d), _ptr(i)))
+        return d, i
+
+    def mask_from_videos(self, video_ids, words=None):
+        """The mask of the entries whose video id is in `video_ids` (cvtmi_opq_mask_videos; int32, numpy or a torch device tensor):
+        `words` uint64 words (default ceil(ntotal / 64)), every bit past ntotal cleared.  Invert or combine masks with plain word
+        operations (~m, a & b)."""
+        n_words = (self.ntotal + 63) // 64 if words is None else int(words)
+        if _is_torch(video_ids):
+            import torch
+            assert video_ids.dtype == torch.int32 and video_ids.is_cuda
+            video_ids = video_ids.reshape(-1)
+            mask = torch.empty(n_words, dtype=torch.int64, device=video_ids.device)
+            _check(lib().cvtmi_opq_mask_videos_dev(self.h, _ptr(video_ids), C.c_int64(video_ids.shape[0]), _ptr(mask), C.c_int64(n_words), _stream()))
+            return mask
+        video_ids = _np(video_ids, np.int32).reshape(-1)
+        mask = np.empty(n_words, dtype=np.uint64)
+        _check(lib().cvtmi_opq_mask_videos(self.h, _ptr(video_ids), C.c_int64(video_ids.shape[0]), _ptr(mask), C.c_int64(n_words)))
+        return mask
+
+    def last_ivf_masked(self):
+        """grid of the last search_ivf_masked on this handle (cvtmi_opq_last_ivf_masked)"""
+        o = (C.c_int64 * 8)()
+        _check(lib().cvtmi_opq_last_ivf_masked(self.h, o))
+        return dict(rule=o[0], G=o[1], groups=o[2], pieces=o[3], rows_per_piece=o[4], parts=o[5], part_bytes=o[6], mask_bytes=o[7])
+
     def range_search_ivf(self, q, nprobe, radius, rotate=True, want_video=False, out=None):
         """Range search (cvtmi_opq_range_search_ivf): every entry of the nprobe nearest coarse lists of a query whose score is
         < radius, in the order of the list-ordered copy.  Returns (lims [nq + 1] int64, distances, ids[, video ids]): the hits of

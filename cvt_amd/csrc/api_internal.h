@@ -121,6 +121,7 @@ struct OpqScratch : ScratchBase {
     static constexpr const char *kLeaseNoMemory = "opq search: out of host memory";
     DevBuf s_qrot, s_part_d, s_part_id, s_lut, s_gthr, s_qlut, s_qp, s_spill, s_items, s_probe;
     DevBuf s_ivf;              // partial lists of an IVF search (ivf_search.hip)
+    DevBuf s_masked;           // masked IVF search: the mask in list order; cvtmi_opq_mask_videos: the marked bitmap and its table
     DevBuf s_range;            // range search (ivf_range.hip): probe order, part counts and offsets, spill area; host entry: lims behind them
     DevBuf s_ref_d, s_ref_i;   // cvtmi_opq_search_refine: the [nq][R] candidate lists between the scan and the rerank
     ScanHPlan hplan;                       // the item table s_items holds ...
@@ -128,10 +129,11 @@ struct OpqScratch : ScratchBase {
     int hplan_splits = 0, hplan_key = 0;
     DevBuf io_q, io_d, io_i;   // device side of the host-pointer search (cvtmi_opq_search)
     DevBuf io_v;               // ... and the video ids of a range search
+    DevBuf io_m;               // ... and the mask words of the host-pointer masked search / cvtmi_opq_mask_videos
     PinBuf io_pin;             // its pinned staging area
     void release_all()
     {
-        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &s_range, &s_ref_d, &s_ref_i, &io_q, &io_d, &io_i, &io_v }) b->release();
+        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &s_masked, &s_range, &s_ref_d, &s_ref_i, &io_q, &io_d, &io_i, &io_v, &io_m }) b->release();
         io_pin.release();
         release_lease_state();
     }
@@ -163,6 +165,7 @@ struct cvtmi_opq_s {
     DevBuf csr_entry;
     bool want_entry = false, csr_entry_valid = false;
     int64_t ivf_last[8] = {};               // grid of the last IVF search (cvtmi_opq_last_ivf_plan), written under pool.mu
+    int64_t ivf_masked_last[8] = {};        // ... of the last masked IVF search (cvtmi_opq_last_ivf_masked)
     int64_t range_last[8] = {};             // ... and of the last range search (cvtmi_opq_last_range_plan)
     // scratch of the calls that run one at a time (query_video: probe lists, rotated queries)
     DevBuf s_qrot, s_probe, s_rot;

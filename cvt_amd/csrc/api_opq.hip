@@ -1028,10 +1028,17 @@ static int opq_ivf_prepare(cvtmi_opq_t h, hipStream_t st)
     h->want_entry = true;
     return opq_build_csr(h, st);
 }
+// mask != null (cvtmi_opq_search_ivf_masked): the caller's words on the device, at least ceil(n / 64) of them.  What is derived from
+// them -- the mask in list order -- lives in the leased set like the partial lists: searches with different masks run side by side
 static int opq_search_ivf_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64_t nq, int rotate, int nprobe, int k, float *dist, int64_t *ids,
-                                 hipStream_t st)
+                                 hipStream_t st, const uint64_t *mask = nullptr)
 {
     if (!h->csr_valid || !h->csr_entry_valid) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf: the index changed while the search was being prepared");
+    const size_t lmb = mask ? ivf_mask_bytes(h->csr_kept) : 0;
+    if (mask) {
+        CVTMI_TRY(S.s_masked.reserve(lmb));
+        CVTMI_TRY(launch_ivf_mask_order(mask, h->csr_entry.as<uint32_t>(), h->csr_kept, S.s_masked.as<uint64_t>(), st));
+    }
     const float *q_rot = q;
     if (rotate && (h->m.perm || h->m.R)) {
         CVTMI_TRY(S.s_qrot.reserve((size_t)nq * h->m.D * sizeof(float)));
@@ -1047,10 +1054,16 @@ static int opq_search_ivf_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, i
     {
         std::lock_guard<std::mutex> g(h->pool.mu);
         const int64_t v[8] = { plan.rule, plan.G, plan.groups, plan.pieces, plan.rows_per_piece, plan.parts(), (int64_t)pb, (int64_t)h->csr_entry.cap };
-        for (int i = 0; i < 8; ++i) h->ivf_last[i] = v[i];
+        if (mask) {
+            for (int i = 0; i < 6; ++i) h->ivf_masked_last[i] = v[i];
+            h->ivf_masked_last[6] = (int64_t)pb; h->ivf_masked_last[7] = (int64_t)lmb;
+        } else {
+            for (int i = 0; i < 8; ++i) h->ivf_last[i] = v[i];
+        }
     }
     return launch_ivf_search(h->m, q_rot, nq, nprobe, S.s_probe.as<int32_t>(), h->csr_off.as<int64_t>(), h->csr_codes.as<uint8_t>(),
-                             h->csr_entry.as<uint32_t>(), k, h->id_base, plan, pb ? S.s_ivf.p : nullptr, dist, ids, st);
+                             h->csr_entry.as<uint32_t>(), k, h->id_base, plan, pb ? S.s_ivf.p : nullptr, dist, ids, st,
+                             mask ? S.s_masked.as<uint64_t>() : nullptr);
 }
 // arguments first, before anything touches the device
 static int opq_search_ivf_check(cvtmi_opq_t h, const float *q, int64_t nq, int *nprobe, int k, const float *dist, const int64_t *ids)
@@ -1124,6 +1137,158 @@ int cvtmi_opq_ivf_plan(int64_t nq, int nprobe, int k, int64_t longest_list, int 
     const IvfPlan p = plan_ivf_search(nq, nprobe, k, longest_list, (size_t)tune_ivf_part_cap_mb.geti() << 20, cus > 0 ? cus : 256);
     const int64_t v[6] = { p.rule, p.G, p.groups, p.pieces, p.rows_per_piece, p.parts() };
     for (int i = 0; i < 6; ++i) out[i] = v[i];
+    return CVTMI_OK;
+}
+
+// ---- masked IVF search: the k nearest entries of the probed lists among those a bitmap of insertion indices allows ----
+// A search like cvtmi_opq_search_ivf: same preparation, shared lock, leased set; the mask's length is checked under the lock.
+static int opq_ivf_masked_check(cvtmi_opq_t h, const float *q, int64_t nq, int *nprobe, int k, const uint64_t *mask, int64_t mask_words, const float *dist,
+                                const int64_t *ids)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf_masked: null handle");
+    if (mask_words < 0 || (nq > 0 && !mask)) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf_masked: bad arguments");
+    return opq_search_ivf_check(h, q, nq, nprobe, k, dist, ids);
+}
+static int opq_mask_covers(cvtmi_opq_t h, int64_t mask_words, const char *fn)
+{
+    if (mask_words < (h->n + 63) / 64)
+        return fail(CVTMI_EINVAL, "%s: %lld mask words, %lld entries need %lld", fn, (long long)mask_words, (long long)h->n, (long long)((h->n + 63) / 64));
+    return CVTMI_OK;
+}
+
+int cvtmi_opq_search_ivf_masked_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k, const uint64_t *mask, int64_t mask_words,
+                                    float *dist, int64_t *ids, void *stream)
+{
+    CVTMI_TRY(opq_ivf_masked_check(h, q, nq, &nprobe, k, mask, mask_words, dist, ids));
+    CVTMI_TRY(use_device(h->device));
+    if (nq == 0) return CVTMI_OK;
+    hipStream_t st = (hipStream_t)stream;
+    for (int attempt = 0;; ++attempt) {   // (an append between the preparation and the shared lock sends the search round again)
+        CVTMI_TRY(opq_ivf_prepare(h, st));
+        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
+        CVTMI_TRY(opq_mask_covers(h, mask_words, "cvtmi_opq_search_ivf_masked"));
+        OpqLease lease;
+        CVTMI_TRY(lease.open(h, st, false));
+        return opq_search_ivf_leased(h, *lease.s, q, nq, rotate, nprobe, k, dist, ids, st, mask);
+    }
+}
+
+// host pointers: queries and mask words up, the two result arrays down, through the leased set's staging buffers and its own stream
+int cvtmi_opq_search_ivf_masked(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k, const uint64_t *mask, int64_t mask_words,
+                                float *dist, int64_t *ids)
+{
+    CVTMI_TRY(opq_ivf_masked_check(h, q, nq, &nprobe, k, mask, mask_words, dist, ids));
+    CVTMI_TRY(use_device(h->device));
+    if (nq == 0) return CVTMI_OK;
+    for (int attempt = 0;; ++attempt) {
+        CVTMI_TRY(opq_ivf_prepare(h, nullptr));
+        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
+        CVTMI_TRY(opq_mask_covers(h, mask_words, "cvtmi_opq_search_ivf_masked"));
+        OpqLease lease;
+        CVTMI_TRY(lease.open(h, nullptr, true));
+        OpqScratch &S = *lease.s;
+        hipStream_t st = lease.st;
+        const size_t qb = (size_t)nq * h->m.D * sizeof(float), mb = (size_t)((h->n + 63) / 64) * 8, db = (size_t)nq * k * sizeof(float),
+                     ib = (size_t)nq * k * sizeof(int64_t);
+        CVTMI_TRY(S.io_q.reserve(qb));
+        CVTMI_TRY(S.io_m.reserve(std::max<size_t>(mb, 16)));
+        CVTMI_TRY(S.io_d.reserve(db));
+        CVTMI_TRY(S.io_i.reserve(ib));
+        CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
+        if (mb) CVTMI_HIP(hipMemcpyAsync(S.io_m.p, mask, mb, hipMemcpyHostToDevice, st));   // (the words behind the entries are never read)
+        CVTMI_TRY(opq_search_ivf_leased(h, S, S.io_q.as<float>(), nq, rotate, nprobe, k, S.io_d.as<float>(), S.io_i.as<int64_t>(), st, S.io_m.as<uint64_t>()));
+        CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(hipMemcpyAsync(ids, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(stream_wait(st));
+        return CVTMI_OK;
+    }
+}
+
+int cvtmi_opq_last_ivf_masked(cvtmi_opq_t h, int64_t out[8])
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_opq_last_ivf_masked: null handle");
+    if (!out) return fail(CVTMI_EINVAL, "cvtmi_opq_last_ivf_masked: null");
+    std::lock_guard<std::mutex> g(h->pool.mu);
+    for (int i = 0; i < 8; ++i) out[i] = h->ivf_masked_last[i];
+    return CVTMI_OK;
+}
+
+// ---- the bitmap of a set of video ids: the mark step of the removal on a leased scratch set (the handle does not change) ----
+static int opq_remove_table(const int32_t *ids, int64_t nv, std::vector<int32_t> &tab);   // (with the removal, below)
+static int opq_mask_videos_check(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, const uint64_t *mask, int64_t mask_words)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_opq_mask_videos: null handle");
+    if (nv < 0 || mask_words < 0 || (nv > 0 && !video_ids) || (mask_words > 0 && !mask)) return fail(CVTMI_EINVAL, "cvtmi_opq_mask_videos: bad arguments");
+    return CVTMI_OK;
+}
+
+// table: the distinct ids of the set, ascending, in host memory; mask: a device pointer of mask_words words.  Under the shared lock
+static int opq_mask_videos_leased(cvtmi_opq_t h, OpqScratch &S, const int32_t *table, int64_t T, uint64_t *mask, int64_t mask_words, hipStream_t st)
+{
+    if (mask_words == 0) return CVTMI_OK;
+    if (h->n == 0 || T == 0) {
+        CVTMI_HIP(hipMemsetAsync(mask, 0, (size_t)mask_words * 8, st));
+        return CVTMI_OK;
+    }
+    const RmPlan p = rm_plan(h->n, 0, T, 0);   // the mark's areas alone (everything before off_codes): no row moves
+    CVTMI_TRY(S.s_masked.reserve(p.off_codes));
+    void *W = S.s_masked.p;
+    CVTMI_HIP(hipMemcpyAsync(static_cast<char *>(W) + p.off_table, table, (size_t)T * 4, hipMemcpyHostToDevice, st));
+    CVTMI_TRY(launch_rm_mark_videos(p, W, h->has_videos ? h->videos.as<int32_t>() : nullptr, st));
+    return launch_flat_masked_copy(p, W, mask, mask_words, st);
+}
+
+int cvtmi_opq_mask_videos_dev(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, uint64_t *mask, int64_t mask_words, void *stream)
+{
+    CVTMI_TRY(opq_mask_videos_check(h, video_ids, nv, mask, mask_words));
+    CVTMI_TRY(use_device(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    CVTMI_TRY(opq_mask_covers(h, mask_words, "cvtmi_opq_mask_videos"));
+    OpqLease lease;
+    CVTMI_TRY(lease.open(h, st, false));
+    std::vector<int32_t> raw, tab;
+    if (nv > 0 && h->n > 0 && mask_words > 0) {   // the set is sorted on the host: it comes down first (4 bytes per id)
+        try {
+            raw.resize((size_t)nv);
+        } catch (...) {
+            return fail(CVTMI_ENOMEM, "cvtmi_opq_mask_videos: out of host memory");
+        }
+        CVTMI_HIP(hipMemcpyAsync(raw.data(), video_ids, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(stream_wait(st));
+        CVTMI_TRY(opq_remove_table(raw.data(), nv, tab));
+    }
+    CVTMI_TRY(opq_mask_videos_leased(h, *lease.s, tab.data(), (int64_t)tab.size(), mask, mask_words, st));
+    if (!tab.empty()) CVTMI_HIP(stream_wait(st));   // (the table leaves host memory that ends with this call)
+    return CVTMI_OK;
+}
+
+int cvtmi_opq_mask_videos(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, uint64_t *mask, int64_t mask_words)
+{
+    CVTMI_TRY(opq_mask_videos_check(h, video_ids, nv, mask, mask_words));
+    CVTMI_TRY(use_device(h->device));
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    CVTMI_TRY(opq_mask_covers(h, mask_words, "cvtmi_opq_mask_videos"));
+    if (mask_words == 0) return CVTMI_OK;
+    if (h->n == 0 || nv == 0) {
+        memset(mask, 0, (size_t)mask_words * 8);
+        return CVTMI_OK;
+    }
+    std::vector<int32_t> tab;
+    CVTMI_TRY(opq_remove_table(video_ids, nv, tab));
+    OpqLease lease;
+    CVTMI_TRY(lease.open(h, nullptr, true));
+    OpqScratch &S = *lease.s;
+    hipStream_t st = lease.st;
+    // only the words that can hold an entry pass through the device; the caller's words behind them are cleared here
+    const int64_t words = (h->n + 63) / 64;
+    CVTMI_TRY(S.io_m.reserve((size_t)words * 8));
+    CVTMI_TRY(opq_mask_videos_leased(h, S, tab.data(), (int64_t)tab.size(), S.io_m.as<uint64_t>(), words, st));
+    CVTMI_HIP(hipMemcpyAsync(mask, S.io_m.p, (size_t)words * 8, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    memset(mask + words, 0, (size_t)(mask_words - words) * 8);
     return CVTMI_OK;
 }
 

@@ -21,6 +21,9 @@
 // Keys are the raw bits of the scores: sums of squares are >= +0, so the bit patterns order like the values, +inf (0x7f800000)
 // after every finite score and NaN patterns after that.  A query holding a NaN scores NaN everywhere; its entries then tie or
 // order by NaN payload bits, and what comes back is min(k, entries) distinct entries with NaN distances.
+//
+// cvtmi_opq_search_ivf_masked is the same scan under a bitmap of allowed entries (the MASKED instantiations, below): the mask is
+// brought into list order once per call, and a workgroup leaves a list whose rows are all disallowed before it builds the table.
 #include <algorithm>
 
 #include "block_topk.h"
@@ -32,6 +35,7 @@ namespace cvtmi {
 
 constexpr int IVF_CAP = 512, IVF_TRIG = 384;   // k <= 128; larger k: kBigCap / kBigTrig, as the generic exact scan
 constexpr unsigned long long IVF_NONE = ~0ull; // an empty slot of a partial list (no entry has key KEY_MAX)
+constexpr uint32_t IVF_NO_ROW = ~0u;           // masked scan: the payload of a row the mask does not allow (fewer than 2^32 entries: no insertion index is ~0u)
 
 __device__ __forceinline__ uint32_t ivf_key(float s)
 {
@@ -55,19 +59,87 @@ __device__ __forceinline__ void ivf_offer(TopKShared<1, CAP> &tk, int k, int til
     });
 }
 
+// Masked search (cvtmi_opq_search_ivf_masked).  The caller's mask addresses insertion indices; this kernel brings it into the order
+// the scan walks: one lane per row r of the list-ordered copy reads the caller's bit of entry[r] (a gather into a bitmap of n / 8
+// bytes, cache-resident), and one __ballot per wave64 is the word of rows [64 w, 64 w + 64), stored by one lane.  No atomics; rows
+// behind the copy's end contribute 0.
+__global__ __launch_bounds__(kBlock) void ivf_mask_order_kernel(const unsigned long long *__restrict__ mask, const uint32_t *__restrict__ entry,
+                                                                int64_t n_csr, unsigned long long *__restrict__ lmask)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool on = false;
+    if (r < n_csr) {
+        const uint32_t i = entry[r];
+        on = (mask[i >> 6] >> (i & 63u)) & 1ull;
+    }
+    const unsigned long long w = __ballot(on);
+    if ((threadIdx.x & 63) == 0 && r < n_csr) lmask[r >> 6] = w;   // (r = 64 w: the word holds at least row r)
+}
+
+__device__ __forceinline__ bool ivf_mask_bit(const unsigned long long *__restrict__ lmask, int64_t r)
+{
+    return (reinterpret_cast<const uint32_t *>(lmask)[r >> 5] >> (r & 31)) & 1u;   // (little endian: bit r of the uint64 view)
+}
+
+// does the mask allow any row of [b, e)?  b < e; the words of the range are spread over the workgroup's threads and the two edge words
+// are cut to the range (b and e are no multiples of 64).  Every thread that saw a bit raises flag[round % 3] and ALL threads read it
+// behind one barrier: every thread gets the same answer, so the caller may branch around barriers on it.  Must be reached by all
+// threads of the workgroup, with the workgroup-uniform count of the calls so far as `round`.  The three flags (zero at the start)
+// rotate like those of topk_tile_end: the flag of round + 1 is cleared here, BEFORE this round's barrier -- its last readers (round
+// - 2) passed the barrier of round - 1 since, and its next writers come after this one.  (__syncthreads_or would do, but the
+// library's reduction costs the kernel 6 VGPRs -- a workgroup per CU -- and 256 bytes of LDS.)
+__device__ __forceinline__ bool ivf_mask_any(const unsigned long long *__restrict__ lmask, int64_t b, int64_t e, int tid, int *flag, int round)
+{
+    const int64_t w0 = b >> 6, w1 = (e - 1) >> 6;
+    unsigned long long acc = 0ull;
+    for (int64_t w = w0 + tid; w <= w1; w += kBlock) {
+        unsigned long long x = lmask[w];
+        if (w == w0) x &= ~0ull << (b & 63);
+        if (w == w1) x &= ~0ull >> (63 - ((e - 1) & 63));
+        acc |= x;
+    }
+    const int f = round % 3;
+    if (acc != 0ull) flag[f] = 1;
+    if (tid == 0) flag[(round + 1) % 3] = 0;
+    __syncthreads();
+    return flag[f] != 0;
+}
+
+// the same question for one tile, [lo, hi) with hi - lo <= kBlock: at most five words, and EVERY thread reads all of them -- the same
+// read-only words at workgroup-uniform addresses, so every thread holds the same answer without a barrier
+__device__ __forceinline__ bool ivf_mask_any_tile(const unsigned long long *__restrict__ lmask, int64_t lo, int64_t hi)
+{
+    const int64_t w0 = lo >> 6, w1 = (hi - 1) >> 6;
+    unsigned long long acc = 0ull;
+    for (int64_t w = w0; w <= w1; ++w) {
+        unsigned long long x = lmask[w];
+        if (w == w0) x &= ~0ull << (lo & 63);
+        if (w == w1) x &= ~0ull >> (63 - ((hi - 1) & 63));
+        acc |= x;
+    }
+    return acc != 0ull;
+}
+
 // part == nullptr: the workgroup holds everything of its query (one group, one piece) and writes the result rows itself;
-// otherwise it writes its k best as sorted (key << 32 | insertion index) words to partial list (group * pieces + piece) of the query
-template <int CAP, int TRIG>
+// otherwise it writes its k best as sorted (key << 32 | insertion index) words to partial list (group * pieces + piece) of the query.
+// MASKED: lmask holds one bit per row of the list-ordered copy (ivf_mask_order_kernel) and only rows whose bit is set are offered.
+// A workgroup whose [b, e) of a list holds no allowed row leaves the list before its table is built -- the table, not the rows, is
+// what a (query, list) pair costs -- and a piece of several tiles skips the tiles without one.  Both decisions are the same in
+// every thread (ivf_mask_any: a flag read behind a barrier; ivf_mask_any_tile: the same words read by all), so they are
+// workgroup-uniform like the other `continue`s, and `tile` counts only the tiles that reach topk_tile_end (its flags rotate with
+// that counter).  The unmasked instantiations take a null lmask and compile no masked line.
+template <int CAP, int TRIG, bool MASKED>
 __global__ __launch_bounds__(kBlock) void ivf_search_kernel(const float *__restrict__ q_rot, int D, int M, int K, int step,
                                                             const float *__restrict__ coarse, const float *__restrict__ books, int nprobe,
                                                             const int32_t *__restrict__ probe, const int64_t *__restrict__ list_off,
                                                             const uint8_t *__restrict__ codes, const uint32_t *__restrict__ entry, int k, int G,
                                                             int groups, int pieces, int rows_per_piece, int64_t id_base,
                                                             float *__restrict__ out_d, int64_t *__restrict__ out_id,
-                                                            unsigned long long *__restrict__ part)
+                                                            unsigned long long *__restrict__ part, const unsigned long long *__restrict__ lmask)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];  // res[D rounded up to 4] + lut[M][256]
     __shared__ TopKShared<1, CAP> tk;
+    __shared__ int any_flag[3];   // MASKED: ivf_mask_any's rotating flags (12 bytes; the unmasked instantiations never touch them)
     float *res = sm;
     float *lut = sm + ((D + 3) & ~3);
     const int piece = (int)(blockIdx.x % (unsigned)pieces);
@@ -76,9 +148,12 @@ __global__ __launch_bounds__(kBlock) void ivf_search_kernel(const float *__restr
     const int64_t qi = qg / groups;
     const int tid = threadIdx.x;
     topk_init(tk);
+    if constexpr (MASKED) {
+        if (tid < 3) any_flag[tid] = 0;
+    }
     __syncthreads();
     const int s0 = g * G, s1 = s0 + G < nprobe ? s0 + G : nprobe;
-    int tile = 0;
+    int tile = 0, round = 0;
     for (int s = s0; s < s1; ++s) {
         const int l = probe[qi * nprobe + s];
         if (l < 0) continue;  // workgroup-uniform
@@ -86,29 +161,45 @@ __global__ __launch_bounds__(kBlock) void ivf_search_kernel(const float *__restr
         int64_t e = b + rows_per_piece;
         e = e < list_off[l + 1] ? e : list_off[l + 1];
         if (b >= e) continue;  // workgroup-uniform: an empty list, or a piece past its end
+        bool tiles = false;    // MASKED: the piece has more than one tile, each is asked for an allowed row
+        if constexpr (MASKED) {
+            if (!ivf_mask_any(lmask, b, e, tid, any_flag, round++)) continue;  // workgroup-uniform (see ivf_mask_any): no allowed row, no table
+            tiles = e - b > kBlock;
+        }
         // the first tile's rows are on their way while the table is built
         ivf_u32x4 v = { 0u, 0u, 0u, 0u };
-        uint32_t pay = 0;
-        if (M == 16 && b + tid < e) {
+        uint32_t pay = MASKED ? IVF_NO_ROW : 0;   // MASKED: the bit of a row travels with it -- pay stays IVF_NO_ROW unless it is set
+        if (M == 16 && b + tid < e && (!MASKED || ivf_mask_bit(lmask, b + tid))) {
             v = __builtin_nontemporal_load(reinterpret_cast<const ivf_u32x4 *>(codes) + (b + tid));
             pay = entry[b + tid];
         }
         ivf_build_table(res, lut, q_rot + qi * D, coarse + (int64_t)l * D, books, D, M, K, step, tid);
-        for (int64_t base = b; base < e; base += kBlock, ++tile) {
+        for (int64_t base = b; base < e; base += kBlock) {
             const int64_t r = base + tid;
-            const bool have = r < e;
+            bool have = r < e;
             float sc = 0.0f;
             if (M == 16) {
                 const ivf_u32x4 cur = v;
                 const uint32_t cur_pay = pay;
+                if constexpr (MASKED) {
+                    have = cur_pay != IVF_NO_ROW;   // (of THIS tile's row: read when it was requested)
+                    pay = IVF_NO_ROW;
+                }
                 const int64_t rn = r + kBlock;   // the next tile's row is requested before this one is summed
-                if (rn < e) {
+                if (rn < e && (!MASKED || ivf_mask_bit(lmask, rn))) {
                     v = __builtin_nontemporal_load(reinterpret_cast<const ivf_u32x4 *>(codes) + rn);
                     pay = entry[rn];
+                }
+                if constexpr (MASKED) {
+                    if (tiles && !ivf_mask_any_tile(lmask, base, base + kBlock < e ? base + kBlock : e)) continue;  // workgroup-uniform: a tile without an allowed row
                 }
                 if (have) sc = ivf_score16(lut, cur);
                 ivf_offer<CAP, TRIG>(tk, k, tile, have, ivf_key(sc), cur_pay);
             } else {
+                if constexpr (MASKED) {
+                    if (tiles && !ivf_mask_any_tile(lmask, base, base + kBlock < e ? base + kBlock : e)) continue;  // workgroup-uniform, as above
+                    have = have && ivf_mask_bit(lmask, r);
+                }
                 uint32_t p = 0;
                 if (have) {
                     sc = ivf_score_row(lut, codes + r * M, M);
@@ -116,6 +207,7 @@ __global__ __launch_bounds__(kBlock) void ivf_search_kernel(const float *__restr
                 }
                 ivf_offer<CAP, TRIG>(tk, k, tile, have, ivf_key(sc), p);
             }
+            ++tile;
         }
         // (every tile ended with a barrier: the table and the residual may be overwritten)
     }
@@ -213,9 +305,19 @@ size_t ivf_part_bytes(const IvfPlan &p, int64_t nq, int k)
     return p.parts() > 1 ? (size_t)nq * p.parts() * k * sizeof(unsigned long long) : 0;
 }
 
+size_t ivf_mask_bytes(int64_t n_csr) { return (size_t)std::max<int64_t>((n_csr + 63) / 64, 2) * 8; }
+
+int launch_ivf_mask_order(const uint64_t *mask, const uint32_t *entry, int64_t n_csr, uint64_t *lmask, hipStream_t st)
+{
+    if (n_csr <= 0) return CVTMI_OK;   // no row, no word: every list is empty and the scan never asks
+    if (!mask || !entry || !lmask) return fail(CVTMI_EINVAL, "search_ivf_masked: bad arguments");
+    return launch("ivf_mask_order_kernel", ivf_mask_order_kernel, blocks_for(n_csr, kBlock), kBlock, 0, st, reinterpret_cast<const unsigned long long *>(mask), entry,
+                  n_csr, reinterpret_cast<unsigned long long *>(lmask));
+}
+
 int launch_ivf_search(const OpqModelDev &m, const float *q_rot, int64_t nq, int nprobe, const int32_t *probe, const int64_t *list_off,
                       const uint8_t *codes, const uint32_t *entry, int k, int64_t id_base, const IvfPlan &p, void *part, float *out_d,
-                      int64_t *out_id, hipStream_t st)
+                      int64_t *out_id, hipStream_t st, const uint64_t *lmask)
 {
     if (nq <= 0) return CVTMI_OK;
     if (m.K > 256) return fail(CVTMI_EUNSUPPORTED, "search_ivf: K=%d > 256", m.K);
@@ -230,8 +332,11 @@ int launch_ivf_search(const OpqModelDev &m, const float *q_rot, int64_t nq, int 
     if (lds + (k <= 128 ? sizeof(TopKShared<1, IVF_CAP>) : sizeof(TopKShared<1, kBigCap>)) > ((size_t)64 << 10))
         return fail(CVTMI_EUNSUPPORTED, "search_ivf: D=%d does not fit the workgroup's LDS", m.D);
     const bool small = k <= 128;   // the selection buffer of block_topk.h that holds k
-    CVTMI_TRY(launch("ivf_search_kernel", small ? ivf_search_kernel<IVF_CAP, IVF_TRIG> : ivf_search_kernel<kBigCap, kBigTrig>, blocks, kBlock, lds, st, q_rot, m.D, m.M, m.K,
-                     m.step, m.coarse, m.books, nprobe, probe, list_off, codes, entry, k, p.G, p.groups, p.pieces, p.rows_per_piece, id_base, out_d, out_id, pw));
+    const unsigned long long *lm = reinterpret_cast<const unsigned long long *>(lmask);
+    auto kern = lm ? (small ? ivf_search_kernel<IVF_CAP, IVF_TRIG, true> : ivf_search_kernel<kBigCap, kBigTrig, true>)
+                   : (small ? ivf_search_kernel<IVF_CAP, IVF_TRIG, false> : ivf_search_kernel<kBigCap, kBigTrig, false>);
+    CVTMI_TRY(launch(lm ? "ivf_search_kernel<masked>" : "ivf_search_kernel", kern, blocks, kBlock, lds, st, q_rot, m.D, m.M, m.K,
+                     m.step, m.coarse, m.books, nprobe, probe, list_off, codes, entry, k, p.G, p.groups, p.pieces, p.rows_per_piece, id_base, out_d, out_id, pw, lm));
     if (parts > 1)
         CVTMI_TRY(launch("ivf_merge_kernel", small ? ivf_merge_kernel<IVF_CAP, IVF_TRIG> : ivf_merge_kernel<kBigCap, kBigTrig>, nq, kBlock, 0, st, pw, parts * k, k, id_base, out_d,
                          out_id));

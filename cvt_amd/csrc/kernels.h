@@ -217,10 +217,15 @@ struct IvfPlan {
 IvfPlan plan_ivf_search(int64_t nq, int nprobe, int k, int64_t longest, size_t part_cap, int cus = 0);
 size_t ivf_part_bytes(const IvfPlan &p, int64_t nq, int k);
 // probe [nq][nprobe] (launch_coarse_probe); list_off / codes / entry: the list-ordered copy with its insertion indices;
-// part: ivf_part_bytes() of scratch (may be null when that is 0); out_d / out_id [nq][k], padded with (+inf, -1)
+// part: ivf_part_bytes() of scratch (may be null when that is 0); out_d / out_id [nq][k], padded with (+inf, -1).
+// lmask != null (cvtmi_opq_search_ivf_masked): one bit per row of the list-ordered copy, only rows whose bit is set are candidates
 int launch_ivf_search(const OpqModelDev &m, const float *q_rot, int64_t nq, int nprobe, const int32_t *probe, const int64_t *list_off,
                       const uint8_t *codes, const uint32_t *entry, int k, int64_t id_base, const IvfPlan &p, void *part, float *out_d,
-                      int64_t *out_id, hipStream_t st);
+                      int64_t *out_id, hipStream_t st, const uint64_t *lmask = nullptr);
+// the caller's mask (bit i & 63 of word i >> 6 = insertion index i; every entry[r] must have a word) in list order: lmask gets
+// ceil(n_csr / 64) words, bit r & 63 of word r >> 6 = row r of the copy; room for ivf_mask_bytes(n_csr)
+size_t ivf_mask_bytes(int64_t n_csr);
+int launch_ivf_mask_order(const uint64_t *mask, const uint32_t *entry, int64_t n_csr, uint64_t *lmask, hipStream_t st);
 
 // ---- ivf_range.hip ----  every entry of the probed lists with score < radius (cvtmi_opq_range_search_ivf)
 struct IvfRangePlan {

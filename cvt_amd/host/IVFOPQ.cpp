@@ -226,6 +226,23 @@ int IVFOPQ::SearchTopKProbe(const float *q, int nq, int nprobe, int k, float *di
     return cvtmi_opq_search_ivf(m_h, q, nq, /*rotate=*/1, nprobe, k, dist, (int64_t *)ids) == CVTMI_OK ? 1 : 0;
 }
 
+int IVFOPQ::SearchTopKProbeMasked(const float *q, int nq, int nprobe, int k, const std::vector<int> &allowedVideos, float *dist, long long *ids)
+{
+    m_err.clear();
+    if (!ensureHandle()) return 0;
+    if (m_hs.size() > 1 || m_comm) {
+        m_err = "SearchTopKProbeMasked: the IVF search runs on one GPU; not available after SetShard / SetDevices";
+        return 0;
+    }
+    static_assert(sizeof(int) == sizeof(int32_t), "video id width");
+    int64_t n = 0;
+    if (cvtmi_opq_ntotal(m_h, &n) != CVTMI_OK) return 0;
+    std::vector<uint64_t> mask((size_t)((n + 63) / 64) + 1);   // (one word more: never an empty array)
+    if (cvtmi_opq_mask_videos(m_h, (const int32_t *)allowedVideos.data(), (int64_t)allowedVideos.size(), mask.data(), (int64_t)mask.size()) != CVTMI_OK)
+        return 0;
+    return cvtmi_opq_search_ivf_masked(m_h, q, nq, /*rotate=*/1, nprobe, k, mask.data(), (int64_t)mask.size(), dist, (int64_t *)ids) == CVTMI_OK ? 1 : 0;
+}
+
 int IVFOPQ::RangeSearchProbe(const float *q, int nq, int nprobe, float radius, std::vector<long long> &lims, std::vector<float> &dist,
                              std::vector<long long> &ids, std::vector<int> *videos)
 {

@@ -49,6 +49,11 @@ public:
     // the row-level query of a coarseK > 1 model, whose Query() only scores videos.  q is RAW (un-rotated); rows short of k are
     // padded with (+inf, -1).  1 ok / 0 failure (lastError()); single-GPU only: fails once SetShard / SetDevices is in force.
     int SearchTopKProbe(const float *q, int nq, int nprobe, int k, float *dist, long long *ids);
+    // SearchTopKProbe among the entries of the videos in allowedVideos -- a video's position in IndexDatabase's list / the index file;
+    // for rows added through AddRows the row's own entry id -- : cvtmi_opq_mask_videos, then cvtmi_opq_search_ivf_masked.  Ids that
+    // name no video and duplicates are ignored; an empty set pads everything.  1 ok / 0 failure (lastError()); single-GPU only, like
+    // SearchTopKProbe.
+    int SearchTopKProbeMasked(const float *q, int nq, int nprobe, int k, const std::vector<int> &allowedVideos, float *dist, long long *ids);
     // every entry of the nprobe nearest coarse lists of a query whose ADC distance is < radius (cvtmi_opq_range_search_ivf), in the
     // order of the list-ordered copy: the hits of query f are [lims[f], lims[f + 1]) of dist / ids / videos (videos may be NULL).
     // q is RAW (un-rotated).  1 ok / 0 failure (lastError()); single-GPU only, like SearchTopKProbe.

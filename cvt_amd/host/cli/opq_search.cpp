@@ -4,13 +4,16 @@
 // search (retrieval/vlindex/lib/FLANN/mpi/index.h:196-226): every rank indexes a contiguous block of rows, searches it,
 // then ONE all-gather of the per-shard top-k + merge (inside libcvtmi: cvtmi_opq_search_sharded).
 //
-//   opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--nprobe N [--radius R]] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]
+//   opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--nprobe N [--radius R | --videos FILE]] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]
 //
 // --nprobe N: the IVF form -- per query the k nearest entries of its N nearest coarse lists (IVFOPQ::SearchTopKProbe), which is how a
 // model with coarseK > 1 is searched row by row; one GPU, one process; same result file.  Without it nothing changes: coarseK == 1 only.
 // --radius R (with --nprobe only): the range form -- per query EVERY entry of its N nearest lists with distance < R
 // (IVFOPQ::RangeSearchProbe), in list order; result.txt then holds two lines per query, "<qid> ids: id ..." and "<qid> dists: d ...",
 // of that query's own length; --k is not used.
+// --videos FILE (with --nprobe only, not with --radius): the filtered form -- FILE holds one video id per line, and only entries of
+// those videos are candidates (IVFOPQ::SearchTopKProbeMasked); the rows of <db_feat.bin> are one video each, numbered from 0, so
+// an id is a row number.  Same result file; queries with fewer than k allowed entries in their lists pad with id -1 and distance inf.
 // --rotation: a dense D x D rotation (raw fp32, e.g. opq_train --learn-rotation) instead of the model's permutation (IVFOPQ::LoadRotation).
 // model: LoadModel format with coarseK == 1; feature files: raw fp32 [n][D] (IVFOPQ.cpp:451-457).
 // --gpus N: ONE process drives the N GPUs (IVFOPQ::SetDevices: ncclCommInitAll + grouped all-gathers inside libcvtmi) -- the
@@ -46,6 +49,7 @@ static string g_rotation;   // --rotation: dense rotation file (IVFOPQ::LoadRota
 static int g_nprobe = 0;    // --nprobe: > 0 = search through IVFOPQ::SearchTopKProbe
 static bool g_range = false;   // --radius: every entry under g_radius (IVFOPQ::RangeSearchProbe)
 static float g_radius = 0.0f;
+static string g_videos;        // --videos: file of allowed video ids (IVFOPQ::SearchTopKProbeMasked)
 
 struct Shared {
     pthread_barrier_t bar;
@@ -214,7 +218,16 @@ static int run_single_process(int gpus, const string &model, const string &db, c
     }
     vector<float> dist((size_t)nq * k);
     vector<long long> ids((size_t)nq * k);
+    vector<int> allowed;
+    if (!g_videos.empty()) {
+        ifstream fv(g_videos.c_str());
+        if (!fv) { fprintf(stderr, "cannot read %s\n", g_videos.c_str()); return 1; }
+        long long v;
+        while (fv >> v) allowed.push_back((int)v);
+        if (!fv.eof()) { fprintf(stderr, "%s: not a list of video ids\n", g_videos.c_str()); return 1; }
+    }
     const int ok = nq <= 0 ? 1
+                 : !g_videos.empty() ? index.SearchTopKProbeMasked(q.data(), (int)nq, g_nprobe, k, allowed, dist.data(), ids.data())
                  : g_nprobe > 0 ? index.SearchTopKProbe(q.data(), (int)nq, g_nprobe, k, dist.data(), ids.data())
                                 : index.SearchTopK(q.data(), (int)nq, k, dist.data(), ids.data());
     if (ok != 1) {
@@ -249,12 +262,14 @@ int main(int argc, char *argv[])
         else if (!strcmp(argv[i], "--rotation") && i + 1 < argc) g_rotation = argv[++i];
         else if (!strcmp(argv[i], "--nprobe") && i + 1 < argc) { g_nprobe = atoi(argv[++i]); nprobe_given = true; }
         else if (!strcmp(argv[i], "--radius") && i + 1 < argc) { g_radius = strtof(argv[++i], NULL); g_range = true; }
+        else if (!strcmp(argv[i], "--videos") && i + 1 < argc) g_videos = argv[++i];
         else pos.push_back(argv[i]);
     }
     // (--nprobe: one GPU, one process, and any k the library takes)
-    const bool bad_probe = (nprobe_given && (g_nprobe < 1 || gpus != 1 || forked || transport != "rccl")) || (g_range && (!nprobe_given || g_radius != g_radius));
+    const bool bad_probe = (nprobe_given && (g_nprobe < 1 || gpus != 1 || forked || transport != "rccl")) || (g_range && (!nprobe_given || g_radius != g_radius)) ||
+                           (!g_videos.empty() && (!nprobe_given || g_range));
     if (pos.size() != 4 || k < 1 || k > (nprobe_given ? CVTMI_K_MAX : 128) || gpus < 1 || (transport != "rccl" && transport != "shm") || bad_probe) {
-        cerr << "usage: opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--nprobe N [--radius R]] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]" << endl;
+        cerr << "usage: opq_search <model> <db_feat.bin> <query_feat.bin> <result.txt> [--k 100] [--nprobe N [--radius R | --videos FILE]] [--gpus N] [--fork] [--transport rccl|shm] [--rotation R.f32]" << endl;
         return 2;
     }
     const bool use_shm = transport == "shm";

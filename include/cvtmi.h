@@ -310,6 +310,58 @@ int cvtmi_opq_search_ivf_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rota
 int cvtmi_opq_ivf_plan(int64_t nq, int nprobe, int k, int64_t longest_list, int cus, int64_t out[6]);
 int cvtmi_opq_last_ivf_plan(cvtmi_opq_t h, int64_t out[8]);
 
+/* Masked IVF search: the k nearest entries of the probed lists among those a bitmap allows -- search under a filter (tenant, date
+ * range, "not these videos", the ids a relational query returned) on the compressed index, the counterpart of faiss's IDSelector in
+ * SearchParametersIVF and of cvtmi_flat_search_masked.  mask is uint64[mask_words].
+ *   Mask     bit i & 63 of word i >> 6 allows the entry with INSERTION INDEX i -- id - id_base, the addressing of
+ *            cvtmi_opq_remove_ids's remap, as removals left it.  One mask serves all nq queries of the call.
+ *            mask_words >= ceil(ntotal / 64), checked under the handle's lock: fewer fails with CVTMI_EINVAL (a mask built before a
+ *            cvtmi_opq_add_codes is too short, not silently wrong).  Bits at positions >= ntotal are ignored whatever they hold, and
+ *            words behind ceil(ntotal / 64) are never read.  Bits of entries whose list id is outside [0, coarseK) are ignored:
+ *            those entries are not in the list-ordered copy and never appear.
+ *   Probing  rotation, probing and the score of an entry are cvtmi_opq_search_ivf's, bit for bit: the mask never changes which
+ *            lists are probed (nprobe > coarseK is clamped, more than 128 after the clamp fails with CVTMI_EUNSUPPORTED, a query
+ *            holding a NaN probes lists 0 .. nprobe-1).
+ *   Result   dist[nq][k] / ids[nq][k]: the k smallest (score, id) pairs among the ALLOWED entries of the probed lists, ascending,
+ *            id = id_base + insertion index, with the tie rule of cvtmi_opq_search_ivf; an allowed entry scoring +inf is a real
+ *            result and precedes the padding.  With fewer than k such entries the list pads with (+inf, -1).  A NaN query returns
+ *            min(k, allowed entries of its lists) distinct allowed entries with NaN distances.  An all-ones mask returns
+ *            cvtmi_opq_search_ivf's lists bit for bit; an all-zero mask or an empty index pads everything.
+ *   In short the result equals cvtmi_opq_search_ivf on a fresh handle of the same model that holds only the allowed entries, in
+ *            their order, with the ids mapped back to the original insertion indices.
+ *   Limits   those of cvtmi_opq_search_ivf: 1 <= k <= CVTMI_K_MAX, K <= 256, M <= 16, fewer than 2^32 entries.
+ * Checked before any device work: what cvtmi_opq_search_ivf checks, and a NULL mask with nq > 0 or mask_words < 0 -> CVTMI_EINVAL.
+ * nq == 0 does nothing.
+ * Concurrency: a masked search is a search.  It takes the shared lock and a scratch set of its own -- everything derived from the
+ * mask lives in that set, nothing in the handle, so threads with different masks run side by side on one handle -- and it goes
+ * round again on an append between preparation and lock, as cvtmi_opq_search_ivf does.  The first masked search on a handle adds the
+ * insertion-index array of the list-ordered copy like the first IVF search.  The _dev entry enqueues on `stream` and never waits for
+ * the device; mask, q and the outputs are device pointers there.
+ * Shards: there is no collective form.  Each rank passes the mask of its own entries and the caller merges with cvtmi_topk_merge.
+ * The work: one launch brings the mask into the order of the list-ordered copy (one bit per entry, in the leased set); the scan of
+ * cvtmi_opq_search_ivf then leaves a probed list BEFORE it builds the list's residual table when no row of the list is allowed --
+ * under a selective mask that is most lists, and the tables are what the unmasked search spends its time on.  The grid is planned for
+ * the unmasked worst case; the host never learns the mask's population. */
+int cvtmi_opq_search_ivf_masked(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k,
+                                const uint64_t *mask, int64_t mask_words, float *dist, int64_t *ids);
+int cvtmi_opq_search_ivf_masked_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k,
+                                    const uint64_t *mask, int64_t mask_words, float *dist, int64_t *ids, void *stream);
+/* The mask of a set of videos: writes all mask_words words -- the bit of every entry whose video id (the id it was added with, or its
+ * insertion index where none was given) is in video_ids[nv] is set, every other bit is cleared, those at positions >= ntotal
+ * included.  The set follows the rules of cvtmi_opq_remove_videos: unsorted, duplicates, foreign ids and any int32 are fine.
+ * nv == 0 clears the mask.  mask_words >= ceil(ntotal / 64), else CVTMI_EINVAL; NULL h, a negative count, a NULL set with nv > 0 or a
+ * NULL mask with mask_words > 0 -> CVTMI_EINVAL before any device work.
+ * Non-mutating: the shared lock and a leased scratch set, like a search; the work is the mark step of cvtmi_opq_remove_videos.  The
+ * _dev entry (set and mask are device pointers) runs on `stream` and waits, like cvtmi_opq_remove_videos_dev, for its set to reach
+ * the host, where it is sorted (4 bytes per id), and for the sorted table to have left host memory again.
+ * The caller inverts or combines masks with plain word operations.  There is no mask_ids: the caller sets bit id - id_base itself. */
+int cvtmi_opq_mask_videos(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, uint64_t *mask, int64_t mask_words);
+int cvtmi_opq_mask_videos_dev(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, uint64_t *mask, int64_t mask_words,
+                              void *stream);
+/* The handle's last masked IVF search: out = the six numbers of cvtmi_opq_ivf_plan, then out[6] = bytes of its partial lists and
+ * out[7] = bytes of the mask in list order (both in the leased scratch set). */
+int cvtmi_opq_last_ivf_masked(cvtmi_opq_t h, int64_t out[8]);
+
 /* Range search over the probed lists: for every query, EVERY entry of its nprobe nearest coarse lists whose score is under
  * `radius` -- the threshold test IVFOPQ::Query / QueryThrehold make (their cells start at 1.0 and fold with min(score, cell):
  * IVFOPQ.cpp:5, :262, :308), reported per entry where cvtmi_opq_query_video reports per video.  Probing, rotation and the score
