@@ -1024,6 +1024,108 @@ def _hnsw_search_adc_rerank(self, opq, q, k, ef, rerank=None, rotate=True):
 HnswIndex.search_adc_rerank = _hnsw_search_adc_rerank
 
 
+def _hnsw_mask_words(self, mask, dev):
+    """`mask` as uint64 words: words stay as they are, a bool array of length ntotal is packed little-endian (bit i & 63 of word
+    i >> 6 = node i)."""
+    if _is_torch(mask):
+        import torch
+        if mask.dtype == torch.bool:
+            pad = (-mask.shape[0]) % 64
+            bits = torch.nn.functional.pad(mask.reshape(-1).to(torch.int64), (0, pad)).reshape(-1, 64)
+            # (bit 63 wraps into the sign of the int64 word: the same 64 bits)
+            return (bits << torch.arange(64, device=mask.device, dtype=torch.int64)).sum(dim=1).contiguous()
+        assert mask.dtype in (torch.int64, torch.uint64) and mask.is_cuda == dev
+        return mask.reshape(-1).contiguous()
+    mask = np.asarray(mask)
+    if mask.dtype == np.bool_:
+        assert mask.ndim == 1 and mask.shape[0] == self.ntotal, "a bool mask has one entry per node"
+        packed = np.packbits(mask, bitorder="little")
+        words = np.zeros((mask.shape[0] + 63) // 64 * 8, dtype=np.uint8)
+        words[:packed.shape[0]] = packed
+        return words.view("<u8").astype(np.uint64, copy=False)
+    assert mask.dtype == np.uint64, "a mask is np.uint64 words or a bool array of length ntotal"
+    return np.ascontiguousarray(mask.reshape(-1))
+
+
+def _hnsw_masked_call(self, name, head, q, k, mask, tail):
+    """One masked entry: `head` / `tail` are the ctypes arguments before the queries and between nq and the mask."""
+    nq = q.shape[0]
+    if _is_torch(q):
+        import torch
+        assert q.is_contiguous() and q.dtype == torch.float32
+        words = self._mask_words(mask, True)
+        assert _is_torch(words) and words.is_cuda
+        d = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        lab = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+        _check(getattr(lib(), name + "_dev")(self.h, *head, _ptr(q), C.c_int64(nq), *tail, _ptr(words), C.c_int64(words.shape[0]),
+                                             _ptr(d), _ptr(lab), _stream()))
+        return d, lab
+    q = _np(q, np.float32)
+    words = self._mask_words(mask, False)
+    d = np.empty((nq, k), dtype=np.float32); lab = np.empty((nq, k), dtype=np.int64)
+    _check(getattr(lib(), name)(self.h, *head, _ptr(q), C.c_int64(nq), *tail, _ptr(words), C.c_int64(words.shape[0]), _ptr(d), _ptr(lab)))
+    return d, lab
+
+
+def _hnsw_search_masked(self, q, k, ef, mask):
+    """search() among the nodes `mask` allows (cvtmi_hnsw_search_masked): hnswlib's filtered searchKnn -- the mask decides what may be
+    a result, never what is traversed.  mask: np.uint64 words, bit i & 63 of word i >> 6 allowing NODE i (the insertion order; at
+    least ceil(ntotal / 64) words, bits past ntotal are ignored), or a bool array of length ntotal; one mask serves every query.
+    Output as search(), padded with (0, -1) when fewer than k allowed nodes are found.  numpy in, numpy out; torch device tensors
+    (mask: int64 / uint64 words or bool) run on torch's current stream."""
+    return _hnsw_masked_call(self, "cvtmi_hnsw_search_masked", (), q, k, mask, (C.c_int(k), C.c_int(ef)))
+
+
+def _hnsw_search_adc_masked(self, opq, q, k, ef, mask, rotate=True):
+    """search_adc() under a node mask (cvtmi_hnsw_search_adc_masked); mask as in search_masked."""
+    return _hnsw_masked_call(self, "cvtmi_hnsw_search_adc_masked", (opq.h,), q, k, mask, (C.c_int(int(rotate)), C.c_int(k), C.c_int(ef)))
+
+
+def _hnsw_search_adc_rerank_masked(self, opq, q, k, ef, mask, rerank=None, rotate=True):
+    """search_adc_rerank() under a node mask (cvtmi_hnsw_search_adc_rerank_masked): the ADC traversal keeps its `rerank` best ALLOWED
+    nodes (default: ef), the exact re-rank sees those alone; mask as in search_masked."""
+    rerank = ef if rerank is None else rerank
+    return _hnsw_masked_call(self, "cvtmi_hnsw_search_adc_rerank_masked", (opq.h,), q, k, mask,
+                             (C.c_int(int(rotate)), C.c_int(k), C.c_int(ef), C.c_int(rerank)))
+
+
+def _hnsw_mask_from_labels(self, labels, words=None):
+    """The mask of the nodes whose label is in `labels` (cvtmi_hnsw_mask_labels; int64, numpy or a torch device tensor; uint64 labels
+    pass as their int64 bit patterns): `words` uint64 words (default ceil(ntotal / 64)), every bit past ntotal cleared.  Invert or
+    combine masks with plain word operations (~m, a & b)."""
+    n_words = (self.ntotal + 63) // 64 if words is None else int(words)
+    if _is_torch(labels):
+        import torch
+        assert labels.dtype == torch.int64 and labels.is_cuda
+        labels = labels.reshape(-1)
+        mask = torch.empty(n_words, dtype=torch.int64, device=labels.device)
+        _check(lib().cvtmi_hnsw_mask_labels_dev(self.h, _ptr(labels), C.c_int64(labels.shape[0]), _ptr(mask), C.c_int64(n_words), _stream()))
+        return mask
+    labels = np.asarray(labels)
+    if labels.dtype == np.uint64:
+        labels = labels.view(np.int64)
+    labels = _np(labels, np.int64).reshape(-1)
+    mask = np.empty(n_words, dtype=np.uint64)
+    _check(lib().cvtmi_hnsw_mask_labels(self.h, _ptr(labels), C.c_int64(labels.shape[0]), _ptr(mask), C.c_int64(n_words)))
+    return mask
+
+
+def _hnsw_last_masked(self):
+    """(slots, candidate-queue capacity per slot in entries, scratch bytes reserved, form) of the last masked search on this handle
+    (cvtmi_hnsw_last_masked); form 0 = fp32, 1 = ADC with tables in the scratch, 2 = ADC with tables in LDS."""
+    o = (C.c_int64 * 4)()
+    _check(lib().cvtmi_hnsw_last_masked(self.h, o))
+    return o[0], o[1], o[2], o[3]
+
+
+HnswIndex._mask_words = _hnsw_mask_words
+HnswIndex.search_masked = _hnsw_search_masked
+HnswIndex.search_adc_masked = _hnsw_search_adc_masked
+HnswIndex.search_adc_rerank_masked = _hnsw_search_adc_rerank_masked
+HnswIndex.mask_from_labels = _hnsw_mask_from_labels
+HnswIndex.last_masked = _hnsw_last_masked
+
+
 def hnsw_build(x, metric, M, ef_construction, labels=None, max_batch=0):
     """cvtmi_hnsw_build[_dev]: a HierarchicalNSW graph over the rows x [n][D] (numpy, or a CUDA tensor with labels on the same
     device), batch-synchronous on the GPU (max_batch = 1: the reference's sequential insertion; 0: the default schedule)."""

@@ -1,12 +1,15 @@
 // api_hnsw.hip -- the HNSW handle of the C ABI (include/cvtmi.h): load / build / save, the search, the search over OPQ codes (ADC)
-// with and without the exact re-rank.
+// with and without the exact re-rank, each of them under a node mask as well, and the mask of a label set.
 #include <string.h>
 
+#include <algorithm>
 #include <cmath>
 #include <random>
+#include <vector>
 
 #include "api_internal.h"
 #include "launch.h"
+#include "rm_common.h"
 
 // ================================================================ HNSW search ==================
 // The graph is immutable once loaded and searchKnn is a pure read in the reference (hnswalg.h:688-728): searches on one handle run side
@@ -271,7 +274,13 @@ int64_t cvtmi_hnsw_ntotal(cvtmi_hnsw_t h) { return (h && h->magic == 0x484e5357u
 
 // scratch of one traversal launch: `slots` concurrent queries (one wave each), a visited bit per node and the spilled queues per slot
 struct HnswPlan { int slots; int64_t words, gcap; };
-static int hnsw_plan(cvtmi_hnsw_t h, HnswScratch &S, int lds_dim, int64_t nq, int k, int ef, HnswPlan &pl, hipStream_t st)
+// Scratch a masked search may reserve (visited bits + queues of all its slots).  A masked slot holds a candidate queue of n entries
+// (8 n bytes, below), 256 times the unmasked bound at 1 M nodes and ef = 64; at 32 slots per CU that would be 65 GB.  8 GiB keeps
+// about 1000 traversals in flight at 1 M nodes (4 per CU) and every traversal of a graph of up to 120 K nodes, and leaves the
+// rest of the 288 GB to the index itself and to the other searches of the handle, each of which leases a set of its own.
+constexpr size_t kHnswMaskedScratch = (size_t)8 << 30;
+// masked_form >= 0: the plan of a masked search (form as cvtmi_hnsw_last_masked reports it)
+static int hnsw_plan(cvtmi_hnsw_t h, HnswScratch &S, int lds_dim, int64_t nq, int k, int ef, HnswPlan &pl, hipStream_t st, int masked_form = -1)
 {
     const int efe = ef > k ? ef : k;
     int per_cu = (159 * 1024) / hnsw_lds_bytes(lds_dim, efe);  // query slots (one wave each) a CU's 160 KB of LDS hold
@@ -284,8 +293,20 @@ static int hnsw_plan(cvtmi_hnsw_t h, HnswScratch &S, int lds_dim, int64_t nq, in
     pl.words = (h->g.n + 31) / 32 + 1;
     int64_t gcap = (int64_t)efe * h->g.maxM0 * 2;
     if (gcap > h->g.n) gcap = h->g.n;
+    // Under a mask that bound does not hold: while few allowed nodes have been found nothing is pruned and every visited node is queued
+    // (measured on the CPU model, (k, ef) = (10, 16), sparse masks: 622 - 1554 entries against 2 ef maxM0 = 384 / 512).  A node enters
+    // the queue at most once, so n entries are always enough and the overflow check behind the launch stays a guard.
+    if (masked_form >= 0) gcap = h->g.n;
     gcap = gcap > hnsw_lcap() ? gcap - hnsw_lcap() : 0;
     pl.gcap = gcap + 64;
+    if (masked_form >= 0) {
+        const size_t per_slot = (size_t)pl.words * 4 + (size_t)(pl.gcap + efe + 1) * 8;
+        const int64_t fit = std::max<int64_t>(1, (int64_t)(kHnswMaskedScratch / per_slot));
+        if (pl.slots > fit) pl.slots = (int)fit;
+        std::lock_guard<std::mutex> g(h->pool.mu);
+        h->masked_last[0] = pl.slots; h->masked_last[1] = hnsw_lcap() + pl.gcap;
+        h->masked_last[2] = (int64_t)(per_slot * (size_t)pl.slots); h->masked_last[3] = masked_form;
+    }
     CVTMI_TRY(S.s_vis.reserve((size_t)pl.slots * pl.words * 4));
     CVTMI_TRY(S.s_cand.reserve((size_t)pl.slots * (pl.gcap + efe + 1) * 8));  // per slot: spilled top queue + spilled candidates
     CVTMI_TRY(S.s_err.reserve(16));
@@ -301,13 +322,15 @@ static int hnsw_check_overflow(HnswScratch &S, const char *who, int ef, hipStrea
     return CVTMI_OK;
 }
 
-static int hnsw_search_leased(cvtmi_hnsw_t h, HnswScratch &S, const float *q, int64_t nq, int k, int ef, float *dist, int64_t *labels, hipStream_t st)
+// mask (device pointer, ceil(n / 64) words) != null: the masked search
+static int hnsw_search_leased(cvtmi_hnsw_t h, HnswScratch &S, const float *q, int64_t nq, int k, int ef, float *dist, int64_t *labels, hipStream_t st,
+                              const uint64_t *mask = nullptr)
 {
     HnswPlan pl;
-    CVTMI_TRY(hnsw_plan(h, S, h->D, nq, k, ef, pl, st));
+    CVTMI_TRY(hnsw_plan(h, S, h->D, nq, k, ef, pl, st, mask ? 0 : -1));
     CVTMI_TRY(launch_hnsw_search(h->g, h->metric, q, nq, k, ef, dist, labels, S.s_vis.as<uint32_t>(), S.s_cand.p, pl.slots, pl.words,
-                                 pl.gcap, S.s_err.as<int>(), st));
-    return hnsw_check_overflow(S, "cvtmi_hnsw_search", ef, st);
+                                 pl.gcap, S.s_err.as<int>(), st, mask));
+    return hnsw_check_overflow(S, mask ? "cvtmi_hnsw_search_masked" : "cvtmi_hnsw_search", ef, st);
 }
 
 static int hnsw_search_args(cvtmi_hnsw_t h, const char *who, const void *q, int64_t nq, int k, int ef, const void *dist, const void *labels)
@@ -364,10 +387,10 @@ int cvtmi_hnsw_search(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int ef,
 // handle's own kernels, into a scratch set leased from the OPQ handle (so a later cvtmi_opq_add waits for this search);
 // the OPQ handle is held shared for the duration, like a search of its own.
 static int hnsw_search_adc_leased(cvtmi_hnsw_t h, HnswScratch &S, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef,
-                                  float *dist, int64_t *labels, hipStream_t st, int raw_ids)
+                                  float *dist, int64_t *labels, hipStream_t st, int raw_ids, const uint64_t *mask = nullptr)
 {
     if (!opq) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc: null OPQ handle");
-    CVTMI_TRY(hnsw_search_args(h, "cvtmi_hnsw_search_adc", q, nq, k, ef, dist, labels));
+    CVTMI_TRY(hnsw_search_args(h, mask ? "cvtmi_hnsw_search_adc_masked" : "cvtmi_hnsw_search_adc", q, nq, k, ef, dist, labels));
     if (opq->m.coarseK != 1) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_search_adc: needs an OPQ model with coarseK == 1");
     if (opq->m.D != h->D) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc: OPQ model is %d-d, graph is %d-d", opq->m.D, h->D);
     if (opq->device != h->device) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc: handles live on different devices");
@@ -388,11 +411,11 @@ static int hnsw_search_adc_leased(cvtmi_hnsw_t h, HnswScratch &S, cvtmi_opq_t op
     CVTMI_TRY(launch_lut(opq->m, q_rot, nq, nullptr, OS.s_lut.as<float>(), st));
     HnswPlan pl;
     const int state_floats = hnsw_adc_state_floats(opq->m.M * opq->m.K);   // one reading of the tuning flag for the slot count AND the launch
-    CVTMI_TRY(hnsw_plan(h, S, state_floats, nq, k, ef, pl, st));
+    CVTMI_TRY(hnsw_plan(h, S, state_floats, nq, k, ef, pl, st, mask ? (state_floats ? 2 : 1) : -1));
     CVTMI_TRY(launch_hnsw_search_adc(h->g, OS.s_lut.as<float>(), opq->codes.as<uint8_t>(), opq->m.M, opq->m.K, nq, k, ef, dist,
                                      labels, S.s_vis.as<uint32_t>(), S.s_cand.p, pl.slots, pl.words, pl.gcap, S.s_err.as<int>(), st, raw_ids,
-                                     state_floats));
-    return hnsw_check_overflow(S, "cvtmi_hnsw_search_adc", ef, st);
+                                     state_floats, mask));
+    return hnsw_check_overflow(S, mask ? "cvtmi_hnsw_search_adc_masked" : "cvtmi_hnsw_search_adc", ef, st);
 }
 
 int cvtmi_hnsw_search_adc_dev(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef, float *dist,
@@ -407,7 +430,7 @@ int cvtmi_hnsw_search_adc_dev(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, i
 // ADC traversal with a result list of `rerank` nodes, then their exact fp32 distances (the graph's own vectors, the summation
 // order of the reference's distance functions) and the k smallest; equal exact distances keep their ADC order
 static int hnsw_search_adc_rerank_leased(cvtmi_hnsw_t h, HnswScratch &S, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef,
-                                         int rerank, float *dist, int64_t *labels, hipStream_t st)
+                                         int rerank, float *dist, int64_t *labels, hipStream_t st, const uint64_t *mask = nullptr)
 {
     if (k < 1 || k > CVTMI_K_MAX) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_search_adc_rerank: k=%d outside 1..%d", k, CVTMI_K_MAX);
     if (rerank < k || rerank > hnsw_ef_max()) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc_rerank: rerank=%d outside k..%d", rerank, hnsw_ef_max());
@@ -415,7 +438,7 @@ static int hnsw_search_adc_rerank_leased(cvtmi_hnsw_t h, HnswScratch &S, cvtmi_o
     if (nq == 0) return CVTMI_OK;
     CVTMI_TRY(S.s_rr_d.reserve((size_t)nq * rerank * sizeof(float)));
     CVTMI_TRY(S.s_rr_id.reserve((size_t)nq * rerank * sizeof(int64_t)));
-    CVTMI_TRY(hnsw_search_adc_leased(h, S, opq, q, nq, rotate, rerank, ef, S.s_rr_d.as<float>(), S.s_rr_id.as<int64_t>(), st, 1));
+    CVTMI_TRY(hnsw_search_adc_leased(h, S, opq, q, nq, rotate, rerank, ef, S.s_rr_d.as<float>(), S.s_rr_id.as<int64_t>(), st, 1, mask));
     CVTMI_TRY(launch_hnsw_rerank(h->g, h->metric, q, nq, rerank, S.s_rr_id.as<int64_t>(), S.s_rr_d.as<float>(), st));
     CVTMI_TRY(launch_topk_select(S.s_rr_d.as<float>(), S.s_rr_id.as<int64_t>(), nq, rerank, k, dist, labels, st));
     return launch_gather_labels(labels, nq * k, h->g.labels, st);
@@ -451,3 +474,203 @@ int cvtmi_hnsw_search_adc(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64
         return hnsw_search_adc_leased(h, S, opq, dq, nq, rotate, k, ef, dd, dl, st, 0);
     });
 }
+
+// ================================================================ masked search ================
+// The entries above under a node mask (hnsw.hip: the MASKED instances).  Same leases, same streams, same argument answers; the mask
+// is checked first, and the host-pointer entries stage its ceil(n / 64) words through the leased set beside the queries.
+#define CHECK_HN_MASKED(h) do { if (!(h)) return fail(CVTMI_EINVAL, "%s: null handle", __func__); CHECK_HN(h); } while (0)
+
+static int hnsw_mask_args(cvtmi_hnsw_t h, const char *who, const void *q, int64_t nq, const uint64_t *mask, int64_t mask_words, const void *dist,
+                          const void *labels)
+{
+    if (nq < 0 || mask_words < 0 || (nq > 0 && (!q || !mask || !dist || !labels))) return fail(CVTMI_EINVAL, "%s: bad arguments", who);
+    if (mask_words < (h->g.n + 63) / 64)
+        return fail(CVTMI_EINVAL, "%s: %lld mask words for %lld nodes (%lld needed)", who, (long long)mask_words, (long long)h->g.n,
+                    (long long)((h->g.n + 63) / 64));
+    return CVTMI_OK;
+}
+// the words that can hold a node, on the device (the caller's words behind them are never read)
+static int hnsw_stage_mask(cvtmi_hnsw_t h, HnswScratch &S, const uint64_t *mask, hipStream_t st)
+{
+    const size_t mb = (size_t)((h->g.n + 63) / 64) * 8;
+    CVTMI_TRY(S.io_m.reserve(mb ? mb : 16));
+    if (mb) CVTMI_HIP(hipMemcpyAsync(S.io_m.p, mask, mb, hipMemcpyHostToDevice, st));
+    return CVTMI_OK;
+}
+
+extern "C" {
+
+int cvtmi_hnsw_search_masked_dev(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int ef, const uint64_t *mask, int64_t mask_words,
+                                 float *dist, int64_t *labels, void *stream)
+{
+    CHECK_HN_MASKED(h);
+    CVTMI_TRY(hnsw_mask_args(h, "cvtmi_hnsw_search_masked", q, nq, mask, mask_words, dist, labels));
+    CVTMI_TRY(hnsw_search_args(h, "cvtmi_hnsw_search_masked", q, nq, k, ef, dist, labels));
+    if (nq == 0) return CVTMI_OK;
+    HnswLease lease;
+    CVTMI_TRY(lease.open(h, (hipStream_t)stream, false));
+    return hnsw_search_leased(h, *lease.s, q, nq, k, ef, dist, labels, lease.st, mask);
+}
+
+int cvtmi_hnsw_search_masked(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int ef, const uint64_t *mask, int64_t mask_words, float *dist,
+                             int64_t *labels)
+{
+    CHECK_HN_MASKED(h);
+    CVTMI_TRY(hnsw_mask_args(h, "cvtmi_hnsw_search_masked", q, nq, mask, mask_words, dist, labels));
+    CVTMI_TRY(hnsw_search_args(h, "cvtmi_hnsw_search_masked", q, nq, k, ef, dist, labels));
+    if (nq == 0) return CVTMI_OK;
+    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
+        CVTMI_TRY(hnsw_stage_mask(h, S, mask, st));
+        return hnsw_search_leased(h, S, dq, nq, k, ef, dd, dl, st, S.io_m.as<uint64_t>());
+    });
+}
+
+int cvtmi_hnsw_search_adc_masked_dev(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef, const uint64_t *mask,
+                                     int64_t mask_words, float *dist, int64_t *labels, void *stream)
+{
+    CHECK_HN_MASKED(h);
+    CVTMI_TRY(hnsw_mask_args(h, "cvtmi_hnsw_search_adc_masked", q, nq, mask, mask_words, dist, labels));
+    if (nq == 0) return CVTMI_OK;   // (the mask pointer selects the kernel: it is there from here on)
+    HnswLease lease;
+    CVTMI_TRY(lease.open(h, (hipStream_t)stream, false));
+    return hnsw_search_adc_leased(h, *lease.s, opq, q, nq, rotate, k, ef, dist, labels, lease.st, 0, mask);
+}
+
+int cvtmi_hnsw_search_adc_masked(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef, const uint64_t *mask,
+                                 int64_t mask_words, float *dist, int64_t *labels)
+{
+    CHECK_HN_MASKED(h);
+    CVTMI_TRY(hnsw_mask_args(h, "cvtmi_hnsw_search_adc_masked", q, nq, mask, mask_words, dist, labels));
+    if (k < 1) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc_masked: bad arguments");   // as cvtmi_hnsw_search_adc answers it
+    if (nq == 0) return CVTMI_OK;
+    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
+        CVTMI_TRY(hnsw_stage_mask(h, S, mask, st));
+        return hnsw_search_adc_leased(h, S, opq, dq, nq, rotate, k, ef, dd, dl, st, 0, S.io_m.as<uint64_t>());
+    });
+}
+
+int cvtmi_hnsw_search_adc_rerank_masked_dev(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef, int rerank,
+                                            const uint64_t *mask, int64_t mask_words, float *dist, int64_t *labels, void *stream)
+{
+    CHECK_HN_MASKED(h);
+    CVTMI_TRY(hnsw_mask_args(h, "cvtmi_hnsw_search_adc_rerank_masked", q, nq, mask, mask_words, dist, labels));
+    if (nq == 0) return CVTMI_OK;
+    HnswLease lease;
+    CVTMI_TRY(lease.open(h, (hipStream_t)stream, false));
+    return hnsw_search_adc_rerank_leased(h, *lease.s, opq, q, nq, rotate, k, ef, rerank, dist, labels, lease.st, mask);
+}
+
+int cvtmi_hnsw_search_adc_rerank_masked(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef, int rerank,
+                                        const uint64_t *mask, int64_t mask_words, float *dist, int64_t *labels)
+{
+    CHECK_HN_MASKED(h);
+    CVTMI_TRY(hnsw_mask_args(h, "cvtmi_hnsw_search_adc_rerank_masked", q, nq, mask, mask_words, dist, labels));
+    if (k < 1) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc_rerank_masked: bad arguments");   // as cvtmi_hnsw_search_adc_rerank answers it
+    if (nq == 0) return CVTMI_OK;
+    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
+        CVTMI_TRY(hnsw_stage_mask(h, S, mask, st));
+        return hnsw_search_adc_rerank_leased(h, S, opq, dq, nq, rotate, k, ef, rerank, dd, dl, st, S.io_m.as<uint64_t>());
+    });
+}
+
+int cvtmi_hnsw_last_masked(cvtmi_hnsw_t h, int64_t out[4])
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_hnsw_last_masked: null handle");
+    if (!out || h->magic != 0x484e5357u) return fail(CVTMI_EINVAL, "cvtmi_hnsw_last_masked: bad arguments");
+    std::lock_guard<std::mutex> g(h->pool.mu);
+    for (int i = 0; i < 4; ++i) out[i] = h->masked_last[i];
+    return CVTMI_OK;
+}
+
+}  // extern "C"
+
+// ---- the bitmap of a label set: the mark step of the flat removal over the graph's labels (flat_remove.hip), on a leased set ----
+static int hnsw_mask_labels_check(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, const uint64_t *mask, int64_t mask_words)
+{
+    if (n_labels < 0 || mask_words < 0 || (n_labels > 0 && !labels) || (mask_words > 0 && !mask)) return fail(CVTMI_EINVAL, "cvtmi_hnsw_mask_labels: bad arguments");
+    if (mask_words < (h->g.n + 63) / 64)
+        return fail(CVTMI_EINVAL, "cvtmi_hnsw_mask_labels: %lld mask words for %lld nodes (%lld needed)", (long long)mask_words, (long long)h->g.n,
+                    (long long)((h->g.n + 63) / 64));
+    return CVTMI_OK;
+}
+// the distinct labels of the set, ascending as int64 (the order the mark's lower bound walks)
+static int hnsw_label_table(const int64_t *labels, int64_t n_labels, std::vector<int64_t> &tab)
+{
+    try {
+        tab.assign(labels, labels + n_labels);
+    } catch (...) {
+        return fail(CVTMI_ENOMEM, "cvtmi_hnsw_mask_labels: out of host memory");
+    }
+    std::sort(tab.begin(), tab.end());
+    tab.erase(std::unique(tab.begin(), tab.end()), tab.end());
+    return CVTMI_OK;
+}
+// table: T > 0 distinct labels in host memory; mask: device pointer of mask_words > 0 words; h->g.n > 0
+static int hnsw_mask_labels_leased(cvtmi_hnsw_t h, HnswScratch &S, const int64_t *table, int64_t T, uint64_t *mask, int64_t mask_words, hipStream_t st)
+{
+    FlatRmPlan p;   // the mark's areas alone: nothing moves
+    p.rm = rm_plan(h->g.n, 0, 0, 0);
+    p.T = T;
+    p.off_table = p.rm.off_table;
+    p.bytes = p.off_table + rm_align((size_t)T * 8);
+    CVTMI_TRY(S.s_mark.reserve(p.bytes));
+    void *W = S.s_mark.p;
+    CVTMI_HIP(hipMemcpyAsync(static_cast<char *>(W) + p.off_table, table, (size_t)T * 8, hipMemcpyHostToDevice, st));
+    CVTMI_TRY(launch_flat_rm_mark_labels(p, W, h->g.labels, st));
+    return launch_flat_masked_copy(p.rm, W, mask, mask_words, st);
+}
+
+extern "C" {
+
+int cvtmi_hnsw_mask_labels_dev(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, uint64_t *mask, int64_t mask_words, void *stream)
+{
+    CHECK_HN_MASKED(h);
+    CVTMI_TRY(hnsw_mask_labels_check(h, labels, n_labels, mask, mask_words));
+    if (mask_words == 0) return CVTMI_OK;
+    HnswLease lease;
+    CVTMI_TRY(lease.open(h, (hipStream_t)stream, false));
+    hipStream_t st = lease.st;
+    if (h->g.n == 0 || n_labels == 0) {
+        CVTMI_HIP(hipMemsetAsync(mask, 0, (size_t)mask_words * 8, st));
+        return CVTMI_OK;
+    }
+    std::vector<int64_t> raw, tab;   // the set is sorted on the host: it comes down first (8 bytes per label)
+    try {
+        raw.resize((size_t)n_labels);
+    } catch (...) {
+        return fail(CVTMI_ENOMEM, "cvtmi_hnsw_mask_labels: out of host memory");
+    }
+    CVTMI_HIP(hipMemcpyAsync(raw.data(), labels, (size_t)n_labels * 8, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    CVTMI_TRY(hnsw_label_table(raw.data(), n_labels, tab));
+    CVTMI_TRY(hnsw_mask_labels_leased(h, *lease.s, tab.data(), (int64_t)tab.size(), mask, mask_words, st));
+    CVTMI_HIP(stream_wait(st));   // (the table leaves host memory that ends with this call)
+    return CVTMI_OK;
+}
+
+int cvtmi_hnsw_mask_labels(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, uint64_t *mask, int64_t mask_words)
+{
+    CHECK_HN_MASKED(h);
+    CVTMI_TRY(hnsw_mask_labels_check(h, labels, n_labels, mask, mask_words));
+    if (mask_words == 0) return CVTMI_OK;
+    if (h->g.n == 0 || n_labels == 0) {
+        memset(mask, 0, (size_t)mask_words * 8);
+        return CVTMI_OK;
+    }
+    std::vector<int64_t> tab;
+    CVTMI_TRY(hnsw_label_table(labels, n_labels, tab));
+    HnswLease lease;
+    CVTMI_TRY(lease.open(h, nullptr, true));
+    HnswScratch &S = *lease.s;
+    hipStream_t st = lease.st;
+    // only the words that can hold a node pass through the device; the caller's words behind them are cleared here
+    const int64_t words = (h->g.n + 63) / 64;
+    CVTMI_TRY(S.io_m.reserve((size_t)words * 8));
+    CVTMI_TRY(hnsw_mask_labels_leased(h, S, tab.data(), (int64_t)tab.size(), S.io_m.as<uint64_t>(), words, st));
+    CVTMI_HIP(hipMemcpyAsync(mask, S.io_m.p, (size_t)words * 8, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    memset(mask + words, 0, (size_t)(mask_words - words) * 8);
+    return CVTMI_OK;
+}
+
+}  // extern "C"

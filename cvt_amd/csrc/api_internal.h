@@ -256,9 +256,11 @@ struct cvtmi_flat_s {
 struct HnswScratch : ScratchBase {
     static constexpr const char *kLeaseNoMemory = "hnsw search: out of host memory";
     DevBuf s_vis, s_cand, s_err, s_rr_d, s_rr_id, io_q, io_d, io_l;
+    DevBuf s_mark;   // cvtmi_hnsw_mask_labels: the marked bitmap, its tile counts and the table of the label set
+    DevBuf io_m;     // the mask words / the label set of the host-pointer masked entries
     void release_all()
     {
-        for (DevBuf *b : { &s_vis, &s_cand, &s_err, &s_rr_d, &s_rr_id, &io_q, &io_d, &io_l }) b->release();
+        for (DevBuf *b : { &s_vis, &s_cand, &s_err, &s_rr_d, &s_rr_id, &io_q, &io_d, &io_l, &s_mark, &io_m }) b->release();
         release_lease_state();
     }
 };
@@ -275,6 +277,7 @@ struct cvtmi_hnsw_s {
     int32_t hdr_maxlevel = 0;
     uint32_t hdr_enterpoint = 0;
     ScratchPool<HnswScratch> pool;
+    int64_t masked_last[4] = {};   // the last masked search (cvtmi_hnsw_last_masked), written under pool.mu
     int slots_per_cu_max = 32, cus = 256;
 };
 

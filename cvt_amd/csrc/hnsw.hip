@@ -44,6 +44,7 @@ struct HnswArgs {
     int raw_ids;              // 1 = out_label receives internal ids instead of labels (the re-rank pass needs the node)
     int top_lds;              // entries of the top queue kept in LDS (the candidate queue: HN_LCAP)
     int dynamic;              // 1 = queries handed out by the counter err[1] (one ticket per wave), 0 = static stride
+    const uint64_t *mask;     // MASKED instances: bit i & 63 of word i >> 6 lets node i into the result queue (ceil(n / 64) words)
 };
 
 // Distance evaluators: per-query state in LDS (`prepare`), one neighbour per lane (`operator()`).
@@ -181,7 +182,16 @@ __device__ __forceinline__ void hn_order_result(float *od, int64_t *ol, int m, b
     }
 }
 
-template <class DIST>
+// MASKED (cvtmi_hnsw_search*_masked) is current hnswlib's searchBaseLayerST with isIdAllowed: a.mask decides what enters the RESULT
+// queue and never what is traversed.  Every accepted neighbour joins the candidate queue, allowed or not; only allowed ones join the
+// top queue; `lower` follows the top queue once it holds something (+inf until then); and the walk may stop on `-c.d > lower` only
+// when the top queue is full -- while it is not, the candidate queue running empty is the only end.  With an all-ones mask every
+// candidate is also in the top queue while that is not full, so `-c.d > lower` cannot hold then and the extra condition is vacuous:
+// the unmasked result, bit for bit.  The candidate queue is no longer bounded by ef (nothing is pruned while few allowed nodes have
+// been found): the plan gives it room for n entries, a node enters it at most once (its visited bit), so it cannot overflow and
+// the loop ends.  The mask is read as 32-bit words, the same word index and bit as the visited bitmap (little-endian halves of the
+// caller's uint64 words); a node id is < n, so nothing behind ceil(n / 64) words is read and bits past n are never looked at.
+template <class DIST, bool MASKED>
 __global__ __launch_bounds__(64, 8) void hnsw_search_kernel(const HnswArgs a)  // <= 64 VGPRs: 8 waves per SIMD, the traversal lives on queries in flight
 {
     extern __shared__ __attribute__((aligned(16))) float hn_smem[];
@@ -252,19 +262,22 @@ __global__ __launch_bounds__(64, 8) void hnsw_search_kernel(const HnswArgs a)  /
 
         // ---- level 0: searchBaseLayerST (:217-280) ----
         int top_n = 0, cand_n = 0;
+        const uint32_t *mask32 = reinterpret_cast<const uint32_t *>(a.mask);
         {
             float o[1];
             o[0] = dist(cur);
-            hn_push(top, top_n, o[0], cur, lane);
+            // (readfirstlane: `cur` holds one value in all 64 lanes, and the branch around the wave-wide push must be a scalar one)
+            const bool ok = !MASKED || __builtin_amdgcn_readfirstlane((int)((mask32[cur >> 5] >> (cur & 31)) & 1u)) != 0;
+            if (ok) hn_push(top, top_n, o[0], cur, lane);
             hn_push(cand, cand_n, -o[0], cur, lane);
             if (w) vis[cur >> 5] |= 1u << (cur & 31);
             __builtin_amdgcn_s_waitcnt(0);
         }
-        float lower = top.get(0).d;
+        float lower = (!MASKED || top_n > 0) ? top.get(0).d : __uint_as_float(0x7f800000u);
         bool overflow = false;
         while (cand_n > 0) {
             const HnEnt c = cand.get(0);
-            if (-c.d > lower) break;
+            if (-c.d > lower && (!MASKED || top_n >= ef)) break;   // under a mask the walk may only stop on a FULL result queue
             // the expanded node's links are requested BEFORE the pop walks the queue (the walk's deeper levels live in HBM): the two
             // latencies overlap instead of adding up
             // (count and first 64 neighbours in ONE round trip: a node's row always holds maxM0 + 1 words, stale ones past the count
@@ -278,15 +291,24 @@ __global__ __launch_bounds__(64, 8) void hnsw_search_kernel(const HnswArgs a)  /
                 bool act = j < size;
                 const uint32_t nb = base == 0 ? nb0 : (act ? ll[1 + j] : 0u);
                 typename DIST::Early pre = dist.early(act ? nb : c.id);
+                bool ok = true;
                 if (act) {
                     const uint32_t bit = 1u << (nb & 31);
+                    // the neighbour's mask word is requested in the round trip of its visited bit (n / 8 bytes for all queries: L2-resident);
+                    // a gather of its own would add one dependent round trip per expanded node
+                    uint32_t mw = 0u;
+                    if (MASKED) mw = mask32[nb >> 5];
                     act = (atomicOr(&vis[nb >> 5], bit) & bit) == 0;
+                    if (MASKED) ok = (mw & bit) != 0;
                 }
                 float o[1] = { 0.0f };
                 if (act) o[0] = dist.finish(nb, pre);
                 // list order.  Once the top queue is full its maximum only falls, so a neighbour that fails `lower > d` now fails it
                 // for the rest of this list: the rejected ones are dropped by ballot, and the walk visits accepted neighbours only
+                // (MASKED: the same holds -- a full top queue stays full, and pushes into it still only lower its maximum)
                 unsigned long long m = __ballot(act && (top_n < ef || lower > o[0]));
+                // the lanes' mask bits as one wave-uniform word: the branch around the wave-wide top-queue operations below is scalar
+                const unsigned long long okm = MASKED ? __ballot(ok) : ~0ull;
                 while (m) {
                     const int b = __ffsll((long long)m) - 1;
                     m &= m - 1;
@@ -294,10 +316,12 @@ __global__ __launch_bounds__(64, 8) void hnsw_search_kernel(const HnswArgs a)  /
                     const uint32_t id = (uint32_t)__shfl((int)nb, b);
                     if (lower > d || top_n < ef) {   // lower == top.get(0).d whenever the queue is non-empty
                         if (cand_n >= cand_cap) { overflow = true; break; }
-                        hn_push(cand, cand_n, -d, id, lane);
-                        hn_push(top, top_n, d, id, lane);
-                        if (top_n > ef) hn_pop(top, top_n, lane);
-                        lower = top.get(0).d;
+                        hn_push(cand, cand_n, -d, id, lane);   // traversed whether allowed or not
+                        if (!MASKED || ((okm >> b) & 1ull)) {
+                            hn_push(top, top_n, d, id, lane);
+                            if (top_n > ef) hn_pop(top, top_n, lane);
+                        }
+                        if (!MASKED || top_n > 0) lower = top.get(0).d;
                         if (top_n >= ef) m &= __ballot(act && lower > o[0]);
                     }
                 }
@@ -338,40 +362,51 @@ static void hnsw_fill_args(HnswArgs &a, const HnswDevGraph &g, int64_t nq, int k
     a.raw_ids = 0;
     a.dynamic = 1;
     a.top_lds = hnsw_top_lds(ef > k ? ef : k);
+    a.mask = nullptr;
+}
+
+template <bool MASKED>
+static decltype(&hnsw_search_kernel<DistF32<true, 4>, MASKED>) hnsw_f32_kernel(bool ip, int lanes)
+{
+    if (ip) return lanes == 4 ? hnsw_search_kernel<DistF32<true, 4>, MASKED> : hnsw_search_kernel<DistF32<true, 1>, MASKED>;
+    if (lanes == 8) return hnsw_search_kernel<DistF32<false, 8>, MASKED>;
+    if (lanes == 4) return hnsw_search_kernel<DistF32<false, 4>, MASKED>;
+    return hnsw_search_kernel<DistF32<false, 1>, MASKED>;
 }
 
 int launch_hnsw_search(const HnswDevGraph &g, int metric, const float *q, int64_t nq, int k, int ef, float *out_d,
                        int64_t *out_label, uint32_t *visited, void *cand_scratch, int slots, int64_t words, int64_t gcap,
-                       int *err, hipStream_t st)
+                       int *err, hipStream_t st, const uint64_t *mask)
 {
     if (nq <= 0) return CVTMI_OK;
     HnswArgs a;
     hnsw_fill_args(a, g, nq, k, ef, out_d, out_label, visited, cand_scratch, words, gcap, err);
     a.q = q;
+    a.mask = mask;
     const size_t lds = (size_t)hnsw_lds_bytes(g.D, ef > k ? ef : k);
     const bool ip = metric == CVTMI_METRIC_IP;
     const int lanes = (g.D % 4 != 0) ? 1 : (ip ? 4 : (g.D % 16 == 0 ? 8 : 4));
-    decltype(&hnsw_search_kernel<DistF32<true, 4> >) kern;
-    if (ip) { if (lanes == 4) kern = hnsw_search_kernel<DistF32<true, 4> >; else kern = hnsw_search_kernel<DistF32<true, 1> >; }
-    else if (lanes == 8) kern = hnsw_search_kernel<DistF32<false, 8> >;
-    else if (lanes == 4) kern = hnsw_search_kernel<DistF32<false, 4> >;
-    else kern = hnsw_search_kernel<DistF32<false, 1> >;
-    return launch_lds("hnsw_search_kernel", kern, slots, 64, lds, st, a);
+    if (mask) return launch_lds("hnsw_search_kernel<masked>", hnsw_f32_kernel<true>(ip, lanes), slots, 64, lds, st, a);
+    return launch_lds("hnsw_search_kernel", hnsw_f32_kernel<false>(ip, lanes), slots, 64, lds, st, a);
 }
 
 // same traversal, distances = ADC over the nodes' PQ codes (codes [n][M] in internal-id order, lut [nq][M][K])
 int launch_hnsw_search_adc(const HnswDevGraph &g, const float *lut, const uint8_t *codes, int M, int K, int64_t nq, int k, int ef,
                            float *out_d, int64_t *out_label, uint32_t *visited, void *cand_scratch, int slots, int64_t words,
-                           int64_t gcap, int *err, hipStream_t st, int raw_ids, int state_floats)
+                           int64_t gcap, int *err, hipStream_t st, int raw_ids, int state_floats, const uint64_t *mask)
 {
     if (nq <= 0) return CVTMI_OK;
     HnswArgs a;
     hnsw_fill_args(a, g, nq, k, ef, out_d, out_label, visited, cand_scratch, words, gcap, err);
     a.lut = lut; a.codes = codes; a.M = M; a.K = K; a.raw_ids = raw_ids;
+    a.mask = mask;
     // state_floats: what the caller sized the slots for (hnsw_adc_state_floats, read ONCE per search: M K = tables in LDS, 0 = in the scratch)
     const bool lds_tables = state_floats != 0;
     const size_t lds = (size_t)hnsw_lds_bytes(state_floats, ef > k ? ef : k);
-    return launch_lds("hnsw_search_kernel", lds_tables ? hnsw_search_kernel<DistADC<true> > : hnsw_search_kernel<DistADC<false> >, slots, 64, lds, st, a);
+    if (mask)
+        return launch_lds("hnsw_search_kernel<masked>", lds_tables ? hnsw_search_kernel<DistADC<true>, true> : hnsw_search_kernel<DistADC<false>, true>,
+                          slots, 64, lds, st, a);
+    return launch_lds("hnsw_search_kernel", lds_tables ? hnsw_search_kernel<DistADC<true>, false> : hnsw_search_kernel<DistADC<false>, false>, slots, 64, lds, st, a);
 }
 
 // Exact re-rank of an ADC result list: ids [nq][R] internal ids (-1 = padding) -> out_d [nq][R] = the fp32 distance of the

@@ -450,13 +450,15 @@ struct HnswDevGraph {
     int D, maxM, maxM0, maxlevel;
     uint32_t enterpoint;
 };
-// one wave per slot; visited: slots x words uint32; cand_scratch: slots x gcap 8-byte entries; *err set on overflow
+// one wave per slot; visited: slots x words uint32; cand_scratch: slots x gcap 8-byte entries; *err set on overflow.
+// mask != null (cvtmi_hnsw_search*_masked): bit i & 63 of word i >> 6 lets node i into the result queue, ceil(n / 64) words are read;
+// the candidate queue is then bounded by n alone (HN_LCAP + gcap >= n rules the overflow out)
 int launch_hnsw_search(const HnswDevGraph &g, int metric, const float *q, int64_t nq, int k, int ef, float *out_d,
                        int64_t *out_label, uint32_t *visited, void *cand_scratch, int slots, int64_t words, int64_t gcap,
-                       int *err, hipStream_t st);
+                       int *err, hipStream_t st, const uint64_t *mask = nullptr);
 int launch_hnsw_search_adc(const HnswDevGraph &g, const float *lut, const uint8_t *codes, int M, int K, int64_t nq, int k, int ef,
                            float *out_d, int64_t *out_label, uint32_t *visited, void *cand_scratch, int slots, int64_t words,
-                           int64_t gcap, int *err, hipStream_t st, int raw_ids = 0, int state_floats = 0);
+                           int64_t gcap, int *err, hipStream_t st, int raw_ids = 0, int state_floats = 0, const uint64_t *mask = nullptr);
 // exact fp32 distances (reference summation order) of the raw queries to the nodes ids [nq][R] (-1 = padding -> +inf)
 int launch_hnsw_rerank(const HnswDevGraph &g, int metric, const float *q, int64_t nq, int R, const int64_t *ids, float *out_d,
                        hipStream_t st);

@@ -253,6 +253,37 @@ public:
         return out;
     }
 
+    // searchKnn among the labels the functor allows (current hnswlib's signature and its searchBaseLayerST rule: the filter decides
+    // what may be a result, never what is traversed; not in the reference, whose hnswlib predates filters).  NULL = the unfiltered
+    // call.  BaseFilterFunctor is bruteforce.h's (hnswlib.h includes it first).
+    std::priority_queue<std::pair<dist_t, labeltype> > searchKnn(void *query_data, size_t k, BaseFilterFunctor *isIdAllowed)
+    {
+        return searchKnnBatch(query_data, 1, k, isIdAllowed)[0];
+    }
+
+    // the functor is evaluated once per node over label_[] on the host, straight into the bitmap cvtmi_hnsw_search_masked takes
+    // (bit i & 63 of word i >> 6 = node i, the insertion order); one bitmap serves all nq queries
+    std::vector<std::priority_queue<std::pair<dist_t, labeltype> > > searchKnnBatch(const void *queries, size_t nq, size_t k,
+                                                                                  BaseFilterFunctor *isIdAllowed)
+    {
+        if (!isIdAllowed) return searchKnnBatch(queries, nq, k);
+        upload();
+        const size_t n = count_;
+        std::vector<uint64_t> mask((n + 63) / 64, 0);
+        for (size_t i = 0; i < n; ++i)
+            if ((*isIdAllowed)(label_[i])) mask[i >> 6] |= (uint64_t)1 << (i & 63);
+        static const uint64_t none = 0;   // (an empty graph: the C entry wants a pointer)
+        std::vector<float> d(nq * k);
+        std::vector<int64_t> l(nq * k);
+        if (cvtmi_hnsw_search_masked(dev_, (const float *)queries, (int64_t)nq, (int)k, (int)ef_, mask.empty() ? &none : mask.data(),
+                                     (int64_t)mask.size(), d.data(), l.data()) != CVTMI_OK)
+            throw std::runtime_error(std::string("cvt_amd: ") + cvtmi_last_error());
+        std::vector<std::priority_queue<std::pair<dist_t, labeltype> > > out(nq);
+        for (size_t q = 0; q < nq; ++q)
+            for (size_t i = 0; i < k && l[q * k + i] >= 0; ++i) out[q].push(std::make_pair((dist_t)d[q * k + i], (labeltype)l[q * k + i]));
+        return out;
+    }
+
 private:
     int draw_level()   // under count_guard_: the i-th element gets the i-th draw (hnswalg.h:139-149)
     {

@@ -1016,6 +1016,57 @@ int cvtmi_hnsw_search_adc_rerank(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q
                                  int rerank, float *dist, int64_t *labels);
 int cvtmi_hnsw_search_adc_rerank_dev(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef,
                                      int rerank, float *dist, int64_t *labels, void *stream);
+/* Masked search: the graph traversal of the entry of the same name, with a bitmap deciding which nodes may be RESULTS -- search under
+ * a filter (tenant, date range, the ids a relational query returned), hnswlib's searchKnn(query, k, BaseFilterFunctor *), the
+ * counterpart of cvtmi_flat_search_masked and cvtmi_opq_search_ivf_masked.  mask is uint64[mask_words].
+ *   Mask     bit i & 63 of word i >> 6 allows NODE i.  A node is an internal id: the insertion order, the row order of
+ *            cvtmi_hnsw_build, the order in which cvtmi_hnsw_search_adc expects code rows.  One mask serves all nq queries of the call.
+ *            mask_words >= ceil(ntotal / 64), fewer fails with CVTMI_EINVAL.  Bits at positions >= ntotal are ignored whatever they
+ *            hold, and words behind ceil(ntotal / 64) are never read: a caller may pass all-ones words.
+ *   Rule     hnswlib's searchBaseLayerST with isIdAllowed: the mask decides what enters the result queue, never what is traversed.
+ *            The greedy descent through the upper levels ignores it.  On level 0 every accepted neighbour joins the candidate queue,
+ *            allowed or not; only allowed ones join the result queue; and the walk stops on "the nearest candidate is farther than
+ *            the worst result" only once the result queue holds ef = max(ef, k) entries -- until then it ends on an empty candidate
+ *            queue alone.  Distances, heap tie mechanics, result order, NaN handling, label reporting and the k, ef <= 1024 limits
+ *            are those of the unmasked entry: it is the same kernel.
+ *   Results  an all-ones mask returns what the unmasked entry returns, bit for bit.  With ef >= the number of allowed nodes reachable
+ *            from the node the descent ends on, the result is exactly those nodes in ascending (distance, label).  With fewer than k
+ *            allowed nodes found the list pads with (0, -1), as cvtmi_hnsw_search pads on a graph smaller than k; an all-zero mask
+ *            pads everything (after walking the whole component: sparse masks cost a long walk).
+ *   Scratch  the candidate queue of a masked traversal is not bounded by ef: every slot gets room for ntotal entries, so it cannot
+ *            overflow, and the number of concurrent traversals is lowered until the scratch stays under 8 GiB (at least one).
+ * Checked before any device work: NULL h, or NULL q / mask / dist / labels with nq > 0, nq < 0, mask_words < 0, a short mask ->
+ * CVTMI_EINVAL; k / ef / rerank out of range answer as in the unmasked entry.  nq == 0 does nothing.
+ * Concurrency: a search like the others -- a leased scratch set (the host-pointer entries stage the mask through it beside the
+ * queries), concurrent with every other search on the handle.  The `_dev` entries take device q / mask / outputs and enqueue on
+ * `stream`. */
+int cvtmi_hnsw_search_masked(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int ef, const uint64_t *mask, int64_t mask_words,
+                             float *dist, int64_t *labels);
+int cvtmi_hnsw_search_masked_dev(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int ef, const uint64_t *mask, int64_t mask_words,
+                                 float *dist, int64_t *labels, void *stream);
+int cvtmi_hnsw_search_adc_masked(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef,
+                                 const uint64_t *mask, int64_t mask_words, float *dist, int64_t *labels);
+int cvtmi_hnsw_search_adc_masked_dev(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef,
+                                     const uint64_t *mask, int64_t mask_words, float *dist, int64_t *labels, void *stream);
+/* the ADC traversal runs under the mask with a result list of `rerank` nodes; the re-rank sees allowed nodes only */
+int cvtmi_hnsw_search_adc_rerank_masked(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef,
+                                        int rerank, const uint64_t *mask, int64_t mask_words, float *dist, int64_t *labels);
+int cvtmi_hnsw_search_adc_rerank_masked_dev(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64_t nq, int rotate, int k, int ef,
+                                            int rerank, const uint64_t *mask, int64_t mask_words, float *dist, int64_t *labels,
+                                            void *stream);
+/* The mask of a label set: writes all mask_words words -- the bit of every node whose label is in labels[n_labels] is set, every
+ * other bit is cleared, those at positions >= ntotal included.  The set follows the rules of cvtmi_flat_mask_labels: unsorted,
+ * duplicates and foreign labels are fine, labels compare as 64-bit patterns, nodes sharing a label are all set; n_labels == 0 clears
+ * the mask.  mask_words >= ceil(ntotal / 64), else CVTMI_EINVAL; NULL h, a negative count, a NULL set with n_labels > 0 or a NULL
+ * mask with mask_words > 0 -> CVTMI_EINVAL before any device work.  The work is the mark step of cvtmi_flat_remove_labels over the
+ * graph's labels, on a leased scratch set.  The _dev entry (set and mask are device pointers) runs on `stream` and waits for its set
+ * to reach the host, where it is sorted (8 bytes per label). */
+int cvtmi_hnsw_mask_labels(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, uint64_t *mask, int64_t mask_words);
+int cvtmi_hnsw_mask_labels_dev(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, uint64_t *mask, int64_t mask_words,
+                               void *stream);
+/* The handle's last masked search: out = { slots (concurrent traversals), candidate-queue capacity per slot in entries (LDS + HBM),
+ * scratch bytes reserved (visited bits + queues), form: 0 fp32, 1 ADC with tables in the scratch, 2 ADC with tables in LDS }. */
+int cvtmi_hnsw_last_masked(cvtmi_hnsw_t h, int64_t out[4]);
 
 #ifdef __cplusplus
 }
