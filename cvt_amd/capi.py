@@ -4,6 +4,7 @@ There is NO fallback: if libcvtmi.so is missing or a call fails, an exception is
 may be numpy (host-pointer entry points) or torch CUDA tensors (``*_dev`` entry points on the
 tensor's device, launched on torch's current stream so torch events/streams order them).
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -78,6 +79,33 @@ def _stream():
 
 def _np(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
+
+
+class _LaunchRecord(C.Structure):
+    _fields_ = [("name", C.c_char * 64), ("grid", C.c_int64 * 3), ("block", C.c_int64), ("lds", C.c_int64)]
+
+
+@contextlib.contextmanager
+def launch_log():
+    """``with launch_log() as log:`` -- the kernels the calling thread launches inside the block (cvtmi_debug_launch_log_*): `log` is a
+    list that is filled when the block ends with one (name, (grid x, y, z), block x, dynamic LDS bytes) per launch, in launch order.
+    Blocks nest (an inner block's launches are in the outer list too); other threads' launches are never seen."""
+    L = lib()
+    for f in (L.cvtmi_debug_launch_log_begin, L.cvtmi_debug_launch_log_end, L.cvtmi_debug_launch_log_read):
+        f.restype = C.c_int64
+    L.cvtmi_debug_launch_log_read.argtypes = [C.c_int64, C.c_int64, C.POINTER(_LaunchRecord)]
+    log = []
+    mark = L.cvtmi_debug_launch_log_begin()
+    try:
+        yield log
+    finally:
+        total = L.cvtmi_debug_launch_log_end()
+        if total < 0:
+            _check(int(total))
+        count = max(0, total - mark)
+        recs = (_LaunchRecord * max(1, count))()
+        L.cvtmi_debug_launch_log_read(mark, count, recs)
+        log.extend((r.name.decode(), tuple(r.grid), int(r.block), int(r.lds)) for r in recs[:count])
 
 
 def device_count():

@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "api_internal.h"
+#include "launch.h"
 
 namespace cvtmi {
 
@@ -24,6 +25,54 @@ int fail(int code, const char *fmt, ...)
     va_end(ap);
     g_err = buf;
     return code;
+}
+
+// ---- the launch log of launch.h: per thread, off unless cvtmi_debug_launch_log_begin turned it on (include/cvtmi.h) ----
+struct LaunchLog {
+    struct Rec { const char *what; int64_t x, y, z, block, lds; };
+    std::vector<Rec> recs;
+    int depth = 0;
+};
+__thread LaunchLog *g_launch_log = nullptr;          // what launch() tests: the thread's log while depth > 0
+static thread_local LaunchLog g_launch_log_store;    // the records outlive the last _end until the next outermost _begin
+
+void launch_log_note(const char *what, const Grid &grid, unsigned block_x, size_t lds)
+{
+    try {
+        g_launch_log->recs.push_back({ what, grid.x, grid.y, grid.z, (int64_t)block_x, (int64_t)lds });
+    } catch (...) {   // out of host memory: the launch goes ahead, the note is lost
+    }
+}
+
+extern "C" int64_t cvtmi_debug_launch_log_begin(void)
+{
+    LaunchLog &L = g_launch_log_store;
+    if (L.depth == 0) L.recs.clear();
+    ++L.depth;
+    g_launch_log = &L;
+    return (int64_t)L.recs.size();
+}
+
+extern "C" int64_t cvtmi_debug_launch_log_end(void)
+{
+    LaunchLog &L = g_launch_log_store;
+    if (L.depth <= 0) return fail(CVTMI_EINVAL, "cvtmi_debug_launch_log_end: no cvtmi_debug_launch_log_begin of this thread is open");
+    if (--L.depth == 0) g_launch_log = nullptr;
+    return (int64_t)L.recs.size();
+}
+
+extern "C" int64_t cvtmi_debug_launch_log_read(int64_t first, int64_t cap, cvtmi_launch_record *out)
+{
+    const LaunchLog &L = g_launch_log_store;
+    const int64_t total = (int64_t)L.recs.size();
+    if (first < 0 || cap < 0 || (cap > 0 && !out)) return fail(CVTMI_EINVAL, "cvtmi_debug_launch_log_read: bad arguments");
+    for (int64_t i = first; i < total && i - first < cap; ++i) {
+        const LaunchLog::Rec &r = L.recs[(size_t)i];
+        cvtmi_launch_record &o = out[i - first];
+        snprintf(o.name, sizeof o.name, "%s", r.what);
+        o.grid[0] = r.x; o.grid[1] = r.y; o.grid[2] = r.z; o.block = r.block; o.lds = r.lds;
+    }
+    return total;
 }
 
 // ---- the tuning values: one object per line of tuning.def, and the four rules that are more than a range ----

@@ -607,7 +607,13 @@ static FlatRoute flat_route(const cvtmi_flat_s *h, const void *q, int64_t nq, in
 }
 
 // the grid rule of launch.h, for the CPU test that pins it (include/cvtmi.h)
-extern "C" int cvtmi_describe_launch_grid(int64_t x, int64_t y, int64_t z) { return check_grid("cvtmi_describe_launch_grid", Grid(x, y, z)); }
+// (a grid that passes is noted in the thread's launch log as launch() notes it, block 1 and no LDS: the log's CPU test needs no device)
+extern "C" int cvtmi_describe_launch_grid(int64_t x, int64_t y, int64_t z)
+{
+    CVTMI_TRY(check_grid("cvtmi_describe_launch_grid", Grid(x, y, z)));
+    log_launch("cvtmi_describe_launch_grid", Grid(x, y, z), 1, 0);
+    return CVTMI_OK;
+}
 
 // which pipeline a flat search would take under the current tuning values, for inspection and for the CPU tests that pin the
 // dispatch rules (include/cvtmi.h)
@@ -625,6 +631,17 @@ extern "C" int cvtmi_flat_describe_dispatch(int metric, int D, int64_t n_rows, i
     out[1] = r.filt_f32 ? 1 : 0;
     out[2] = r.big_u8 ? 2 : (r.filt_u8 ? 1 : 0);
     out[3] = (metric == CVTMI_METRIC_L2U8 && !r.filt_u8 && !r.big_u8 && flat_u8_mstream_applies(D, n_rows, std::min<int64_t>(nq, 128), k)) ? 1 : 0;
+    return CVTMI_OK;
+}
+
+// how the uint8 stream's finish kernel would be cut for one pass of nq queries over n_rows rows, for the CPU test that pins the slice
+// rule against the kernel's round tables (include/cvtmi.h)
+extern "C" int cvtmi_flat_describe_stream_finish(int64_t n_rows, int64_t nq, int out[3])
+{
+    if (!out || n_rows < 1 || n_rows >= 0x7fffffff || nq < 1 || nq > 128) return fail(CVTMI_EINVAL, "cvtmi_flat_describe_stream_finish: bad arguments");
+    int waves = 0;
+    (void)flat_u8_mstream_scratch(n_rows, nq, nullptr, &waves);
+    out[0] = flat_u8_stream_finish_plan(n_rows, nq, waves, &out[1], &out[2]);
     return CVTMI_OK;
 }
 

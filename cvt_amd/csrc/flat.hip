@@ -17,6 +17,8 @@
 // Round-1 mapping: one lane per row, QT queries staged in LDS share every row read; selection by
 // the shared LDS top-k (block_topk.h).  The uint8 metric runs on v_dot4_u32_u8:
 // sum (q-x)^2 = |q|^2 + |x|^2 - 2<q,x>, all three exact in 32-bit integers (<= 512*255^2).
+#include <algorithm>
+
 #include "block_topk.h"
 #include "kernels.h"
 #include "dist_f32.h"
@@ -387,7 +389,13 @@ __global__ __launch_bounds__(kBlock) void flat_u8_kernel(const FlatArgs a)
 // grid = nq * S workgroups; workgroup (q, s) derives theta from all G wave minima of its query, then selects among the rows the
 // qualifying waves wrote inside ITS slice of the rows.  Wave w owns rows (w + t G) rpi + j, t = 0.., j < rpi; the slice's entries are fed
 // in ascending row order (t outermost, then wave, then j), which is the order block_topk.h's tie rule asks for.
+// FIN_MAXR: entries of the kernel's per-slice round tables.  Invariant: no slice spans more rounds than that -- a slice of c_total / S
+// chunks spans up to c_total / S / G + 2 rounds of G chunks, so FEWER slices mean MORE rounds per slice.  The host picks S with
+// flat_u8_stream_finish_plan (below), which counts the rounds exactly as the kernel does and never halves S past the bound;
+// launch_flat_u8_mstream_finish refuses what no S satisfies, as flat_u8_mstream_applies (flat_mfma.hip) does before it.
+// FIN_CAP: the selection buffer, whose 1024 words also hold the wave minima under the first bound -- at most G of them, so G <= FIN_CAP.
 constexpr int FIN_CAP = 1024, FIN_TRIG = 768, FIN_R = 4, FIN_MAXG = 8192, FIN_MAXR = 160, FIN_CL = 1024;
+static_assert(kMstreamWaves <= FIN_CAP && kMstreamWaves <= FIN_MAXG, "the finish kernel gathers up to G wave minima in FIN_CAP words");
 struct StreamFinishArgs {
     int64_t n;
     const int32_t *gmin;
@@ -452,42 +460,20 @@ __global__ __launch_bounds__(kBlock) void flat_u8_stream_finish_kernel(const Str
             }
         }
         __syncthreads();
-        const int n2 = qn_s;
-        if (n2 <= FIN_CAP) {   // workgroup-uniform; the usual case by far (n2 is about k)
-            if (tid < 64) {
-                unsigned long long e[FIN_CAP / 64];
+        const int n2 = qn_s;   // about k; never more than G <= FIN_CAP (the launch checks G), so every one of them has its word
+        if (tid < 64) {
+            unsigned long long e[FIN_CAP / 64];
 #pragma unroll
-                for (int r = 0; r < FIN_CAP / 64; ++r) {
-                    const int p = r * 64 + tid;
-                    e[r] = p < n2 ? ((unsigned long long)sel_v[p] << 32) | (uint32_t)p : ~0ull;
-                }
-                const uint32_t t = n2 >= k ? (uint32_t)(wave_select<FIN_CAP / 64>(e, k) >> 32) : KEY_MAX;   // fewer than k waves: everything qualifies
-                if (tid == 0) r_first[0] = (int)t;
+            for (int r = 0; r < FIN_CAP / 64; ++r) {
+                const int p = r * 64 + tid;
+                e[r] = p < n2 ? ((unsigned long long)sel_v[p] << 32) | (uint32_t)p : ~0ull;
             }
-            __syncthreads();
-            theta = (uint32_t)r_first[0];
-            __syncthreads();
-        } else {               // masses of equal minima: the sorting path
-            __syncthreads();
-            topk_init(tk);
-            __syncthreads();
-            int tile = 0;
-            for (int base = 0; base < G; base += kBlock * FIN_R, ++tile) {
-                uint32_t key[FIN_R][1], pay[FIN_R];
-#pragma unroll
-                for (int r = 0; r < FIN_R; ++r) {
-                    const int i = base + r * kBlock + tid;
-                    pay[r] = (uint32_t)i;
-                    const uint32_t v = i < G ? (uint32_t)gm[i] : KEY_MAX;
-                    key[r][0] = v <= theta1 ? v : KEY_MAX;
-                }
-                topk_tile<1, FIN_R, FIN_CAP, FIN_TRIG>(tk, k, tile, key, pay);
-            }
-            __syncthreads();
-            topk_compact(tk, k);
-            theta = tk.thr[0];
-            __syncthreads();
+            const uint32_t t = n2 >= k ? (uint32_t)(wave_select<FIN_CAP / 64>(e, k) >> 32) : KEY_MAX;   // fewer than k waves: everything qualifies
+            if (tid == 0) r_first[0] = (int)t;
         }
+        __syncthreads();
+        theta = (uint32_t)r_first[0];
+        __syncthreads();
     }
     // all qualifying waves, ascending (wave 0: one ballot per 64 waves)
     if (tid < 64) {
@@ -510,7 +496,7 @@ __global__ __launch_bounds__(kBlock) void flat_u8_stream_finish_kernel(const Str
     const int64_t c_total = (n + ((int64_t)1 << rpi_log2) - 1) >> rpi_log2;
     const int64_t c_lo = c_total * sl / S, c_hi = c_total * (sl + 1) / S;
     const int64_t t_a = c_lo / G;
-    const int n_rounds = c_hi > c_lo ? (int)((c_hi - 1) / G - t_a + 1) : 0;   // <= FIN_MAXR: n < 2^31, G * rpi >= 2^16, S = 64
+    const int n_rounds = c_hi > c_lo ? (int)((c_hi - 1) / G - t_a + 1) : 0;   // <= FIN_MAXR: flat_u8_stream_finish_plan chose S so
     if (tid < n_rounds) {
         const int64_t first = (t_a + tid) * G;
         const int lo_w = (int)(c_lo > first ? c_lo - first : 0), hi_w = (int)(c_hi - first < G ? c_hi - first : G);
@@ -1326,18 +1312,41 @@ int launch_count_nonzero(const uint32_t *flags, int64_t count, uint32_t *out, hi
     return launch("count_nonzero_kernel", count_nonzero_kernel, 1, kBlock, 0, st, flags, count, out);
 }
 
-constexpr int STREAM_SLICES = 64;
+constexpr int STREAM_SLICES = 64, STREAM_RPI_LOG2 = 5;   // (a chunk = the 32 rows of one tile)
+// the most rounds a slice spans when the chunks of n rows are cut into S slices: the kernel's own n_rounds, over every slice
+static int stream_finish_rounds(int64_t n, int G, int S)
+{
+    const int64_t c_total = (n + ((int64_t)1 << STREAM_RPI_LOG2) - 1) >> STREAM_RPI_LOG2;
+    int64_t worst = 0;
+    for (int sl = 0; sl < S; ++sl) {
+        const int64_t c_lo = c_total * sl / S, c_hi = c_total * (sl + 1) / S;
+        if (c_hi > c_lo) worst = std::max(worst, (c_hi - 1) / G - c_lo / G + 1);
+    }
+    return (int)std::min<int64_t>(worst, INT32_MAX);
+}
+// slices per query: every slice repeats the query's threshold selection, so no more of them than fill the chip once
+// (64 queries x 64 slices = 4096 workgroups took 112 us; x 16 ...): halved from 64 while queries x slices pass 1024, down to 8, on
+// tables up to 64 Mi rows -- and never to a count whose slices would span more than FIN_MAXR rounds (65 .. 128 queries from
+// 41.7 M rows on keep 16 slices; the rule used to give them 8 and 161 .. 257 rounds: writes past the kernel's round tables)
+int flat_u8_stream_finish_plan(int64_t n, int64_t nq, int G, int *rounds, int *max_rounds)
+{
+    int S = STREAM_SLICES;
+    if (n <= ((int64_t)64 << 20))
+        while (S > 8 && nq * S > 1024 && stream_finish_rounds(n, G, S >> 1) <= FIN_MAXR) S >>= 1;
+    if (rounds) *rounds = stream_finish_rounds(n, G, S);
+    if (max_rounds) *max_rounds = FIN_MAXR;
+    return S;
+}
 // selection after flat_u8_mstream_kernel (flat_mfma.hip): wave minima wmin[nq][G], tile minima tmin[tiles][nqp] -> part [nq][slices][k] -> merge
 int launch_flat_u8_mstream_finish(int D, const uint8_t *data, int64_t n, const uint8_t *q, int64_t nq, int k, const int32_t *wmin, int G,
                                   const int32_t *tmin, int nqp, int tile_group, float *part_d, int64_t *part_id, float *out_d, int64_t *out_rows, hipStream_t st)
 {
-    // slices per query: every slice repeats the query's threshold selection, so no more of them than fill the chip once
-    // (64 queries x 64 slices = 4096 workgroups took 112 us; x 16 ...); long indexes keep 64 (rounds per slice <= FIN_MAXR)
-    int S = STREAM_SLICES;
-    if (n <= ((int64_t)64 << 20))
-        while (S > 4 && nq * S > 1024) S >>= 1;
+    int rounds = 0;
+    const int S = flat_u8_stream_finish_plan(n, nq, G >= 1 ? G : 1, &rounds, nullptr);
+    if (G < 1 || G > FIN_CAP || rounds > FIN_MAXR)
+        return fail(CVTMI_EUNSUPPORTED, "flat_u8_mstream_finish: %d waves / %d rounds per slice outside the kernel's tables (%d / %d)", G, rounds, FIN_CAP, FIN_MAXR);
     StreamFinishArgs fa = {};
-    fa.n = n; fa.gmin = wmin; fa.G = G; fa.S = S; fa.rpi_log2 = 5; fa.k = k; fa.part_d = part_d; fa.part_id = part_id;
+    fa.n = n; fa.gmin = wmin; fa.G = G; fa.S = S; fa.rpi_log2 = STREAM_RPI_LOG2; fa.k = k; fa.part_d = part_d; fa.part_id = part_id;
     fa.tmin = tmin; fa.nqp = nqp; fa.tile_group = tile_group; fa.X = data; fa.Q = q; fa.D = D;
     CVTMI_TRY(launch("flat_u8_stream_finish_kernel", flat_u8_stream_finish_kernel, nq * S, kBlock, 0, st, fa));
     return launch_topk_merge(part_d, part_id, nq, S, k, out_d, out_rows, st);

@@ -1252,10 +1252,14 @@ constexpr int MSTREAM_BLOCKS = 256;   // one 4-wave workgroup per CU (one wave p
 // waves without a tile publish "no minimum" and are never looked at.  It was 262 144 (eight tiles per wave) until a sweep over table
 // sizes (round 5, tools/sweep_flat_small_tables.py) showed the row-tile kernels 2-20x behind on everything smaller: 65 536 x 512-d,
 // 16 / 100 / 1000 queries 0.39 / 0.84 / 1.06 ms against 0.046 / 0.060 / 0.47.  (cvtmi_set_tuning("flat_u8_mstream_min_rows"))
+static_assert(MSTREAM_BLOCKS * 4 == kMstreamWaves, "kernels.h names the stream's wave count for the finish kernel's tables");
 bool flat_u8_mstream_applies(int D, int64_t n, int64_t nq, int k)
 {
-    return (D == 128 || D == 256 || D == 512) && nq >= tune_flat_u8_mstream_min.geti() && nq <= 128 && n >= tune_flat_u8_mstream_min_rows.get() && n < 0x7fffffff && k <= 128 &&
-           n / 32 / 64 / (MSTREAM_BLOCKS * 4) + 2 <= 160;   // rounds a finish slice can span (FIN_MAXR, flat.hip): 331 M rows
+    if (!((D == 128 || D == 256 || D == 512) && nq >= tune_flat_u8_mstream_min.geti() && nq <= 128 && n >= tune_flat_u8_mstream_min_rows.get() && n < 0x7fffffff && k <= 128))
+        return false;
+    int rounds = 0, max_rounds = 0;   // rounds a finish slice spans under the slice count the launch will take (FIN_MAXR, flat.hip): up to ~333 M rows
+    (void)flat_u8_stream_finish_plan(n, nq, kMstreamWaves, &rounds, &max_rounds);
+    return rounds <= max_rounds;
 }
 // entries of the tile-group minima array: groups of MS_GROUP tiles per wave, (group, wave) major
 int64_t flat_u8_mstream_groups(int64_t n)

@@ -391,6 +391,11 @@ int launch_flat_u8_mstream(int D, const uint8_t *data, const int32_t *norms, int
 int launch_flat_u8_mstream_finish(int D, const uint8_t *data, int64_t n, const uint8_t *q, int64_t nq, int k, const int32_t *wmin, int G,
                                   const int32_t *tmin, int nqp, int tile_group, float *part_d, int64_t *part_id, float *out_d, int64_t *out_rows, hipStream_t st);
 int flat_u8_stream_slices();
+// waves of the stream's grid (flat_mfma.hip: MSTREAM_BLOCKS * 4) = wave minima per query the finish kernel selects among (flat.hip: <= FIN_CAP)
+constexpr int kMstreamWaves = 1024;
+// slices per query of the finish kernel for nq queries of one pass over n rows whose minima come from G waves, and through *rounds the
+// most rounds one of those slices spans; the choice never lets them pass *max_rounds = FIN_MAXR while any slice count allows it
+int flat_u8_stream_finish_plan(int64_t n, int64_t nq, int G, int *rounds, int *max_rounds);
 bool flat_u8_gfilter_shape(int D);
 int launch_gather_labels(int64_t *ids, int64_t count, const int64_t *labels, hipStream_t st);
 // ids[i] = ids[i] >= 0 ? ids[i] + base : -1

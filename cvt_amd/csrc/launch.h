@@ -28,11 +28,23 @@ inline int check_grid(const char *what, const Grid &g)
     return CVTMI_OK;
 }
 
+// The launch log (cvtmi_debug_launch_log_begin / _end / _read, include/cvtmi.h): while the calling thread has it on, every launch that
+// passed the grid rule is noted with its name, grid, block and dynamic LDS.  Off -- the default -- it costs a launch the test of one
+// thread-local pointer: no lock, no allocation, nothing on the device.  `what` is kept as a pointer: pass string literals.
+struct LaunchLog;
+extern __thread LaunchLog *g_launch_log;   // api.hip; null while the thread's log is off
+void launch_log_note(const char *what, const Grid &grid, unsigned block_x, size_t lds);
+inline void log_launch(const char *what, const Grid &grid, unsigned block_x, size_t lds)
+{
+    if (__builtin_expect(g_launch_log != nullptr, 0)) launch_log_note(what, grid, block_x, lds);
+}
+
 // `what` names the kernel in the messages.  The arguments convert to the kernel's parameter types exactly as in a direct launch.
 template <class... KA, class... A>
 inline int launch(const char *what, void (*kernel)(KA...), const Grid &grid, dim3 block, size_t lds, hipStream_t st, A &&...args)
 {
     CVTMI_TRY(check_grid(what, grid));
+    log_launch(what, grid, block.x, lds);
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid.x, (unsigned)grid.y, (unsigned)grid.z), block, lds, st, static_cast<A &&>(args)...);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(CVTMI_EHIP, "launch of %s failed: %s", what, hipGetErrorString(e));

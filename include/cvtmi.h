@@ -504,6 +504,32 @@ int cvtmi_flat_describe_dispatch(int metric, int D, int64_t n_rows, int64_t nq, 
  * cvtmi_last_error().  What tests/test_launch.py pins the rule with. */
 int cvtmi_describe_launch_grid(int64_t x, int64_t y, int64_t z);
 
+/* How the selection behind the uint8 streaming kernel would be cut for ONE pass of nq queries (1 .. 128) over n_rows rows (pure host
+ * logic): out[0] = slices per query (8, 16, 32 or 64), out[1] = the most rounds of wave minima one slice spans, out[2] = the rounds the
+ * kernel's per-slice tables hold.  out[1] <= out[2] wherever cvtmi_flat_describe_dispatch reports the stream (out[3]); the slice count
+ * is never lowered to one that would break it.  What tests/test_flat_u8_stream_plan.py pins the rule with. */
+int cvtmi_flat_describe_stream_finish(int64_t n_rows, int64_t nq, int out[3]);
+
+/* The launch log, a debugging and testing aid: which kernels a call launched.  Per thread and off by default; while it is off a launch
+ * pays one test of a thread-local pointer.  cvtmi_debug_launch_log_begin() turns the calling thread's log on and returns the number of
+ * records it holds -- 0 for an outermost begin, which also empties it; begins nest, and a nested one returns the mark at which its own
+ * records start.  cvtmi_debug_launch_log_end() closes the innermost begin and returns the number of records (CVTMI_EINVAL, negative,
+ * without an open begin); after the outermost end the log is off and keeps its records until the thread's next begin.
+ * cvtmi_debug_launch_log_read() copies records first .. first + cap - 1 (those that exist) to out and returns the number of records in
+ * the log, whatever cap is.  A record: the kernel's name as the sources spell it (template arguments are not part of it), the grid, the
+ * block's x and the dynamic LDS bytes of a launch that passed the grid rule, in launch order; cvtmi_describe_launch_grid notes a grid
+ * it accepts the same way (block 1, no LDS).  None of the three touches a device or a stream, and other threads' launches are never
+ * seen. */
+typedef struct cvtmi_launch_record {
+    char name[64];
+    int64_t grid[3];
+    int64_t block;
+    int64_t lds;
+} cvtmi_launch_record;
+int64_t cvtmi_debug_launch_log_begin(void);
+int64_t cvtmi_debug_launch_log_end(void);
+int64_t cvtmi_debug_launch_log_read(int64_t first, int64_t cap, cvtmi_launch_record *out);
+
 /* Page-locked host memory.  The host-pointer entries move their arrays through pinned staging areas (one extra host copy each way);
  * arrays that already ARE page-locked -- from here, or the caller's own hipHostMalloc / hipHostRegister -- need none: page-locked
  * queries go to the copy engine as they are, and page-locked RESULT arrays of cvtmi_opq_search are written by the kernels themselves

@@ -117,16 +117,30 @@ def test_flat_u8_mfma_query_tiles(amd, orc, D, nq, k):
     dist0 = ((db[:5000].astype(np.int64) - q[0].astype(np.int64)) ** 2).sum(axis=1)
     db[:5000] = db[:5000][np.argsort(-dist0, kind="stable")]
     ix = amd.FlatIndex(L2U8, D); ix.add(db)
-    d, i = ix.search(q, k)
     _, odi, oi = orc.flat_search(L2U8, db, q, k)
-    assert np.array_equal(d, odi), (D, nq, k)
-    assert np.array_equal(i, oi), (D, nq, k)
+    # the default route (since round 5 the stream takes these tables at 128 / 256 / 512-d) and flat_variant 1, which must still run the
+    # matrix-core kernels this test was shaped for: the 32-query kernel or a row-tile kernel, as flat_u8_mfma_qtile says
+    qt = 32 if k > 80 or (k > 24 and nq <= 64) or nq <= 32 else (128 if k > 24 or 64 < nq <= 128 else (256 if nq > 128 else 64))
+    want = ("flat_u8_mfma_kernel", 256) if qt == 32 else ("flat_u8_rowtile_kernel", 64 * (4 if k > 24 else qt // 32))
+    for variant in (0, 1):
+        try:
+            amd.set_tuning("flat_variant", variant)
+            with amd.launch_log() as log:
+                d, i = ix.search(q, k)
+        finally:
+            amd.set_tuning("flat_variant", 0)
+        assert np.array_equal(d, odi), (D, nq, k, variant)
+        assert np.array_equal(i, oi), (D, nq, k, variant)
+        if variant == 1:
+            ran = {(name, block) for name, _, block, _ in log if name.startswith("flat_u8_") and "norms" not in name}
+            assert ran == {want}, (ran, want)
 
 
 def test_flat_u8_many_splits_parity(amd, orc):
     """200 K rows -> 24 row splits of one 128-query workgroup column: the splits exchange their k-th best and, for
     k <= 16, their minima (k slots per query) to tighten each other's filter; the merged result must still be
-    the oracle's, bit for bit, incl. duplicate rows in different splits."""
+    the oracle's, bit for bit, incl. duplicate rows in different splits.  (The default route is the stream since round 5;
+    flat_variant 1 runs the row-tile kernel described here, which the launch log confirms: 24 workgroups of 4 waves.)"""
     rng = np.random.default_rng(31)
     n, D, nq = 200_000, 128, 100
     db = rng.integers(0, 256, size=(n, D), dtype=np.uint8)
@@ -135,10 +149,19 @@ def test_flat_u8_many_splits_parity(amd, orc):
     q[2] = db[77_777]
     ix = amd.FlatIndex(L2U8, D); ix.add(db)
     for k in (10, 3, 16):
-        d, i = ix.search(q, k)
         _, odi, oi = orc.flat_search(L2U8, db, q, k)
-        assert np.array_equal(d, odi), k
-        assert np.array_equal(i, oi), k
+        for variant in (0, 1):
+            try:
+                amd.set_tuning("flat_variant", variant)
+                with amd.launch_log() as log:
+                    d, i = ix.search(q, k)
+            finally:
+                amd.set_tuning("flat_variant", 0)
+            assert np.array_equal(d, odi), (k, variant)
+            assert np.array_equal(i, oi), (k, variant)
+            if variant == 1:
+                ran = [(name, grid, block) for name, grid, block, _ in log if name.startswith("flat_u8_") and "norms" not in name]
+                assert ran == [("flat_u8_rowtile_kernel", (24, 1, 1), 256)], ran
 
 
 def test_flat_u8_row_tile_empty_last_split(amd, orc):
