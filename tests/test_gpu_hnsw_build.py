@@ -2,8 +2,11 @@
 
 max_batch = 1 is the reference's sequential insertion: the saved file is compared byte for byte with the golden graphs the reference
 wrote, with the reference compiled in place (oracle/_ref, where built), and with the host mirror's sequential build (the hnsw_build
-CLI, itself pinned to the reference by tests/test_host_hnsw_build.py).  Larger batches give a different, deterministic graph: it is
-checked for determinism, soundness, agreement of the GPU search with the reference's searchKnn on the saved file, and recall."""
+CLI, itself pinned to the reference by tests/test_host_hnsw_build.py).  Larger batches give a different, deterministic graph.  What
+that graph must be, byte for byte, is checked in tests/test_gpu_hnsw_build_batches.py against a Python model of DESIGN 4.11
+(tests/hnsw_build_model.py, pinned on the CPU by tests/test_hnsw_build_model.py) on graphs of a few thousand rows; the graphs here
+are beyond that model's reach and are checked for determinism, soundness, agreement of the GPU search with the reference's
+searchKnn on the saved file, and recall."""
 import os
 import struct
 import subprocess
@@ -230,6 +233,9 @@ def recall(amd, blob, metric, D, q, truth, ef):
 
 @pytest.mark.parametrize("metric", [0, 1])
 def test_recall_matches_host_build(amd, tmp_path, metric):
+    """The host graph is the sequential one (one addPoint per row: the reference's own file, a fixed graph).  A 16-thread host build
+    depends on how its threads interleave, and on these rows its recall@10 at ef = 64 moved between 0.723 and 0.753 over six
+    builds, three times the 0.01 allowed here, around the sequential graph's 0.7397; the GPU graph is a fixed 0.7355."""
     import torch
     x, q = config5_rows(100_000)
     xd, qd = torch.from_numpy(x).cuda(), torch.from_numpy(q).cuda()
@@ -238,7 +244,7 @@ def test_recall_matches_host_build(amd, tmp_path, metric):
     else:
         truth = torch.topk(-torch.cdist(qd, xd), 10, dim=1).indices.cpu().numpy()
     gpu = gpu_build(amd, x, metric, 16, 40, max_batch=0)
-    host = host_build(tmp_path, x, metric, 16, 40, "host", threads=16)
+    host = host_build(tmp_path, x, metric, 16, 40, "host")
     rg = recall(amd, gpu, metric, 128, q, truth, 64)
     rh = recall(amd, host, metric, 128, q, truth, 64)
     assert rg[0] >= rh[0] - 0.01 and rg[1] >= rh[1] - 0.01, (rg, rh)
