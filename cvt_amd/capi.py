@@ -1154,6 +1154,58 @@ HnswIndex.mask_from_labels = _hnsw_mask_from_labels
 HnswIndex.last_masked = _hnsw_last_masked
 
 
+def _hnsw_add(self, x, labels=None, max_batch=0):
+    """cvtmi_hnsw_add[_dev]: the rows x [m][D] (numpy, or a CUDA tensor with labels on the same device) appended as internal ids
+    ntotal .. ntotal + m - 1, labels as given (None: the internal ids), batch-synchronous on the GPU as in hnsw_build, the schedule
+    continued from the rows the graph holds (max_batch = 1: the reference's sequential addPoint; 0: the default schedule)."""
+    m, D = x.shape
+    assert D == self.D
+    if _is_torch(x):
+        import torch
+        assert x.is_contiguous() and x.dtype == torch.float32
+        lab = None
+        if labels is not None:
+            lab = labels if _is_torch(labels) else torch.as_tensor(np.ascontiguousarray(labels, dtype=np.uint64).view(np.int64))
+            lab = lab.to(device=x.device, dtype=torch.int64).contiguous()
+        _check(lib().cvtmi_hnsw_add_dev(self.h, _ptr(x), C.c_int64(m), _ptr(lab), C.c_int(max_batch), _stream()))
+        return
+    x = _np(x, np.float32)
+    lab = None if labels is None else _np(labels, np.uint64)
+    _check(lib().cvtmi_hnsw_add(self.h, _ptr(x), C.c_int64(m), _ptr(lab), C.c_int(max_batch)))
+
+
+def _hnsw_reserve(self, n):
+    """cvtmi_hnsw_reserve: the header's max_elements becomes at least n (never lowered)"""
+    _check(lib().cvtmi_hnsw_reserve(self.h, C.c_int64(n)))
+
+
+def _hnsw_level_draws(self):
+    """draws taken from the handle's level stream (cvtmi_hnsw_level_draws): n after a build of n rows, 0 after a load, + m per add"""
+    n = C.c_int64(0)
+    _check(lib().cvtmi_hnsw_level_draws(self.h, C.byref(n)))
+    return n.value
+
+
+def _hnsw_set_level_draws(self, n):
+    """cvtmi_hnsw_set_level_draws: the level stream re-seeded and advanced by n draws (n = ntotal after a load: later adds
+    continue the build that wrote the file)"""
+    _check(lib().cvtmi_hnsw_set_level_draws(self.h, C.c_int64(n)))
+
+
+def _hnsw_last_add(self):
+    """(first internal id, batches, largest batch, max_elements afterwards) of the last add that added rows (cvtmi_hnsw_last_add)"""
+    o = (C.c_int64 * 4)()
+    _check(lib().cvtmi_hnsw_last_add(self.h, o))
+    return o[0], o[1], o[2], o[3]
+
+
+HnswIndex.add = _hnsw_add
+HnswIndex.reserve = _hnsw_reserve
+HnswIndex.level_draws = _hnsw_level_draws
+HnswIndex.set_level_draws = _hnsw_set_level_draws
+HnswIndex.last_add = _hnsw_last_add
+
+
 def hnsw_build(x, metric, M, ef_construction, labels=None, max_batch=0):
     """cvtmi_hnsw_build[_dev]: a HierarchicalNSW graph over the rows x [n][D] (numpy, or a CUDA tensor with labels on the same
     device), batch-synchronous on the GPU (max_batch = 1: the reference's sequential insertion; 0: the default schedule)."""

@@ -1,4 +1,4 @@
-// api_hnsw.hip -- the HNSW handle of the C ABI (include/cvtmi.h): load / build / save, the search, the search over OPQ codes (ADC)
+// api_hnsw.hip -- the HNSW handle of the C ABI (include/cvtmi.h): load / build / add / save, the search, the search over OPQ codes (ADC)
 // with and without the exact re-rank, each of them under a node mask as well, and the mask of a label set.
 #include <string.h>
 
@@ -12,9 +12,10 @@
 #include "rm_common.h"
 
 // ================================================================ HNSW search ==================
-// The graph is immutable once loaded and searchKnn is a pure read in the reference (hnswalg.h:688-728): searches on one handle run side
-// by side, each on a leased scratch set (visited bits, spilled queues, re-rank lists, host staging) and the stream of its caller (the
-// host-pointer entries: the set's own stream).
+// searchKnn is a pure read in the reference (hnswalg.h:688-728): searches on one handle run side by side, each on a leased scratch set
+// (visited bits, spilled queues, re-rank lists, host staging) and the stream of its caller (the host-pointer entries: the set's own
+// stream).  The one call that changes a graph, cvtmi_hnsw_add, holds the handle exclusively (HnswLease holds it shared); every search
+// plans its scratch from the node count it finds, so a set that served a smaller graph is re-sized, never reused as it was.
 
 int cvtmi_hnsw_load(const void *file, int64_t bytes, int metric, int D, cvtmi_hnsw_t *out)
 {
@@ -112,6 +113,7 @@ int cvtmi_hnsw_load(const void *file, int64_t bytes, int metric, int D, cvtmi_hn
     h->levels.swap(levels);
     h->max_elements = max_elements; h->M = M; h->efc = efc; h->mult = mult;
     h->hdr_maxlevel = maxlevel; h->hdr_enterpoint = enterpoint;
+    h->upper_words = (int64_t)upper.size();   // (the level stream stays at its initialiser: 0 draws, as after the reference's loadIndex)
     *out = h;
     return CVTMI_OK;
 }
@@ -138,10 +140,10 @@ static int hnsw_build_impl(const float *x, bool dev, int64_t n, int D, int metri
     int32_t maxlevel = 0;
     uint32_t ep = 0;
     int64_t upper_words = 0;
+    std::default_random_engine rng(100);
     try {
         levels.resize((size_t)n);
         uoff.assign((size_t)n, -1);
-        std::default_random_engine rng(100);
         std::uniform_real_distribution<double> u01(0.0, 1.0);
         for (int64_t i = 0; i < n; ++i) {
             levels[(size_t)i] = (int32_t)(-log(u01(rng)) * mult);
@@ -175,14 +177,16 @@ static int hnsw_build_impl(const float *x, bool dev, int64_t n, int D, int metri
         h->g.upper_off = h->upper_off.as<int64_t>(); h->g.upper = h->upper.as<uint32_t>();
         h->g.n = n; h->g.D = D; h->g.maxM = maxM; h->g.maxM0 = maxM0; h->g.maxlevel = maxlevel; h->g.enterpoint = ep;
         // (launch_hnsw_build synchronises the stream before it returns: the host vectors above outlive every copy from them)
-        return launch_hnsw_build(h->g, h->links0.as<uint32_t>(), h->upper.as<uint32_t>(), levels.data(), metric, M, efe, max_batch,
-                                 h->cus, st);
+        return launch_hnsw_build("cvtmi_hnsw_build", h->g, h->links0.as<uint32_t>(), h->upper.as<uint32_t>(), levels.data(), 0, 0u, 0, metric, M,
+                                 efe, max_batch, h->cus, st, nullptr, nullptr);
     };
     const int rc = run();
     if (rc != CVTMI_OK) { (void)hipStreamSynchronize(st); cvtmi_hnsw_destroy(h); return rc; }
     h->levels.swap(levels);
     h->max_elements = (uint64_t)n; h->M = (uint64_t)M; h->efc = (uint64_t)efe; h->mult = mult;
     h->hdr_maxlevel = maxlevel; h->hdr_enterpoint = ep;
+    h->upper_words = upper_words;
+    h->level_rng = rng; h->level_draws = n;   // cvtmi_hnsw_add continues the stream: build + add draws what a longer build draws
     *out = h;
     return CVTMI_OK;
 }
@@ -204,12 +208,166 @@ int cvtmi_hnsw_build_phases(double *ms)
     return CVTMI_OK;
 }
 
+// ================================================================ incremental insertion ========
+// cvtmi_hnsw_add: the build's batches continued from the graph as it stands.  Everything comes from the handle:
+// M / maxM / maxM0 / mult / ef_construction from its header, the levels from its level stream, the entry point and the top level
+// from the graph.  Order: checks, level draws (on a copy of the engine), storage -- every buffer grown, contents kept, before anything
+// is written --, the new rows' vectors / labels / zeroed lists behind the rows in use (no search reads there), launch_hnsw_build
+// from row ntotal, and only then the counts, the header fields and the level stream.  A failure before the first kernel leaves the
+// handle as it was; one after it (a launch that failed, a candidate queue that overflowed) has rewritten some link lists: broken.
+static int hnsw_grow(DevBuf &b, size_t bytes, size_t keep, hipStream_t st)
+{
+    if (bytes <= b.cap) return CVTMI_OK;
+    if (2 * b.cap > bytes && b.grow(2 * b.cap, keep, st) == CVTMI_OK) return CVTMI_OK;   // geometric; where that does not fit, what is needed
+    return b.grow(bytes, keep, st);
+}
+
+static int hnsw_add_impl(cvtmi_hnsw_t h, const float *x, bool dev, int64_t m, const uint64_t *labels, int max_batch, hipStream_t st)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_hnsw_add: null handle");
+    if (m < 0 || max_batch < 0 || (m > 0 && !x))
+        return fail(CVTMI_EINVAL, "cvtmi_hnsw_add: bad arguments (m >= 0, max_batch >= 0, rows for m > 0)");
+    CHECK_HN(h);
+    std::unique_lock<std::shared_timed_mutex> wr(h->rw);
+    if (m == 0) return CVTMI_OK;
+    const int64_t n0 = h->g.n, n1 = n0 + m;
+    const int D = h->D, maxM = h->g.maxM, maxM0 = h->g.maxM0;
+    if (maxM0 > 64 || maxM > maxM0 || maxM < 1)
+        return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_add: maxM=%d, maxM0=%d (a list of at most 64 links is one wave, and maxM <= maxM0)", maxM, maxM0);
+    if (h->M < 1 || h->M > (uint64_t)maxM) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_add: M=%llu outside 1..maxM=%d", (unsigned long long)h->M, maxM);
+    if (h->efc < 1 || h->efc > (uint64_t)hnsw_ef_max())
+        return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_add: ef_construction=%llu outside 1..%d", (unsigned long long)h->efc, hnsw_ef_max());
+    if (n1 > 0x7fffffffLL) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_add: %lld + %lld rows: too many", (long long)n0, (long long)m);
+    if (D > 4096) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_add: D=%d > 4096", D);
+    if (!(h->mult >= 0.0 && h->mult <= 16.0)) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_add: level multiplier %g outside 0..16", h->mult);
+    std::vector<int32_t> lv;
+    std::vector<int64_t> uoff, lab;
+    std::default_random_engine rng = h->level_rng;
+    int64_t uw = h->upper_words;
+    int32_t top = n0 > 0 ? h->g.maxlevel : 0;
+    uint32_t ep = h->g.enterpoint;
+    try {
+        lv.resize((size_t)m);
+        uoff.assign((size_t)m, -1);
+        std::uniform_real_distribution<double> u01(0.0, 1.0);
+        for (int64_t i = 0; i < m; ++i) {
+            lv[(size_t)i] = (int32_t)(-log(u01(rng)) * h->mult);
+            if (lv[(size_t)i] > 0) { uoff[(size_t)i] = uw; uw += (int64_t)lv[(size_t)i] * (maxM + 1); }
+            if ((n0 == 0 && i == 0) || lv[(size_t)i] > top) { top = lv[(size_t)i]; ep = (uint32_t)(n0 + i); }
+        }
+        if (!labels) { lab.resize((size_t)m); for (int64_t i = 0; i < m; ++i) lab[(size_t)i] = n0 + i; }
+        h->levels.reserve((size_t)n1);   // (the append below cannot fail any more)
+    } catch (const std::exception &) {
+        return fail(CVTMI_ENOMEM, "cvtmi_hnsw_add: out of host memory for %lld rows", (long long)m);
+    }
+    // searches still in flight on other streams read the buffers that growing frees
+    h->pool.mutation_begin(st);
+    const size_t l0w = (size_t)maxM0 + 1;
+    int rc = hnsw_grow(h->vec, (size_t)n1 * D * 4, (size_t)n0 * D * 4, st);
+    if (rc == CVTMI_OK) rc = hnsw_grow(h->links0, (size_t)n1 * l0w * 4, (size_t)n0 * l0w * 4, st);
+    if (rc == CVTMI_OK) rc = hnsw_grow(h->labels, (size_t)n1 * 8, (size_t)n0 * 8, st);
+    if (rc == CVTMI_OK) rc = hnsw_grow(h->upper_off, (size_t)n1 * 8, (size_t)n0 * 8, st);
+    if (rc == CVTMI_OK) rc = hnsw_grow(h->upper, (size_t)(uw ? uw : 4) * 4, (size_t)h->upper_words * 4, st);
+    // (a buffer that grew before another failed holds what it held, at a new address)
+    h->g.vec = h->vec.as<float>(); h->g.links0 = h->links0.as<uint32_t>(); h->g.labels = h->labels.as<int64_t>();
+    h->g.upper_off = h->upper_off.as<int64_t>(); h->g.upper = h->upper.as<uint32_t>();
+    if (rc != CVTMI_OK) return rc;
+    const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    bool launched = false;
+    int64_t stats[2] = { 0, 0 };
+    auto run = [&]() -> int {
+        CVTMI_HIP(hipMemcpyAsync(h->vec.as<float>() + (size_t)n0 * D, x, (size_t)m * D * 4, in, st));
+        CVTMI_HIP(hipMemsetAsync(h->links0.as<uint32_t>() + (size_t)n0 * l0w, 0, (size_t)m * l0w * 4, st));
+        if (uw > h->upper_words) CVTMI_HIP(hipMemsetAsync(h->upper.as<uint32_t>() + h->upper_words, 0, (size_t)(uw - h->upper_words) * 4, st));
+        if (labels) CVTMI_HIP(hipMemcpyAsync(h->labels.as<int64_t>() + n0, labels, (size_t)m * 8, in, st));
+        else CVTMI_HIP(hipMemcpyAsync(h->labels.as<int64_t>() + n0, lab.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+        CVTMI_HIP(hipMemcpyAsync(h->upper_off.as<int64_t>() + n0, uoff.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+        HnswDevGraph g1 = h->g;
+        g1.n = n1;
+        CVTMI_TRY(launch_hnsw_build("cvtmi_hnsw_add", g1, h->links0.as<uint32_t>(), h->upper.as<uint32_t>(), lv.data(), n0, h->g.enterpoint,
+                                    h->g.maxlevel, h->metric, (int)h->M, (int)h->efc, max_batch, h->cus, st, stats, &launched));
+        CVTMI_HIP(hipStreamSynchronize(st));   // (a call that only seeds launches nothing: the copies above still read host vectors)
+        return CVTMI_OK;
+    };
+    rc = run();
+    if (rc != CVTMI_OK) {
+        const std::string why = g_err;
+        (void)hipStreamSynchronize(st);
+        if (launched) h->broken = true;
+        return fail(rc, "%s%s", why.c_str(), launched ? " -- the graph is incomplete: the handle is broken, destroy it" : "");
+    }
+    h->levels.insert(h->levels.end(), lv.begin(), lv.end());
+    h->g.n = n1; h->g.maxlevel = top; h->g.enterpoint = ep;
+    h->hdr_maxlevel = top; h->hdr_enterpoint = ep;
+    h->upper_words = uw;
+    h->level_rng = rng; h->level_draws += m;
+    if (h->max_elements < (uint64_t)n1) h->max_elements = (uint64_t)n1;
+    h->add_last[0] = n0; h->add_last[1] = stats[0]; h->add_last[2] = stats[1]; h->add_last[3] = (int64_t)h->max_elements;
+    h->pool.mutation_end(st);
+    return CVTMI_OK;
+}
+
+int cvtmi_hnsw_add(cvtmi_hnsw_t h, const float *x, int64_t m, const uint64_t *labels, int max_batch)
+{
+    return hnsw_add_impl(h, x, false, m, labels, max_batch, nullptr);
+}
+int cvtmi_hnsw_add_dev(cvtmi_hnsw_t h, const float *x, int64_t m, const uint64_t *labels, int max_batch, void *stream)
+{
+    return hnsw_add_impl(h, x, true, m, labels, max_batch, (hipStream_t)stream);
+}
+
+int cvtmi_hnsw_reserve(cvtmi_hnsw_t h, int64_t max_elements)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_hnsw_reserve: null handle");
+    if (max_elements < 0) return fail(CVTMI_EINVAL, "cvtmi_hnsw_reserve: negative max_elements");
+    CHECK_HN(h);
+    if (max_elements > 0x7fffffffLL) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_reserve: max_elements too large");
+    std::unique_lock<std::shared_timed_mutex> wr(h->rw);
+    if ((uint64_t)max_elements > h->max_elements) h->max_elements = (uint64_t)max_elements;   // (never lowered; device storage follows the rows, not this)
+    return CVTMI_OK;
+}
+
+int cvtmi_hnsw_level_draws(cvtmi_hnsw_t h, int64_t *draws)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_hnsw_level_draws: null handle");
+    if (!draws) return fail(CVTMI_EINVAL, "cvtmi_hnsw_level_draws: null pointer");
+    CHECK_HN(h);
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    *draws = h->level_draws;
+    return CVTMI_OK;
+}
+
+// re-seed and draw: a draw is one call of the distribution, however many engine steps libstdc++ spends on it
+int cvtmi_hnsw_set_level_draws(cvtmi_hnsw_t h, int64_t draws)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_hnsw_set_level_draws: null handle");
+    if (draws < 0) return fail(CVTMI_EINVAL, "cvtmi_hnsw_set_level_draws: negative count");
+    CHECK_HN(h);
+    std::unique_lock<std::shared_timed_mutex> wr(h->rw);
+    std::default_random_engine rng(100);
+    std::uniform_real_distribution<double> u01(0.0, 1.0);
+    for (int64_t i = 0; i < draws; ++i) (void)u01(rng);
+    h->level_rng = rng; h->level_draws = draws;
+    return CVTMI_OK;
+}
+
+int cvtmi_hnsw_last_add(cvtmi_hnsw_t h, int64_t out[4])
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_hnsw_last_add: null handle");
+    if (!out) return fail(CVTMI_EINVAL, "cvtmi_hnsw_last_add: null pointer");
+    CHECK_HN(h);
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    for (int i = 0; i < 4; ++i) out[i] = h->add_last[i];
+    return CVTMI_OK;
+}
+
 // saveIndex (:491-519): header, max_elements level-0 blocks (links, vector, label), then per element the size of its upper-level
 // block and the block.  Slots past cur_element_count are written as zeros.
 int cvtmi_hnsw_save(cvtmi_hnsw_t h, void *buf, int64_t cap, int64_t *bytes)
 {
     CHECK_HN(h);
     if (!bytes) return fail(CVTMI_EINVAL, "cvtmi_hnsw_save: null size pointer");
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
     const int64_t n = h->g.n;
     const uint64_t maxM = (uint64_t)h->g.maxM, maxM0 = (uint64_t)h->g.maxM0, D = (uint64_t)h->D;
     const uint64_t link0 = 4 + 4 * maxM0, per = link0 + 4 * D + 8, upb = 4 * maxM + 4;
@@ -261,7 +419,8 @@ int cvtmi_hnsw_save(cvtmi_hnsw_t h, void *buf, int64_t cap, int64_t *bytes)
 int cvtmi_hnsw_destroy(cvtmi_hnsw_t h)
 {
     if (!h) return CVTMI_OK;
-    CHECK_HN(h);
+    if (h->magic != 0x484e5357u) return fail(CVTMI_EINVAL, "bad hnsw handle");
+    CVTMI_TRY(use_device(h->device));   // (a handle cvtmi_hnsw_add left broken is destroyed like any other)
     h->vec.release(); h->links0.release(); h->labels.release(); h->upper_off.release(); h->upper.release();
     (void)hipDeviceSynchronize();   // searches still in flight on other streams read the graph
     h->pool.destroy();
@@ -270,7 +429,7 @@ int cvtmi_hnsw_destroy(cvtmi_hnsw_t h)
     return CVTMI_OK;
 }
 
-int64_t cvtmi_hnsw_ntotal(cvtmi_hnsw_t h) { return (h && h->magic == 0x484e5357u) ? h->g.n : -1; }
+int64_t cvtmi_hnsw_ntotal(cvtmi_hnsw_t h) { return (h && h->magic == 0x484e5357u && !h->broken) ? h->g.n : -1; }
 
 // scratch of one traversal launch: `slots` concurrent queries (one wave each), a visited bit per node and the spilled queues per slot
 struct HnswPlan { int slots; int64_t words, gcap; };
@@ -577,6 +736,7 @@ int cvtmi_hnsw_last_masked(cvtmi_hnsw_t h, int64_t out[4])
 {
     if (!h) return fail(CVTMI_EINVAL, "cvtmi_hnsw_last_masked: null handle");
     if (!out || h->magic != 0x484e5357u) return fail(CVTMI_EINVAL, "cvtmi_hnsw_last_masked: bad arguments");
+    if (h->broken) return fail(CVTMI_EINVAL, "cvtmi_hnsw_last_masked: the handle is broken (a cvtmi_hnsw_add failed part-way)");
     std::lock_guard<std::mutex> g(h->pool.mu);
     for (int i = 0; i < 4; ++i) out[i] = h->masked_last[i];
     return CVTMI_OK;

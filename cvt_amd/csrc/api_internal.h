@@ -4,6 +4,7 @@
 #pragma once
 #include <functional>
 #include <new>
+#include <random>
 #include <shared_mutex>
 #include <vector>
 
@@ -36,7 +37,7 @@ template <class S> struct ScratchPool {
     std::vector<S *> sets;
     hipEvent_t mutated = nullptr;   // recorded on the stream of the last mutation: searches on other streams wait for it
     hipStream_t mut_stream = nullptr;
-    bool mut_pending = false;       // (never set on a handle nothing mutates: HNSW)
+    bool mut_pending = false;       // (never set on a handle nothing has mutated yet)
     // a mutation on stream st, between the two calls (the caller holds the handle exclusively): the stream first waits for every
     // search that is still in flight on another stream and for the last mutation, and the searches that follow wait for this one
     void mutation_begin(hipStream_t st)
@@ -279,11 +280,29 @@ struct cvtmi_hnsw_s {
     ScratchPool<HnswScratch> pool;
     int64_t masked_last[4] = {};   // the last masked search (cvtmi_hnsw_last_masked), written under pool.mu
     int slots_per_cu_max = 32, cus = 256;
+    // cvtmi_hnsw_add: searches (and cvtmi_hnsw_save) hold `rw` shared -- HnswLease takes it --, add / reserve / set_level_draws exclusively
+    std::shared_timed_mutex rw;
+    int64_t upper_words = 0;       // words of `upper` in use: where the next row's upper-level block goes
+    // the level stream (hnswalg.h:139-149): the engine after `level_draws` draws.  A build of n rows leaves n, a load 0 (the
+    // reference's loadIndex leaves level_generator_ at its initialiser)
+    std::default_random_engine level_rng = std::default_random_engine(100);
+    int64_t level_draws = 0;
+    int64_t add_last[4] = {};      // the last cvtmi_hnsw_add (cvtmi_hnsw_last_add)
+    bool broken = false;           // an add failed after its kernels had begun to rewrite link lists: only destroy is answered
 };
 
 using OpqLease = Lease<OpqScratch>;
 using FlatLease = Lease<FlatScratch>;
-using HnswLease = Lease<HnswScratch>;
+// a search on an HNSW handle: the scratch set, and the handle held shared against cvtmi_hnsw_add for as long as the set is
+struct HnswLease : Lease<HnswScratch> {
+    std::shared_lock<std::shared_timed_mutex> rd;
+    int open(cvtmi_hnsw_s *handle, hipStream_t stream, bool host)
+    {
+        rd = std::shared_lock<std::shared_timed_mutex>(handle->rw);
+        return Lease<HnswScratch>::open(handle, stream, host);
+    }
+    ~HnswLease() { close(); }   // the set's event is recorded before the handle is let go
+};
 
 namespace cvtmi {
 
@@ -306,4 +325,6 @@ int sharded_all(cvtmi_comm_t *comms, int ndev, const void *q, size_t q_bytes, in
 #define CHECK_H(h) \
     if (!(h)) return fail(CVTMI_EINVAL, "%s: null handle", __func__); \
     CVTMI_TRY(use_device((h)->device))
-#define CHECK_HN(h) do { if (!(h) || (h)->magic != 0x484e5357u) return fail(CVTMI_EINVAL, "bad hnsw handle"); CVTMI_TRY(use_device((h)->device)); } while (0)
+#define CHECK_HN(h) do { if (!(h) || (h)->magic != 0x484e5357u) return fail(CVTMI_EINVAL, "bad hnsw handle"); \
+    if ((h)->broken) return fail(CVTMI_EINVAL, "hnsw handle: a cvtmi_hnsw_add failed part-way, the graph is incomplete; destroy the handle"); \
+    CVTMI_TRY(use_device((h)->device)); } while (0)

@@ -15,6 +15,8 @@
 //                                mutuallyConnectNewElement applies it (:383-441): append while there is room, else re-select with
 //                                getNeighborsByHeuristic2(Mcurmax) over (d(new, t), new) and the current list.
 // A memset of four counters opens each batch: seven launches per batch.
+// cvtmi_hnsw_build starts from an empty graph (row 0 seeds it), cvtmi_hnsw_add from the graph a handle holds: the same batches, the
+// schedule continued from the rows already there (launch_hnsw_build: `first`, and the entry point and top level at that row).
 #include <atomic>
 #include <chrono>
 #include <vector>
@@ -34,7 +36,7 @@ struct HbArgs {
     uint32_t *links0;          // [n][maxM0 + 1]
     const int64_t *upper_off;  // [n]
     uint32_t *upper;
-    const int32_t *levels;     // [n] drawn levels
+    const int32_t *levels;     // [rows] drawn levels of this batch's rows
     int D, M, maxM, maxM0, efc;
     // this batch
     int64_t row0;
@@ -96,7 +98,7 @@ __global__ __launch_bounds__(64, 8) void hnsw_build_search_kernel(const HbArgs a
         const int r = __builtin_amdgcn_readfirstlane((int)t);
         if (r >= a.rows) break;
         const int64_t row = a.row0 + r;
-        const int lvl = a.levels[row];
+        const int lvl = a.levels[r];
         for (int i = lane; i < a.D; i += 64) qs[i] = a.vec[row * a.D + i];
         __builtin_amdgcn_s_waitcnt(0);
         __threadfence_block();
@@ -409,58 +411,73 @@ void hnsw_build_phase_ms(double *ms)
 
 struct HbBatch { int64_t s, e; int maxlevel; uint32_t ep; int64_t toff; int ntask; };
 
-void hnsw_build_schedule(const int32_t *levels, int64_t n, int max_batch, std::vector<int64_t> &bounds)
+// bounds of the batches that insert rows first .. n-1 into a graph of `first` rows whose top level is top0 (first == 0: row 0 seeds the
+// graph alone, top0 is not read)
+void hnsw_build_schedule(const int32_t *levels, int64_t first, int64_t n, int top0, int max_batch, std::vector<int64_t> &bounds)
 {
     const int64_t frac = tune_hnsw_build_frac.geti();
     const int64_t cap = max_batch > 0 ? max_batch : tune_hnsw_build_cap.geti();
     bounds.clear();
-    bounds.push_back(0);
-    if (n == 0) return;
-    bounds.push_back(1);   // row 0 seeds the graph
-    int maxlevel = levels[0];
-    int64_t s = 1;
+    bounds.push_back(first);
+    if (first >= n) return;
+    int maxlevel = top0;
+    int64_t s = first;
+    if (first == 0) {
+        bounds.push_back(1);   // row 0 seeds the graph
+        maxlevel = levels[0];
+        s = 1;
+    }
     while (s < n) {
         int64_t b = s / frac;
         if (b < 1) b = 1;
         if (b > cap) b = cap;
         int64_t e = s + b < n ? s + b : n;
         for (int64_t i = s; i < e; ++i)
-            if (levels[i] > maxlevel) { e = i + 1; maxlevel = levels[i]; break; }   // a row that raises the top level ends its batch
+            if (levels[i - first] > maxlevel) { e = i + 1; maxlevel = levels[i - first]; break; }   // a row that raises the top level ends its batch
         bounds.push_back(e);
         s = e;
     }
 }
 
-int launch_hnsw_build(const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, const int32_t *levels, int metric, int M, int efc,
-                      int max_batch, int cus, hipStream_t st)
+// Inserts rows first .. g.n-1 into the graph of rows 0 .. first-1 (entry point ep0, top level top0; first == 0: an empty graph, row 0
+// seeds it).  levels: the drawn levels of the inserted rows alone, [g.n - first].  stats (optional): { batches, largest batch }, the
+// seed row counted as a batch; *launched (optional) is set once the first kernel that writes the graph is about to be enqueued --
+// an error before that leaves the graph as it was.  Per call: the n-word cnt / slot_of arrays and one memset of n words.
+int launch_hnsw_build(const char *who, const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, const int32_t *levels, int64_t first,
+                      uint32_t ep0, int top0, int metric, int M, int efc, int max_batch, int cus, hipStream_t st, int64_t *stats,
+                      bool *launched)
 {
     const auto h0 = std::chrono::steady_clock::now();
-    const int64_t n = g.n;
+    const int64_t n = g.n, m = n - first;
+    if (stats) stats[0] = stats[1] = 0;
+    if (m <= 0) return CVTMI_OK;
     std::vector<int64_t> bounds;
-    hnsw_build_schedule(levels, n, max_batch, bounds);
+    hnsw_build_schedule(levels, first, n, top0, max_batch, bounds);
     const int nb = (int)bounds.size() - 1;
     // tasks: (row, level) for every level a row is searched on, batch after batch
     std::vector<HbBatch> batches;
-    std::vector<int32_t> tbase((size_t)n, 0), trow, tlv;
-    int maxlevel = levels[0];
-    uint32_t ep = 0;
+    std::vector<int32_t> tbase((size_t)m, 0), trow, tlv;
+    int maxlevel = first == 0 ? levels[0] : top0;
+    uint32_t ep = first == 0 ? 0u : ep0;
     int64_t tmax = 0, rmax = 0;
-    for (int b = 1; b < nb; ++b) {
+    for (int b = first == 0 ? 1 : 0; b < nb; ++b) {
         HbBatch B;
         B.s = bounds[b]; B.e = bounds[b + 1]; B.maxlevel = maxlevel; B.ep = ep; B.toff = (int64_t)trow.size();
         int32_t tb = 0;
         for (int64_t i = B.s; i < B.e; ++i) {
-            const int top = levels[i] < maxlevel ? levels[i] : maxlevel;
-            tbase[(size_t)i] = tb;
+            const int li = levels[i - first];
+            const int top = li < maxlevel ? li : maxlevel;
+            tbase[(size_t)(i - first)] = tb;
             for (int l = 0; l <= top; ++l) { trow.push_back((int32_t)i); tlv.push_back(l); }
             tb += top + 1;
         }
         B.ntask = tb;
-        if (levels[B.e - 1] > maxlevel) { maxlevel = levels[B.e - 1]; ep = (uint32_t)(B.e - 1); }
+        if (levels[B.e - 1 - first] > maxlevel) { maxlevel = levels[B.e - 1 - first]; ep = (uint32_t)(B.e - 1); }
         tmax = tb > tmax ? tb : tmax;
         rmax = B.e - B.s > rmax ? B.e - B.s : rmax;
         batches.push_back(B);
     }
+    if (stats) { stats[0] = nb; stats[1] = rmax > 1 ? rmax : 1; }
     if (batches.empty()) return CVTMI_OK;
     const int efc1 = efc + 1;
     const int64_t pmax = tmax * M;
@@ -478,7 +495,7 @@ int launch_hnsw_build(const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, 
     CVTMI_TRY(d_tbase.upload(tbase.data(), tbase.size() * 4));
     CVTMI_TRY(d_trow.upload(trow.data(), trow.size() * 4));
     CVTMI_TRY(d_tlv.upload(tlv.data(), tlv.size() * 4));
-    CVTMI_TRY(d_lev.upload(levels, (size_t)n * 4));
+    CVTMI_TRY(d_lev.upload(levels, (size_t)m * 4));
     CVTMI_TRY(res.alloc((size_t)tmax * efc1 * sizeof(HnEnt)));
     CVTMI_TRY(res_n.alloc((size_t)tmax * 4));
     CVTMI_TRY(prop.alloc((size_t)pmax * 4));
@@ -497,7 +514,7 @@ int launch_hnsw_build(const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, 
     CVTMI_HIP(hipMemsetAsync(err.p, 0, 16, st));
 
     HbArgs a;
-    a.vec = g.vec; a.links0 = links0; a.upper_off = g.upper_off; a.upper = upper; a.levels = d_lev.as<int32_t>();
+    a.vec = g.vec; a.links0 = links0; a.upper_off = g.upper_off; a.upper = upper;
     a.D = g.D; a.M = M; a.maxM = g.maxM; a.maxM0 = g.maxM0; a.efc = efc;
     a.res = res.as<HnEnt>(); a.res_n = res_n.as<int32_t>(); a.prop = prop.as<uint32_t>(); a.prop_n = prop_n.as<int32_t>();
     a.cnt = cnt.as<int32_t>(); a.slot_of = slot_of.as<int32_t>(); a.touched = touched.as<uint32_t>();
@@ -535,9 +552,11 @@ int launch_hnsw_build(const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, 
     CVTMI_TRY(set_max_lds("hnsw_build_select_kernel", select, sel_lds));
     const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
     CVTMI_TRY(mark());
+    if (launched) *launched = true;
     for (const HbBatch &B : batches) {
         a.row0 = B.s; a.rows = (int)(B.e - B.s); a.ntask = B.ntask; a.maxlevel = B.maxlevel; a.enterpoint = B.ep;
-        a.tbase = d_tbase.as<int32_t>() + B.s;
+        a.levels = d_lev.as<int32_t>() + (B.s - first);
+        a.tbase = d_tbase.as<int32_t>() + (B.s - first);
         a.task_row = d_trow.as<int32_t>() + B.toff;
         a.task_lv = d_tlv.as<int32_t>() + B.toff;
         a.words = (B.s + 31) / 32 + 1;
@@ -574,7 +593,7 @@ int launch_hnsw_build(const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, 
         std::lock_guard<std::mutex> gl(g_hb_ms_mu);
         for (int i = 0; i < 5; ++i) g_hb_ms[i] = ms[i];
     }
-    if (e) return fail(CVTMI_EUNSUPPORTED, "cvtmi_hnsw_build: candidate queue overflow");
+    if (e) return fail(CVTMI_EUNSUPPORTED, "%s: candidate queue overflow", who);
     return CVTMI_OK;
 }
 

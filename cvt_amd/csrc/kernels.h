@@ -474,10 +474,15 @@ int hnsw_top_lds(int ef);
 int hnsw_adc_state_floats(int MK);
 
 // ---- hnsw_build.hip ----
-// batch-synchronous construction into a zeroed graph: g.vec holds all n rows, links0 / upper are zero, g.upper_off is laid out
-// from `levels` (host, the drawn level of every row); returns when the graph is complete
-int launch_hnsw_build(const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, const int32_t *levels, int metric, int M, int efc,
-                      int max_batch, int cus, hipStream_t st);
+// batch-synchronous insertion of rows first .. g.n-1 into the graph of rows 0 .. first-1 (cvtmi_hnsw_build: first = 0, an empty
+// graph; cvtmi_hnsw_add: the graph as it stands, whose entry point and top level are ep0 / top0): g.vec holds all g.n rows, the
+// lists of the new rows in links0 / upper are zero, g.upper_off is laid out for them from `levels` (host, the drawn levels of the
+// NEW rows, [g.n - first]); returns when the graph is complete.  M: links a new row asks for (<= g.maxM <= g.maxM0 <= 64).
+// stats (may be null): { batches, largest batch }; *launched (may be null): set when the first kernel is about to be enqueued, so a
+// failure that leaves it false has not touched the graph.  `who` names the C entry in messages.
+int launch_hnsw_build(const char *who, const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, const int32_t *levels, int64_t first,
+                      uint32_t ep0, int top0, int metric, int M, int efc, int max_batch, int cus, hipStream_t st, int64_t *stats,
+                      bool *launched);
 void hnsw_build_phase_ms(double *ms);   // [traversal, selection, back links, batches, host ms] of the last build with phases on
 
 }  // namespace cvtmi

@@ -3,8 +3,9 @@
 //  * SEARCH runs on the MI355X (cvtmi_hnsw_search: one wave per query, the reference's labels and distances
 //    bit for bit).  searchKnnBatch is the call that fills the GPU.
 //  * CONSTRUCTION is a host algorithm in the reference (one insertion at a time, every insertion sees the
-//    graph the previous ones left) and stays one here (addPointsGpu builds on the GPU instead, batch-synchronous:
-//    cvtmi_hnsw_build): addPoint follows hnswalg.h:584-684 -- level drawn from
+//    graph the previous ones left) and stays one here (addPointsGpu inserts on the GPU instead, batch-synchronous:
+//    cvtmi_hnsw_build into an empty graph, cvtmi_hnsw_add into one that holds rows; resizeIndex
+//    makes room in a loaded index, as in current hnswlib): addPoint follows hnswalg.h:584-684 -- level drawn from
 //    std::default_random_engine(100) (:139-149), greedy descent through the upper levels, a best-first search
 //    with ef_construction on every level the new node lives on (:152-216), neighbour selection by the
 //    "closer to the query than to any already selected neighbour" rule (:283-325), mutual links with
@@ -183,13 +184,76 @@ public:
         }
     }
 
-    // the whole graph built on the GPU in one call (cvtmi_hnsw_build: batch-synchronous insertion, max_batch = 1 is the sequential
-    // algorithm and the file addPoint would write; 0 = the default schedule).  The graph must be empty; its capacity becomes n.  The
-    // host structures are filled from the saved file, and the device graph is kept as the search handle.
+    // resizeIndex of current hnswlib (not in the reference, whose capacity is fixed at construction): the capacity becomes
+    // new_max_elements, contents are kept.  Not thread-safe against insertions.
+    void resizeIndex(size_t new_max_elements)
+    {
+        if (new_max_elements < count_) throw std::runtime_error("Cannot resize, max element is less than the current number of elements");
+        if (new_max_elements == cap_) return;
+        std::unique_ptr<float[]> vec(new float[new_max_elements * dim_]);
+        std::unique_ptr<tableint[]> link0(new tableint[new_max_elements * (maxM0_ + 1)]);
+        if (count_) {
+            std::copy(&vec_[0], &vec_[0] + count_ * dim_, &vec[0]);
+            std::copy(&link0_[0], &link0_[0] + count_ * (maxM0_ + 1), &link0[0]);
+        }
+        vec_.swap(vec);
+        link0_.swap(link0);
+        label_.resize(new_max_elements, 0);
+        level_.resize(new_max_elements, 0);
+        upper_.resize(new_max_elements);
+        seq_.reset(new std::atomic<uint32_t>[new_max_elements]());
+        cap_ = new_max_elements;
+        dirty_ = true;   // (the header's max_elements is part of the device copy)
+    }
+    size_t maxElements() const { return cap_; }
+
+    // the level stream: draws taken from std::default_random_engine(100) so far (0 after loadIndex into a new object, as in the
+    // reference, whose loadIndex leaves level_generator_ at its initialiser), and the stream repositioned to a given number of draws
+    size_t levelDraws() const { return draws_; }
+    void setLevelDraws(size_t draws)
+    {
+        std::lock_guard<std::mutex> g(count_guard_);
+        rng_ = std::default_random_engine(100);
+        draws_ = 0;
+        for (size_t i = 0; i < draws; ++i) (void)draw_level();
+    }
+
+    // rows inserted on the GPU, batch-synchronous (max_batch = 1 is the sequential algorithm and the file addPoint would write; 0 =
+    // the default schedule).  An empty graph is built in one call (cvtmi_hnsw_build; its capacity becomes n).  A graph that holds
+    // rows grows (cvtmi_hnsw_add on the device copy, whose level stream is first put where this object's stands), and throws at
+    // capacity like addPoint.  Either way the host structures are filled from the saved file, the level stream advances by the rows
+    // added, and the device graph is kept as the search handle.
     void addPointsGpu(const void *rows, const labeltype *labels, size_t n, int max_batch = 0)
     {
-        if (count_) throw std::runtime_error("HierarchicalNSW::addPointsGpu: the graph must be empty");
         static_assert(sizeof(labeltype) == sizeof(uint64_t), "labels are 64-bit");
+        if (count_) {
+            if (!n) return;
+            if (count_ + n > cap_) throw std::runtime_error("The number of elements exceeds the specified limit");
+            upload();
+            if (cvtmi_hnsw_set_level_draws(dev_, (int64_t)draws_) != CVTMI_OK ||
+                cvtmi_hnsw_add(dev_, (const float *)rows, (int64_t)n, (const uint64_t *)labels, max_batch) != CVTMI_OK) {
+                dirty_ = true;   // (the device copy may be broken: the next upload replaces it)
+                throw std::runtime_error(std::string("cvt_amd: ") + cvtmi_last_error());
+            }
+            int64_t bytes = 0;
+            std::vector<char> buf;
+            if (cvtmi_hnsw_save(dev_, NULL, 0, &bytes) == CVTMI_OK) {
+                buf.resize((size_t)bytes);
+                if (cvtmi_hnsw_save(dev_, buf.data(), bytes, &bytes) != CVTMI_OK) buf.clear();
+            }
+            if (buf.empty()) {
+                dirty_ = true;
+                broken_ = true;   // the device graph holds rows the host structures do not
+                throw std::runtime_error(std::string("cvt_amd: ") + cvtmi_last_error());
+            }
+            parse(buf);
+            {
+                std::lock_guard<std::mutex> g(count_guard_);
+                for (size_t i = 0; i < n; ++i) (void)draw_level();
+            }
+            dirty_ = false;
+            return;
+        }
         cvtmi_hnsw_t g = NULL;
         if (cvtmi_hnsw_build((const float *)rows, (int64_t)n, (int)dim_, metric_, (int)M_, (int)efc_, (const uint64_t *)labels, max_batch,
                              &g) != CVTMI_OK)
@@ -206,6 +270,10 @@ public:
             throw std::runtime_error(err);
         }
         parse(buf);
+        {
+            std::lock_guard<std::mutex> gl(count_guard_);
+            for (size_t i = 0; i < n; ++i) (void)draw_level();
+        }
         if (dev_) cvtmi_hnsw_destroy(dev_);
         dev_ = g;
         dirty_ = false;
@@ -288,6 +356,7 @@ private:
     int draw_level()   // under count_guard_: the i-th element gets the i-th draw (hnswalg.h:139-149)
     {
         std::uniform_real_distribution<double> u01(0.0, 1.0);
+        ++draws_;
         return (int)(-log(u01(rng_)) * mult_);
     }
 
@@ -646,6 +715,7 @@ private:
     std::mutex count_guard_, global_;
     std::atomic<uint64_t> top_{0};                     // (entry + 1) << 32 | (top level + 1): what an insertion starts from, read without the global lock
     std::default_random_engine rng_ = std::default_random_engine(100);  // hnswalg.h:139
+    size_t draws_ = 0;                                                  // draws taken from rng_
     cvtmi_hnsw_t dev_;
     bool dirty_ = true;
 };

@@ -19,7 +19,7 @@
  *     handle's pool (tables, partial top-k lists, visited bitmaps, staging buffers; the pool grows to the number of calls
  *     in flight) and runs on its caller's stream (host-pointer entries: the set's own stream), so searches from several
  *     threads or streams proceed side by side and every one returns what a search alone would.  Calls that CHANGE a
- *     handle (add, add_codes, set_param, load) take it exclusively: they wait for the searches in flight, and searches
+ *     handle (add, add_codes, set_param, load, cvtmi_hnsw_add) take it exclusively: they wait for the searches in flight, and searches
  *     issued later wait for them; the result is that of some serial order.  cvtmi_hnsw_search_adc* holds its OPQ handle
  *     the way a search of that handle would.  A sharded search additionally serialises on its communicator (below).  The
  *     small accessors (ntotal, set_id_base) take no lock: do not race them with calls that change the handle.
@@ -987,7 +987,8 @@ int cvtmi_opq_learn_rotation_dev(const float *x, int64_t n, int D, int M, int K,
  *   summation order of the reference's distance functions and both priority queues replay libstdc++'s
  *   push_heap / pop_heap (the reference compares by distance only, so heap mechanics decide ties): labels
  *   and distances are bit-identical to the reference's on the same graph.  k, ef <= 1024.
- * Graphs are loaded from the reference's files or built on the GPU (cvtmi_hnsw_build, below). */
+ * Graphs are loaded from the reference's files or built on the GPU (cvtmi_hnsw_build, below), and grow on the GPU
+ * (cvtmi_hnsw_add). */
 int cvtmi_hnsw_load(const void *file, int64_t bytes, int metric, int D, cvtmi_hnsw_t *out);
 int cvtmi_hnsw_destroy(cvtmi_hnsw_t h);
 int64_t cvtmi_hnsw_ntotal(cvtmi_hnsw_t h);
@@ -1023,6 +1024,47 @@ int cvtmi_hnsw_save(cvtmi_hnsw_t h, void *buf, int64_t cap, int64_t *bytes);
 /* measurement hook: with cvtmi_set_tuning("hnsw_build_phases", 1), ms[5] = device milliseconds of the last build spent in
  * traversal, selection and back links (bucketing included), its batch count, and host milliseconds (level draw, schedule) */
 int cvtmi_hnsw_build_phases(double *ms);
+/* Incremental insertion: HierarchicalNSW(space, location) + addPoint, the way a saved index is grown.  Appends
+ * the rows x [m][D] as internal ids ntotal .. ntotal + m - 1 with the labels `labels` [m] (NULL = the internal id), on any handle,
+ * built or loaded.  The result is the graph after one reference addPoint per row (hnswalg.h:584-684) except for the batch rule of
+ * cvtmi_hnsw_build: batches of consecutive rows, a row sees the graph as the batches before its own left it, back links per target
+ * in increasing (level, source).
+ *   Schedule   the build's, continued: the first batch of a call starts at the current ntotal; a batch holds
+ *              clamp(rows in the graph / "hnsw_build_frac", 1, cap) rows, cap = max_batch, or "hnsw_build_cap" for max_batch = 0; a
+ *              row that raises the top level ends its batch; on an empty graph (a loaded file with cur_element_count == 0) row 0
+ *              seeds alone.  max_batch = 1 is the reference's sequential addPoint.  cvtmi_hnsw_build(x[:n0], b) followed by
+ *              cvtmi_hnsw_add(x[n0:], b) gives the bytes of cvtmi_hnsw_build(x, b) whenever n0 is a batch boundary of the latter.
+ *   Parameters M, maxM, maxM0, mult and ef_construction are the header's (a loaded file may have maxM0 != 2 M).  maxM0 > 64,
+ *              maxM > maxM0, M outside 1..maxM, ef_construction outside 1..1024, D > 4096, mult outside 0..16 or
+ *              ntotal + m > 2^31 - 1: CVTMI_EUNSUPPORTED before any device work.
+ *   Levels     the handle owns the level stream: std::default_random_engine(100) and the number of draws taken from it.  After
+ *              cvtmi_hnsw_build of n rows that number is n, so build + add draws what a longer build draws.  After cvtmi_hnsw_load
+ *              it is 0: the reference's loadIndex leaves level_generator_ at its initialiser, rows added after a load repeat the
+ *              draws from the start, and so do ours -- load + add writes the reference's file.  cvtmi_hnsw_level_draws reads the
+ *              number, cvtmi_hnsw_set_level_draws repositions the stream (re-seed, then that many draws: O(draws) on the host).
+ *   Capacity   the header's max_elements becomes max(max_elements, ntotal + m); cvtmi_hnsw_reserve raises it and never lowers it;
+ *              cvtmi_hnsw_save keeps writing zeros for the unused slots.  Device storage follows the rows, not that number: it
+ *              grows geometrically and keeps its contents.
+ *   Cost       per call, beyond the insertions: two arrays of ntotal + m words and one memset of them, and the copy of whatever
+ *              buffer had to grow.
+ *   Calling    mutating and exclusive, like cvtmi_flat_add: it waits for the searches in flight on the handle, searches issued later
+ *              wait for it and plan their scratch (visited bits, the ntotal-entry queues of a masked search) for the grown graph.
+ *              m == 0 does nothing.  NULL h, NULL x with m > 0, m < 0, max_batch < 0 -> CVTMI_EINVAL before any device work.  Rows
+ *              must be finite.  All storage is reserved before the graph changes: on CVTMI_ENOMEM the handle is unchanged.  If the
+ *              kernels report a candidate-queue overflow (or a launch fails) mid-call some link lists are already rewritten: the
+ *              handle is marked broken and every entry but cvtmi_hnsw_destroy fails with a message from then on.  The `_dev` entry
+ *              takes device rows and labels, runs on `stream` and returns when the graph is complete.
+ *   Not here   deletion, and replacing the vector of an existing label (a repeated label gets a second node, as in the
+ *              reference); the PQ codes cvtmi_hnsw_search_adc needs -- append them with cvtmi_opq_add_codes; until then the ADC
+ *              entries answer CVTMI_EINVAL for the row-count mismatch.
+ * cvtmi_hnsw_last_add: out = { first internal id of the last call that added rows, its batches (a seed row counts as one), its
+ * largest batch, max_elements afterwards }. */
+int cvtmi_hnsw_add(cvtmi_hnsw_t h, const float *x, int64_t m, const uint64_t *labels, int max_batch);
+int cvtmi_hnsw_add_dev(cvtmi_hnsw_t h, const float *x, int64_t m, const uint64_t *labels, int max_batch, void *stream);
+int cvtmi_hnsw_reserve(cvtmi_hnsw_t h, int64_t max_elements);
+int cvtmi_hnsw_level_draws(cvtmi_hnsw_t h, int64_t *draws);
+int cvtmi_hnsw_set_level_draws(cvtmi_hnsw_t h, int64_t draws);
+int cvtmi_hnsw_last_add(cvtmi_hnsw_t h, int64_t out[4]);
 /* HNSW over OPQ-compressed vectors (BASELINE config 5; not in the reference, whose HNSW holds fp32 vectors):
  * the same traversal over the same graph, but a node's distance is the ADC sum of the query's tables over the
  * node's PQ code (IVFOPQ.cpp:273-291 tables, :302-306 sum) -- M bytes gathered per neighbour instead of 4 D.
