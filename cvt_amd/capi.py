@@ -1206,6 +1206,58 @@ HnswIndex.set_level_draws = _hnsw_set_level_draws
 HnswIndex.last_add = _hnsw_last_add
 
 
+def _hnsw_set_deleted(self, name, labels):
+    if _is_torch(labels):
+        import torch
+        assert labels.dtype == torch.int64 and labels.is_cuda
+        labels = labels.reshape(-1).contiguous()
+        changed = C.c_int64(0)
+        _check(getattr(lib(), name + "_dev")(self.h, _ptr(labels), C.c_int64(labels.shape[0]), C.byref(changed), _stream()))
+        return changed.value
+    labels = np.asarray(labels)
+    if labels.dtype == np.uint64:
+        labels = labels.view(np.int64)
+    labels = _np(labels, np.int64).reshape(-1)
+    changed = C.c_int64(0)
+    _check(getattr(lib(), name)(self.h, _ptr(labels), C.c_int64(labels.shape[0]), C.byref(changed)))
+    return changed.value
+
+
+def _hnsw_mark_deleted(self, labels):
+    """cvtmi_hnsw_mark_deleted[_dev]: hnswlib's markDelete for every node that carries one of `labels` (int64 / uint64, numpy or a
+    torch device tensor; duplicates and foreign labels are fine).  A deleted node is still walked through but is never a result, and
+    add() links no new row to it; save() keeps the mark (bit 16 of the node's level-0 count word).  Returns the number of nodes
+    whose state changed."""
+    return _hnsw_set_deleted(self, "cvtmi_hnsw_mark_deleted", labels)
+
+
+def _hnsw_unmark_deleted(self, labels):
+    """cvtmi_hnsw_unmark_deleted[_dev]: the nodes that carry one of `labels` are live again; returns the number that were deleted"""
+    return _hnsw_set_deleted(self, "cvtmi_hnsw_unmark_deleted", labels)
+
+
+def _hnsw_deleted_count(self):
+    """deleted nodes of the graph (cvtmi_hnsw_deleted_count)"""
+    n = C.c_int64(0)
+    _check(lib().cvtmi_hnsw_deleted_count(self.h, C.byref(n)))
+    return n.value
+
+
+def _hnsw_deleted_mask(self, words=None):
+    """the delete bitmap (cvtmi_hnsw_get_deleted) as np.uint64 words, bit i & 63 of word i >> 6 = node i is deleted; `words` words
+    (default ceil(ntotal / 64)), every bit past ntotal zero"""
+    n_words = (self.ntotal + 63) // 64 if words is None else int(words)
+    mask = np.empty(n_words, dtype=np.uint64)
+    _check(lib().cvtmi_hnsw_get_deleted(self.h, _ptr(mask), C.c_int64(n_words)))
+    return mask
+
+
+HnswIndex.mark_deleted = _hnsw_mark_deleted
+HnswIndex.unmark_deleted = _hnsw_unmark_deleted
+HnswIndex.deleted_count = _hnsw_deleted_count
+HnswIndex.deleted_mask = _hnsw_deleted_mask
+
+
 def hnsw_build(x, metric, M, ef_construction, labels=None, max_batch=0):
     """cvtmi_hnsw_build[_dev]: a HierarchicalNSW graph over the rows x [n][D] (numpy, or a CUDA tensor with labels on the same
     device), batch-synchronous on the GPU (max_batch = 1: the reference's sequential insertion; 0: the default schedule)."""

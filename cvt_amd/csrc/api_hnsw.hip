@@ -1,5 +1,5 @@
 // api_hnsw.hip -- the HNSW handle of the C ABI (include/cvtmi.h): load / build / add / save, the search, the search over OPQ codes (ADC)
-// with and without the exact re-rank, each of them under a node mask as well, and the mask of a label set.
+// with and without the exact re-rank, each of them under a node mask as well, the mask of a label set, and the delete state of the nodes.
 #include <string.h>
 
 #include <algorithm>
@@ -42,6 +42,8 @@ int cvtmi_hnsw_load(const void *file, int64_t bytes, int metric, int D, cvtmi_hn
     std::vector<uint32_t> links0, upper;
     std::vector<int64_t> labels, uoff;
     std::vector<int32_t> levels;  // upper levels a node has link blocks for
+    std::vector<uint64_t> dead;   // current hnswlib's markDelete: DELETE_MARK = 0x01 in byte 2 of the level-0 count word, the count below it
+    int64_t n_dead = 0;
     const uint64_t links_per = 4 * maxM + 4;
     try {
         vec.resize((size_t)n * D);
@@ -49,10 +51,14 @@ int cvtmi_hnsw_load(const void *file, int64_t bytes, int metric, int D, cvtmi_hn
         labels.resize((size_t)n);
         uoff.assign((size_t)n, -1);
         levels.assign((size_t)n, 0);
+        dead.assign((size_t)((n + 63) / 64), 0ull);
         for (int64_t i = 0; i < n; ++i) {
             const uint8_t *e = l0 + (uint64_t)i * size_per;
-            memcpy(&links0[(size_t)i * (maxM0 + 1)], e, 4 * (maxM0 + 1));
-            if (links0[(size_t)i * (maxM0 + 1)] > maxM0) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: corrupt link count");
+            uint32_t &cw = links0[(size_t)i * (maxM0 + 1)];
+            memcpy(&cw, e, 4 * (maxM0 + 1));
+            if ((cw >> 17) != 0 || (cw & 0xffffu) > maxM0) return fail(CVTMI_EINVAL, "cvtmi_hnsw_load: corrupt link count");
+            if (cw >> 16) { dead[(size_t)(i >> 6)] |= 1ull << (i & 63); ++n_dead; }
+            cw &= 0xffffu;   // the device copy holds plain counts
             memcpy(&vec[(size_t)i * D], e + offsetData, 4 * (size_t)D);
             uint64_t lab; memcpy(&lab, e + label_off, 8);
             labels[(size_t)i] = (int64_t)lab;
@@ -105,7 +111,9 @@ int cvtmi_hnsw_load(const void *file, int64_t bytes, int metric, int D, cvtmi_hn
     if (rc == CVTMI_OK) rc = up(h->labels, labels.data(), labels.size() * 8);
     if (rc == CVTMI_OK) rc = up(h->upper_off, uoff.data(), uoff.size() * 8);
     if (rc == CVTMI_OK) rc = up(h->upper, upper.data(), upper.size() * 4);
+    if (rc == CVTMI_OK) rc = up(h->dead, dead.data(), dead.size() * 8);
     if (rc != CVTMI_OK) { cvtmi_hnsw_destroy(h); return rc; }
+    h->n_dead = n_dead;
     h->g.vec = h->vec.as<float>(); h->g.links0 = h->links0.as<uint32_t>(); h->g.labels = h->labels.as<int64_t>();
     h->g.upper_off = h->upper_off.as<int64_t>(); h->g.upper = h->upper.as<uint32_t>();
     h->g.n = n; h->g.D = D; h->g.maxM = (int)maxM; h->g.maxM0 = (int)maxM0; h->g.maxlevel = n > 0 ? maxlevel : 0;
@@ -167,6 +175,8 @@ static int hnsw_build_impl(const float *x, bool dev, int64_t n, int D, int metri
         CVTMI_TRY(h->labels.reserve((size_t)n * 8));
         CVTMI_TRY(h->upper_off.reserve((size_t)n * 8));
         CVTMI_TRY(h->upper.reserve(ub ? ub : 16));
+        CVTMI_TRY(h->dead.reserve((size_t)((n + 63) / 64) * 8));
+        CVTMI_HIP(hipMemsetAsync(h->dead.p, 0, (size_t)((n + 63) / 64) * 8, st));
         CVTMI_HIP(hipMemcpyAsync(h->vec.p, x, vb, in, st));
         CVTMI_HIP(hipMemsetAsync(h->links0.p, 0, l0b, st));
         if (ub) CVTMI_HIP(hipMemsetAsync(h->upper.p, 0, ub, st));
@@ -268,6 +278,8 @@ static int hnsw_add_impl(cvtmi_hnsw_t h, const float *x, bool dev, int64_t m, co
     if (rc == CVTMI_OK) rc = hnsw_grow(h->labels, (size_t)n1 * 8, (size_t)n0 * 8, st);
     if (rc == CVTMI_OK) rc = hnsw_grow(h->upper_off, (size_t)n1 * 8, (size_t)n0 * 8, st);
     if (rc == CVTMI_OK) rc = hnsw_grow(h->upper, (size_t)(uw ? uw : 4) * 4, (size_t)h->upper_words * 4, st);
+    const size_t dw0 = (size_t)((n0 + 63) / 64), dw1 = (size_t)((n1 + 63) / 64);   // the delete bitmap: contents kept, new rows arrive live
+    if (rc == CVTMI_OK) rc = hnsw_grow(h->dead, dw1 * 8, dw0 * 8, st);
     // (a buffer that grew before another failed holds what it held, at a new address)
     h->g.vec = h->vec.as<float>(); h->g.links0 = h->links0.as<uint32_t>(); h->g.labels = h->labels.as<int64_t>();
     h->g.upper_off = h->upper_off.as<int64_t>(); h->g.upper = h->upper.as<uint32_t>();
@@ -282,10 +294,12 @@ static int hnsw_add_impl(cvtmi_hnsw_t h, const float *x, bool dev, int64_t m, co
         if (labels) CVTMI_HIP(hipMemcpyAsync(h->labels.as<int64_t>() + n0, labels, (size_t)m * 8, in, st));
         else CVTMI_HIP(hipMemcpyAsync(h->labels.as<int64_t>() + n0, lab.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
         CVTMI_HIP(hipMemcpyAsync(h->upper_off.as<int64_t>() + n0, uoff.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+        if (dw1 > dw0) CVTMI_HIP(hipMemsetAsync(h->dead.as<uint64_t>() + dw0, 0, (dw1 - dw0) * 8, st));   // (the bits past n0 in word dw0 - 1 are zero already)
         HnswDevGraph g1 = h->g;
         g1.n = n1;
         CVTMI_TRY(launch_hnsw_build("cvtmi_hnsw_add", g1, h->links0.as<uint32_t>(), h->upper.as<uint32_t>(), lv.data(), n0, h->g.enterpoint,
-                                    h->g.maxlevel, h->metric, (int)h->M, (int)h->efc, max_batch, h->cus, st, stats, &launched));
+                                    h->g.maxlevel, h->metric, (int)h->M, (int)h->efc, max_batch, h->cus, st, stats, &launched,
+                                    h->n_dead > 0 ? h->dead.as<uint64_t>() : nullptr));
         CVTMI_HIP(hipStreamSynchronize(st));   // (a call that only seeds launches nothing: the copies above still read host vectors)
         return CVTMI_OK;
     };
@@ -380,11 +394,13 @@ int cvtmi_hnsw_save(cvtmi_hnsw_t h, void *buf, int64_t cap, int64_t *bytes)
     std::vector<uint32_t> links0, upper;
     std::vector<float> vec;
     std::vector<int64_t> labels, uoff;
+    std::vector<uint64_t> dead;
     size_t upper_words = 0;
     for (int64_t i = 0; i < n; ++i) upper_words += (size_t)h->levels[(size_t)i] * (maxM + 1);
     try {
         links0.resize((size_t)n * (maxM0 + 1)); vec.resize((size_t)n * D); labels.resize((size_t)n); uoff.resize((size_t)n);
         upper.resize(upper_words);
+        if (h->n_dead > 0) dead.resize((size_t)((n + 63) / 64));
     } catch (const std::exception &) {
         return fail(CVTMI_ENOMEM, "cvtmi_hnsw_save: out of host memory");
     }
@@ -394,7 +410,11 @@ int cvtmi_hnsw_save(cvtmi_hnsw_t h, void *buf, int64_t cap, int64_t *bytes)
         CVTMI_HIP(hipMemcpy(labels.data(), h->labels.p, labels.size() * 8, hipMemcpyDeviceToHost));
         CVTMI_HIP(hipMemcpy(uoff.data(), h->upper_off.p, uoff.size() * 8, hipMemcpyDeviceToHost));
         if (upper_words) CVTMI_HIP(hipMemcpy(upper.data(), h->upper.p, upper_words * 4, hipMemcpyDeviceToHost));
+        if (!dead.empty()) CVTMI_HIP(hipMemcpy(dead.data(), h->dead.p, dead.size() * 8, hipMemcpyDeviceToHost));
     }
+    // hnswlib's DELETE_MARK: bit 16 of a dead node's level-0 count word; a graph without dead nodes writes the bytes it always wrote
+    for (size_t w = 0; w < dead.size(); ++w)
+        for (uint64_t b = dead[w]; b; b &= b - 1) links0[(w * 64 + (size_t)__builtin_ctzll(b)) * (maxM0 + 1)] |= 1u << 16;
     uint8_t *p = static_cast<uint8_t *>(buf);
     auto put = [&](const void *src, size_t nb) { memcpy(p, src, nb); p += nb; };
     const uint64_t zero = 0, cnt = (uint64_t)n, offd = link0, offl = link0 + 4 * D;
@@ -421,7 +441,7 @@ int cvtmi_hnsw_destroy(cvtmi_hnsw_t h)
     if (!h) return CVTMI_OK;
     if (h->magic != 0x484e5357u) return fail(CVTMI_EINVAL, "bad hnsw handle");
     CVTMI_TRY(use_device(h->device));   // (a handle cvtmi_hnsw_add left broken is destroyed like any other)
-    h->vec.release(); h->links0.release(); h->labels.release(); h->upper_off.release(); h->upper.release();
+    h->vec.release(); h->links0.release(); h->labels.release(); h->upper_off.release(); h->upper.release(); h->dead.release();
     (void)hipDeviceSynchronize();   // searches still in flight on other streams read the graph
     h->pool.destroy();
     h->magic = 0;
@@ -481,11 +501,24 @@ static int hnsw_check_overflow(HnswScratch &S, const char *who, int ef, hipStrea
     return CVTMI_OK;
 }
 
+// A handle with dead nodes (cvtmi_hnsw_mark_deleted) answers every search through the MASKED kernels: hnswlib's rule for a deleted node
+// is the rule for a node the mask forbids.  The mask is what the caller allows (everything, on the unmasked entries) without the
+// dead nodes, formed in the leased set; the caller's words are only read.  n_dead == 0: nothing happens here, the mask stays the caller's.
+static int hnsw_live_mask(cvtmi_hnsw_t h, HnswScratch &S, const uint64_t *&mask, hipStream_t st)
+{
+    if (h->n_dead == 0 || h->g.n == 0) return CVTMI_OK;
+    CVTMI_TRY(S.s_live.reserve((size_t)((h->g.n + 63) / 64) * 8));
+    CVTMI_TRY(launch_hnsw_live_mask(h->dead.as<uint64_t>(), mask, S.s_live.as<uint64_t>(), h->g.n, st));
+    mask = S.s_live.as<uint64_t>();
+    return CVTMI_OK;
+}
+
 // mask (device pointer, ceil(n / 64) words) != null: the masked search
 static int hnsw_search_leased(cvtmi_hnsw_t h, HnswScratch &S, const float *q, int64_t nq, int k, int ef, float *dist, int64_t *labels, hipStream_t st,
                               const uint64_t *mask = nullptr)
 {
     HnswPlan pl;
+    CVTMI_TRY(hnsw_live_mask(h, S, mask, st));
     CVTMI_TRY(hnsw_plan(h, S, h->D, nq, k, ef, pl, st, mask ? 0 : -1));
     CVTMI_TRY(launch_hnsw_search(h->g, h->metric, q, nq, k, ef, dist, labels, S.s_vis.as<uint32_t>(), S.s_cand.p, pl.slots, pl.words,
                                  pl.gcap, S.s_err.as<int>(), st, mask));
@@ -568,6 +601,7 @@ static int hnsw_search_adc_leased(cvtmi_hnsw_t h, HnswScratch &S, cvtmi_opq_t op
     }
     CVTMI_TRY(OS.s_lut.reserve((size_t)nq * opq->m.M * opq->m.K * sizeof(float)));
     CVTMI_TRY(launch_lut(opq->m, q_rot, nq, nullptr, OS.s_lut.as<float>(), st));
+    CVTMI_TRY(hnsw_live_mask(h, S, mask, st));
     HnswPlan pl;
     const int state_floats = hnsw_adc_state_floats(opq->m.M * opq->m.K);   // one reading of the tuning flag for the slot count AND the launch
     CVTMI_TRY(hnsw_plan(h, S, state_floats, nq, k, ef, pl, st, mask ? (state_floats ? 2 : 1) : -1));
@@ -831,6 +865,125 @@ int cvtmi_hnsw_mask_labels(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labe
     CVTMI_HIP(stream_wait(st));
     memset(mask + words, 0, (size_t)(mask_words - words) * 8);
     return CVTMI_OK;
+}
+
+}  // extern "C"
+
+// ================================================================ deletion =====================
+// cvtmi_hnsw_mark_deleted / _unmark_deleted: hnswlib's markDelete over a label set.  The mark step of
+// cvtmi_hnsw_mask_labels finds the nodes that carry one of the labels; hnsw_dead_fold_kernel folds them into the handle's bitmap and
+// counts the bits that flip.  Mutating and exclusive, like cvtmi_hnsw_add: the scratch set is leased under the handle's exclusive lock
+// (Lease, not HnswLease, which would take it shared), the stream first waits for the searches in flight, later searches wait for it.
+// labels: a host pointer, or (dev) a device pointer that comes down first, as in cvtmi_hnsw_mask_labels_dev.
+static int hnsw_set_deleted(cvtmi_hnsw_t h, const char *who, const int64_t *labels, bool dev, int64_t n_labels, int64_t *changed, int unmark,
+                            hipStream_t stream)
+{
+    if (!h) return fail(CVTMI_EINVAL, "%s: null handle", who);
+    if (n_labels < 0 || (n_labels > 0 && !labels)) return fail(CVTMI_EINVAL, "%s: bad arguments (n_labels >= 0, labels for n_labels > 0)", who);
+    CHECK_HN(h);
+    std::unique_lock<std::shared_timed_mutex> wr(h->rw);
+    if (changed) *changed = 0;
+    if (n_labels == 0 || h->g.n == 0 || (unmark && h->n_dead == 0)) return CVTMI_OK;
+    Lease<HnswScratch> lease;
+    CVTMI_TRY(lease.open(h, stream, !dev));
+    HnswScratch &S = *lease.s;
+    hipStream_t st = lease.st;
+    std::vector<int64_t> raw, tab;
+    if (dev) {
+        try {
+            raw.resize((size_t)n_labels);
+        } catch (...) {
+            return fail(CVTMI_ENOMEM, "%s: out of host memory", who);
+        }
+        CVTMI_HIP(hipMemcpyAsync(raw.data(), labels, (size_t)n_labels * 8, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(stream_wait(st));
+        labels = raw.data();
+    }
+    CVTMI_TRY(hnsw_label_table(labels, n_labels, tab));
+    FlatRmPlan p;   // the mark's areas, the table, and one word behind it for the count of flipped bits
+    p.rm = rm_plan(h->g.n, 0, 0, 0);
+    p.T = (int64_t)tab.size();
+    p.off_table = p.rm.off_table;
+    const size_t off_flips = p.off_table + rm_align((size_t)p.T * 8);
+    p.bytes = off_flips + rm_align(8);
+    CVTMI_TRY(S.s_mark.reserve(p.bytes));
+    void *W = S.s_mark.p;
+    unsigned long long *flips = rm_at<unsigned long long>(W, off_flips);
+    h->pool.mutation_begin(st);
+    CVTMI_HIP(hipMemcpyAsync(rm_at<char>(W, p.off_table), tab.data(), (size_t)p.T * 8, hipMemcpyHostToDevice, st));
+    CVTMI_HIP(hipMemsetAsync(flips, 0, 8, st));
+    CVTMI_TRY(launch_flat_rm_mark_labels(p, W, h->g.labels, st));
+    // (the marked bitmap holds ntiles * kRmWords >= ceil(n / 64) words and no bit past the nodes: the tail of `dead` stays zero)
+    CVTMI_TRY(launch_hnsw_dead_fold(rm_at<uint64_t>(W, p.rm.off_drop), h->dead.as<uint64_t>(), (h->g.n + 63) / 64, unmark, flips, st));
+    unsigned long long f = 0;
+    CVTMI_HIP(hipMemcpyAsync(&f, flips, 8, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));   // (the table and the count live in host memory that ends with this call)
+    h->n_dead += unmark ? -(int64_t)f : (int64_t)f;
+    h->pool.mutation_end(st);
+    if (changed) *changed = (int64_t)f;
+    return CVTMI_OK;
+}
+
+static int hnsw_get_deleted_impl(cvtmi_hnsw_t h, uint64_t *mask, int64_t mask_words, bool dev, hipStream_t stream)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_hnsw_get_deleted: null handle");
+    if (mask_words < 0 || (mask_words > 0 && !mask)) return fail(CVTMI_EINVAL, "cvtmi_hnsw_get_deleted: bad arguments");
+    CHECK_HN(h);
+    HnswLease lease;
+    CVTMI_TRY(lease.open(h, stream, !dev));
+    const int64_t words = (h->g.n + 63) / 64;
+    if (mask_words < words)
+        return fail(CVTMI_EINVAL, "cvtmi_hnsw_get_deleted: %lld mask words for %lld nodes (%lld needed)", (long long)mask_words, (long long)h->g.n,
+                    (long long)words);
+    if (mask_words == 0) return CVTMI_OK;
+    hipStream_t st = lease.st;
+    if (dev) {
+        if (words) CVTMI_HIP(hipMemcpyAsync(mask, h->dead.p, (size_t)words * 8, hipMemcpyDeviceToDevice, st));
+        if (mask_words > words) CVTMI_HIP(hipMemsetAsync(mask + words, 0, (size_t)(mask_words - words) * 8, st));
+        return CVTMI_OK;
+    }
+    if (words) CVTMI_HIP(hipMemcpyAsync(mask, h->dead.p, (size_t)words * 8, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    memset(mask + words, 0, (size_t)(mask_words - words) * 8);
+    return CVTMI_OK;
+}
+
+extern "C" {
+
+int cvtmi_hnsw_mark_deleted(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, int64_t *changed)
+{
+    return hnsw_set_deleted(h, "cvtmi_hnsw_mark_deleted", labels, false, n_labels, changed, 0, nullptr);
+}
+int cvtmi_hnsw_mark_deleted_dev(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, int64_t *changed, void *stream)
+{
+    return hnsw_set_deleted(h, "cvtmi_hnsw_mark_deleted", labels, true, n_labels, changed, 0, (hipStream_t)stream);
+}
+int cvtmi_hnsw_unmark_deleted(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, int64_t *changed)
+{
+    return hnsw_set_deleted(h, "cvtmi_hnsw_unmark_deleted", labels, false, n_labels, changed, 1, nullptr);
+}
+int cvtmi_hnsw_unmark_deleted_dev(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, int64_t *changed, void *stream)
+{
+    return hnsw_set_deleted(h, "cvtmi_hnsw_unmark_deleted", labels, true, n_labels, changed, 1, (hipStream_t)stream);
+}
+
+int cvtmi_hnsw_deleted_count(cvtmi_hnsw_t h, int64_t *count)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_hnsw_deleted_count: null handle");
+    if (!count) return fail(CVTMI_EINVAL, "cvtmi_hnsw_deleted_count: null pointer");
+    CHECK_HN(h);
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    *count = h->n_dead;
+    return CVTMI_OK;
+}
+
+int cvtmi_hnsw_get_deleted(cvtmi_hnsw_t h, uint64_t *mask, int64_t mask_words)
+{
+    return hnsw_get_deleted_impl(h, mask, mask_words, false, nullptr);
+}
+int cvtmi_hnsw_get_deleted_dev(cvtmi_hnsw_t h, uint64_t *mask, int64_t mask_words, void *stream)
+{
+    return hnsw_get_deleted_impl(h, mask, mask_words, true, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -259,9 +259,10 @@ struct HnswScratch : ScratchBase {
     DevBuf s_vis, s_cand, s_err, s_rr_d, s_rr_id, io_q, io_d, io_l;
     DevBuf s_mark;   // cvtmi_hnsw_mask_labels: the marked bitmap, its tile counts and the table of the label set
     DevBuf io_m;     // the mask words / the label set of the host-pointer masked entries
+    DevBuf s_live;   // a search on a graph with dead nodes: the caller's mask (or all ones) without the dead nodes
     void release_all()
     {
-        for (DevBuf *b : { &s_vis, &s_cand, &s_err, &s_rr_d, &s_rr_id, &io_q, &io_d, &io_l, &s_mark, &io_m }) b->release();
+        for (DevBuf *b : { &s_vis, &s_cand, &s_err, &s_rr_d, &s_rr_id, &io_q, &io_d, &io_l, &s_mark, &io_m, &s_live }) b->release();
         release_lease_state();
     }
 };
@@ -270,6 +271,10 @@ struct cvtmi_hnsw_s {
     int device = 0, metric = 0, D = 0;
     HnswDevGraph g{};
     DevBuf vec, links0, labels, upper_off, upper;
+    // the delete state (cvtmi_hnsw_mark_deleted): bit i & 63 of word i >> 6 = node i is deleted, ceil(n / 64) words in
+    // use, the bits past n zero; n_dead = the bits set.  links0 keeps plain counts: the file's mark bit exists in save / load alone.
+    DevBuf dead;
+    int64_t n_dead = 0;
     // what cvtmi_hnsw_save needs beyond the device graph: the header fields as the file (or the build) set them, and the number
     // of upper levels of every element
     std::vector<int32_t> levels;
@@ -280,7 +285,7 @@ struct cvtmi_hnsw_s {
     ScratchPool<HnswScratch> pool;
     int64_t masked_last[4] = {};   // the last masked search (cvtmi_hnsw_last_masked), written under pool.mu
     int slots_per_cu_max = 32, cus = 256;
-    // cvtmi_hnsw_add: searches (and cvtmi_hnsw_save) hold `rw` shared -- HnswLease takes it --, add / reserve / set_level_draws exclusively
+    // cvtmi_hnsw_add: searches (and cvtmi_hnsw_save) hold `rw` shared -- HnswLease takes it --, add / reserve / set_level_draws / mark_deleted / unmark_deleted exclusively
     std::shared_timed_mutex rw;
     int64_t upper_words = 0;       // words of `upper` in use: where the next row's upper-level block goes
     // the level stream (hnswalg.h:139-149): the engine after `level_draws` draws.  A build of n rows leaves n, a load 0 (the

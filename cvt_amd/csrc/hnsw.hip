@@ -440,6 +440,59 @@ int launch_hnsw_rerank(const HnswDevGraph &g, int metric, const float *q, int64_
     return launch("hnsw_rerank_kernel", kern, blocks_for(total, kBlock), kBlock, 0, st, g.vec, g.D, q, ids, total, R, out_d);
 }
 
+// ---- the delete state (cvtmi_hnsw_mark_deleted) ----
+// hits: the bitmap the mark step of cvtmi_hnsw_mask_labels left (no bit past the nodes).  One word per thread; the flipped bits are
+// counted by a popcount per word, summed over the wave and the workgroup, one atomic per workgroup that flipped something.
+__global__ __launch_bounds__(kBlock) void hnsw_dead_fold_kernel(const unsigned long long *__restrict__ hits, unsigned long long *__restrict__ dead,
+                                                                int64_t words, int unmark, unsigned long long *__restrict__ flipped)
+{
+    __shared__ int part[kBlock / 64];
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    int c = 0;
+    if (i < words) {
+        const unsigned long long old = dead[i], hit = hits[i];
+        const unsigned long long now = unmark ? old & ~hit : old | hit;
+        c = __popcll(old ^ now);
+        if (c) dead[i] = now;
+    }
+    for (int sh = 32; sh >= 1; sh >>= 1) c += __shfl_xor(c, sh);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int j = 0; j < kBlock / 64; ++j) s += part[j];
+        if (s) atomicAdd(flipped, (unsigned long long)s);
+    }
+}
+
+int launch_hnsw_dead_fold(const uint64_t *hits, uint64_t *dead, int64_t words, int unmark, unsigned long long *flipped, hipStream_t st)
+{
+    if (words <= 0) return CVTMI_OK;
+    return launch("hnsw_dead_fold_kernel", hnsw_dead_fold_kernel, blocks_for(words, kBlock), kBlock, 0, st,
+                  reinterpret_cast<const unsigned long long *>(hits), reinterpret_cast<unsigned long long *>(dead), words, unmark, flipped);
+}
+
+// the mask of a search on a graph with dead nodes: what the caller allows (everything, without a mask of theirs) and is not dead
+__global__ __launch_bounds__(kBlock) void hnsw_live_mask_kernel(const unsigned long long *__restrict__ dead, const unsigned long long *__restrict__ user,
+                                                                unsigned long long *__restrict__ out, int64_t words, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= words) return;
+    unsigned long long w = ~dead[i];
+    if (user) w &= user[i];
+    if (i == words - 1 && (n & 63)) w &= (1ull << (n & 63)) - 1ull;   // the caller's tail bits may hold anything
+    out[i] = w;
+}
+
+int launch_hnsw_live_mask(const uint64_t *dead, const uint64_t *user, uint64_t *out, int64_t n, hipStream_t st)
+{
+    const int64_t words = (n + 63) / 64;
+    if (words <= 0) return CVTMI_OK;
+    return launch("hnsw_live_mask_kernel", hnsw_live_mask_kernel, blocks_for(words, kBlock), kBlock, 0, st,
+                  reinterpret_cast<const unsigned long long *>(dead), reinterpret_cast<const unsigned long long *>(user),
+                  reinterpret_cast<unsigned long long *>(out), words, n);
+}
+
 // LDS bytes of one query slot: query state (floats) + top queue (ef + 1) + the LDS part of the candidate queue
 // Entries of the top queue (ef + 1) kept in LDS; the rest of it lives in HBM like the candidate queue's.  Keeping all of it in LDS (8 KB at
 // ef = 1000) was measured: fp32 ef = 1000 174 K -> 151 K queries/s, ADC 101 K -> 97 K at 1 M nodes -- the query slots lost per CU cost more than

@@ -61,6 +61,7 @@ struct HbArgs {
     int64_t words, gcap;
     int top_lds;
     int *err;
+    const uint32_t *dead;      // DEL: a bit per node, set = deleted (the handle's bitmap read as 32-bit words, like `visited`)
 };
 
 __device__ __forceinline__ const uint32_t *hb_list(const HbArgs &a, uint32_t id, int level)
@@ -69,7 +70,13 @@ __device__ __forceinline__ const uint32_t *hb_list(const HbArgs &a, uint32_t id,
 }
 
 // ---- 1. construction traversal --------------------------------------------------------------------------------------------------
-template <bool IP, int LANES>
+// DEL (cvtmi_hnsw_add on a graph with deleted nodes) is current hnswlib's searchBaseLayer / addPoint over marked
+// nodes, the MASKED rule of hnsw_search_kernel with "allowed" = "not in a.dead": the descent walks dead nodes like live ones; on a
+// level every accepted neighbour joins the candidate queue and only live ones the result queue; `lower` follows the result queue once
+// it holds something (+inf until then); the walk stops on `-c.d > lower` only on a FULL result queue; and when the batch's entry point
+// is dead it is pushed into every level's result queue after the walk (hnswlib's epDeleted step), so a graph whose live part cannot
+// be reached still links something.  The candidate queue is bounded by the node count alone: the host gives it room for every node.
+template <bool IP, int LANES, bool DEL>
 __global__ __launch_bounds__(64, 8) void hnsw_build_search_kernel(const HbArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float hb_smem[];
@@ -141,28 +148,36 @@ __global__ __launch_bounds__(64, 8) void hnsw_build_search_kernel(const HbArgs a
             int top_n = 0, cand_n = 0;
             {
                 const float d0 = dist(cur);
-                hn_push(top, top_n, d0, cur, lane);
+                // (readfirstlane: `cur` is one value in all lanes, and the branch around the wave-wide push must be a scalar one)
+                const bool live = !DEL || __builtin_amdgcn_readfirstlane((int)((a.dead[cur >> 5] >> (cur & 31)) & 1u)) == 0;
+                if (live) hn_push(top, top_n, d0, cur, lane);
                 hn_push(cand, cand_n, -d0, cur, lane);
                 if (w) vis[cur >> 5] |= 1u << (cur & 31);
                 __builtin_amdgcn_s_waitcnt(0);
             }
-            float lower = top.get(0).d;
+            float lower = (!DEL || top_n > 0) ? top.get(0).d : __uint_as_float(0x7f800000u);
             while (cand_n > 0) {
                 const HnEnt c = cand.get(0);
-                if (-c.d > lower) break;
+                if (-c.d > lower && (!DEL || top_n >= ef)) break;
                 const uint32_t *ll = hb_list(a, c.id, level);
                 const uint32_t nb0 = lane < width ? ll[1 + lane] : 0u;
                 const int size = (int)ll[0];
                 hn_pop(cand, cand_n, lane);
                 bool act = lane < size;
                 const uint32_t nb = nb0;
+                bool ok = true;
                 if (act) {
                     const uint32_t bit = 1u << (nb & 31);
+                    uint32_t dw = 0u;
+                    if (DEL) dw = a.dead[nb >> 5];   // requested in the round trip of the visited bit
                     act = (atomicOr(&vis[nb >> 5], bit) & bit) == 0;
+                    if (DEL) ok = (dw & bit) == 0;
                 }
                 float o = 0.0f;
                 if (act) o = dist(nb);
                 unsigned long long m = __ballot(act && (top_n < ef || lower > o));
+                // the lanes' live bits as one wave-uniform word: the branch around the wave-wide result-queue operations is scalar
+                const unsigned long long okm = DEL ? __ballot(ok) : ~0ull;
                 while (m) {
                     const int b = __ffsll((long long)m) - 1;
                     m &= m - 1;
@@ -170,16 +185,27 @@ __global__ __launch_bounds__(64, 8) void hnsw_build_search_kernel(const HbArgs a
                     const uint32_t id = (uint32_t)__shfl((int)nb, b);
                     if (lower > d || top_n < ef) {
                         if (cand_n >= cand_cap) { overflow = true; break; }
-                        hn_push(cand, cand_n, -d, id, lane);
-                        hn_push(top, top_n, d, id, lane);
-                        if (top_n > ef) hn_pop(top, top_n, lane);
-                        lower = top.get(0).d;
+                        hn_push(cand, cand_n, -d, id, lane);   // traversed whether deleted or not
+                        if (!DEL || ((okm >> b) & 1ull)) {
+                            hn_push(top, top_n, d, id, lane);
+                            if (top_n > ef) hn_pop(top, top_n, lane);
+                        }
+                        if (!DEL || top_n > 0) lower = top.get(0).d;
                         if (top_n >= ef) m &= __ballot(act && lower > o);
                     }
                 }
                 if (overflow) break;
             }
             if (overflow) break;
+            if (DEL) {
+                // a dead entry point never entered the queue through the walk (dead nodes do not): no duplicate
+                const uint32_t ep = a.enterpoint;
+                if (__builtin_amdgcn_readfirstlane((int)((a.dead[ep >> 5] >> (ep & 31)) & 1u)) != 0) {
+                    const float de = dist(ep);
+                    hn_push(top, top_n, de, ep, lane);
+                    if (top_n > ef) hn_pop(top, top_n, lane);
+                }
+            }
             // the result queue, in its heap layout
             const int task = a.tbase[r] + level;
             HnEnt *out = a.res + (int64_t)task * ef_cap;
@@ -410,6 +436,9 @@ void hnsw_build_phase_ms(double *ms)
 }
 
 struct HbBatch { int64_t s, e; int maxlevel; uint32_t ep; int64_t toff; int ntask; };
+// Scratch the DEL traversals of one call may hold (visited bits + queues of n entries per slot): the budget of a masked search
+// (api_hnsw.hip, kHnswMaskedScratch) -- every slot of a graph of up to 120 K nodes, about 1000 traversals in flight at 1 M.
+constexpr size_t kHbDelScratch = (size_t)8 << 30;
 
 // bounds of the batches that insert rows first .. n-1 into a graph of `first` rows whose top level is top0 (first == 0: row 0 seeds the
 // graph alone, top0 is not read)
@@ -445,7 +474,7 @@ void hnsw_build_schedule(const int32_t *levels, int64_t first, int64_t n, int to
 // an error before that leaves the graph as it was.  Per call: the n-word cnt / slot_of arrays and one memset of n words.
 int launch_hnsw_build(const char *who, const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, const int32_t *levels, int64_t first,
                       uint32_t ep0, int top0, int metric, int M, int efc, int max_batch, int cus, hipStream_t st, int64_t *stats,
-                      bool *launched)
+                      bool *launched, const uint64_t *dead)
 {
     const auto h0 = std::chrono::steady_clock::now();
     const int64_t n = g.n, m = n - first;
@@ -485,11 +514,19 @@ int launch_hnsw_build(const char *who, const HnswDevGraph &g, uint32_t *links0, 
     const int lds_search = hnsw_lds_bytes(g.D, efc);
     int per_cu = (159 * 1024) / lds_search;
     per_cu = per_cu > 32 ? 32 : (per_cu < 1 ? 1 : per_cu);
-    const int64_t slots_max = (int64_t)cus * per_cu < rmax ? (int64_t)cus * per_cu : rmax;
+    int64_t slot_cap = (int64_t)cus * per_cu;
     const int64_t words_max = (n + 31) / 32 + 1;
     int64_t gcap = (int64_t)efc * g.maxM0 * 2;
-    if (gcap > n) gcap = n;
+    // DEL: while few live nodes have been found nothing is pruned and every visited node is queued; a node enters the queue at most
+    // once, so room for n entries (HN_LCAP + gcap >= n) rules the overflow out, as hnsw_plan does for a masked search
+    if (gcap > n || dead) gcap = n;
     gcap = (gcap > HN_LCAP ? gcap - HN_LCAP : 0) + 64;
+    if (dead) {   // ... and the traversals in flight are bounded by the scratch they need (at least one)
+        const size_t per_slot = (size_t)words_max * 4 + (size_t)(gcap + efc1) * sizeof(HnEnt);
+        const int64_t fit = (int64_t)(kHbDelScratch / per_slot);
+        if (slot_cap > fit) slot_cap = fit > 1 ? fit : 1;
+    }
+    const int64_t slots_max = slot_cap < rmax ? slot_cap : rmax;
 
     Tmp d_tbase, d_trow, d_tlv, d_lev, res, res_n, prop, prop_n, cnt, slot_of, touched, t_cnt, t_off, bucket, ctr, vis, candg, err;
     CVTMI_TRY(d_tbase.upload(tbase.data(), tbase.size() * 4));
@@ -520,6 +557,7 @@ int launch_hnsw_build(const char *who, const HnswDevGraph &g, uint32_t *links0, 
     a.cnt = cnt.as<int32_t>(); a.slot_of = slot_of.as<int32_t>(); a.touched = touched.as<uint32_t>();
     a.t_cnt = t_cnt.as<int32_t>(); a.t_off = t_off.as<int32_t>(); a.bucket = bucket.as<uint64_t>(); a.ctr = ctr.as<HbCounters>();
     a.visited = vis.as<uint32_t>(); a.cand_g = candg.as<HnEnt>(); a.gcap = gcap; a.top_lds = hnsw_top_lds(efc); a.err = err.as<int>();
+    a.dead = reinterpret_cast<const uint32_t *>(dead);
 
     const bool ip = metric == CVTMI_METRIC_IP;
     const int lanes = (g.D % 4 != 0) ? 1 : (ip ? 4 : (g.D % 16 == 0 ? 8 : 4));
@@ -535,9 +573,11 @@ int launch_hnsw_build(const char *who, const HnswDevGraph &g, uint32_t *links0, 
         return CVTMI_OK;
     };
     // the <IP, LANES> instance of the three kernel families that suits the index
-    static constexpr decltype(&hnsw_build_search_kernel<true, 4>) search_k[5] = {
-        hnsw_build_search_kernel<true, 4>, hnsw_build_search_kernel<true, 1>, hnsw_build_search_kernel<false, 8>, hnsw_build_search_kernel<false, 4>,
-        hnsw_build_search_kernel<false, 1> };
+    static constexpr decltype(&hnsw_build_search_kernel<true, 4, false>) search_k[2][5] = {
+        { hnsw_build_search_kernel<true, 4, false>, hnsw_build_search_kernel<true, 1, false>, hnsw_build_search_kernel<false, 8, false>,
+          hnsw_build_search_kernel<false, 4, false>, hnsw_build_search_kernel<false, 1, false> },
+        { hnsw_build_search_kernel<true, 4, true>, hnsw_build_search_kernel<true, 1, true>, hnsw_build_search_kernel<false, 8, true>,
+          hnsw_build_search_kernel<false, 4, true>, hnsw_build_search_kernel<false, 1, true> } };
     static constexpr decltype(&hnsw_build_select_kernel<true, 4>) select_k[5] = {
         hnsw_build_select_kernel<true, 4>, hnsw_build_select_kernel<true, 1>, hnsw_build_select_kernel<false, 8>, hnsw_build_select_kernel<false, 4>,
         hnsw_build_select_kernel<false, 1> };
@@ -545,7 +585,8 @@ int launch_hnsw_build(const char *who, const HnswDevGraph &g, uint32_t *links0, 
         hnsw_build_link_kernel<true, 4>, hnsw_build_link_kernel<true, 1>, hnsw_build_link_kernel<false, 8>, hnsw_build_link_kernel<false, 4>,
         hnsw_build_link_kernel<false, 1> };
     const int form = ip ? (lanes == 4 ? 0 : 1) : (lanes == 8 ? 2 : lanes == 4 ? 3 : 4);
-    const auto search = search_k[form];
+    const auto search = search_k[dead ? 1 : 0][form];
+    const char *search_name = dead ? "hnsw_build_search_kernel<del>" : "hnsw_build_search_kernel";
     const auto select = select_k[form];
     const auto link = link_k[form];
     CVTMI_TRY(set_max_lds("hnsw_build_search_kernel", search, lds_search));
@@ -560,11 +601,11 @@ int launch_hnsw_build(const char *who, const HnswDevGraph &g, uint32_t *links0, 
         a.task_row = d_trow.as<int32_t>() + B.toff;
         a.task_lv = d_tlv.as<int32_t>() + B.toff;
         a.words = (B.s + 31) / 32 + 1;
-        const int64_t slots = (int64_t)cus * per_cu < a.rows ? (int64_t)cus * per_cu : a.rows;
+        const int64_t slots = slot_cap < a.rows ? slot_cap : a.rows;
         const int64_t np = (int64_t)B.ntask * M;
         const int64_t pb = blocks_for(np, 256);
         CVTMI_HIP(hipMemsetAsync(ctr.p, 0, sizeof(HbCounters), st));
-        CVTMI_TRY(launch("hnsw_build_search_kernel", search, slots, 64, lds_search, st, a));
+        CVTMI_TRY(launch(search_name, search, slots, 64, lds_search, st, a));
         CVTMI_TRY(mark());
         const int64_t sel_grid = B.ntask < (int64_t)cus * 32 ? B.ntask : (int64_t)cus * 32;
         CVTMI_TRY(launch("hnsw_build_select_kernel", select, sel_grid, 64, sel_lds, st, a));

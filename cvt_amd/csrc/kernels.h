@@ -472,6 +472,12 @@ int hnsw_ef_max();
 int hnsw_lcap();
 int hnsw_top_lds(int ef);
 int hnsw_adc_state_floats(int MK);
+// the delete state of a graph (cvtmi_hnsw_mark_deleted): dead[i] |= hits[i] (unmark == 0) or dead[i] &= ~hits[i] over `words` 64-bit
+// words; *flipped (device, zeroed by the caller) += the bits that changed
+int launch_hnsw_dead_fold(const uint64_t *hits, uint64_t *dead, int64_t words, int unmark, unsigned long long *flipped, hipStream_t st);
+// the mask a search of a graph with dead nodes runs under: out[i] = (user ? user[i] : ~0) & ~dead[i] over ceil(n / 64) words, the bits
+// of the last word at positions >= n cleared; `user` is only read
+int launch_hnsw_live_mask(const uint64_t *dead, const uint64_t *user, uint64_t *out, int64_t n, hipStream_t st);
 
 // ---- hnsw_build.hip ----
 // batch-synchronous insertion of rows first .. g.n-1 into the graph of rows 0 .. first-1 (cvtmi_hnsw_build: first = 0, an empty
@@ -480,9 +486,11 @@ int hnsw_adc_state_floats(int MK);
 // NEW rows, [g.n - first]); returns when the graph is complete.  M: links a new row asks for (<= g.maxM <= g.maxM0 <= 64).
 // stats (may be null): { batches, largest batch }; *launched (may be null): set when the first kernel is about to be enqueued, so a
 // failure that leaves it false has not touched the graph.  `who` names the C entry in messages.
+// dead != null (cvtmi_hnsw_add on a graph with deleted nodes): ceil(g.n / 64) words, bit i = node i is deleted (the
+// bits of the new rows are zero); the traversal runs its DEL instance, whose candidate queue has room for every node.
 int launch_hnsw_build(const char *who, const HnswDevGraph &g, uint32_t *links0, uint32_t *upper, const int32_t *levels, int64_t first,
                       uint32_t ep0, int top0, int metric, int M, int efc, int max_batch, int cus, hipStream_t st, int64_t *stats,
-                      bool *launched);
+                      bool *launched, const uint64_t *dead = nullptr);
 void hnsw_build_phase_ms(double *ms);   // [traversal, selection, back links, batches, host ms] of the last build with phases on
 
 }  // namespace cvtmi

@@ -27,6 +27,12 @@
 //    insert.  One thread = the sequential algorithm, the byte-identical file; more threads = a graph that depends on
 //    the interleaving, as in the reference.
 //
+//  * DELETION is current hnswlib's markDelete / unmarkDelete (not in the reference, whose hnswlib predates it): the mark is bit 16 of a
+//    node's level-0 count word (DELETE_MARK 0x01 in byte 2), here as in the file, so parse / saveIndex / upload carry it as they carry
+//    the count; a device copy that is up to date is told (cvtmi_hnsw_mark_deleted).  Searches never return a marked node, and
+//    addPoint / addPoints on a graph with marked nodes follow hnswlib's rule: marked nodes are walked through and
+//    never chosen, except for a marked entry point, which is offered to every level's selection after the walk.
+//
 // Host data layout is the mirror's own (separate arrays for vectors / links / labels); only the file is the
 // reference's interleaved block.
 #pragma once
@@ -38,6 +44,7 @@
 #include <sched.h>
 #endif
 #include <fstream>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <random>
@@ -207,6 +214,23 @@ public:
     }
     size_t maxElements() const { return cap_; }
 
+    // ---- deletion (current hnswlib's markDelete / unmarkDelete; not thread-safe against insertions) ----
+    // every node that carries one of labels[n] changes state; returns the nodes whose state changed.  Duplicate and foreign labels
+    // are fine, as in cvtmi_hnsw_mark_deleted, which a device copy that is up to date receives the same set through.
+    size_t markDeleteBatch(const labeltype *labels, size_t n) { return set_deleted(labels, n, true); }
+    size_t unmarkDeleteBatch(const labeltype *labels, size_t n) { return set_deleted(labels, n, false); }
+    void markDelete(labeltype label)
+    {
+        if (!carried(label)) throw std::runtime_error("Label not found");
+        (void)set_deleted(&label, 1, true);
+    }
+    void unmarkDelete(labeltype label)
+    {
+        if (!carried(label)) throw std::runtime_error("Label not found");
+        (void)set_deleted(&label, 1, false);
+    }
+    size_t deletedCount() const { return n_dead_; }
+
     // the level stream: draws taken from std::default_random_engine(100) so far (0 after loadIndex into a new object, as in the
     // reference, whose loadIndex leaves level_generator_ at its initialiser), and the stream repositioned to a given number of draws
     size_t levelDraws() const { return draws_; }
@@ -353,6 +377,37 @@ public:
     }
 
 private:
+    enum { kDeleteMark = 1u << 16, kCountMask = 0xffffu };   // the level-0 count word: hnswlib's DELETE_MARK in byte 2, the count below it
+    bool marked(tableint id) const { return (__atomic_load_n(&link0_[(size_t)id * (maxM0_ + 1)], __ATOMIC_RELAXED) & kDeleteMark) != 0; }
+    bool carried(labeltype label) const
+    {
+        for (size_t i = 0; i < count_; ++i)
+            if (label_[i] == label) return true;
+        return false;
+    }
+    size_t set_deleted(const labeltype *labels, size_t n, bool on)
+    {
+        static_assert(sizeof(labeltype) == sizeof(int64_t), "labels are 64-bit");
+        if (broken_) throw std::runtime_error("HierarchicalNSW: an insertion failed part-way; rebuild the graph");
+        const std::unordered_set<labeltype> set(labels, labels + n);
+        size_t changed = 0;
+        if (!set.empty())
+            for (size_t i = 0; i < count_; ++i) {
+                tableint &w = link0_[i * (maxM0_ + 1)];
+                if (((w & kDeleteMark) != 0) == on || !set.count(label_[i])) continue;
+                w ^= kDeleteMark;
+                ++changed;
+            }
+        n_dead_ = on ? n_dead_ + changed : n_dead_ - changed;
+        if (changed && dev_ && !dirty_) {   // (a stale device copy is replaced by the next upload anyway)
+            int64_t got = 0;
+            const int rc = on ? cvtmi_hnsw_mark_deleted(dev_, (const int64_t *)labels, (int64_t)n, &got)
+                              : cvtmi_hnsw_unmark_deleted(dev_, (const int64_t *)labels, (int64_t)n, &got);
+            if (rc != CVTMI_OK || (size_t)got != changed) dirty_ = true;
+        }
+        return changed;
+    }
+
     int draw_level()   // under count_guard_: the i-th element gets the i-th draw (hnswalg.h:139-149)
     {
         std::uniform_real_distribution<double> u01(0.0, 1.0);
@@ -373,6 +428,7 @@ private:
         const int top = (int)(tv & 0xffffffffu) - 1;
         const bool seed = (tv >> 32) == 0;
         tableint cur = seed ? 0 : (tableint)((tv >> 32) - 1);
+        const tableint ep = cur;
         level_[id] = lvl;
         std::copy(x, x + dim_, &vec_[(size_t)id * dim_]);
         label_[id] = label;
@@ -401,6 +457,10 @@ private:
         }
         for (int l = std::min(lvl, top); l >= 0; --l) {  // every search starts from the same entry (:660-667)
             DistHeap found = search_level(cur, x, l);
+            if (n_dead_ && marked(ep)) {   // hnswlib's epDeleted step: a graph whose live part cannot be reached still links something
+                found.emplace(dist(x, row(ep)), ep);
+                if (found.size() > efc_) found.pop();
+            }
             connect(id, found, l);
         }
         if (lvl > top) {
@@ -417,7 +477,7 @@ private:
         for (;;) {
             const uint32_t s0 = seq_[node].load(std::memory_order_acquire);
             if (s0 & 1u) { relax(); continue; }
-            const tableint cnt = std::min<tableint>(__atomic_load_n(ll, __ATOMIC_RELAXED), (tableint)kMaxLinks);
+            const tableint cnt = std::min<tableint>(__atomic_load_n(ll, __ATOMIC_RELAXED) & (tableint)kCountMask, (tableint)kMaxLinks);
             for (tableint i = 0; i < cnt; ++i) out[i] = __atomic_load_n(ll + 1 + i, __ATOMIC_RELAXED);
             std::atomic_thread_fence(std::memory_order_acquire);
             if (seq_[node].load(std::memory_order_relaxed) == s0) {
@@ -446,6 +506,8 @@ private:
         ~WriteLock() { s.fetch_add(1, std::memory_order_release); }
     };
     static void put_link(tableint *p, tableint v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
+    // a list's count word, its delete mark kept (level 0 alone carries one; the upper levels' words hold plain counts)
+    static void put_count(tableint *p, tableint v) { __atomic_store_n(p, v | (__atomic_load_n(p, __ATOMIC_RELAXED) & (tableint)kDeleteMark), __ATOMIC_RELAXED); }
 
     void bind(SpaceInterface<dist_t> *s)
     {
@@ -494,15 +556,18 @@ private:
         std::vector<Cand> best_store, frontier_store;
         best_store.reserve(efc_ + 2); frontier_store.reserve(4 * efc_ + 64);
         DistHeap best(ByDist(), std::move(best_store)), frontier(ByDist(), std::move(frontier_store));
+        // with marked nodes in the graph (hnswlib's searchBaseLayer): they are traversed and never results, `bound` follows the
+        // result queue once it holds something, and the walk may stop on the bound only when that queue is full
+        const bool del = n_dead_ != 0;
         const dist_t d0 = dist(x, row(start));
-        best.emplace(d0, start);
+        dist_t bound = std::numeric_limits<dist_t>::infinity();
+        if (!del || !marked(start)) { best.emplace(d0, start); bound = d0; }
         frontier.emplace(-d0, start);
         seen[start] = stamp;
-        dist_t bound = d0;
         tableint nbs[kMaxLinks];
         while (!frontier.empty()) {
             const Cand c = frontier.top();
-            if (-c.first > bound) break;
+            if (-c.first > bound && (!del || best.size() >= efc_)) break;
             frontier.pop();
             const tableint cnt = snapshot(c.second, l, nbs);
             // (the neighbours' vectors are scattered over hundreds of megabytes: ask for the next one while this one is scored -- the
@@ -518,11 +583,13 @@ private:
                 if (seen[nb] == stamp) continue;
                 seen[nb] = stamp;
                 const dist_t d = dist(x, row(nb));
-                if (best.top().first > d || best.size() < efc_) {
+                if (best.size() < efc_ || best.top().first > d) {
                     frontier.emplace(-d, nb);
-                    best.emplace(d, nb);
-                    if (best.size() > efc_) best.pop();
-                    bound = best.top().first;
+                    if (!del || !marked(nb)) {
+                        best.emplace(d, nb);
+                        if (best.size() > efc_) best.pop();
+                    }
+                    if (!best.empty()) bound = best.top().first;
                 }
             }
         }
@@ -566,7 +633,7 @@ private:
             // linked itself to the still empty list (the reference makes it wait on this node's lock instead, hnswalg.h:602 -- two
             // nodes that are each other's entry on the same level wait for ever).  Its links are kept: the list becomes the chosen
             // neighbours plus those early links, cut back by the selection rule if that is more than the level holds.
-            const size_t early = mine[0];
+            const size_t early = mine[0] & (tableint)kCountMask;
             std::vector<tableint> all(chosen);
             for (size_t j = 0; j < early; ++j)
                 if (std::find(chosen.begin(), chosen.end(), mine[1 + j]) == chosen.end()) all.push_back(mine[1 + j]);
@@ -578,7 +645,7 @@ private:
                 while (!pool.empty()) { all.push_back(pool.top().second); pool.pop(); }
             }
             for (size_t i = 0; i < all.size(); ++i) put_link(mine + 1 + i, all[i]);
-            put_link(mine, (tableint)all.size());
+            put_count(mine, (tableint)all.size());
         }
         for (size_t i = 0; i < chosen.size(); ++i) {
             const tableint other = chosen[i];
@@ -605,10 +672,10 @@ private:
                 std::atomic_thread_fence(std::memory_order_release);
                 if (have < room) {
                     put_link(ol + 1 + have, id);
-                    put_link(ol, (tableint)(have + 1));
+                    put_count(ol, (tableint)(have + 1));
                 } else {
                     for (size_t j = 0; j < cnt; ++j) put_link(ol + 1 + j, new_list[j]);
-                    put_link(ol, (tableint)cnt);
+                    put_count(ol, (tableint)cnt);
                 }
                 seq_[other].fetch_add(1, std::memory_order_release);
                 break;
@@ -669,12 +736,16 @@ private:
         vec_.reset(new float[cap_ * dim_]); label_.assign(cap_, 0); level_.assign(cap_, 0);
         link0_.reset(new tableint[cap_ * (maxM0_ + 1)]); upper_.assign(cap_, std::vector<tableint>());
         seq_.reset(new std::atomic<uint32_t>[cap_]());
+        n_dead_ = 0;
         if (maxM0_ > kMaxLinks) throw std::runtime_error("cvt_amd: more than 512 links per node");
         for (size_t i = 0; i < count_; ++i) {
             const char *e = p + i * per_elem;
             memcpy(&link0_[i * (maxM0_ + 1)], e + off_level0, 4 + 4 * maxM0_);
             memcpy(&vec_[i * dim_], e + off_data, 4 * dim_);
             memcpy(&label_[i], e + off_label, 8);
+            const tableint w = link0_[i * (maxM0_ + 1)];
+            if ((w >> 17) != 0 || (w & (tableint)kCountMask) > maxM0_) throw std::runtime_error("cvt_amd: corrupt link count in saveIndex file");
+            n_dead_ += (w & (tableint)kDeleteMark) != 0;
         }
         p += cap_ * per_elem;
         const size_t upper_bytes = 4 * maxM_ + 4;
@@ -708,6 +779,7 @@ private:
     std::unique_ptr<float[]> vec_;                // [cap][dim]; elements past count_ are never read
     std::vector<labeltype> label_;
     std::vector<int> level_;
+    size_t n_dead_ = 0;                           // nodes whose level-0 count word carries the delete mark
     bool broken_ = false;                         // an insertion threw after count_ had been advanced
     std::unique_ptr<tableint[]> link0_;           // [cap][maxM0 + 1]: count, neighbours
     std::vector<std::vector<tableint> > upper_;   // per node: levels x (maxM + 1)

@@ -1054,8 +1054,10 @@ int cvtmi_hnsw_build_phases(double *ms);
  *              kernels report a candidate-queue overflow (or a launch fails) mid-call some link lists are already rewritten: the
  *              handle is marked broken and every entry but cvtmi_hnsw_destroy fails with a message from then on.  The `_dev` entry
  *              takes device rows and labels, runs on `stream` and returns when the graph is complete.
- *   Not here   deletion, and replacing the vector of an existing label (a repeated label gets a second node, as in the
- *              reference); the PQ codes cvtmi_hnsw_search_adc needs -- append them with cvtmi_opq_add_codes; until then the ADC
+ *   Deleted    on a handle with deleted nodes (cvtmi_hnsw_mark_deleted, below) the new rows are linked to live nodes only, by
+ *              current hnswlib's rule; the new rows arrive live and the marks are kept.
+ *   Not here   replacing the vector of an existing label (a repeated label gets a second node, as in the reference), reusing the
+ *              slot of a deleted node; the PQ codes cvtmi_hnsw_search_adc needs -- append them with cvtmi_opq_add_codes; until then the ADC
  *              entries answer CVTMI_EINVAL for the row-count mismatch.
  * cvtmi_hnsw_last_add: out = { first internal id of the last call that added rows, its batches (a seed row counts as one), its
  * largest batch, max_elements afterwards }. */
@@ -1135,6 +1137,39 @@ int cvtmi_hnsw_mask_labels_dev(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_
 /* The handle's last masked search: out = { slots (concurrent traversals), candidate-queue capacity per slot in entries (LDS + HBM),
  * scratch bytes reserved (visited bits + queues), form: 0 fp32, 1 ADC with tables in the scratch, 2 ADC with tables in LDS }. */
 int cvtmi_hnsw_last_masked(cvtmi_hnsw_t h, int64_t out[4]);
+/* Deletion: current hnswlib's markDelete / unmarkDelete over a label set.  A deleted node stays in the graph and is
+ * still walked through, but it is never a result and no new row links to it; its slot, vector and (in an OPQ index beside the graph)
+ * code row stay where they are.  The state is a bitmap of ceil(ntotal / 64) words on the device beside the labels.
+ *   Set      every node that carries one of labels[n_labels] is marked (unmarked).  The set follows cvtmi_hnsw_mask_labels: unsorted,
+ *            duplicates and foreign labels are fine, labels compare as 64-bit patterns, nodes sharing a label all change.  `changed`
+ *            (may be NULL; host memory in both forms) receives the number of nodes whose state actually changed: marking a marked
+ *            node changes nothing.  n_labels == 0 does nothing.
+ *   Search   with at least one deleted node, EVERY search entry of the handle runs the masked kernel under "not deleted" (the unmasked
+ *            entries) or "allowed and not deleted" (the _masked entries; the caller's mask is only read), with the scratch plan of a
+ *            masked search -- a candidate queue of ntotal entries per traversal, see cvtmi_hnsw_search_masked -- and
+ *            cvtmi_hnsw_last_masked reports it.  The result is, bit for bit, that of the _masked entry on the unmarked graph under that
+ *            mask.  With no deleted node (none marked yet, or all unmarked again) the handle answers through the unmasked kernels.
+ *   Add      cvtmi_hnsw_add on a handle with deleted nodes: the greedy descent walks deleted nodes like live ones; on a level every
+ *            accepted neighbour is traversed and only live ones enter the result queue, the walk stops on "nearest candidate farther
+ *            than the worst result" only on a full result queue, and a deleted entry point is pushed into each level's result queue
+ *            after the walk (hnswlib's addPoint).  Selection and back links are unchanged.
+ *   File     cvtmi_hnsw_save writes hnswlib's mark: bit 16 of the node's level-0 count word (DELETE_MARK 0x01 in byte 2, the count in
+ *            the low 16 bits); cvtmi_hnsw_load reads it, and refuses a count word with any higher bit.  A graph without deleted nodes
+ *            writes and reads the bytes it always did.
+ *   Calling  mark / unmark are mutating and exclusive, like cvtmi_hnsw_add.  NULL h, n_labels < 0, NULL labels with n_labels > 0 ->
+ *            CVTMI_EINVAL before any device work, the handle stays usable.  The _dev forms take a device label set (it comes down to
+ *            be sorted, as in cvtmi_hnsw_mask_labels_dev) and run on `stream`; they return when the state has changed.
+ * cvtmi_hnsw_deleted_count: the deleted nodes.  cvtmi_hnsw_get_deleted: the bitmap into mask[mask_words], bit i & 63 of word i >> 6 =
+ * node i is deleted, every bit at a position >= ntotal zero; mask_words >= ceil(ntotal / 64), else CVTMI_EINVAL (the checks of
+ * cvtmi_hnsw_mask_labels); the _dev form writes device memory on `stream`.
+ * Not here: reusing a deleted node's slot (hnswlib's replace_deleted / updatePoint), compacting the graph, sharded forms. */
+int cvtmi_hnsw_mark_deleted(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, int64_t *changed);
+int cvtmi_hnsw_mark_deleted_dev(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, int64_t *changed, void *stream);
+int cvtmi_hnsw_unmark_deleted(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, int64_t *changed);
+int cvtmi_hnsw_unmark_deleted_dev(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labels, int64_t *changed, void *stream);
+int cvtmi_hnsw_deleted_count(cvtmi_hnsw_t h, int64_t *count);
+int cvtmi_hnsw_get_deleted(cvtmi_hnsw_t h, uint64_t *mask, int64_t mask_words);
+int cvtmi_hnsw_get_deleted_dev(cvtmi_hnsw_t h, uint64_t *mask, int64_t mask_words, void *stream);
 
 #ifdef __cplusplus
 }
