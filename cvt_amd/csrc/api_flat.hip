@@ -201,36 +201,14 @@ static int flat_remove_check(cvtmi_flat_t h, const int64_t *labels, int64_t n_la
     return CVTMI_OK;
 }
 
-// the distinct labels of the set, ascending
-static int flat_remove_table(const int64_t *labels, int64_t n_labels, std::vector<int64_t> &tab)
-{
-    try {
-        tab.assign(labels, labels + n_labels);
-    } catch (...) {
-        return fail(CVTMI_ENOMEM, "cvtmi_flat_remove_labels: out of host memory");
-    }
-    std::sort(tab.begin(), tab.end());
-    tab.erase(std::unique(tab.begin(), tab.end()), tab.end());
-    return CVTMI_OK;
-}
-
 int cvtmi_flat_remove_labels_dev(cvtmi_flat_t h, const int64_t *labels, int64_t n_labels, int64_t *removed, int64_t *remap, void *stream)
 {
     CVTMI_TRY(flat_remove_check(h, labels, n_labels));
     CHECK_H(h);
     hipStream_t st = (hipStream_t)stream;
     FlatMutation mut(h, st);
-    std::vector<int64_t> raw, tab;
-    if (!h->identity && n_labels > 0 && h->n > 0) {   // explicit labels: the set is sorted on the host, it comes down first (8 bytes per label)
-        try {
-            raw.resize((size_t)n_labels);
-        } catch (...) {
-            return fail(CVTMI_ENOMEM, "cvtmi_flat_remove_labels: out of host memory");
-        }
-        CVTMI_HIP(hipMemcpyAsync(raw.data(), labels, (size_t)n_labels * 8, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(stream_wait(st));
-        CVTMI_TRY(flat_remove_table(raw.data(), n_labels, tab));
-    }
+    std::vector<int64_t> tab;   // explicit labels: the table of the set
+    if (!h->identity && n_labels > 0 && h->n > 0) CVTMI_TRY(sorted_unique_dev("cvtmi_flat_remove_labels", labels, n_labels, tab, st));
     return flat_remove_common(h, labels, n_labels, tab.data(), (int64_t)tab.size(), removed, remap, st);
 }
 
@@ -244,7 +222,7 @@ int cvtmi_flat_remove_labels(cvtmi_flat_t h, const int64_t *labels, int64_t n_la
     Tmp ds, dm;
     if (n_labels > 0 && n0 > 0) {
         if (h->identity) CVTMI_TRY(ds.upload(labels, (size_t)n_labels * sizeof(int64_t)));
-        else CVTMI_TRY(flat_remove_table(labels, n_labels, tab));
+        else CVTMI_TRY(sorted_unique("cvtmi_flat_remove_labels", labels, n_labels, tab));
     }
     if (remap && n0 > 0) CVTMI_TRY(dm.alloc((size_t)n0 * sizeof(int64_t)));
     CVTMI_TRY(flat_remove_common(h, ds.as<int64_t>(), ds.p ? n_labels : 0, tab.data(), (int64_t)tab.size(), removed, dm.as<int64_t>(), nullptr));
@@ -918,8 +896,7 @@ int cvtmi_flat_range_search(cvtmi_flat_t h, const void *q, int64_t nq, double ra
 int cvtmi_flat_last_range_plan(cvtmi_flat_t h, int64_t out[6])
 {
     if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_flat_last_range_plan: null");
-    std::lock_guard<std::mutex> g(h->pool.mu);
-    for (int i = 0; i < 6; ++i) out[i] = h->range_last[i];
+    copy_last(h->pool, h->range_last, out);
     return CVTMI_OK;
 }
 
@@ -1126,27 +1103,16 @@ int cvtmi_flat_rerank(cvtmi_flat_t h, const void *q, int64_t nq, const int64_t *
     std::shared_lock<std::shared_timed_mutex> rd(h->rw);
     FlatLease lease;
     CVTMI_TRY(lease.open(h, nullptr, true));
-    FlatScratch &S = *lease.s;
-    hipStream_t st = lease.st;
-    const size_t qb = (size_t)nq * h->row_bytes, cb = (size_t)nq * R * sizeof(int64_t), db = (size_t)nq * k * 4, ib = (size_t)nq * k * sizeof(int64_t);
-    CVTMI_TRY(S.io_q.reserve(qb));
-    CVTMI_TRY(S.io_c.reserve(cb));
-    CVTMI_TRY(S.io_d.reserve(db));
-    CVTMI_TRY(S.io_i.reserve(ib));
-    CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
-    CVTMI_HIP(hipMemcpyAsync(S.io_c.p, cand, cb, hipMemcpyHostToDevice, st));
-    CVTMI_TRY(flat_rerank_leased(h, S.io_q.p, nq, S.io_c.as<int64_t>(), R, cand_base, false, k, S.io_d.p, S.io_i.as<int64_t>(), st));
-    CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(hipMemcpyAsync(labels, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(stream_wait(st));
-    return CVTMI_OK;
+    return host_call(lease, q, (size_t)nq * h->row_bytes, HostUpload{ &lease.s->io_c, cand, (size_t)nq * R * sizeof(int64_t) }, dist, (size_t)nq * k * 4, labels,
+                     (size_t)nq * k * sizeof(int64_t), [&](FlatScratch &, const void *dq, const void *dc, void *dd, int64_t *dl, hipStream_t st) {
+                         return flat_rerank_leased(h, dq, nq, static_cast<const int64_t *>(dc), R, cand_base, false, k, dd, dl, st);
+                     });
 }
 
 int cvtmi_flat_last_rerank(cvtmi_flat_t h, int64_t out[4])
 {
     if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_flat_last_rerank: null");
-    std::lock_guard<std::mutex> g(h->pool.mu);
-    for (int i = 0; i < 4; ++i) out[i] = h->rerank_last[i];
+    copy_last(h->pool, h->rerank_last, out);
     return CVTMI_OK;
 }
 
@@ -1228,20 +1194,24 @@ static int flat_mask_labels_leased(cvtmi_flat_t h, FlatScratch &S, const int64_t
         CVTMI_HIP(hipMemsetAsync(mask, 0, (size_t)mask_words * 8, st));
         return CVTMI_OK;
     }
-    FlatRmPlan p;   // the mark's areas alone: no row moves, so no chunk scratch
-    p.rm = rm_plan(h->n, 0, 0, 0);
-    p.T = h->identity ? 0 : T;
+    if (!h->identity) return labels_to_mask(S.s_masked, h->labels.as<int64_t>(), h->n, table, T, mask, mask_words, st);
+    const RmPlan p = rm_plan(h->n, 0, 0, 0);   // the mark's areas alone: no row moves, so no chunk scratch
+    CVTMI_TRY(S.s_masked.reserve(p.off_table + rm_align(8)));
+    CVTMI_TRY(launch_rm_mark_ids(p, S.s_masked.p, set_dev, n_set, h->id_base, st));
+    return launch_flat_masked_copy(p, S.s_masked.p, mask, mask_words, st);
+}
+
+int cvtmi::labels_to_mask(DevBuf &W, const int64_t *labels_dev, int64_t n, const int64_t *table, int64_t T, uint64_t *mask, int64_t mask_words, hipStream_t st)
+{
+    FlatRmPlan p;   // the mark's areas and the table alone: nothing moves
+    p.rm = rm_plan(n, 0, 0, 0);
+    p.T = T;
     p.off_table = p.rm.off_table;
-    p.bytes = p.off_table + rm_align((size_t)std::max<int64_t>(p.T, 1) * 8);
-    CVTMI_TRY(S.s_masked.reserve(p.bytes));
-    void *W = S.s_masked.p;
-    if (h->identity) {
-        CVTMI_TRY(launch_rm_mark_ids(p.rm, W, set_dev, n_set, h->id_base, st));
-    } else {
-        CVTMI_HIP(hipMemcpyAsync(static_cast<char *>(W) + p.off_table, table, (size_t)T * 8, hipMemcpyHostToDevice, st));
-        CVTMI_TRY(launch_flat_rm_mark_labels(p, W, h->labels.as<int64_t>(), st));
-    }
-    return launch_flat_masked_copy(p.rm, W, mask, mask_words, st);
+    p.bytes = p.off_table + rm_align((size_t)T * 8);
+    CVTMI_TRY(W.reserve(p.bytes));
+    CVTMI_HIP(hipMemcpyAsync(rm_at<char>(W.p, p.off_table), table, (size_t)T * 8, hipMemcpyHostToDevice, st));
+    CVTMI_TRY(launch_flat_rm_mark_labels(p, W.p, labels_dev, st));
+    return launch_flat_masked_copy(p.rm, W.p, mask, mask_words, st);
 }
 
 extern "C" {
@@ -1275,27 +1245,17 @@ int cvtmi_flat_search_masked(cvtmi_flat_t h, const void *q, int64_t nq, int k, c
     }
     FlatLease lease;
     CVTMI_TRY(lease.open(h, nullptr, true));
-    FlatScratch &S = *lease.s;
-    hipStream_t st = lease.st;
-    const size_t qb = (size_t)nq * h->row_bytes, mb = (size_t)((h->n + 63) / 64) * 8, db = (size_t)nq * k * 4, ib = (size_t)nq * k * sizeof(int64_t);
-    CVTMI_TRY(S.io_q.reserve(qb));
-    CVTMI_TRY(S.io_m.reserve(mb));
-    CVTMI_TRY(S.io_d.reserve(db));
-    CVTMI_TRY(S.io_i.reserve(ib));
-    CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
-    CVTMI_HIP(hipMemcpyAsync(S.io_m.p, mask, mb, hipMemcpyHostToDevice, st));   // (the words behind the rows are never read)
-    CVTMI_TRY(flat_masked_leased(h, S, S.io_q.p, nq, k, S.io_m.as<uint64_t>(), S.io_d.p, S.io_i.as<int64_t>(), st));
-    CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(hipMemcpyAsync(labels, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(stream_wait(st));
-    return CVTMI_OK;
+    const HostUpload words{ &lease.s->io_m, mask, (size_t)((h->n + 63) / 64) * 8 };   // (the words behind the rows are never read)
+    return host_call(lease, q, (size_t)nq * h->row_bytes, words, dist, (size_t)nq * k * 4, labels, (size_t)nq * k * sizeof(int64_t),
+                     [&](FlatScratch &S, const void *dq, const void *dm, void *dd, int64_t *dl, hipStream_t st) {
+                         return flat_masked_leased(h, S, dq, nq, k, static_cast<const uint64_t *>(dm), dd, dl, st);
+                     });
 }
 
 int cvtmi_flat_last_masked(cvtmi_flat_t h, int64_t out[4])
 {
     if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_flat_last_masked: null");
-    std::lock_guard<std::mutex> g(h->pool.mu);
-    for (int i = 0; i < 4; ++i) out[i] = h->masked_last[i];
+    copy_last(h->pool, h->masked_last, out);
     return CVTMI_OK;
 }
 
@@ -1308,17 +1268,8 @@ int cvtmi_flat_mask_labels_dev(cvtmi_flat_t h, const int64_t *labels, int64_t n_
     CVTMI_TRY(flat_mask_covers(h, mask_words, "cvtmi_flat_mask_labels"));
     FlatLease lease;
     CVTMI_TRY(lease.open(h, st, false));
-    std::vector<int64_t> raw, tab;
-    if (!h->identity && n_labels > 0 && h->n > 0 && mask_words > 0) {   // explicit labels: the set is sorted on the host, it comes down first (8 bytes per label)
-        try {
-            raw.resize((size_t)n_labels);
-        } catch (...) {
-            return fail(CVTMI_ENOMEM, "cvtmi_flat_mask_labels: out of host memory");
-        }
-        CVTMI_HIP(hipMemcpyAsync(raw.data(), labels, (size_t)n_labels * 8, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(stream_wait(st));
-        CVTMI_TRY(flat_remove_table(raw.data(), n_labels, tab));
-    }
+    std::vector<int64_t> tab;   // explicit labels: the table of the set
+    if (!h->identity && n_labels > 0 && h->n > 0 && mask_words > 0) CVTMI_TRY(sorted_unique_dev("cvtmi_flat_mask_labels", labels, n_labels, tab, st));
     CVTMI_TRY(flat_mask_labels_leased(h, *lease.s, labels, n_labels, tab.data(), (int64_t)tab.size(), mask, mask_words, st));
     if (!tab.empty()) CVTMI_HIP(stream_wait(st));   // (the table leaves host memory that ends with this call)
     return CVTMI_OK;
@@ -1339,21 +1290,17 @@ int cvtmi_flat_mask_labels(cvtmi_flat_t h, const int64_t *labels, int64_t n_labe
     CVTMI_TRY(lease.open(h, nullptr, true));
     FlatScratch &S = *lease.s;
     hipStream_t st = lease.st;
-    // only the words that can hold a row pass through the device; the caller's words behind them are cleared here
-    const int64_t words = (h->n + 63) / 64;
+    const int64_t words = (h->n + 63) / 64;   // (the words that can hold a row)
     std::vector<int64_t> tab;
     if (h->identity) {
         CVTMI_TRY(S.io_c.reserve((size_t)n_labels * 8));
         CVTMI_HIP(hipMemcpyAsync(S.io_c.p, labels, (size_t)n_labels * 8, hipMemcpyHostToDevice, st));
     } else {
-        CVTMI_TRY(flat_remove_table(labels, n_labels, tab));
+        CVTMI_TRY(sorted_unique("cvtmi_flat_mask_labels", labels, n_labels, tab));
     }
     CVTMI_TRY(S.io_m.reserve((size_t)words * 8));
     CVTMI_TRY(flat_mask_labels_leased(h, S, S.io_c.as<int64_t>(), n_labels, tab.data(), (int64_t)tab.size(), S.io_m.as<uint64_t>(), words, st));
-    CVTMI_HIP(hipMemcpyAsync(mask, S.io_m.p, (size_t)words * 8, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(stream_wait(st));
-    memset(mask + words, 0, (size_t)(mask_words - words) * 8);
-    return CVTMI_OK;
+    return mask_host_finish(S.io_m, words, mask, mask_words, st);
 }
 
 }  // extern "C"

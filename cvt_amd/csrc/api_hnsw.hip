@@ -545,23 +545,14 @@ int cvtmi_hnsw_search_dev(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int
     return hnsw_search_leased(h, *lease.s, q, nq, k, ef, dist, labels, lease.st);
 }
 
-// host pointers in and out: staged through the leased set's own buffers, on its own stream
-template <typename F> static int hnsw_host_call(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, float *dist, int64_t *labels, F &&run)
+// The host-pointer entries: queries in and [nq][k] distances and labels out, staged through the leased set's own buffers on its own
+// stream (host_call); masked: with the mask words that can hold a node beside the queries (the caller's words behind them are never read)
+template <typename F> static int hnsw_host_search(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, const uint64_t *mask, float *dist, int64_t *labels, F &&run)
 {
     HnswLease lease;
     CVTMI_TRY(lease.open(h, nullptr, true));
-    HnswScratch &S = *lease.s;
-    hipStream_t st = lease.st;
-    const size_t qb = (size_t)nq * h->D * sizeof(float), db = (size_t)nq * k * 4, lb = (size_t)nq * k * 8;
-    CVTMI_TRY(S.io_q.reserve(qb));
-    CVTMI_TRY(S.io_d.reserve(db));
-    CVTMI_TRY(S.io_l.reserve(lb));
-    CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
-    CVTMI_TRY(run(S, S.io_q.as<float>(), S.io_d.as<float>(), S.io_l.as<int64_t>(), st));
-    CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(hipMemcpyAsync(labels, S.io_l.p, lb, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(stream_wait(st));
-    return CVTMI_OK;
+    const HostUpload words = mask ? HostUpload{ &lease.s->io_m, mask, (size_t)((h->g.n + 63) / 64) * 8 } : HostUpload{};
+    return host_call(lease, q, (size_t)nq * h->D * sizeof(float), words, dist, (size_t)nq * k * 4, labels, (size_t)nq * k * 8, run);
 }
 
 int cvtmi_hnsw_search(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int ef, float *dist, int64_t *labels)
@@ -569,7 +560,7 @@ int cvtmi_hnsw_search(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, int ef,
     CHECK_HN(h);
     CVTMI_TRY(hnsw_search_args(h, "cvtmi_hnsw_search", q, nq, k, ef, dist, labels));
     if (nq == 0) return CVTMI_OK;
-    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
+    return hnsw_host_search(h, q, nq, k, nullptr, dist, labels, [&](HnswScratch &S, const float *dq, const void *, float *dd, int64_t *dl, hipStream_t st) {
         return hnsw_search_leased(h, S, dq, nq, k, ef, dd, dl, st);
     });
 }
@@ -593,12 +584,8 @@ static int hnsw_search_adc_leased(cvtmi_hnsw_t h, HnswScratch &S, cvtmi_opq_t op
     OpqLease ol;
     CVTMI_TRY(ol.open(opq, st, false));
     OpqScratch &OS = *ol.s;
-    const float *q_rot = q;
-    if (rotate && (opq->m.perm || opq->m.R)) {
-        CVTMI_TRY(OS.s_qrot.reserve((size_t)nq * opq->m.D * sizeof(float)));
-        CVTMI_TRY(opq_rotate_impl(opq, q, nq, OS.s_qrot.as<float>(), st));
-        q_rot = OS.s_qrot.as<float>();
-    }
+    const float *q_rot = nullptr;
+    CVTMI_TRY(opq_rotate_probe(opq, OS, q, nq, rotate, 0, st, &q_rot));
     CVTMI_TRY(OS.s_lut.reserve((size_t)nq * opq->m.M * opq->m.K * sizeof(float)));
     CVTMI_TRY(launch_lut(opq->m, q_rot, nq, nullptr, OS.s_lut.as<float>(), st));
     CVTMI_TRY(hnsw_live_mask(h, S, mask, st));
@@ -652,7 +639,7 @@ int cvtmi_hnsw_search_adc_rerank(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q
     CHECK_HN(h);
     if (nq < 0 || k < 1 || (nq > 0 && (!q || !dist || !labels))) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc_rerank: bad arguments");
     if (nq == 0) return CVTMI_OK;
-    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
+    return hnsw_host_search(h, q, nq, k, nullptr, dist, labels, [&](HnswScratch &S, const float *dq, const void *, float *dd, int64_t *dl, hipStream_t st) {
         return hnsw_search_adc_rerank_leased(h, S, opq, dq, nq, rotate, k, ef, rerank, dd, dl, st);
     });
 }
@@ -663,7 +650,7 @@ int cvtmi_hnsw_search_adc(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q, int64
     CHECK_HN(h);
     if (nq < 0 || k < 1 || (nq > 0 && (!q || !dist || !labels))) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc: bad arguments");
     if (nq == 0) return CVTMI_OK;
-    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
+    return hnsw_host_search(h, q, nq, k, nullptr, dist, labels, [&](HnswScratch &S, const float *dq, const void *, float *dd, int64_t *dl, hipStream_t st) {
         return hnsw_search_adc_leased(h, S, opq, dq, nq, rotate, k, ef, dd, dl, st, 0);
     });
 }
@@ -680,14 +667,6 @@ static int hnsw_mask_args(cvtmi_hnsw_t h, const char *who, const void *q, int64_
     if (mask_words < (h->g.n + 63) / 64)
         return fail(CVTMI_EINVAL, "%s: %lld mask words for %lld nodes (%lld needed)", who, (long long)mask_words, (long long)h->g.n,
                     (long long)((h->g.n + 63) / 64));
-    return CVTMI_OK;
-}
-// the words that can hold a node, on the device (the caller's words behind them are never read)
-static int hnsw_stage_mask(cvtmi_hnsw_t h, HnswScratch &S, const uint64_t *mask, hipStream_t st)
-{
-    const size_t mb = (size_t)((h->g.n + 63) / 64) * 8;
-    CVTMI_TRY(S.io_m.reserve(mb ? mb : 16));
-    if (mb) CVTMI_HIP(hipMemcpyAsync(S.io_m.p, mask, mb, hipMemcpyHostToDevice, st));
     return CVTMI_OK;
 }
 
@@ -712,9 +691,8 @@ int cvtmi_hnsw_search_masked(cvtmi_hnsw_t h, const float *q, int64_t nq, int k, 
     CVTMI_TRY(hnsw_mask_args(h, "cvtmi_hnsw_search_masked", q, nq, mask, mask_words, dist, labels));
     CVTMI_TRY(hnsw_search_args(h, "cvtmi_hnsw_search_masked", q, nq, k, ef, dist, labels));
     if (nq == 0) return CVTMI_OK;
-    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
-        CVTMI_TRY(hnsw_stage_mask(h, S, mask, st));
-        return hnsw_search_leased(h, S, dq, nq, k, ef, dd, dl, st, S.io_m.as<uint64_t>());
+    return hnsw_host_search(h, q, nq, k, mask, dist, labels, [&](HnswScratch &S, const float *dq, const void *dm, float *dd, int64_t *dl, hipStream_t st) {
+        return hnsw_search_leased(h, S, dq, nq, k, ef, dd, dl, st, static_cast<const uint64_t *>(dm));
     });
 }
 
@@ -736,9 +714,8 @@ int cvtmi_hnsw_search_adc_masked(cvtmi_hnsw_t h, cvtmi_opq_t opq, const float *q
     CVTMI_TRY(hnsw_mask_args(h, "cvtmi_hnsw_search_adc_masked", q, nq, mask, mask_words, dist, labels));
     if (k < 1) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc_masked: bad arguments");   // as cvtmi_hnsw_search_adc answers it
     if (nq == 0) return CVTMI_OK;
-    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
-        CVTMI_TRY(hnsw_stage_mask(h, S, mask, st));
-        return hnsw_search_adc_leased(h, S, opq, dq, nq, rotate, k, ef, dd, dl, st, 0, S.io_m.as<uint64_t>());
+    return hnsw_host_search(h, q, nq, k, mask, dist, labels, [&](HnswScratch &S, const float *dq, const void *dm, float *dd, int64_t *dl, hipStream_t st) {
+        return hnsw_search_adc_leased(h, S, opq, dq, nq, rotate, k, ef, dd, dl, st, 0, static_cast<const uint64_t *>(dm));
     });
 }
 
@@ -760,9 +737,8 @@ int cvtmi_hnsw_search_adc_rerank_masked(cvtmi_hnsw_t h, cvtmi_opq_t opq, const f
     CVTMI_TRY(hnsw_mask_args(h, "cvtmi_hnsw_search_adc_rerank_masked", q, nq, mask, mask_words, dist, labels));
     if (k < 1) return fail(CVTMI_EINVAL, "cvtmi_hnsw_search_adc_rerank_masked: bad arguments");   // as cvtmi_hnsw_search_adc_rerank answers it
     if (nq == 0) return CVTMI_OK;
-    return hnsw_host_call(h, q, nq, k, dist, labels, [&](HnswScratch &S, const float *dq, float *dd, int64_t *dl, hipStream_t st) {
-        CVTMI_TRY(hnsw_stage_mask(h, S, mask, st));
-        return hnsw_search_adc_rerank_leased(h, S, opq, dq, nq, rotate, k, ef, rerank, dd, dl, st, S.io_m.as<uint64_t>());
+    return hnsw_host_search(h, q, nq, k, mask, dist, labels, [&](HnswScratch &S, const float *dq, const void *dm, float *dd, int64_t *dl, hipStream_t st) {
+        return hnsw_search_adc_rerank_leased(h, S, opq, dq, nq, rotate, k, ef, rerank, dd, dl, st, static_cast<const uint64_t *>(dm));
     });
 }
 
@@ -771,8 +747,7 @@ int cvtmi_hnsw_last_masked(cvtmi_hnsw_t h, int64_t out[4])
     if (!h) return fail(CVTMI_EINVAL, "cvtmi_hnsw_last_masked: null handle");
     if (!out || h->magic != 0x484e5357u) return fail(CVTMI_EINVAL, "cvtmi_hnsw_last_masked: bad arguments");
     if (h->broken) return fail(CVTMI_EINVAL, "cvtmi_hnsw_last_masked: the handle is broken (a cvtmi_hnsw_add failed part-way)");
-    std::lock_guard<std::mutex> g(h->pool.mu);
-    for (int i = 0; i < 4; ++i) out[i] = h->masked_last[i];
+    copy_last(h->pool, h->masked_last, out);
     return CVTMI_OK;
 }
 
@@ -787,32 +762,8 @@ static int hnsw_mask_labels_check(cvtmi_hnsw_t h, const int64_t *labels, int64_t
                     (long long)((h->g.n + 63) / 64));
     return CVTMI_OK;
 }
-// the distinct labels of the set, ascending as int64 (the order the mark's lower bound walks)
-static int hnsw_label_table(const int64_t *labels, int64_t n_labels, std::vector<int64_t> &tab)
-{
-    try {
-        tab.assign(labels, labels + n_labels);
-    } catch (...) {
-        return fail(CVTMI_ENOMEM, "cvtmi_hnsw_mask_labels: out of host memory");
-    }
-    std::sort(tab.begin(), tab.end());
-    tab.erase(std::unique(tab.begin(), tab.end()), tab.end());
-    return CVTMI_OK;
-}
-// table: T > 0 distinct labels in host memory; mask: device pointer of mask_words > 0 words; h->g.n > 0
-static int hnsw_mask_labels_leased(cvtmi_hnsw_t h, HnswScratch &S, const int64_t *table, int64_t T, uint64_t *mask, int64_t mask_words, hipStream_t st)
-{
-    FlatRmPlan p;   // the mark's areas alone: nothing moves
-    p.rm = rm_plan(h->g.n, 0, 0, 0);
-    p.T = T;
-    p.off_table = p.rm.off_table;
-    p.bytes = p.off_table + rm_align((size_t)T * 8);
-    CVTMI_TRY(S.s_mark.reserve(p.bytes));
-    void *W = S.s_mark.p;
-    CVTMI_HIP(hipMemcpyAsync(static_cast<char *>(W) + p.off_table, table, (size_t)T * 8, hipMemcpyHostToDevice, st));
-    CVTMI_TRY(launch_flat_rm_mark_labels(p, W, h->g.labels, st));
-    return launch_flat_masked_copy(p.rm, W, mask, mask_words, st);
-}
+// (the table of the set -- sorted_unique: its distinct labels, ascending as int64, the order the mark's lower bound walks -- goes through
+//  labels_to_mask on the leased set's s_mark)
 
 extern "C" {
 
@@ -828,16 +779,9 @@ int cvtmi_hnsw_mask_labels_dev(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_
         CVTMI_HIP(hipMemsetAsync(mask, 0, (size_t)mask_words * 8, st));
         return CVTMI_OK;
     }
-    std::vector<int64_t> raw, tab;   // the set is sorted on the host: it comes down first (8 bytes per label)
-    try {
-        raw.resize((size_t)n_labels);
-    } catch (...) {
-        return fail(CVTMI_ENOMEM, "cvtmi_hnsw_mask_labels: out of host memory");
-    }
-    CVTMI_HIP(hipMemcpyAsync(raw.data(), labels, (size_t)n_labels * 8, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(stream_wait(st));
-    CVTMI_TRY(hnsw_label_table(raw.data(), n_labels, tab));
-    CVTMI_TRY(hnsw_mask_labels_leased(h, *lease.s, tab.data(), (int64_t)tab.size(), mask, mask_words, st));
+    std::vector<int64_t> tab;
+    CVTMI_TRY(sorted_unique_dev("cvtmi_hnsw_mask_labels", labels, n_labels, tab, st));
+    CVTMI_TRY(labels_to_mask(lease.s->s_mark, h->g.labels, h->g.n, tab.data(), (int64_t)tab.size(), mask, mask_words, st));
     CVTMI_HIP(stream_wait(st));   // (the table leaves host memory that ends with this call)
     return CVTMI_OK;
 }
@@ -852,19 +796,15 @@ int cvtmi_hnsw_mask_labels(cvtmi_hnsw_t h, const int64_t *labels, int64_t n_labe
         return CVTMI_OK;
     }
     std::vector<int64_t> tab;
-    CVTMI_TRY(hnsw_label_table(labels, n_labels, tab));
+    CVTMI_TRY(sorted_unique("cvtmi_hnsw_mask_labels", labels, n_labels, tab));
     HnswLease lease;
     CVTMI_TRY(lease.open(h, nullptr, true));
     HnswScratch &S = *lease.s;
     hipStream_t st = lease.st;
-    // only the words that can hold a node pass through the device; the caller's words behind them are cleared here
-    const int64_t words = (h->g.n + 63) / 64;
+    const int64_t words = (h->g.n + 63) / 64;   // (the words that can hold a node)
     CVTMI_TRY(S.io_m.reserve((size_t)words * 8));
-    CVTMI_TRY(hnsw_mask_labels_leased(h, S, tab.data(), (int64_t)tab.size(), S.io_m.as<uint64_t>(), words, st));
-    CVTMI_HIP(hipMemcpyAsync(mask, S.io_m.p, (size_t)words * 8, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(stream_wait(st));
-    memset(mask + words, 0, (size_t)(mask_words - words) * 8);
-    return CVTMI_OK;
+    CVTMI_TRY(labels_to_mask(S.s_mark, h->g.labels, h->g.n, tab.data(), (int64_t)tab.size(), S.io_m.as<uint64_t>(), words, st));
+    return mask_host_finish(S.io_m, words, mask, mask_words, st);
 }
 
 }  // extern "C"
@@ -888,18 +828,9 @@ static int hnsw_set_deleted(cvtmi_hnsw_t h, const char *who, const int64_t *labe
     CVTMI_TRY(lease.open(h, stream, !dev));
     HnswScratch &S = *lease.s;
     hipStream_t st = lease.st;
-    std::vector<int64_t> raw, tab;
-    if (dev) {
-        try {
-            raw.resize((size_t)n_labels);
-        } catch (...) {
-            return fail(CVTMI_ENOMEM, "%s: out of host memory", who);
-        }
-        CVTMI_HIP(hipMemcpyAsync(raw.data(), labels, (size_t)n_labels * 8, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(stream_wait(st));
-        labels = raw.data();
-    }
-    CVTMI_TRY(hnsw_label_table(labels, n_labels, tab));
+    std::vector<int64_t> tab;
+    if (dev) CVTMI_TRY(sorted_unique_dev(who, labels, n_labels, tab, st));
+    else CVTMI_TRY(sorted_unique(who, labels, n_labels, tab));
     FlatRmPlan p;   // the mark's areas, the table, and one word behind it for the count of flipped bits
     p.rm = rm_plan(h->g.n, 0, 0, 0);
     p.T = (int64_t)tab.size();

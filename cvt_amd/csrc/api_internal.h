@@ -1,7 +1,11 @@
 // api_internal.h -- what the files of the C-ABI glue share (api.hip: library level, api_opq.hip, api_flat.hip, api_models.hip,
-// api_hnsw.hip): the scratch pool of a handle with its lease and its mutation ordering, the handle structs, and the few helpers
-// that cross a file.  Everything a single file uses stays static in that file.
+// api_hnsw.hip): the scratch pool of a handle with its lease and its mutation ordering, the staging of a host-pointer entry through
+// a leased set (host_call), the set-to-bitmap glue of the mask_* / remove_* / mark_deleted entries (sorted_unique, labels_to_mask,
+// mask_host_finish), the handle structs, and the few helpers that cross a file.  Everything a single file uses stays static in that file.
 #pragma once
+#include <string.h>
+
+#include <algorithm>
 #include <functional>
 #include <new>
 #include <random>
@@ -11,6 +15,9 @@
 #include "host_util.h"
 #include "kernels.h"
 #include "shard.h"
+
+// a helper of the glue alone: shared between its files, kept out of the library's symbol table (the exports are the C ABI's business)
+#define CVTMI_INTERNAL __attribute__((visibility("hidden")))
 
 namespace cvtmi {
 
@@ -23,8 +30,11 @@ struct ScratchBase {
     hipEvent_t done = nullptr;
     hipStream_t last = nullptr;
     bool pending = false, busy = false;
-    void release_lease_state()
+    // staging of the host-pointer entries, on `own`: the queries, the two result arrays, the mask words (or the label set) -- see host_call
+    DevBuf io_q, io_d, io_i, io_m;
+    CVTMI_INTERNAL void release_lease_state()
     {
+        for (DevBuf *b : { &io_q, &io_d, &io_i, &io_m }) b->release();
         if (own) (void)hipStreamDestroy(own);
         if (done) (void)hipEventDestroy(done);
         own = nullptr; done = nullptr;
@@ -112,6 +122,79 @@ template <class S> struct Lease {
     Lease &operator=(const Lease &) = delete;
 };
 
+// The second upload of a host-pointer entry beside its queries (mask words, candidate lists): `bytes` from `src` into `to`, a buffer
+// of the leased set.  An empty one still reserves 16 bytes -- the pointer selects the masked kernels -- and copies nothing.
+struct HostUpload {
+    DevBuf *to = nullptr;
+    const void *src = nullptr;
+    size_t bytes = 0;
+};
+
+// A host-pointer entry on an opened host lease (OPQ and flat entries check the mask length under the shared lock before they lease):
+// queries, and `extra` where there is one, up through the set's staging buffers; run(S, q_dev, extra_dev, d_dev, i_dev, st) on the
+// set's own stream; the result arrays (ib == 0: there is one) down; one wait -- the caller's arrays are complete when this returns.
+template <class L, class Q, class D, class F>
+CVTMI_INTERNAL int host_call(L &lease, const Q *q, size_t qb, HostUpload extra, D *out_d, size_t db, int64_t *out_i, size_t ib, F &&run)
+{
+    auto &S = *lease.s;
+    hipStream_t st = lease.st;
+    CVTMI_TRY(S.io_q.reserve(qb));
+    if (extra.to) CVTMI_TRY(extra.to->reserve(std::max<size_t>(extra.bytes, 16)));
+    CVTMI_TRY(S.io_d.reserve(db));
+    if (ib) CVTMI_TRY(S.io_i.reserve(ib));
+    CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
+    if (extra.bytes) CVTMI_HIP(hipMemcpyAsync(extra.to->p, extra.src, extra.bytes, hipMemcpyHostToDevice, st));
+    const void *extra_dev = extra.to ? extra.to->p : nullptr;
+    CVTMI_TRY(run(S, static_cast<const Q *>(S.io_q.p), extra_dev, static_cast<D *>(S.io_d.p), S.io_i.template as<int64_t>(), st));
+    CVTMI_HIP(hipMemcpyAsync(out_d, S.io_d.p, db, hipMemcpyDeviceToHost, st));
+    if (ib) CVTMI_HIP(hipMemcpyAsync(out_i, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    return CVTMI_OK;
+}
+
+// the distinct values of a set in host memory, ascending: the table the mark kernels search (mask_*, remove_*, mark_deleted)
+template <class T> CVTMI_INTERNAL int sorted_unique(const char *who, const T *set, int64_t n, std::vector<T> &tab)
+{
+    try {
+        tab.assign(set, set + n);
+    } catch (...) {
+        return fail(CVTMI_ENOMEM, "%s: out of host memory", who);
+    }
+    std::sort(tab.begin(), tab.end());
+    tab.erase(std::unique(tab.begin(), tab.end()), tab.end());
+    return CVTMI_OK;
+}
+// ... of a set on the device: it is sorted on the host, so it comes down first (sizeof(T) bytes per value, one wait on st)
+template <class T> CVTMI_INTERNAL int sorted_unique_dev(const char *who, const T *set_dev, int64_t n, std::vector<T> &tab, hipStream_t st)
+{
+    std::vector<T> raw;
+    try {
+        raw.resize((size_t)n);
+    } catch (...) {
+        return fail(CVTMI_ENOMEM, "%s: out of host memory", who);
+    }
+    CVTMI_HIP(hipMemcpyAsync(raw.data(), set_dev, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    return sorted_unique(who, raw.data(), n, tab);
+}
+
+// The end of a host-pointer mask_* entry.  Only the `words` words that can hold a row pass through the device (io_m): they come down,
+// the call waits, and the caller's words behind them are cleared here.
+CVTMI_INTERNAL inline int mask_host_finish(const DevBuf &io_m, int64_t words, uint64_t *mask, int64_t mask_words, hipStream_t st)
+{
+    CVTMI_HIP(hipMemcpyAsync(mask, io_m.p, (size_t)words * 8, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    memset(mask + words, 0, (size_t)(mask_words - words) * 8);
+    return CVTMI_OK;
+}
+
+// a cvtmi_*_last_* getter: the small array a search left on its handle, copied under the lock it was written under
+template <class P, int N> CVTMI_INTERNAL void copy_last(P &pool, const int64_t (&last)[N], int64_t *out)
+{
+    std::lock_guard<std::mutex> g(pool.mu);
+    for (int i = 0; i < N; ++i) out[i] = last[i];
+}
+
 }  // namespace cvtmi
 
 using namespace cvtmi;   // (as every glue file did for itself: this header is theirs alone)
@@ -128,13 +211,11 @@ struct OpqScratch : ScratchBase {
     ScanHPlan hplan;                       // the item table s_items holds ...
     int64_t hplan_n = -1, hplan_nq = -1;   // ... and the (rows, queries, forced splits, planner settings) it was built for
     int hplan_splits = 0, hplan_key = 0;
-    DevBuf io_q, io_d, io_i;   // device side of the host-pointer search (cvtmi_opq_search)
-    DevBuf io_v;               // ... and the video ids of a range search
-    DevBuf io_m;               // ... and the mask words of the host-pointer masked search / cvtmi_opq_mask_videos
-    PinBuf io_pin;             // its pinned staging area
+    DevBuf io_v;               // host-pointer range search: the video ids (beside ScratchBase's io_q / io_d / io_i)
+    PinBuf io_pin;             // the pinned staging area of the host-pointer search (cvtmi_opq_search)
     void release_all()
     {
-        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &s_masked, &s_range, &s_ref_d, &s_ref_i, &io_q, &io_d, &io_i, &io_v, &io_m }) b->release();
+        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &s_masked, &s_range, &s_ref_d, &s_ref_i, &io_v }) b->release();
         io_pin.release();
         release_lease_state();
     }
@@ -200,15 +281,13 @@ struct FlatScratch : ScratchBase {
     DevBuf fs_redo, fs_scratch;                                                                // fp32 stream
     DevBuf redo_count;                                                                         // "flat_count_redo": the count of the flags
     DevBuf s_range;                 // range search (flat_range.hip): part counts and offsets, spill area; host entry: lims behind them
-    DevBuf io_q, io_d, io_i;                                                                   // staging of the host-pointer entry
-    DevBuf io_c;                    // ... and the candidate lists of cvtmi_flat_rerank
+    DevBuf io_c;                    // host-pointer entries: the candidate lists of cvtmi_flat_rerank, the label set of cvtmi_flat_mask_labels
     DevBuf s_masked;                // masked search (flat_masked.hip): tile offsets, scan levels, the row list; mask_labels: the marked bitmap and its table
-    DevBuf io_m;                    // ... and the mask words / the label set of the host-pointer entries
     PinBuf io_pin;                  // small calls: [queries | distances | labels] in page-locked memory the kernels write into
     void release_all()
     {
         for (DevBuf *b : { &s_part_d, &s_part_id, &s_gthr, &s_stage, &f_stats, &f_thr, &f_marg, &f_cnt, &f_cand, &f_sd, &f_si, &f_sd2,
-                           &f_si2, &f_seld, &f_seli, &fs_redo, &fs_scratch, &redo_count, &s_range, &io_q, &io_d, &io_i, &io_c, &s_masked, &io_m })
+                           &f_si2, &f_seld, &f_seli, &fs_redo, &fs_scratch, &redo_count, &s_range, &io_c, &s_masked })
             b->release();
         io_pin.release();
         release_lease_state();
@@ -253,16 +332,15 @@ struct cvtmi_flat_s {
     bool fs_nonfinite = false;
 };
 
-// per-call scratch of an HNSW search: visited bits, spilled queues, re-rank lists, host staging
+// per-call scratch of an HNSW search: visited bits, spilled queues, re-rank lists
 struct HnswScratch : ScratchBase {
     static constexpr const char *kLeaseNoMemory = "hnsw search: out of host memory";
-    DevBuf s_vis, s_cand, s_err, s_rr_d, s_rr_id, io_q, io_d, io_l;
+    DevBuf s_vis, s_cand, s_err, s_rr_d, s_rr_id;
     DevBuf s_mark;   // cvtmi_hnsw_mask_labels: the marked bitmap, its tile counts and the table of the label set
-    DevBuf io_m;     // the mask words / the label set of the host-pointer masked entries
     DevBuf s_live;   // a search on a graph with dead nodes: the caller's mask (or all ones) without the dead nodes
     void release_all()
     {
-        for (DevBuf *b : { &s_vis, &s_cand, &s_err, &s_rr_d, &s_rr_id, &io_q, &io_d, &io_l, &s_mark, &io_m, &s_live }) b->release();
+        for (DevBuf *b : { &s_vis, &s_cand, &s_err, &s_rr_d, &s_rr_id, &s_mark, &s_live }) b->release();
         release_lease_state();
     }
 };
@@ -316,6 +394,13 @@ extern std::atomic<int> g_scanh_key;   // bumped by a REPLAN tuning key (api.hip
 
 int use_device(int dev);
 int opq_rotate_impl(cvtmi_opq_t h, const float *x, int64_t n, float *y, hipStream_t st);   // api_opq.hip
+// api_opq.hip: the first steps of a search on the leased set S: *q_rot = the queries as the codes see them (q itself, or S.s_qrot after
+// the rotation), and for nprobe >= 1 the nprobe nearest lists of every query in S.s_probe (int32 [nq][nprobe]); nprobe == 0 rotates only
+CVTMI_INTERNAL int opq_rotate_probe(cvtmi_opq_t h, OpqScratch &S, const float *q, int64_t nq, int rotate, int nprobe, hipStream_t st, const float **q_rot);
+// api_flat.hip: the bitmap of the rows (nodes) whose label is in a set, on the scratch buffer W: the mark step of the flat removal over
+// the n explicit labels `labels_dev`.  table: the T > 0 distinct labels of the set, ascending, in host memory (the caller waits for st
+// before it lets them go); mask: a device pointer of mask_words > 0 words; n > 0
+CVTMI_INTERNAL int labels_to_mask(DevBuf &W, const int64_t *labels_dev, int64_t n, const int64_t *table, int64_t T, uint64_t *mask, int64_t mask_words, hipStream_t st);
 // api_flat.hip: cvtmi_flat_rerank_dev behind its argument checks (device pointers, stream st); skip_minus_one: a candidate of -1 is padding
 int flat_rerank_on_stream(cvtmi_flat_t h, const void *q, int64_t nq, const int64_t *cand, int R, int64_t cand_base, bool skip_minus_one, int k,
                           void *dist, int64_t *labels, hipStream_t st);

@@ -61,6 +61,20 @@ int cvtmi::opq_rotate_impl(cvtmi_opq_t h, const float *x, int64_t n, float *y, h
     return CVTMI_OK;
 }
 
+int cvtmi::opq_rotate_probe(cvtmi_opq_t h, OpqScratch &S, const float *q, int64_t nq, int rotate, int nprobe, hipStream_t st, const float **q_rot)
+{
+    *q_rot = q;
+    if (rotate && (h->m.perm || h->m.R)) {
+        CVTMI_TRY(S.s_qrot.reserve((size_t)nq * h->m.D * sizeof(float)));
+        CVTMI_TRY(opq_rotate_impl(h, q, nq, S.s_qrot.as<float>(), st));
+        *q_rot = S.s_qrot.as<float>();
+    }
+    if (nprobe == 0) return CVTMI_OK;
+    const size_t probe_bytes = ((size_t)nq * nprobe * sizeof(int32_t) + 15) / 16 * 16;
+    CVTMI_TRY(S.s_probe.reserve(probe_bytes + coarse_probe_scratch_bytes(nq, nprobe)));
+    return launch_coarse_probe(h->m, *q_rot, nq, nprobe, S.s_probe.as<int32_t>(), st, S.s_probe.as<char>() + probe_bytes);
+}
+
 extern "C" {
 
 // ================================================================ OPQ =========================
@@ -606,12 +620,8 @@ static int opq_search_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64
         }
         return CVTMI_OK;
     }
-    const float *q_rot = q;
-    if (rotate && (h->m.perm || h->m.R)) {
-        CVTMI_TRY(S.s_qrot.reserve((size_t)nq * h->m.D * sizeof(float)));
-        CVTMI_TRY(opq_rotate_impl(h, q, nq, S.s_qrot.as<float>(), st));
-        q_rot = S.s_qrot.as<float>();
-    }
+    const float *q_rot = nullptr;
+    CVTMI_TRY(opq_rotate_probe(h, S, q, nq, rotate, 0, st, &q_rot));
     if (tune_scan_bigk.geti() && h->p_variant == 7 && h->p_qtile == 0 && h->p_splits == 0 && scank_applies(h->m, h->n, nq, k)) {
         // k = 129 .. 2048 (round 6): sampled histogram bound, candidate lists, one selection workgroup per query (adc_scan_h.hip); the
         // queries it could not answer (a list that overflowed, a crowded band, tables that bound nothing) are flagged and go through the
@@ -946,77 +956,8 @@ static int opq_query_prepare(cvtmi_opq_t h, hipStream_t st)
     OpqExclusive excl(h, st);
     return opq_build_csr(h, st);
 }
-static int opq_query_video_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64_t nq, int rotate, int nprobe, int img_num, float *match_score,
-                                  hipStream_t st)
-{
-    if (!h->csr_valid) return fail(CVTMI_EINVAL, "cvtmi_opq_query_video: the index changed while the query was being prepared");
-    if (nprobe > h->m.coarseK) nprobe = h->m.coarseK;  // the reference pops an empty heap here (UB)
-    if (h->csr_kept > 0 && (h->csr_vmin < 0 || h->csr_vmax >= img_num))
-        return fail(CVTMI_EINVAL, "cvtmi_opq_query_video: video id %d outside img_num=%d", h->csr_vmin < 0 ? h->csr_vmin : h->csr_vmax, img_num);
-    const float *q_rot = q;
-    if (rotate && (h->m.perm || h->m.R)) {
-        CVTMI_TRY(S.s_qrot.reserve((size_t)nq * h->m.D * sizeof(float)));
-        CVTMI_TRY(opq_rotate_impl(h, q, nq, S.s_qrot.as<float>(), st));
-        q_rot = S.s_qrot.as<float>();
-    }
-    const size_t probe_bytes = ((size_t)nq * nprobe * sizeof(int32_t) + 15) / 16 * 16;
-    CVTMI_TRY(S.s_probe.reserve(probe_bytes + coarse_probe_scratch_bytes(nq, nprobe)));
-    CVTMI_TRY(launch_coarse_probe(h->m, q_rot, nq, nprobe, S.s_probe.as<int32_t>(), st, S.s_probe.as<char>() + probe_bytes));
-    return launch_query_video(h->m, q_rot, nq, nprobe, S.s_probe.as<int32_t>(), h->csr_off.as<int64_t>(), h->csr_codes.as<uint8_t>(),
-                              h->csr_videos.as<int32_t>(), img_num, match_score, h->csr_longest, st);
-}
-
-int cvtmi_opq_query_video_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int img_num, float *match_score,
-                              void *stream)
-{
-    CHECK_H(h);
-    if (nq < 0 || img_num < 0 || (nq > 0 && img_num > 0 && (!q || !match_score)))
-        return fail(CVTMI_EINVAL, "cvtmi_opq_query_video: bad arguments");
-    if (nprobe < 1) return fail(CVTMI_EINVAL, "cvtmi_opq_query_video: nprobe=%d", nprobe);
-    if (nq == 0 || img_num == 0) return CVTMI_OK;
-    hipStream_t st = (hipStream_t)stream;
-    for (int attempt = 0;; ++attempt) {   // (an append between the preparation and the shared lock sends the query round again)
-        CVTMI_TRY(opq_query_prepare(h, st));
-        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
-        if (!h->csr_valid && attempt < 8) continue;
-        OpqLease lease;
-        CVTMI_TRY(lease.open(h, st, false));
-        return opq_query_video_leased(h, *lease.s, q, nq, rotate, nprobe, img_num, match_score, st);
-    }
-}
-
-// host pointers: frames in and the dense [frames][videos] score matrix out through the leased set's staging buffers (kept between
-// calls: the reference's own call is a handful of frames, a device allocation per call would cost more than the query)
-int cvtmi_opq_query_video(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int img_num,
-                          float *match_score)
-{
-    CHECK_H(h);
-    if (nq < 0 || img_num < 0 || (nq > 0 && img_num > 0 && (!q || !match_score)))
-        return fail(CVTMI_EINVAL, "cvtmi_opq_query_video: bad arguments");
-    if (nprobe < 1) return fail(CVTMI_EINVAL, "cvtmi_opq_query_video: nprobe=%d", nprobe);
-    if (nq == 0 || img_num == 0) return CVTMI_OK;
-    for (int attempt = 0;; ++attempt) {
-        CVTMI_TRY(opq_query_prepare(h, nullptr));
-        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
-        if (!h->csr_valid && attempt < 8) continue;
-        OpqLease lease;
-        CVTMI_TRY(lease.open(h, nullptr, true));
-        OpqScratch &S = *lease.s;
-        hipStream_t st = lease.st;
-        const size_t qb = (size_t)nq * h->m.D * sizeof(float), mb = (size_t)nq * img_num * sizeof(float);
-        CVTMI_TRY(S.io_q.reserve(qb));
-        CVTMI_TRY(S.io_d.reserve(mb));
-        CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
-        CVTMI_TRY(opq_query_video_leased(h, S, S.io_q.as<float>(), nq, rotate, nprobe, img_num, S.io_d.as<float>(), st));
-        CVTMI_HIP(hipMemcpyAsync(match_score, S.io_d.p, mb, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(stream_wait(st));
-        return CVTMI_OK;
-    }
-}
-
-// ---- IVF search: the k nearest ENTRIES of the nprobe nearest lists (ivf_search.hip) ----
-// Concurrency as for query_video: shared lock + leased scratch set; the first search after an append (or the first IVF search of
-// a handle whose list-ordered copy has no insertion indices yet) rebuilds the copy under the exclusive lock.
+// ... and for the entries that report ENTRY ids (the IVF searches): the first of them on a handle whose list-ordered copy has no
+// insertion indices yet rebuilds the copy as well
 static int opq_ivf_prepare(cvtmi_opq_t h, hipStream_t st)
 {
     {
@@ -1028,6 +969,82 @@ static int opq_ivf_prepare(cvtmi_opq_t h, hipStream_t st)
     h->want_entry = true;
     return opq_build_csr(h, st);
 }
+// under the shared lock: the mask covers the entries there are now
+static int opq_mask_covers(cvtmi_opq_t h, int64_t mask_words, const char *fn)
+{
+    if (mask_words < (h->n + 63) / 64)
+        return fail(CVTMI_EINVAL, "%s: %lld mask words, %lld entries need %lld", fn, (long long)mask_words, (long long)h->n, (long long)((h->n + 63) / 64));
+    return CVTMI_OK;
+}
+}  // extern "C"
+
+// The way into every entry that reads the list-ordered copy, in this order: the preparation under the exclusive lock (entry_ids: the
+// insertion indices are needed too), `rw` shared -- an append between the two sends the call round again, at most 8 times; after that
+// the _leased body answers "the index changed" --, the mask length against the entries there are now (mask_words >= 0: a masked search),
+// the lease on (stream, host), and run(lease) under both.
+template <class F> static int opq_ivf_enter(cvtmi_opq_t h, bool entry_ids, hipStream_t stream, bool host, int64_t mask_words, F &&run)
+{
+    for (int attempt = 0;; ++attempt) {
+        CVTMI_TRY(entry_ids ? opq_ivf_prepare(h, stream) : opq_query_prepare(h, stream));
+        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+        if (!(h->csr_valid && (h->csr_entry_valid || !entry_ids)) && attempt < 8) continue;
+        if (mask_words >= 0) CVTMI_TRY(opq_mask_covers(h, mask_words, "cvtmi_opq_search_ivf_masked"));
+        OpqLease lease;
+        CVTMI_TRY(lease.open(h, stream, host));
+        return run(lease);
+    }
+}
+
+extern "C" {
+
+static int opq_query_video_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64_t nq, int rotate, int nprobe, int img_num, float *match_score,
+                                  hipStream_t st)
+{
+    if (!h->csr_valid) return fail(CVTMI_EINVAL, "cvtmi_opq_query_video: the index changed while the query was being prepared");
+    if (nprobe > h->m.coarseK) nprobe = h->m.coarseK;  // the reference pops an empty heap here (UB)
+    if (h->csr_kept > 0 && (h->csr_vmin < 0 || h->csr_vmax >= img_num))
+        return fail(CVTMI_EINVAL, "cvtmi_opq_query_video: video id %d outside img_num=%d", h->csr_vmin < 0 ? h->csr_vmin : h->csr_vmax, img_num);
+    const float *q_rot = nullptr;
+    CVTMI_TRY(opq_rotate_probe(h, S, q, nq, rotate, nprobe, st, &q_rot));
+    return launch_query_video(h->m, q_rot, nq, nprobe, S.s_probe.as<int32_t>(), h->csr_off.as<int64_t>(), h->csr_codes.as<uint8_t>(),
+                              h->csr_videos.as<int32_t>(), img_num, match_score, h->csr_longest, st);
+}
+
+// host = true: frames in and the dense [frames][videos] score matrix out through the leased set's staging buffers (kept between
+// calls: the reference's own call is a handful of frames, a device allocation per call would cost more than the query)
+static int opq_query_video_common(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int img_num, float *match_score, hipStream_t stream,
+                                  bool host)
+{
+    if (nq < 0 || img_num < 0 || (nq > 0 && img_num > 0 && (!q || !match_score)))
+        return fail(CVTMI_EINVAL, "cvtmi_opq_query_video: bad arguments");
+    if (nprobe < 1) return fail(CVTMI_EINVAL, "cvtmi_opq_query_video: nprobe=%d", nprobe);
+    if (nq == 0 || img_num == 0) return CVTMI_OK;
+    const auto run = [&](OpqScratch &S, const float *dq, const void *, float *ms, int64_t *, hipStream_t st) {
+        return opq_query_video_leased(h, S, dq, nq, rotate, nprobe, img_num, ms, st);
+    };
+    return opq_ivf_enter(h, false, stream, host, -1, [&](OpqLease &lease) {
+        if (!host) return run(*lease.s, q, nullptr, match_score, nullptr, lease.st);
+        return host_call(lease, q, (size_t)nq * h->m.D * sizeof(float), HostUpload{}, match_score, (size_t)nq * img_num * sizeof(float), nullptr, 0, run);
+    });
+}
+
+int cvtmi_opq_query_video_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int img_num, float *match_score,
+                              void *stream)
+{
+    CHECK_H(h);
+    return opq_query_video_common(h, q, nq, rotate, nprobe, img_num, match_score, (hipStream_t)stream, false);
+}
+
+int cvtmi_opq_query_video(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int img_num,
+                          float *match_score)
+{
+    CHECK_H(h);
+    return opq_query_video_common(h, q, nq, rotate, nprobe, img_num, match_score, nullptr, true);
+}
+
+// ---- IVF search: the k nearest ENTRIES of the nprobe nearest lists (ivf_search.hip) ----
+// Concurrency as for query_video: shared lock + leased scratch set; the first search after an append (or the first IVF search of
+// a handle whose list-ordered copy has no insertion indices yet) rebuilds the copy under the exclusive lock (opq_ivf_enter).
 // mask != null (cvtmi_opq_search_ivf_masked): the caller's words on the device, at least ceil(n / 64) of them.  What is derived from
 // them -- the mask in list order -- lives in the leased set like the partial lists: searches with different masks run side by side
 static int opq_search_ivf_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64_t nq, int rotate, int nprobe, int k, float *dist, int64_t *ids,
@@ -1039,15 +1056,8 @@ static int opq_search_ivf_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, i
         CVTMI_TRY(S.s_masked.reserve(lmb));
         CVTMI_TRY(launch_ivf_mask_order(mask, h->csr_entry.as<uint32_t>(), h->csr_kept, S.s_masked.as<uint64_t>(), st));
     }
-    const float *q_rot = q;
-    if (rotate && (h->m.perm || h->m.R)) {
-        CVTMI_TRY(S.s_qrot.reserve((size_t)nq * h->m.D * sizeof(float)));
-        CVTMI_TRY(opq_rotate_impl(h, q, nq, S.s_qrot.as<float>(), st));
-        q_rot = S.s_qrot.as<float>();
-    }
-    const size_t probe_bytes = ((size_t)nq * nprobe * sizeof(int32_t) + 15) / 16 * 16;
-    CVTMI_TRY(S.s_probe.reserve(probe_bytes + coarse_probe_scratch_bytes(nq, nprobe)));
-    CVTMI_TRY(launch_coarse_probe(h->m, q_rot, nq, nprobe, S.s_probe.as<int32_t>(), st, S.s_probe.as<char>() + probe_bytes));
+    const float *q_rot = nullptr;
+    CVTMI_TRY(opq_rotate_probe(h, S, q, nq, rotate, nprobe, st, &q_rot));
     const IvfPlan plan = plan_ivf_search(nq, nprobe, k, h->csr_longest, (size_t)tune_ivf_part_cap_mb.geti() << 20);
     const size_t pb = ivf_part_bytes(plan, nq, k);
     if (pb) CVTMI_TRY(S.s_ivf.reserve(pb));
@@ -1079,54 +1089,49 @@ static int opq_search_ivf_check(cvtmi_opq_t h, const float *q, int64_t nq, int *
     return CVTMI_OK;
 }
 
-int cvtmi_opq_search_ivf_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k, float *dist, int64_t *ids, void *stream)
+// ... of the masked search (cvtmi_opq_search_ivf_masked): the k nearest entries of the probed lists among those a bitmap of insertion
+// indices allows.  A search like cvtmi_opq_search_ivf: same preparation, shared lock, leased set; the mask's length is checked under the lock.
+static int opq_ivf_masked_check(cvtmi_opq_t h, const float *q, int64_t nq, int *nprobe, int k, const uint64_t *mask, int64_t mask_words, const float *dist,
+                                const int64_t *ids)
 {
-    CVTMI_TRY(opq_search_ivf_check(h, q, nq, &nprobe, k, dist, ids));
-    CVTMI_TRY(use_device(h->device));
-    if (nq == 0) return CVTMI_OK;
-    hipStream_t st = (hipStream_t)stream;
-    for (int attempt = 0;; ++attempt) {   // (an append between the preparation and the shared lock sends the search round again)
-        CVTMI_TRY(opq_ivf_prepare(h, st));
-        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
-        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
-        OpqLease lease;
-        CVTMI_TRY(lease.open(h, st, false));
-        return opq_search_ivf_leased(h, *lease.s, q, nq, rotate, nprobe, k, dist, ids, st);
-    }
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf_masked: null handle");
+    if (mask_words < 0 || (nq > 0 && !mask)) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf_masked: bad arguments");
+    return opq_search_ivf_check(h, q, nq, nprobe, k, dist, ids);
 }
 
-// host pointers: queries in and the two result arrays out through the leased set's staging buffers and its own stream
-int cvtmi_opq_search_ivf(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k, float *dist, int64_t *ids)
+// The four entries of the two searches.  host = true: queries (and the mask words that can hold an entry: the words behind them are
+// never read) up, the two result arrays down, through the leased set's staging buffers and its own stream
+static int opq_search_ivf_common(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k, bool masked, const uint64_t *mask,
+                                 int64_t mask_words, float *dist, int64_t *ids, hipStream_t stream, bool host)
 {
-    CVTMI_TRY(opq_search_ivf_check(h, q, nq, &nprobe, k, dist, ids));
+    if (masked) CVTMI_TRY(opq_ivf_masked_check(h, q, nq, &nprobe, k, mask, mask_words, dist, ids));
+    else CVTMI_TRY(opq_search_ivf_check(h, q, nq, &nprobe, k, dist, ids));
     CVTMI_TRY(use_device(h->device));
     if (nq == 0) return CVTMI_OK;
-    for (int attempt = 0;; ++attempt) {
-        CVTMI_TRY(opq_ivf_prepare(h, nullptr));
-        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
-        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
-        OpqLease lease;
-        CVTMI_TRY(lease.open(h, nullptr, true));
-        OpqScratch &S = *lease.s;
-        hipStream_t st = lease.st;
-        const size_t qb = (size_t)nq * h->m.D * sizeof(float), db = (size_t)nq * k * sizeof(float), ib = (size_t)nq * k * sizeof(int64_t);
-        CVTMI_TRY(S.io_q.reserve(qb));
-        CVTMI_TRY(S.io_d.reserve(db));
-        CVTMI_TRY(S.io_i.reserve(ib));
-        CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
-        CVTMI_TRY(opq_search_ivf_leased(h, S, S.io_q.as<float>(), nq, rotate, nprobe, k, S.io_d.as<float>(), S.io_i.as<int64_t>(), st));
-        CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(hipMemcpyAsync(ids, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(stream_wait(st));
-        return CVTMI_OK;
-    }
+    const auto run = [&](OpqScratch &S, const float *dq, const void *dm, float *dd, int64_t *di, hipStream_t st) {
+        return opq_search_ivf_leased(h, S, dq, nq, rotate, nprobe, k, dd, di, st, static_cast<const uint64_t *>(dm));
+    };
+    return opq_ivf_enter(h, true, stream, host, masked ? mask_words : -1, [&](OpqLease &lease) {
+        if (!host) return run(*lease.s, q, mask, dist, ids, lease.st);
+        const HostUpload words = masked ? HostUpload{ &lease.s->io_m, mask, (size_t)((h->n + 63) / 64) * 8 } : HostUpload{};
+        return host_call(lease, q, (size_t)nq * h->m.D * sizeof(float), words, dist, (size_t)nq * k * sizeof(float), ids, (size_t)nq * k * sizeof(int64_t), run);
+    });
+}
+
+int cvtmi_opq_search_ivf_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k, float *dist, int64_t *ids, void *stream)
+{
+    return opq_search_ivf_common(h, q, nq, rotate, nprobe, k, false, nullptr, 0, dist, ids, (hipStream_t)stream, false);
+}
+
+int cvtmi_opq_search_ivf(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k, float *dist, int64_t *ids)
+{
+    return opq_search_ivf_common(h, q, nq, rotate, nprobe, k, false, nullptr, 0, dist, ids, nullptr, true);
 }
 
 int cvtmi_opq_last_ivf_plan(cvtmi_opq_t h, int64_t out[8])
 {
     if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_opq_last_ivf_plan: null");
-    std::lock_guard<std::mutex> g(h->pool.mu);
-    for (int i = 0; i < 8; ++i) out[i] = h->ivf_last[i];
+    copy_last(h->pool, h->ivf_last, out);
     out[7] = (int64_t)h->csr_entry.cap;
     return CVTMI_OK;
 }
@@ -1140,83 +1145,27 @@ int cvtmi_opq_ivf_plan(int64_t nq, int nprobe, int k, int64_t longest_list, int 
     return CVTMI_OK;
 }
 
-// ---- masked IVF search: the k nearest entries of the probed lists among those a bitmap of insertion indices allows ----
-// A search like cvtmi_opq_search_ivf: same preparation, shared lock, leased set; the mask's length is checked under the lock.
-static int opq_ivf_masked_check(cvtmi_opq_t h, const float *q, int64_t nq, int *nprobe, int k, const uint64_t *mask, int64_t mask_words, const float *dist,
-                                const int64_t *ids)
-{
-    if (!h) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf_masked: null handle");
-    if (mask_words < 0 || (nq > 0 && !mask)) return fail(CVTMI_EINVAL, "cvtmi_opq_search_ivf_masked: bad arguments");
-    return opq_search_ivf_check(h, q, nq, nprobe, k, dist, ids);
-}
-static int opq_mask_covers(cvtmi_opq_t h, int64_t mask_words, const char *fn)
-{
-    if (mask_words < (h->n + 63) / 64)
-        return fail(CVTMI_EINVAL, "%s: %lld mask words, %lld entries need %lld", fn, (long long)mask_words, (long long)h->n, (long long)((h->n + 63) / 64));
-    return CVTMI_OK;
-}
-
 int cvtmi_opq_search_ivf_masked_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k, const uint64_t *mask, int64_t mask_words,
                                     float *dist, int64_t *ids, void *stream)
 {
-    CVTMI_TRY(opq_ivf_masked_check(h, q, nq, &nprobe, k, mask, mask_words, dist, ids));
-    CVTMI_TRY(use_device(h->device));
-    if (nq == 0) return CVTMI_OK;
-    hipStream_t st = (hipStream_t)stream;
-    for (int attempt = 0;; ++attempt) {   // (an append between the preparation and the shared lock sends the search round again)
-        CVTMI_TRY(opq_ivf_prepare(h, st));
-        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
-        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
-        CVTMI_TRY(opq_mask_covers(h, mask_words, "cvtmi_opq_search_ivf_masked"));
-        OpqLease lease;
-        CVTMI_TRY(lease.open(h, st, false));
-        return opq_search_ivf_leased(h, *lease.s, q, nq, rotate, nprobe, k, dist, ids, st, mask);
-    }
+    return opq_search_ivf_common(h, q, nq, rotate, nprobe, k, true, mask, mask_words, dist, ids, (hipStream_t)stream, false);
 }
 
-// host pointers: queries and mask words up, the two result arrays down, through the leased set's staging buffers and its own stream
 int cvtmi_opq_search_ivf_masked(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe, int k, const uint64_t *mask, int64_t mask_words,
                                 float *dist, int64_t *ids)
 {
-    CVTMI_TRY(opq_ivf_masked_check(h, q, nq, &nprobe, k, mask, mask_words, dist, ids));
-    CVTMI_TRY(use_device(h->device));
-    if (nq == 0) return CVTMI_OK;
-    for (int attempt = 0;; ++attempt) {
-        CVTMI_TRY(opq_ivf_prepare(h, nullptr));
-        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
-        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
-        CVTMI_TRY(opq_mask_covers(h, mask_words, "cvtmi_opq_search_ivf_masked"));
-        OpqLease lease;
-        CVTMI_TRY(lease.open(h, nullptr, true));
-        OpqScratch &S = *lease.s;
-        hipStream_t st = lease.st;
-        const size_t qb = (size_t)nq * h->m.D * sizeof(float), mb = (size_t)((h->n + 63) / 64) * 8, db = (size_t)nq * k * sizeof(float),
-                     ib = (size_t)nq * k * sizeof(int64_t);
-        CVTMI_TRY(S.io_q.reserve(qb));
-        CVTMI_TRY(S.io_m.reserve(std::max<size_t>(mb, 16)));
-        CVTMI_TRY(S.io_d.reserve(db));
-        CVTMI_TRY(S.io_i.reserve(ib));
-        CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
-        if (mb) CVTMI_HIP(hipMemcpyAsync(S.io_m.p, mask, mb, hipMemcpyHostToDevice, st));   // (the words behind the entries are never read)
-        CVTMI_TRY(opq_search_ivf_leased(h, S, S.io_q.as<float>(), nq, rotate, nprobe, k, S.io_d.as<float>(), S.io_i.as<int64_t>(), st, S.io_m.as<uint64_t>()));
-        CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(hipMemcpyAsync(ids, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(stream_wait(st));
-        return CVTMI_OK;
-    }
+    return opq_search_ivf_common(h, q, nq, rotate, nprobe, k, true, mask, mask_words, dist, ids, nullptr, true);
 }
 
 int cvtmi_opq_last_ivf_masked(cvtmi_opq_t h, int64_t out[8])
 {
     if (!h) return fail(CVTMI_EINVAL, "cvtmi_opq_last_ivf_masked: null handle");
     if (!out) return fail(CVTMI_EINVAL, "cvtmi_opq_last_ivf_masked: null");
-    std::lock_guard<std::mutex> g(h->pool.mu);
-    for (int i = 0; i < 8; ++i) out[i] = h->ivf_masked_last[i];
+    copy_last(h->pool, h->ivf_masked_last, out);
     return CVTMI_OK;
 }
 
 // ---- the bitmap of a set of video ids: the mark step of the removal on a leased scratch set (the handle does not change) ----
-static int opq_remove_table(const int32_t *ids, int64_t nv, std::vector<int32_t> &tab);   // (with the removal, below)
 static int opq_mask_videos_check(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, const uint64_t *mask, int64_t mask_words)
 {
     if (!h) return fail(CVTMI_EINVAL, "cvtmi_opq_mask_videos: null handle");
@@ -1249,17 +1198,8 @@ int cvtmi_opq_mask_videos_dev(cvtmi_opq_t h, const int32_t *video_ids, int64_t n
     CVTMI_TRY(opq_mask_covers(h, mask_words, "cvtmi_opq_mask_videos"));
     OpqLease lease;
     CVTMI_TRY(lease.open(h, st, false));
-    std::vector<int32_t> raw, tab;
-    if (nv > 0 && h->n > 0 && mask_words > 0) {   // the set is sorted on the host: it comes down first (4 bytes per id)
-        try {
-            raw.resize((size_t)nv);
-        } catch (...) {
-            return fail(CVTMI_ENOMEM, "cvtmi_opq_mask_videos: out of host memory");
-        }
-        CVTMI_HIP(hipMemcpyAsync(raw.data(), video_ids, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(stream_wait(st));
-        CVTMI_TRY(opq_remove_table(raw.data(), nv, tab));
-    }
+    std::vector<int32_t> tab;
+    if (nv > 0 && h->n > 0 && mask_words > 0) CVTMI_TRY(sorted_unique_dev("cvtmi_opq_mask_videos", video_ids, nv, tab, st));
     CVTMI_TRY(opq_mask_videos_leased(h, *lease.s, tab.data(), (int64_t)tab.size(), mask, mask_words, st));
     if (!tab.empty()) CVTMI_HIP(stream_wait(st));   // (the table leaves host memory that ends with this call)
     return CVTMI_OK;
@@ -1277,19 +1217,15 @@ int cvtmi_opq_mask_videos(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, u
         return CVTMI_OK;
     }
     std::vector<int32_t> tab;
-    CVTMI_TRY(opq_remove_table(video_ids, nv, tab));
+    CVTMI_TRY(sorted_unique("cvtmi_opq_mask_videos", video_ids, nv, tab));
     OpqLease lease;
     CVTMI_TRY(lease.open(h, nullptr, true));
     OpqScratch &S = *lease.s;
     hipStream_t st = lease.st;
-    // only the words that can hold an entry pass through the device; the caller's words behind them are cleared here
-    const int64_t words = (h->n + 63) / 64;
+    const int64_t words = (h->n + 63) / 64;   // (the words that can hold an entry)
     CVTMI_TRY(S.io_m.reserve((size_t)words * 8));
     CVTMI_TRY(opq_mask_videos_leased(h, S, tab.data(), (int64_t)tab.size(), S.io_m.as<uint64_t>(), words, st));
-    CVTMI_HIP(hipMemcpyAsync(mask, S.io_m.p, (size_t)words * 8, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(stream_wait(st));
-    memset(mask + words, 0, (size_t)(mask_words - words) * 8);
-    return CVTMI_OK;
+    return mask_host_finish(S.io_m, words, mask, mask_words, st);
 }
 
 // ---- refine: R ADC candidates per query (IVF lists, or the exhaustive scan for nprobe == 0), exact finish against a flat index ----
@@ -1331,27 +1267,19 @@ static int opq_refine_common(cvtmi_opq_t h, cvtmi_flat_t flat, const float *q, i
     CVTMI_TRY(opq_refine_check(h, flat, q, nq, &nprobe, k, R, dist, labels));
     CVTMI_TRY(use_device(h->device));
     if (nq == 0) return CVTMI_OK;
-    for (int attempt = 0;; ++attempt) {   // (as cvtmi_opq_search_ivf: an append between the preparation and the shared lock sends it round again)
-        if (nprobe >= 1) CVTMI_TRY(opq_ivf_prepare(h, stream));
-        else CVTMI_TRY(opq_prepare(h, nq, R, stream));
-        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
-        if (nprobe >= 1 && !(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
-        OpqLease lease;
-        CVTMI_TRY(lease.open(h, stream, host));
-        if (!host) return opq_refine_leased(h, flat, *lease.s, q, nq, rotate, nprobe, k, R, dist, labels, stream);
-        OpqScratch &S = *lease.s;
-        hipStream_t st = lease.st;
-        const size_t qb = (size_t)nq * h->m.D * sizeof(float), db = (size_t)nq * k * sizeof(float), ib = (size_t)nq * k * sizeof(int64_t);
-        CVTMI_TRY(S.io_q.reserve(qb));
-        CVTMI_TRY(S.io_d.reserve(db));
-        CVTMI_TRY(S.io_i.reserve(ib));
-        CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
-        CVTMI_TRY(opq_refine_leased(h, flat, S, S.io_q.as<float>(), nq, rotate, nprobe, k, R, S.io_d.as<float>(), S.io_i.as<int64_t>(), st));
-        CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(hipMemcpyAsync(labels, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(stream_wait(st));
-        return CVTMI_OK;
-    }
+    const auto run = [&](OpqScratch &S, const float *dq, const void *, float *dd, int64_t *dl, hipStream_t st) {
+        return opq_refine_leased(h, flat, S, dq, nq, rotate, nprobe, k, R, dd, dl, st);
+    };
+    const auto leased = [&](OpqLease &lease) {
+        if (!host) return run(*lease.s, q, nullptr, dist, labels, lease.st);
+        return host_call(lease, q, (size_t)nq * h->m.D * sizeof(float), HostUpload{}, dist, (size_t)nq * k * sizeof(float), labels, (size_t)nq * k * sizeof(int64_t), run);
+    };
+    if (nprobe >= 1) return opq_ivf_enter(h, true, stream, host, -1, leased);   // (the way in of cvtmi_opq_search_ivf)
+    CVTMI_TRY(opq_prepare(h, nq, R, stream));   // nprobe == 0: the way in of cvtmi_opq_search_dev
+    std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+    OpqLease lease;
+    CVTMI_TRY(lease.open(h, stream, host));
+    return leased(lease);
 }
 
 int cvtmi_opq_search_refine_dev(cvtmi_opq_t h, cvtmi_flat_t flat, const float *q, int64_t nq, int rotate, int nprobe, int k, int R, float *dist,
@@ -1379,15 +1307,7 @@ static int opq_range_count_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, 
                                   int64_t *lims, OpqRangeCall &c, hipStream_t st)
 {
     if (!h->csr_valid || !h->csr_entry_valid) return fail(CVTMI_EINVAL, "cvtmi_opq_range_search_ivf: the index changed while the search was being prepared");
-    c.q_rot = q;
-    if (rotate && (h->m.perm || h->m.R)) {
-        CVTMI_TRY(S.s_qrot.reserve((size_t)nq * h->m.D * sizeof(float)));
-        CVTMI_TRY(opq_rotate_impl(h, q, nq, S.s_qrot.as<float>(), st));
-        c.q_rot = S.s_qrot.as<float>();
-    }
-    const size_t probe_bytes = ((size_t)nq * nprobe * sizeof(int32_t) + 15) / 16 * 16;
-    CVTMI_TRY(S.s_probe.reserve(probe_bytes + coarse_probe_scratch_bytes(nq, nprobe)));
-    CVTMI_TRY(launch_coarse_probe(h->m, c.q_rot, nq, nprobe, S.s_probe.as<int32_t>(), st, S.s_probe.as<char>() + probe_bytes));
+    CVTMI_TRY(opq_rotate_probe(h, S, q, nq, rotate, nprobe, st, &c.q_rot));
     c.plan = plan_ivf_range(nq, nprobe, h->csr_longest, spill ? tune_ivf_range_spill.get() : 0, (size_t)tune_ivf_part_cap_mb.geti() << 20);
     const size_t carved = ivf_range_carve(nullptr, c.plan, nq, nprobe, nullptr);
     CVTMI_TRY(S.s_range.reserve(carved + ((size_t)nq + 1) * sizeof(int64_t)));
@@ -1436,17 +1356,12 @@ int cvtmi_opq_range_search_ivf_dev(cvtmi_opq_t h, const float *q, int64_t nq, in
         CVTMI_HIP(hipMemsetAsync(lims, 0, sizeof(int64_t), st));
         return CVTMI_OK;
     }
-    for (int attempt = 0;; ++attempt) {   // (an append between the preparation and the shared lock sends the search round again)
-        CVTMI_TRY(opq_ivf_prepare(h, st));
-        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
-        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
-        OpqLease lease;
-        CVTMI_TRY(lease.open(h, st, false));
+    return opq_ivf_enter(h, true, st, false, -1, [&](OpqLease &lease) -> int {
         OpqRangeCall c;
         CVTMI_TRY(opq_range_count_leased(h, *lease.s, q, nq, rotate, nprobe, radius, cap > 0, lims, c, st));
         if (cap == 0) return CVTMI_OK;   // a count-only call
         return opq_range_fill_leased(h, c, nq, nprobe, radius, lims, cap, dist, ids, video, st);
-    }
+    });
 }
 
 // host pointers: the queries go up and lims comes back through the leased set's staging buffers -- the one wait the call needs to
@@ -1458,12 +1373,7 @@ int cvtmi_opq_range_search_ivf(cvtmi_opq_t h, const float *q, int64_t nq, int ro
     CVTMI_TRY(use_device(h->device));
     lims[0] = 0;
     if (nq == 0) return CVTMI_OK;
-    for (int attempt = 0;; ++attempt) {
-        CVTMI_TRY(opq_ivf_prepare(h, nullptr));
-        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
-        if (!(h->csr_valid && h->csr_entry_valid) && attempt < 8) continue;
-        OpqLease lease;
-        CVTMI_TRY(lease.open(h, nullptr, true));
+    return opq_ivf_enter(h, true, nullptr, true, -1, [&](OpqLease &lease) -> int {
         OpqScratch &S = *lease.s;
         hipStream_t st = lease.st;
         const size_t qb = (size_t)nq * h->m.D * sizeof(float);
@@ -1489,14 +1399,13 @@ int cvtmi_opq_range_search_ivf(cvtmi_opq_t h, const float *q, int64_t nq, int ro
         if (video) CVTMI_HIP(hipMemcpyAsync(video, S.io_v.p, vb, hipMemcpyDeviceToHost, st));
         CVTMI_HIP(stream_wait(st));
         return CVTMI_OK;
-    }
+    });
 }
 
 int cvtmi_opq_last_range_plan(cvtmi_opq_t h, int64_t out[8])
 {
     if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_opq_last_range_plan: null");
-    std::lock_guard<std::mutex> g(h->pool.mu);
-    for (int i = 0; i < 8; ++i) out[i] = h->range_last[i];
+    copy_last(h->pool, h->range_last, out);
     return CVTMI_OK;
 }
 
@@ -1556,35 +1465,13 @@ static int opq_remove_check(const char *fn, cvtmi_opq_t h, const void *set, int6
     return CVTMI_OK;
 }
 
-// the distinct ids of the set, ascending
-static int opq_remove_table(const int32_t *ids, int64_t nv, std::vector<int32_t> &tab)
-{
-    try {
-        tab.assign(ids, ids + nv);
-    } catch (...) {
-        return fail(CVTMI_ENOMEM, "cvtmi_opq_remove_videos: out of host memory");
-    }
-    std::sort(tab.begin(), tab.end());
-    tab.erase(std::unique(tab.begin(), tab.end()), tab.end());
-    return CVTMI_OK;
-}
-
 int cvtmi_opq_remove_videos_dev(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv, int renumber, int64_t *removed, int64_t *remap, void *stream)
 {
     CVTMI_TRY(opq_remove_check(__func__, h, video_ids, nv));
     CHECK_H_SERIAL(h, stream);
     hipStream_t st = (hipStream_t)stream;
-    std::vector<int32_t> raw, tab;
-    if (nv > 0) {   // the set is sorted on the host: it comes down first (4 bytes per id)
-        try {
-            raw.resize((size_t)nv);
-        } catch (...) {
-            return fail(CVTMI_ENOMEM, "cvtmi_opq_remove_videos: out of host memory");
-        }
-        CVTMI_HIP(hipMemcpyAsync(raw.data(), video_ids, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(stream_wait(st));
-        CVTMI_TRY(opq_remove_table(raw.data(), nv, tab));
-    }
+    std::vector<int32_t> tab;
+    if (nv > 0) CVTMI_TRY(sorted_unique_dev("cvtmi_opq_remove_videos", video_ids, nv, tab, st));
     return opq_remove_common(h, tab.data(), (int64_t)tab.size(), nullptr, 0, false, renumber, removed, remap, st);
 }
 
@@ -1593,7 +1480,7 @@ int cvtmi_opq_remove_videos(cvtmi_opq_t h, const int32_t *video_ids, int64_t nv,
     CVTMI_TRY(opq_remove_check(__func__, h, video_ids, nv));
     CHECK_H_SERIAL(h, nullptr);
     std::vector<int32_t> tab;
-    if (nv > 0) CVTMI_TRY(opq_remove_table(video_ids, nv, tab));
+    if (nv > 0) CVTMI_TRY(sorted_unique("cvtmi_opq_remove_videos", video_ids, nv, tab));
     const int64_t n0 = h->n;
     Tmp dm;
     if (remap && n0 > 0) CVTMI_TRY(dm.alloc((size_t)n0 * sizeof(int64_t)));
