@@ -692,7 +692,11 @@ int cvtmi_flat_set_param(cvtmi_flat_t h, const char *name, int64_t value);
 /* searchKnn (brutoforce.hpp:73-93) for nq queries: k smallest (distance, label), ascending.
  * dist is float[nq][k] for IP / L2F and int32_t[nq][k] for L2U8.  1 <= k <= CVTMI_K_MAX.  An index with fewer than k rows pads:
  * label -1, distance field 0x7f800000 -- +inf as a float, and for L2U8 the same bit pattern read as int32 (2139095040: larger than
- * any real distance, which is what lets the padded lists of row shards merge like all others). */
+ * any real distance, which is what lets the padded lists of row shards merge like all others).
+ * Floats compare as in cvtmi_topk_select: -0.0 == +0.0, NaN by its key.  A NaN distance is a real candidate, ordered by its key: a
+ * query holding a NaN returns min(k, rows) distinct rows, all with NaN distances.  (The key of a NaN with the sign bit is below -inf's,
+ * and the subtractions q - x and 1 - sum negate their second operand, a NaN included: for a finite query a row holding a +NaN leads
+ * the list.) */
 int cvtmi_flat_search(cvtmi_flat_t h, const void *q, int64_t nq, int k, void *dist, int64_t *labels);
 int cvtmi_flat_search_dev(cvtmi_flat_t h, const void *q, int64_t nq, int k, void *dist, int64_t *labels,
                           void *stream);
