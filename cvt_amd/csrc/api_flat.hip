@@ -876,21 +876,10 @@ int cvtmi_flat_range_search(cvtmi_flat_t h, const void *q, int64_t nq, double ra
     CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
     FlatRangeCall c;
     CVTMI_TRY(flat_range_count_leased(h, S, S.io_q.p, nq, radius, cap > 0, nullptr, c, st));
-    CVTMI_HIP(hipMemcpyAsync(lims, c.lims_scratch, ((size_t)nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(stream_wait(st));
-    const int64_t total = lims[nq];
-    if (cap == 0 && !dist && !labels) return CVTMI_OK;   // a count-only call: lims is the answer
-    if (total > cap)
-        return fail(CVTMI_ESPACE, "cvtmi_flat_range_search: %lld hits, room for %lld (lims holds the sizes)", (long long)total, (long long)cap);
-    if (total == 0) return CVTMI_OK;
-    const size_t db = (size_t)total * 4, ib = (size_t)total * sizeof(int64_t);
-    CVTMI_TRY(S.io_d.reserve(db));
-    CVTMI_TRY(S.io_i.reserve(ib));
-    CVTMI_TRY(launch_flat_range_fill(c.rows, S.io_q.p, nq, c.thr, c.plan, c.bufs, c.lims_scratch, total, S.io_d.p, S.io_i.as<int64_t>(), st));
-    CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(hipMemcpyAsync(labels, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
-    CVTMI_HIP(stream_wait(st));
-    return CVTMI_OK;
+    const RangeOut outs[] = { { dist, &S.io_d, 4 }, { labels, &S.io_i, sizeof(int64_t) } };
+    return range_host_finish("cvtmi_flat_range_search", nq, cap, lims, c.lims_scratch, outs, st, [&](int64_t total) {
+        return launch_flat_range_fill(c.rows, S.io_q.p, nq, c.thr, c.plan, c.bufs, c.lims_scratch, total, S.io_d.p, S.io_i.as<int64_t>(), st);
+    });
 }
 
 int cvtmi_flat_last_range_plan(cvtmi_flat_t h, int64_t out[6])

@@ -188,6 +188,40 @@ CVTMI_INTERNAL inline int mask_host_finish(const DevBuf &io_m, int64_t words, ui
     return CVTMI_OK;
 }
 
+// One result array of a host-pointer range search: `elem` bytes per hit, down from the staging buffer `stage` of the leased set
+// into `host` (null: the caller does not want it).
+struct RangeOut {
+    void *host;
+    DevBuf *stage;
+    size_t elem;
+};
+
+// The end of a host-pointer range entry (`who`), behind the count that left lims on the device at lims_dev: lims comes down and the
+// call waits -- the one wait it needs to know whether the result fits.  Without room and arrays that is the answer; more hits than
+// room fail with the sizes in lims; otherwise the staging buffers grow to lims[nq] hits, fill(total) writes them there and they
+// come down.  An array whose host pointer is null gets no staging room: fill must skip it (the entries' argument checks refuse a
+// null array the fill always writes whenever cap > 0).
+template <size_t N, class F>
+CVTMI_INTERNAL int range_host_finish(const char *who, int64_t nq, int64_t cap, int64_t *lims, const int64_t *lims_dev, const RangeOut (&outs)[N],
+                                     hipStream_t st, F &&fill)
+{
+    CVTMI_HIP(hipMemcpyAsync(lims, lims_dev, ((size_t)nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    const int64_t total = lims[nq];
+    bool wanted = false;
+    for (const RangeOut &o : outs) wanted = wanted || o.host;
+    if (cap == 0 && !wanted) return CVTMI_OK;   // a count-only call: lims is the answer
+    if (total > cap) return fail(CVTMI_ESPACE, "%s: %lld hits, room for %lld (lims holds the sizes)", who, (long long)total, (long long)cap);
+    if (total == 0) return CVTMI_OK;
+    for (const RangeOut &o : outs)
+        if (o.host) CVTMI_TRY(o.stage->reserve((size_t)total * o.elem));
+    CVTMI_TRY(fill(total));
+    for (const RangeOut &o : outs)
+        if (o.host) CVTMI_HIP(hipMemcpyAsync(o.host, o.stage->p, (size_t)total * o.elem, hipMemcpyDeviceToHost, st));
+    CVTMI_HIP(stream_wait(st));
+    return CVTMI_OK;
+}
+
 // a cvtmi_*_last_* getter: the small array a search left on its handle, copied under the lock it was written under
 template <class P, int N> CVTMI_INTERNAL void copy_last(P &pool, const int64_t (&last)[N], int64_t *out)
 {

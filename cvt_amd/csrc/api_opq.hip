@@ -1381,24 +1381,11 @@ int cvtmi_opq_range_search_ivf(cvtmi_opq_t h, const float *q, int64_t nq, int ro
         CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
         OpqRangeCall c;
         CVTMI_TRY(opq_range_count_leased(h, S, S.io_q.as<float>(), nq, rotate, nprobe, radius, cap > 0, nullptr, c, st));
-        CVTMI_HIP(hipMemcpyAsync(lims, c.lims_scratch, ((size_t)nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(stream_wait(st));
-        const int64_t total = lims[nq];
-        if (cap == 0 && !dist && !ids && !video) return CVTMI_OK;   // a count-only call: lims is the answer
-        if (total > cap)
-            return fail(CVTMI_ESPACE, "cvtmi_opq_range_search_ivf: %lld hits, room for %lld (lims holds the sizes)", (long long)total, (long long)cap);
-        if (total == 0) return CVTMI_OK;
-        const size_t db = (size_t)total * sizeof(float), ib = (size_t)total * sizeof(int64_t), vb = (size_t)total * sizeof(int32_t);
-        CVTMI_TRY(S.io_d.reserve(db));
-        CVTMI_TRY(S.io_i.reserve(ib));
-        if (video) CVTMI_TRY(S.io_v.reserve(vb));
-        CVTMI_TRY(opq_range_fill_leased(h, c, nq, nprobe, radius, c.lims_scratch, total, S.io_d.as<float>(), S.io_i.as<int64_t>(),
-                                        video ? S.io_v.as<int32_t>() : nullptr, st));
-        CVTMI_HIP(hipMemcpyAsync(dist, S.io_d.p, db, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(hipMemcpyAsync(ids, S.io_i.p, ib, hipMemcpyDeviceToHost, st));
-        if (video) CVTMI_HIP(hipMemcpyAsync(video, S.io_v.p, vb, hipMemcpyDeviceToHost, st));
-        CVTMI_HIP(stream_wait(st));
-        return CVTMI_OK;
+        const RangeOut outs[] = { { dist, &S.io_d, sizeof(float) }, { ids, &S.io_i, sizeof(int64_t) }, { video, &S.io_v, sizeof(int32_t) } };
+        return range_host_finish("cvtmi_opq_range_search_ivf", nq, cap, lims, c.lims_scratch, outs, st, [&](int64_t total) {
+            return opq_range_fill_leased(h, c, nq, nprobe, radius, c.lims_scratch, total, S.io_d.as<float>(), S.io_i.as<int64_t>(),
+                                         video ? S.io_v.as<int32_t>() : nullptr, st);
+        });
     });
 }
 

@@ -147,6 +147,42 @@ __device__ void topk_compact(TopKShared<QT, CAP> &s, int k, const Fix &fix = Fix
     }
 }
 
+// The key of an fp32 distance on its way into the selection: KEY_MAX is kept for "no row" (an entry past the end of the rows), so a
+// NaN distance, whose key it would be, sorts one below it.
+__device__ __forceinline__ uint32_t topk_key_f32(float d, bool valid)
+{
+    uint32_t kk = f32_key(d);
+    kk = kk == KEY_MAX ? KEY_MAX - 1 : kk;
+    return valid ? kk : KEY_MAX;
+}
+
+// The partial lists of a workgroup after its last topk_compact: for its queries q0 .. q0 + QT - 1 (those below nq) the kept entries
+// go to part_d / part_id [query][parts][k] at part `part`, padded to k with (0x7f800000, -1).  FBITS: the distance field is the float
+// the key stands for (fp32 metrics), else the key itself (the int32 distances of uint8 rows).  empty: write padding alone (tk unread).
+template <bool FBITS, int QT, int CAP>
+__device__ __forceinline__ void topk_write_parts(const TopKShared<QT, CAP> &tk, int q0, int nq, int part, int parts, int k,
+                                                 float *part_d, int64_t *part_id, bool empty = false)
+{
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+        const int qi = q0 + q;
+        if (qi >= nq) break;
+        const int cnt = empty ? 0 : tk.cnt[q];
+        const int64_t o = ((int64_t)qi * parts + part) * k;
+        for (int i = threadIdx.x; i < k; i += kBlock) {
+            if (i < cnt) {
+                const unsigned long long e = tk.buf[q][i];
+                const uint32_t kk = (uint32_t)(e >> 32);
+                part_d[o + i] = FBITS ? key_f32(kk) : __uint_as_float(kk);
+                part_id[o + i] = (int64_t)(uint32_t)e;
+            } else {
+                part_d[o + i] = __uint_as_float(0x7f800000u);
+                part_id[o + i] = -1;
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Barrier-free compaction for buffers of at most 256 entries: ONE WAVE per query keeps the buffer in
 // registers (entry idx = r*64 + lane, r < 4) and sorts it with a bitonic network whose exchanges at

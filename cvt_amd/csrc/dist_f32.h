@@ -61,10 +61,40 @@ __device__ __forceinline__ void dist_f32_row(const float *__restrict__ row, cons
     }
 }
 
-// The same distances for R rows of the 64-row blocked layout (flat_block_kernel: float4 c of a row lies 64 float4 behind its
-// float4 c - 1) with the queries behind uniform constant-address-space pointers, i.e. in SGPRs, as flat_f32_sq_kernel reads them.
-// Per lane and query the operations and their order are dist_f32_row's, hence the same bits.  LANES = 4 or 8, D % LANES == 0.
+// The queries of a workgroup as dist_f32_row reads them: queries group * QT .. + QT - 1 of Q[nq][D] copied to qs[QT][D] in LDS.  A
+// query past the batch is a copy of the last one (its result is never written).  The caller's next barrier makes qs visible.
+// I: the caller's index type (int or int64_t)
+template <int QT, class I>
+__device__ __forceinline__ void dist_f32_stage(float *qs, const float *Q, I group, I nq, int D)
+{
+    for (int i = threadIdx.x; i < QT * D; i += kBlock) {
+        const int q = i / D, d = i - q * D;
+        I qi = group * QT + q;
+        qi = qi < nq ? qi : nq - 1;
+        qs[i] = Q[(int64_t)qi * D + d];
+    }
+}
+
+// The same queries as dist_f32_blocked reads them: constant address space + uniform address = s_load_dword*, the values land in
+// SGPRs.  Clamped as above.
 typedef const __attribute__((address_space(4))) float dist_cfloat;
+template <int QT, class I>
+__device__ __forceinline__ void dist_f32_uniform(dist_cfloat *(&qp)[QT], const void *Q, I group, I nq, int D)
+{
+    dist_cfloat *Qc = (dist_cfloat *)(uintptr_t)Q;
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+        I qi = group * QT + q;
+        qi = qi < nq ? qi : nq - 1;
+        qp[q] = Qc + (int64_t)qi * D;   // wave-uniform
+    }
+}
+
+// The same distances for R rows of the 64-row blocked layout (flat_block_kernel: float4 c of a row lies 64 float4 behind its
+// float4 c - 1) with the queries behind uniform constant-address-space pointers, i.e. in SGPRs: every query value is the same for
+// all 64 lanes, so the multiply / subtract take it as a scalar operand and the distance loop has no LDS traffic at all.  The loop is
+// unrolled so that the scalar loads of 16 dimensions x QT queries are in flight together.
+// Per lane and query the operations and their order are dist_f32_row's, hence the same bits.  LANES = 4 or 8, D % LANES == 0.
 template <bool IP, int LANES, int QT, int R>
 __device__ __forceinline__ void dist_f32_blocked(const float4 *const (&rowp)[R], dist_cfloat *const (&qp)[QT], int D, float (&out)[R][QT])
 {

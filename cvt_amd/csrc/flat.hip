@@ -22,6 +22,7 @@
 #include "block_topk.h"
 #include "kernels.h"
 #include "dist_f32.h"
+#include "dist_u8.h"
 #include "launch.h"
 
 namespace cvtmi {
@@ -63,13 +64,7 @@ __global__ __launch_bounds__(kBlock) void flat_f32_kernel(const FlatArgs a)
     const int split = blockIdx.x % a.splits, group = blockIdx.x / a.splits;
     if (flat_skip<QT>(a, group)) return;
     const int tid = threadIdx.x;
-    const float *Q = reinterpret_cast<const float *>(a.q);
-    for (int i = tid; i < QT * a.D; i += kBlock) {
-        const int q = i / a.D, d = i - q * a.D;
-        int qi = group * QT + q;
-        qi = qi < a.nq ? qi : a.nq - 1;
-        qs[i] = Q[(int64_t)qi * a.D + d];
-    }
+    dist_f32_stage<QT>(qs, reinterpret_cast<const float *>(a.q), group, a.nq, a.D);
     topk_init(tk);
     __syncthreads();
     const int64_t row_begin = (int64_t)split * a.rows_per_split;
@@ -88,33 +83,13 @@ __global__ __launch_bounds__(kBlock) void flat_f32_kernel(const FlatArgs a)
             dist_f32_row<IP, LANES, QT>(X + (valid ? row : row_begin) * a.D, qs, a.D, d);
             pay[r] = (uint32_t)row;
 #pragma unroll
-            for (int q = 0; q < QT; ++q) {
-                uint32_t kk = f32_key(d[q]);
-                kk = kk == KEY_MAX ? KEY_MAX - 1 : kk;
-                key[r][q] = valid ? kk : KEY_MAX;
-            }
+            for (int q = 0; q < QT; ++q) key[r][q] = topk_key_f32(d[q], valid);
         }
         topk_tile<QT, FLAT_R, CAP, TRIG>(tk, a.k, tile, key, pay);
     }
     __syncthreads();
     topk_compact(tk, a.k);
-#pragma unroll
-    for (int q = 0; q < QT; ++q) {
-        const int qi = group * QT + q;
-        if (qi >= a.nq) break;
-        const int cnt = tk.cnt[q];
-        const int64_t o = ((int64_t)qi * a.splits + split) * a.k;
-        for (int i = tid; i < a.k; i += kBlock) {
-            if (i < cnt) {
-                const unsigned long long e = tk.buf[q][i];
-                a.part_d[o + i] = key_f32((uint32_t)(e >> 32));
-                a.part_id[o + i] = (int64_t)(uint32_t)e;
-            } else {
-                a.part_d[o + i] = __uint_as_float(0x7f800000u);
-                a.part_id[o + i] = -1;
-            }
-        }
-    }
+    topk_write_parts<true>(tk, group * QT, a.nq, split, a.splits, a.k, a.part_d, a.part_id);
 }
 
 // Same search with the queries in SCALAR registers.  The kernel above re-reads every query value from LDS for
@@ -130,16 +105,8 @@ __global__ __launch_bounds__(kBlock) void flat_f32_sq_kernel(const FlatArgs a)
     const int split = blockIdx.x % a.splits, group = blockIdx.x / a.splits;
     if (flat_skip<QT>(a, group)) return;
     const int tid = threadIdx.x;
-    // constant address space + uniform address = s_load_dword*: the values land in SGPRs
-    typedef const __attribute__((address_space(4))) float cfloat;
-    cfloat *Q = (cfloat *)(uintptr_t)a.q;
-    cfloat *qp[QT];
-#pragma unroll
-    for (int q = 0; q < QT; ++q) {
-        int qi = group * QT + q;
-        qi = qi < a.nq ? qi : a.nq - 1;
-        qp[q] = Q + (int64_t)qi * a.D;  // wave-uniform
-    }
+    dist_cfloat *qp[QT];
+    dist_f32_uniform<QT>(qp, a.q, group, a.nq, a.D);
     topk_init(tk);
     __syncthreads();
     const int64_t row_begin = (int64_t)split * a.rows_per_split;
@@ -163,74 +130,17 @@ __global__ __launch_bounds__(kBlock) void flat_f32_sq_kernel(const FlatArgs a)
             rowp[r] = reinterpret_cast<const float4 *>(X) + (rc >> 6) * (int64_t)(D >> 2) * 64 + (rc & 63);
             pay[r] = (uint32_t)row;
         }
-        float acc[FLAT_R][QT][LANES];
+        float d[FLAT_R][QT];
+        dist_f32_blocked<IP, LANES, QT, FLAT_R>(rowp, qp, D, d);   // D % LANES == 0 (the launcher picks LANES)
 #pragma unroll
         for (int r = 0; r < FLAT_R; ++r)
 #pragma unroll
-            for (int q = 0; q < QT; ++q)
-#pragma unroll
-                for (int l = 0; l < LANES; ++l) acc[r][q][l] = 0.0f;
-        // unrolled so that the scalar loads of 16 dimensions x QT queries (64 SGPRs) are in flight together
-#pragma unroll(16 / LANES)
-        for (int i = 0; i < D; i += LANES) {  // D % LANES == 0 (the launcher picks LANES)
-            float xv[FLAT_R][LANES];
-#pragma unroll
-            for (int r = 0; r < FLAT_R; ++r)
-#pragma unroll
-                for (int l4 = 0; l4 < LANES / 4; ++l4) {
-                    const float4 v = rowp[r][(int64_t)((i >> 2) + l4) * 64];
-                    xv[r][4 * l4 + 0] = v.x; xv[r][4 * l4 + 1] = v.y; xv[r][4 * l4 + 2] = v.z; xv[r][4 * l4 + 3] = v.w;
-                }
-#pragma unroll
-            for (int q = 0; q < QT; ++q) {
-#pragma unroll
-                for (int l = 0; l < LANES; ++l) {
-                    const float qv = qp[q][i + l];  // uniform address: scalar load
-#pragma unroll
-                    for (int r = 0; r < FLAT_R; ++r) {
-                        if constexpr (IP) {
-                            acc[r][q][l] = __fadd_rn(acc[r][q][l], __fmul_rn(qv, xv[r][l]));
-                        } else {
-                            const float t = __fsub_rn(qv, xv[r][l]);
-                            acc[r][q][l] = __fadd_rn(acc[r][q][l], __fmul_rn(t, t));
-                        }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < FLAT_R; ++r)
-#pragma unroll
-            for (int q = 0; q < QT; ++q) {
-                float sum = acc[r][q][0];
-#pragma unroll
-                for (int l = 1; l < LANES; ++l) sum = __fadd_rn(sum, acc[r][q][l]);
-                const float d = IP ? __fsub_rn(1.0f, sum) : sum;
-                uint32_t kk = f32_key(d);
-                kk = kk == KEY_MAX ? KEY_MAX - 1 : kk;
-                key[r][q] = valid[r] ? kk : KEY_MAX;
-            }
+            for (int q = 0; q < QT; ++q) key[r][q] = topk_key_f32(d[r][q], valid[r]);
         topk_tile<QT, FLAT_R, CAP, TRIG>(tk, a.k, tile, key, pay);
     }
     __syncthreads();
     topk_compact(tk, a.k);
-#pragma unroll
-    for (int q = 0; q < QT; ++q) {
-        const int qi = group * QT + q;
-        if (qi >= a.nq) break;
-        const int cnt = tk.cnt[q];
-        const int64_t o = ((int64_t)qi * a.splits + split) * a.k;
-        for (int i = tid; i < a.k; i += kBlock) {
-            if (i < cnt) {
-                const unsigned long long e = tk.buf[q][i];
-                a.part_d[o + i] = key_f32((uint32_t)(e >> 32));
-                a.part_id[o + i] = (int64_t)(uint32_t)e;
-            } else {
-                a.part_d[o + i] = __uint_as_float(0x7f800000u);
-                a.part_id[o + i] = -1;
-            }
-        }
-    }
+    topk_write_parts<true>(tk, group * QT, a.nq, split, a.splits, a.k, a.part_d, a.part_id);
 }
 
 // rows [row0, row0 + n) of a row-major [n][D] fp32 block -> the blocked layout above (D % 4 == 0):
@@ -292,26 +202,15 @@ __global__ __launch_bounds__(kBlock) void flat_u8_kernel(const FlatArgs a)
     extern __shared__ __attribute__((aligned(16))) uint32_t qw[];  // [QT][ceil(D/4)] packed query bytes
     __shared__ TopKShared<QT, CAP> tk;
     __shared__ uint32_t qq[QT];
+    constexpr int FORM = VEC ? U8_PIECES : U8_BYTES;
     const int split = blockIdx.x % a.splits, group = blockIdx.x / a.splits;
     if (flat_skip<QT>(a, group)) return;   // (round 6: the uint8 threshold filter's flagged queries come here under a predicate)
     const int tid = threadIdx.x;
-    const int Dq = (a.D >> 2) << 2;  // the reference drops a dim % 4 tail (space_l2.h:198)
-    const int W = Dq >> 2;           // 32-bit words per row that take part
-    const uint8_t *Q = reinterpret_cast<const uint8_t *>(a.q);
-    for (int i = tid; i < QT * W; i += kBlock) {
-        const int q = i / W, w = i - q * W;
-        int qi = group * QT + q;
-        qi = qi < a.nq ? qi : a.nq - 1;
-        const uint8_t *p = Q + (int64_t)qi * a.D + 4 * w;
-        qw[i] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-    }
+    const int W = a.D >> 2;   // 32-bit words per row that take part (dist_u8.h)
+    dist_u8_stage<FORM, QT>(qw, reinterpret_cast<const uint8_t *>(a.q), group, a.nq, a.D);
     topk_init(tk);
     __syncthreads();
-    if (tid < QT) {
-        uint32_t s = 0;
-        for (int w = 0; w < W; ++w) s = __builtin_amdgcn_udot4(qw[tid * W + w], qw[tid * W + w], s, false);
-        qq[tid] = s;
-    }
+    dist_u8_qnorms<FORM, QT>(qq, qw, W);
     __syncthreads();
     const int64_t row_begin = (int64_t)split * a.rows_per_split;
     int64_t row_end = row_begin + a.rows_per_split;
@@ -325,58 +224,17 @@ __global__ __launch_bounds__(kBlock) void flat_u8_kernel(const FlatArgs a)
         for (int r = 0; r < FLAT_R; ++r) {
             const int64_t row = base + r * kBlock + tid;
             const bool valid = row < row_end;
-            const uint8_t *xr = X + (valid ? row : row_begin) * a.D;
-            uint32_t xx = 0, qx[QT];
-#pragma unroll
-            for (int q = 0; q < QT; ++q) qx[q] = 0;
-            if constexpr (VEC) {
-                for (int w = 0; w < W; w += 4) {
-                    const uint4 v = *reinterpret_cast<const uint4 *>(xr + 4 * w);
-                    const uint32_t xv[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        xx = __builtin_amdgcn_udot4(xv[e], xv[e], xx, false);
-#pragma unroll
-                        for (int q = 0; q < QT; ++q) qx[q] = __builtin_amdgcn_udot4(qw[q * W + w + e], xv[e], qx[q], false);
-                    }
-                }
-            } else {
-                for (int w = 0; w < W; ++w) {
-                    const uint8_t *p = xr + 4 * w;
-                    const uint32_t xv = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-                    xx = __builtin_amdgcn_udot4(xv, xv, xx, false);
-#pragma unroll
-                    for (int q = 0; q < QT; ++q) qx[q] = __builtin_amdgcn_udot4(qw[q * W + w], xv, qx[q], false);
-                }
-            }
+            uint32_t d[QT];
+            dist_u8_row<FORM, QT>(X + (valid ? row : row_begin) * a.D, qw, qq, W, nullptr, d);
             pay[r] = (uint32_t)row;
 #pragma unroll
-            for (int q = 0; q < QT; ++q) {
-                const uint32_t d = qq[q] + xx - 2u * qx[q];  // exact: every term < 2^26
-                key[r][q] = valid ? d : KEY_MAX;
-            }
+            for (int q = 0; q < QT; ++q) key[r][q] = valid ? d[q] : KEY_MAX;
         }
         topk_tile<QT, FLAT_R, CAP, TRIG>(tk, a.k, tile, key, pay);
     }
     __syncthreads();
     topk_compact(tk, a.k);
-#pragma unroll
-    for (int q = 0; q < QT; ++q) {
-        const int qi = group * QT + q;
-        if (qi >= a.nq) break;
-        const int cnt = tk.cnt[q];
-        const int64_t o = ((int64_t)qi * a.splits + split) * a.k;
-        for (int i = tid; i < a.k; i += kBlock) {
-            if (i < cnt) {
-                const unsigned long long e = tk.buf[q][i];
-                a.part_d[o + i] = __uint_as_float((uint32_t)(e >> 32));  // int32 distance bits
-                a.part_id[o + i] = (int64_t)(uint32_t)e;
-            } else {
-                a.part_d[o + i] = __uint_as_float(0x7f800000u);
-                a.part_id[o + i] = -1;
-            }
-        }
-    }
+    topk_write_parts<false>(tk, group * QT, a.nq, split, a.splits, a.k, a.part_d, a.part_id);
 }
 
 // ---- selection behind the streaming matrix-core kernel (flat_u8_mstream_kernel, flat_mfma.hip; 1 .. 128 queries) ---------------

@@ -17,6 +17,7 @@
 
 #include "block_topk.h"
 #include "dist_f32.h"
+#include "dist_u8.h"
 #include "launch.h"
 #include "rm_common.h"
 
@@ -126,37 +127,6 @@ __device__ __forceinline__ void fm_rows(const FlatMaskedArgs &a, int64_t base, i
     }
 }
 
-// FBITS: the distance field is the float the key stands for (fp32 metrics), or the key itself (the int32 distances of uint8 rows)
-template <bool FBITS, int QT, int CAP>
-__device__ __forceinline__ void fm_write(TopKShared<QT, CAP> &tk, const FlatMaskedArgs &a, int group, int part, bool empty)
-{
-#pragma unroll
-    for (int q = 0; q < QT; ++q) {
-        const int qi = group * QT + q;
-        if (qi >= a.nq) break;
-        const int cnt = empty ? 0 : tk.cnt[q];
-        const int64_t o = ((int64_t)qi * a.parts + part) * a.k;
-        for (int i = threadIdx.x; i < a.k; i += kBlock) {
-            if (i < cnt) {
-                const unsigned long long e = tk.buf[q][i];
-                const uint32_t kk = (uint32_t)(e >> 32);
-                a.part_d[o + i] = FBITS ? key_f32(kk) : __uint_as_float(kk);
-                a.part_id[o + i] = (int64_t)(uint32_t)e;
-            } else {
-                a.part_d[o + i] = __uint_as_float(0x7f800000u);
-                a.part_id[o + i] = -1;
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ uint32_t fm_key(float d, bool valid)
-{
-    uint32_t kk = f32_key(d);
-    kk = kk == KEY_MAX ? KEY_MAX - 1 : kk;
-    return valid ? kk : KEY_MAX;
-}
-
 // fp32 rows in the blocked layout (D % 4 == 0), queries in SGPRs: flat_f32_sq_kernel
 template <bool IP, int LANES, int QT, int CAP = FM_CAP, int TRIG = FM_TRIG>
 __global__ __launch_bounds__(kBlock) void flat_masked_f32_sq_kernel(const FlatMaskedArgs a)
@@ -166,17 +136,11 @@ __global__ __launch_bounds__(kBlock) void flat_masked_f32_sq_kernel(const FlatMa
     int64_t begin, end;
     const int part = fm_slice(a, group, blockIdx.x % a.parts, &begin, &end);
     if (begin >= end) {   // (workgroup-uniform)
-        fm_write<true>(tk, a, group, part, true);
+        topk_write_parts<true>(tk, group * QT, a.nq, part, a.parts, a.k, a.part_d, a.part_id, true);
         return;
     }
-    dist_cfloat *Q = (dist_cfloat *)(uintptr_t)a.q;
     dist_cfloat *qp[QT];
-#pragma unroll
-    for (int q = 0; q < QT; ++q) {
-        int qi = group * QT + q;
-        qi = qi < a.nq ? qi : a.nq - 1;
-        qp[q] = Q + (int64_t)qi * a.D;   // wave-uniform
-    }
+    dist_f32_uniform<QT>(qp, a.q, group, a.nq, a.D);
     topk_init(tk);
     __syncthreads();
     const float4 *X = reinterpret_cast<const float4 *>(a.data);
@@ -194,12 +158,12 @@ __global__ __launch_bounds__(kBlock) void flat_masked_f32_sq_kernel(const FlatMa
 #pragma unroll
         for (int r = 0; r < FM_R; ++r)
 #pragma unroll
-            for (int q = 0; q < QT; ++q) key[r][q] = fm_key(d[r][q], valid[r]);
+            for (int q = 0; q < QT; ++q) key[r][q] = topk_key_f32(d[r][q], valid[r]);
         topk_tile<QT, FM_R, CAP, TRIG>(tk, a.k, tile, key, pay);
     }
     __syncthreads();
     topk_compact(tk, a.k);
-    fm_write<true>(tk, a, group, part, false);
+    topk_write_parts<true>(tk, group * QT, a.nq, part, a.parts, a.k, a.part_d, a.part_id);
 }
 
 // fp32 row-major rows (D % 4 != 0), queries in LDS: flat_f32_kernel
@@ -212,17 +176,10 @@ __global__ __launch_bounds__(kBlock) void flat_masked_f32_kernel(const FlatMaske
     int64_t begin, end;
     const int part = fm_slice(a, group, blockIdx.x % a.parts, &begin, &end);
     if (begin >= end) {
-        fm_write<true>(tk, a, group, part, true);
+        topk_write_parts<true>(tk, group * QT, a.nq, part, a.parts, a.k, a.part_d, a.part_id, true);
         return;
     }
-    const int tid = threadIdx.x;
-    const float *Q = reinterpret_cast<const float *>(a.q);
-    for (int i = tid; i < QT * a.D; i += kBlock) {
-        const int q = i / a.D, d = i - q * a.D;
-        int qi = group * QT + q;
-        qi = qi < a.nq ? qi : a.nq - 1;
-        fm_qs[i] = Q[(int64_t)qi * a.D + d];
-    }
+    dist_f32_stage<QT>(fm_qs, reinterpret_cast<const float *>(a.q), group, a.nq, a.D);
     topk_init(tk);
     __syncthreads();
     const float *X = reinterpret_cast<const float *>(a.data);
@@ -236,13 +193,13 @@ __global__ __launch_bounds__(kBlock) void flat_masked_f32_kernel(const FlatMaske
             float d[QT];
             dist_f32_row<IP, 1, QT>(X + (int64_t)pay[r] * a.D, fm_qs, a.D, d);
 #pragma unroll
-            for (int q = 0; q < QT; ++q) key[r][q] = fm_key(d[q], valid[r]);
+            for (int q = 0; q < QT; ++q) key[r][q] = topk_key_f32(d[q], valid[r]);
         }
         topk_tile<QT, FM_R, CAP, TRIG>(tk, a.k, tile, key, pay);
     }
     __syncthreads();
     topk_compact(tk, a.k);
-    fm_write<true>(tk, a, group, part, false);
+    topk_write_parts<true>(tk, group * QT, a.nq, part, a.parts, a.k, a.part_d, a.part_id);
 }
 
 // uint8 rows: flat_u8_kernel.  VEC: rows are whole 16-byte pieces (D % 16 == 0)
@@ -252,30 +209,19 @@ __global__ __launch_bounds__(kBlock) void flat_masked_u8_kernel(const FlatMasked
     extern __shared__ __attribute__((aligned(16))) uint32_t fm_qw[];   // [QT][D / 4] packed query bytes
     __shared__ TopKShared<QT, CAP> tk;
     __shared__ uint32_t qq[QT];
+    constexpr int FORM = VEC ? U8_PIECES : U8_BYTES;
     const int group = blockIdx.x / a.parts;
     int64_t begin, end;
     const int part = fm_slice(a, group, blockIdx.x % a.parts, &begin, &end);
     if (begin >= end) {
-        fm_write<false>(tk, a, group, part, true);
+        topk_write_parts<false>(tk, group * QT, a.nq, part, a.parts, a.k, a.part_d, a.part_id, true);
         return;
     }
-    const int tid = threadIdx.x;
-    const int W = a.D >> 2;   // 32-bit words per row that take part: the D % 4 tail is dropped, as L2SqrI does
-    const uint8_t *Q = reinterpret_cast<const uint8_t *>(a.q);
-    for (int i = tid; i < QT * W; i += kBlock) {
-        const int q = i / W, w = i - q * W;
-        int qi = group * QT + q;
-        qi = qi < a.nq ? qi : a.nq - 1;
-        const uint8_t *p = Q + (int64_t)qi * a.D + 4 * w;
-        fm_qw[i] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-    }
+    const int W = a.D >> 2;   // 32-bit words per row that take part (dist_u8.h)
+    dist_u8_stage<FORM, QT>(fm_qw, reinterpret_cast<const uint8_t *>(a.q), group, a.nq, a.D);
     topk_init(tk);
     __syncthreads();
-    if (tid < QT) {
-        uint32_t s = 0;
-        for (int w = 0; w < W; ++w) s = __builtin_amdgcn_udot4(fm_qw[tid * W + w], fm_qw[tid * W + w], s, false);
-        qq[tid] = s;
-    }
+    dist_u8_qnorms<FORM, QT>(qq, fm_qw, W);
     __syncthreads();
     const uint8_t *X = reinterpret_cast<const uint8_t *>(a.data);
     int tile = 0;
@@ -285,6 +231,8 @@ __global__ __launch_bounds__(kBlock) void flat_masked_u8_kernel(const FlatMasked
         fm_rows(a, base, begin, end, pay, valid);
 #pragma unroll
         for (int r = 0; r < FM_R; ++r) {
+            // dist_u8_row's loops, written out: behind the call the 4-query kernels are scheduled differently and the sparse-mask
+            // cases of tools/flat_masked_times.py run up to 1 % slower (10 M x 512 bytes, 16 queries, 0.1 %: 0.1203 -> 0.1213 ms)
             const uint8_t *xr = X + (int64_t)pay[r] * a.D;
             uint32_t xx = 0, qx[QT];
 #pragma unroll
@@ -319,7 +267,7 @@ __global__ __launch_bounds__(kBlock) void flat_masked_u8_kernel(const FlatMasked
     }
     __syncthreads();
     topk_compact(tk, a.k);
-    fm_write<false>(tk, a, group, part, false);
+    topk_write_parts<false>(tk, group * QT, a.nq, part, a.parts, a.k, a.part_d, a.part_id);
 }
 
 // ---- host side ----

@@ -22,8 +22,10 @@
 #include <algorithm>
 
 #include "dist_f32.h"
+#include "dist_u8.h"
 #include "kernels.h"
 #include "launch.h"
+#include "range_common.h"
 
 namespace cvtmi {
 
@@ -90,35 +92,15 @@ template <int QT, bool FINAL>
 __device__ __forceinline__ void flat_range_place(const FlatRangeArgs &a, FlatRangeGroup<QT> &g, uint32_t (*wcnt)[QT][4], int tile, int64_t row,
                                                  const bool (&hit)[QT], const uint32_t (&bits)[QT])
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long bal[QT];
-#pragma unroll
-    for (int q = 0; q < QT; ++q) {
-        bal[q] = __ballot(hit[q]);
-        if (lane == 0) wcnt[tile & 1][q][wave] = (uint32_t)__popcll(bal[q]);
-    }
-    __syncthreads();   // (two count buffers: the next tile's writes cannot pass this tile's reads)
-#pragma unroll
-    for (int q = 0; q < QT; ++q) {
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const uint32_t c = wcnt[tile & 1][q][w];
-            before += w < wave ? c : 0u;
-            total += c;
+    range_rank<QT>(wcnt, tile, hit, g.run, [&](int q, uint32_t rank) {
+        if (FINAL) {
+            const int64_t o = g.out0[q] + rank;
+            a.dist[o] = bits[q];
+            a.out_labels[o] = a.labels ? a.labels[row] : a.id_base + row;
+        } else if (rank < a.C) {
+            a.spill[g.cell[q] * (int64_t)a.C + rank] = ((unsigned long long)bits[q] << 32) | (uint32_t)row;
         }
-        if (hit[q]) {
-            const uint32_t rank = g.run[q] + before + (uint32_t)__popcll(bal[q] & ((1ull << lane) - 1ull));
-            if (FINAL) {
-                const int64_t o = g.out0[q] + rank;
-                a.dist[o] = bits[q];
-                a.out_labels[o] = a.labels ? a.labels[row] : a.id_base + row;
-            } else if (rank < a.C) {
-                a.spill[g.cell[q] * (int64_t)a.C + rank] = ((unsigned long long)bits[q] << 32) | (uint32_t)row;
-            }
-        }
-        g.run[q] += total;
-    }
+    });
 }
 
 template <int QT, bool FINAL>
@@ -145,10 +127,8 @@ __global__ __launch_bounds__(kBlock) void flat_range_f32_blocked_kernel(const Fl
     FlatRangeGroup<QT> g;
     if (!flat_range_open<QT, FINAL>(a, g)) { flat_range_skip<QT, FINAL>(a, g); return; }
     const int tid = threadIdx.x;
-    dist_cfloat *Q = (dist_cfloat *)(uintptr_t)a.q;
     dist_cfloat *qp[QT];
-#pragma unroll
-    for (int q = 0; q < QT; ++q) qp[q] = Q + g.qi[q] * a.D;   // wave-uniform
+    dist_f32_uniform<QT>(qp, a.q, g.group, a.nq, a.D);
     const float4 *X = reinterpret_cast<const float4 *>(a.data);
     const float t = __uint_as_float(a.thr);
     const int D = a.D;
@@ -190,13 +170,7 @@ __global__ __launch_bounds__(kBlock) void flat_range_f32_rows_kernel(const FlatR
     FlatRangeGroup<QT> g;
     if (!flat_range_open<QT, FINAL>(a, g)) { flat_range_skip<QT, FINAL>(a, g); return; }
     const int tid = threadIdx.x;
-    const float *Q = reinterpret_cast<const float *>(a.q);
-    for (int i = tid; i < QT * a.D; i += kBlock) {
-        const int q = i / a.D, d = i - q * a.D;
-        int64_t qi = g.group * QT + q;
-        qi = qi < a.nq ? qi : a.nq - 1;
-        qs[i] = Q[qi * a.D + d];
-    }
+    dist_f32_stage<QT>(qs, reinterpret_cast<const float *>(a.q), g.group, a.nq, a.D);
     __syncthreads();
     const float *X = reinterpret_cast<const float *>(a.data);
     const float t = __uint_as_float(a.thr);
@@ -218,8 +192,7 @@ __global__ __launch_bounds__(kBlock) void flat_range_f32_rows_kernel(const FlatR
     flat_range_close<QT, FINAL>(a, g);
 }
 
-// ---- uint8 rows.  MODE 0: single bytes (any D); 1: 16-byte pieces (D % 16 == 0), |x|^2 summed here; 2: 16-byte pieces with the
-// handle's norms: q' = q - 128, x' = x - 128 (one xor per word), |q'|^2 + |x'|^2 - 2<q',x'> on the signed dot4 -- the same integer ----
+// ---- uint8 rows.  MODE: dist_u8.h's forms -- U8_BYTES (any D), U8_PIECES (D % 16 == 0), U8_SIGNED (... with the handle's norms) ----
 template <int MODE, int QT, bool FINAL>
 __global__ __launch_bounds__(kBlock) void flat_range_u8_kernel(const FlatRangeArgs a)
 {
@@ -229,82 +202,26 @@ __global__ __launch_bounds__(kBlock) void flat_range_u8_kernel(const FlatRangeAr
     FlatRangeGroup<QT> g;
     if (!flat_range_open<QT, FINAL>(a, g)) { flat_range_skip<QT, FINAL>(a, g); return; }
     const int tid = threadIdx.x;
-    const int W = a.D >> 2;   // 32-bit words per row that take part: the reference drops a dim % 4 tail (space_l2.h:198)
-    const uint8_t *Q = reinterpret_cast<const uint8_t *>(a.q);
-    for (int i = tid; i < QT * W; i += kBlock) {
-        const int q = i / W, w = i - q * W;
-        int64_t qi = g.group * QT + q;
-        qi = qi < a.nq ? qi : a.nq - 1;
-        const uint8_t *p = Q + qi * a.D + 4 * w;
-        const uint32_t v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-        qw[i] = MODE == 2 ? v ^ 0x80808080u : v;
-    }
+    const int W = a.D >> 2;   // 32-bit words per row that take part (dist_u8.h)
+    dist_u8_stage<MODE, QT>(qw, reinterpret_cast<const uint8_t *>(a.q), g.group, a.nq, a.D);
     __syncthreads();
-    if (tid < QT) {
-        uint32_t s = 0;
-        for (int w = 0; w < W; ++w) {
-            const uint32_t v = qw[tid * W + w];
-            s = MODE == 2 ? (uint32_t)__builtin_amdgcn_sdot4((int)v, (int)v, (int)s, false) : __builtin_amdgcn_udot4(v, v, s, false);
-        }
-        qq[tid] = s;
-    }
+    dist_u8_qnorms<MODE, QT>(qq, qw, W);
     __syncthreads();
+    // QT > 1: U x 16 bytes of the row are requested before the first is used -- with one 16-byte load in flight per lane the
+    // walk waits for memory latency, not bandwidth (10 M x 512-d, 8 queries: 1.84 -> 1.35 ms; U = 8 gains nothing more).
+    // One query: the plain loop, which the compiler already unrolls with its loads ahead (1.00 ms against 1.16 - 1.24)
+    constexpr int U = QT == 1 ? 1 : 4;
     const uint8_t *X = reinterpret_cast<const uint8_t *>(a.data);
     int tile = 0;
     for (int64_t base = g.row_begin; base < g.row_end; base += kBlock, ++tile) {
         const int64_t row = base + tid;
         const bool valid = row < g.row_end;
         const int64_t rc = valid ? row : g.row_begin;
-        const uint8_t *xr = X + rc * a.D;
-        uint32_t xx = 0, qx[QT];
-#pragma unroll
-        for (int q = 0; q < QT; ++q) qx[q] = 0;
-        if constexpr (MODE == 0) {
-            for (int w = 0; w < W; ++w) {
-                const uint8_t *p = xr + 4 * w;
-                const uint32_t xv = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-                xx = __builtin_amdgcn_udot4(xv, xv, xx, false);
-#pragma unroll
-                for (int q = 0; q < QT; ++q) qx[q] = __builtin_amdgcn_udot4(qw[q * W + w], xv, qx[q], false);
-            }
-        } else {
-            // QT > 1: U x 16 bytes of the row are requested before the first is used -- with one 16-byte load in flight per lane the
-            // walk waits for memory latency, not bandwidth (10 M x 512-d, 8 queries: 1.84 -> 1.35 ms; U = 8 gains nothing more).
-            // One query: the plain loop, which the compiler already unrolls with its loads ahead (1.00 ms against 1.16 - 1.24)
-            constexpr int U = QT == 1 ? 1 : 4;
-            for (int w0 = 0; w0 < W; w0 += 4 * U) {
-                uint4 v[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (w0 + 4 * u < W) v[u] = *reinterpret_cast<const uint4 *>(xr + 4 * (w0 + 4 * u));   // (uniform: W is)
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int w = w0 + 4 * u;
-                    if (w >= W) break;
-                    const uint32_t xv[4] = { v[u].x, v[u].y, v[u].z, v[u].w };
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        if constexpr (MODE == 2) {
-                            const int xs = (int)(xv[e] ^ 0x80808080u);
-#pragma unroll
-                            for (int q = 0; q < QT; ++q) qx[q] = (uint32_t)__builtin_amdgcn_sdot4((int)qw[q * W + w + e], xs, (int)qx[q], false);
-                        } else {
-                            xx = __builtin_amdgcn_udot4(xv[e], xv[e], xx, false);
-#pragma unroll
-                            for (int q = 0; q < QT; ++q) qx[q] = __builtin_amdgcn_udot4(qw[q * W + w + e], xv[e], qx[q], false);
-                        }
-                    }
-                }
-            }
-            if constexpr (MODE == 2) xx = (uint32_t)a.norms[rc];
-        }
         bool hit[QT];
         uint32_t bits[QT];
+        dist_u8_row<MODE, QT, U>(X + rc * a.D, qw, qq, W, MODE == U8_SIGNED ? a.norms + rc : nullptr, bits);
 #pragma unroll
-        for (int q = 0; q < QT; ++q) {
-            bits[q] = qq[q] + xx - 2u * qx[q];   // exact modulo 2^32, and the distance is below 2^31 (D <= 4096)
-            hit[q] = valid && g.active[q] && bits[q] < a.thr;
-        }
+        for (int q = 0; q < QT; ++q) hit[q] = valid && g.active[q] && bits[q] < a.thr;
         flat_range_place<QT, FINAL>(a, g, wcnt, tile, row, hit, bits);
     }
     flat_range_close<QT, FINAL>(a, g);
@@ -324,56 +241,6 @@ __global__ __launch_bounds__(kBlock) void flat_range_fill_kernel(const FlatRange
         const int64_t row = (int64_t)(uint32_t)w;
         a.dist[out0 + i] = (uint32_t)(w >> 32);
         a.out_labels[out0 + i] = a.labels ? a.labels[row] : a.id_base + row;
-    }
-}
-
-// inclusive scan over the workgroup; s[kBlock - 1] holds the total until the caller's next barrier
-template <class T>
-__device__ __forceinline__ T flat_range_block_scan(T v, T *s)
-{
-    const int tid = threadIdx.x;
-    s[tid] = v;
-    __syncthreads();
-    for (int o = 1; o < kBlock; o <<= 1) {
-        const T t = tid >= o ? s[tid - o] : (T)0;
-        __syncthreads();
-        s[tid] += t;
-        __syncthreads();
-    }
-    return s[tid];
-}
-
-// one workgroup per query: part_off = exclusive scan of its part counts, lims[q + 1] = its hit count (summed over the batch below)
-__global__ __launch_bounds__(kBlock) void flat_range_part_offsets_kernel(const uint32_t *__restrict__ part_cnt, int parts,
-                                                                         uint32_t *__restrict__ part_off, int64_t *__restrict__ lims)
-{
-    __shared__ uint32_t s[kBlock];
-    const int64_t qi = blockIdx.x;
-    uint32_t run = 0;   // (a query's hits are distinct rows: fewer than 2^32)
-    for (int base = 0; base < parts; base += kBlock) {
-        const int i = base + threadIdx.x;
-        const uint32_t v = i < parts ? part_cnt[qi * parts + i] : 0u;
-        const uint32_t incl = flat_range_block_scan(v, s);
-        if (i < parts) part_off[qi * parts + i] = run + incl - v;
-        run += s[kBlock - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) lims[qi + 1] = (int64_t)run;
-}
-
-// one workgroup: lims[0] = 0, lims[q + 1] = hits of queries 0 .. q
-__global__ __launch_bounds__(kBlock) void flat_range_lims_kernel(int64_t *__restrict__ lims, int64_t nq)
-{
-    __shared__ unsigned long long s[kBlock];
-    unsigned long long run = 0;
-    if (threadIdx.x == 0) lims[0] = 0;
-    for (int64_t base = 0; base < nq; base += kBlock) {
-        const int64_t i = base + threadIdx.x;
-        const unsigned long long v = i < nq ? (unsigned long long)lims[i + 1] : 0ull;
-        const unsigned long long incl = flat_range_block_scan(v, s);
-        if (i < nq) lims[i + 1] = (int64_t)(run + incl);
-        run += s[kBlock - 1];
-        __syncthreads();
     }
 }
 
@@ -403,26 +270,14 @@ FlatRangePlan plan_flat_range(int metric, int D, bool has_norms, int64_t n, int6
     p.parts = (int)std::min<int64_t>(blocks_for(rows, rpp), 0x7fffffff);
     int64_t c = spill < 0 ? kFlatRangeSpill : spill;
     c = std::min(c, rpp);
-    const int64_t fit = (int64_t)(kFlatRangeSpillBytes / ((size_t)std::max<int64_t>(nq, 1) * p.parts * sizeof(unsigned long long)));
-    p.spill = std::min(c, fit);
+    p.spill = std::min(c, range_spill_fit(kFlatRangeSpillBytes, nq, p.parts));
     p.spill_bytes = (size_t)std::max<int64_t>(nq, 0) * p.parts * (size_t)p.spill * sizeof(unsigned long long);
     return p;
 }
 
-static size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-
 size_t flat_range_carve(void *base, const FlatRangePlan &p, int64_t nq, FlatRangeBufs *b)
 {
-    const size_t cells = (size_t)nq * p.parts;
-    const size_t o_cnt = 0, o_off = o_cnt + up16(cells * sizeof(uint32_t)), o_spill = o_off + up16(cells * sizeof(uint32_t));
-    const size_t end = o_spill + up16(cells * (size_t)p.spill * sizeof(unsigned long long));
-    if (base && b) {
-        char *c = static_cast<char *>(base);
-        b->part_cnt = reinterpret_cast<uint32_t *>(c + o_cnt);
-        b->part_off = reinterpret_cast<uint32_t *>(c + o_off);
-        b->spill = reinterpret_cast<unsigned long long *>(c + o_spill);
-    }
-    return end;
+    return range_carve(base, 0, nq, p.parts, p.spill, b);
 }
 
 static int flat_range_args(FlatRangeArgs &a, const FlatRangeRows &x, const void *q, int64_t nq, uint32_t thr, const FlatRangePlan &p,
@@ -484,8 +339,7 @@ int launch_flat_range_count(const FlatRangeRows &x, const void *q, int64_t nq, u
     FlatRangeArgs a;
     CVTMI_TRY(flat_range_args(a, x, q, nq, thr, p, b, lims));
     CVTMI_TRY(flat_range_walk<false>("flat_range_scan_kernel", a, x, p, st));
-    CVTMI_TRY(launch("flat_range_part_offsets_kernel", flat_range_part_offsets_kernel, nq, kBlock, 0, st, b.part_cnt, p.parts, b.part_off, lims));
-    return launch("flat_range_lims_kernel", flat_range_lims_kernel, 1, kBlock, 0, st, lims, nq);
+    return launch_range_offsets(b, p.parts, nq, lims, st);
 }
 
 int launch_flat_range_fill(const FlatRangeRows &x, const void *q, int64_t nq, uint32_t thr, const FlatRangePlan &p, const FlatRangeBufs &b,

@@ -21,6 +21,7 @@
 #include "ivf_table.h"
 #include "kernels.h"
 #include "launch.h"
+#include "range_common.h"
 
 namespace cvtmi {
 
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(128) void ivf_range_order_kernel(const int32_t *__r
 // The rows of part blockIdx.x = (query * groups + group) * pieces + piece, hits in the order of the copy.
 // FINAL = false: hits of rank < C to the part's spill segment, the count to part_cnt.  FINAL = true: hits to their final places.
 template <bool FINAL>
-__device__ __forceinline__ void ivf_range_walk(const IvfRangeArgs &a, float *sm, uint32_t (*wcnt)[4])
+__device__ __forceinline__ void ivf_range_walk(const IvfRangeArgs &a, float *sm, uint32_t (*wcnt)[1][4])
 {
     float *res = sm;
     float *lut = sm + ((a.D + 3) & ~3);
@@ -70,12 +71,12 @@ __device__ __forceinline__ void ivf_range_walk(const IvfRangeArgs &a, float *sm,
     const int64_t qg = blockIdx.x / (unsigned)a.pieces;
     const int g = (int)(qg % a.groups);
     const int64_t qi = qg / a.groups;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int M = a.M;
     int64_t out0 = 0;
     if (FINAL) out0 = a.lims[qi] + a.part_off[blk];
     const int s0 = g * a.G, s1 = s0 + a.G < a.nprobe ? s0 + a.G : a.nprobe;
-    uint32_t run = 0;   // hits of the part so far (workgroup-uniform)
+    uint32_t run[1] = { 0 };   // hits of the part so far (workgroup-uniform)
     int tile = 0;
     for (int s = s0; s < s1; ++s) {
         const int l = a.order[qi * a.nprobe + s];
@@ -99,19 +100,8 @@ __device__ __forceinline__ void ivf_range_walk(const IvfRangeArgs &a, float *sm,
             } else if (have) {
                 sc = ivf_score_row(lut, a.codes + r * M, M);
             }
-            const bool hit = have && sc < a.radius;
-            const unsigned long long bal = __ballot(hit);
-            if (lane == 0) wcnt[tile & 1][wave] = (uint32_t)__popcll(bal);
-            __syncthreads();   // (two count buffers: the next tile's writes cannot pass this tile's reads)
-            uint32_t before = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const uint32_t c = wcnt[tile & 1][w];
-                before += w < wave ? c : 0u;
-                total += c;
-            }
-            if (hit) {
-                const uint32_t rank = run + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+            const bool hit[1] = { have && sc < a.radius };
+            range_rank<1>(wcnt, tile, hit, run, [&](int, uint32_t rank) {   // (holds a barrier)
                 if (FINAL) {
                     const int64_t o = out0 + rank;
                     a.dist[o] = sc;
@@ -120,25 +110,24 @@ __device__ __forceinline__ void ivf_range_walk(const IvfRangeArgs &a, float *sm,
                 } else if (rank < a.C) {
                     a.spill[blk * a.C + rank] = ((unsigned long long)__float_as_uint(sc) << 32) | (uint32_t)r;
                 }
-            }
-            run += total;
+            });
         }
         // (every thread passed the last tile's barrier after its last table read: the next list may overwrite res and lut)
     }
-    if (!FINAL && tid == 0) a.part_cnt[blk] = run;
+    if (!FINAL && tid == 0) a.part_cnt[blk] = run[0];
 }
 
 __global__ __launch_bounds__(kBlock) void ivf_range_scan_kernel(const IvfRangeArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];  // res[D rounded up to 4] + lut[M][256]
-    __shared__ uint32_t wcnt[2][4];
+    __shared__ uint32_t wcnt[2][1][4];
     ivf_range_walk<false>(a, sm, wcnt);
 }
 
 __global__ __launch_bounds__(kBlock) void ivf_range_rescan_kernel(const IvfRangeArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    __shared__ uint32_t wcnt[2][4];
+    __shared__ uint32_t wcnt[2][1][4];
     if (a.lims[a.nq] > a.cap || a.part_cnt[blockIdx.x] <= a.C) return;   // workgroup-uniform
     ivf_range_walk<true>(a, sm, wcnt);
 }
@@ -160,33 +149,18 @@ __global__ __launch_bounds__(kBlock) void ivf_range_fill_kernel(const IvfRangeAr
     }
 }
 
-// inclusive scan over the workgroup; s[kBlock - 1] holds the total until the caller's next barrier
-template <class T>
-__device__ __forceinline__ T ivf_range_block_scan(T v, T *s)
-{
-    const int tid = threadIdx.x;
-    s[tid] = v;
-    __syncthreads();
-    for (int o = 1; o < kBlock; o <<= 1) {
-        const T t = tid >= o ? s[tid - o] : (T)0;
-        __syncthreads();
-        s[tid] += t;
-        __syncthreads();
-    }
-    return s[tid];
-}
-
+// ---- offsets, for both range searches (launch_range_offsets) ----
 // one workgroup per query: part_off = exclusive scan of its part counts, lims[q + 1] = its hit count (summed over the batch below)
-__global__ __launch_bounds__(kBlock) void ivf_range_part_offsets_kernel(const uint32_t *__restrict__ part_cnt, int parts,
-                                                                        uint32_t *__restrict__ part_off, int64_t *__restrict__ lims)
+__global__ __launch_bounds__(kBlock) void range_part_offsets_kernel(const uint32_t *__restrict__ part_cnt, int parts,
+                                                                    uint32_t *__restrict__ part_off, int64_t *__restrict__ lims)
 {
     __shared__ uint32_t s[kBlock];
     const int64_t qi = blockIdx.x;
-    uint32_t run = 0;   // (a query's hits are distinct entries: fewer than 2^32)
+    uint32_t run = 0;   // (a query's hits are distinct rows or entries: fewer than 2^32)
     for (int base = 0; base < parts; base += kBlock) {
         const int i = base + threadIdx.x;
         const uint32_t v = i < parts ? part_cnt[qi * parts + i] : 0u;
-        const uint32_t incl = ivf_range_block_scan(v, s);
+        const uint32_t incl = range_block_scan(v, s);
         if (i < parts) part_off[qi * parts + i] = run + incl - v;
         run += s[kBlock - 1];
         __syncthreads();
@@ -195,7 +169,7 @@ __global__ __launch_bounds__(kBlock) void ivf_range_part_offsets_kernel(const ui
 }
 
 // one workgroup: lims[0] = 0, lims[q + 1] = hits of queries 0 .. q
-__global__ __launch_bounds__(kBlock) void ivf_range_lims_kernel(int64_t *__restrict__ lims, int64_t nq)
+__global__ __launch_bounds__(kBlock) void range_lims_kernel(int64_t *__restrict__ lims, int64_t nq)
 {
     __shared__ unsigned long long s[kBlock];
     unsigned long long run = 0;
@@ -203,11 +177,17 @@ __global__ __launch_bounds__(kBlock) void ivf_range_lims_kernel(int64_t *__restr
     for (int64_t base = 0; base < nq; base += kBlock) {
         const int64_t i = base + threadIdx.x;
         const unsigned long long v = i < nq ? (unsigned long long)lims[i + 1] : 0ull;
-        const unsigned long long incl = ivf_range_block_scan(v, s);
+        const unsigned long long incl = range_block_scan(v, s);
         if (i < nq) lims[i + 1] = (int64_t)(run + incl);
         run += s[kBlock - 1];
         __syncthreads();
     }
+}
+
+int launch_range_offsets(const RangeBufs &b, int parts, int64_t nq, int64_t *lims, hipStream_t st)
+{
+    CVTMI_TRY(launch("range_part_offsets_kernel", range_part_offsets_kernel, nq, kBlock, 0, st, b.part_cnt, parts, b.part_off, lims));
+    return launch("range_lims_kernel", range_lims_kernel, 1, kBlock, 0, st, lims, nq);
 }
 
 // Grid rules (pure host logic): plan_ivf_search's rules 1-3 with nothing to merge, then
@@ -227,7 +207,7 @@ IvfRangePlan plan_ivf_range(int64_t nq, int nprobe, int64_t longest, int64_t spi
     }
     const int64_t part_rows = g.pieces > 1 ? g.rows_per_piece : (int64_t)g.G * std::max<int64_t>(longest, 1);
     p.spill = std::max<int64_t>(0, std::min<int64_t>(std::min(spill, part_rows), 0x7fffffff));
-    const int64_t fit = (int64_t)(cap_bytes / ((size_t)std::max<int64_t>(nq, 1) * g.parts() * sizeof(unsigned long long)));
+    const int64_t fit = range_spill_fit(cap_bytes, nq, g.parts());
     if (p.spill > fit) {
         p.spill = fit;
         g.rule = 4;
@@ -235,21 +215,10 @@ IvfRangePlan plan_ivf_range(int64_t nq, int nprobe, int64_t longest, int64_t spi
     return p;
 }
 
-static size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-
 size_t ivf_range_carve(void *base, const IvfRangePlan &p, int64_t nq, int nprobe, IvfRangeBufs *b)
 {
-    const size_t cells = (size_t)nq * p.grid.parts();
-    const size_t o_order = 0, o_cnt = o_order + up16((size_t)nq * nprobe * sizeof(int32_t)), o_off = o_cnt + up16(cells * sizeof(uint32_t));
-    const size_t o_spill = o_off + up16(cells * sizeof(uint32_t)), end = o_spill + up16(cells * (size_t)p.spill * sizeof(unsigned long long));
-    if (base && b) {
-        char *c = static_cast<char *>(base);
-        b->order = reinterpret_cast<int32_t *>(c + o_order);
-        b->part_cnt = reinterpret_cast<uint32_t *>(c + o_cnt);
-        b->part_off = reinterpret_cast<uint32_t *>(c + o_off);
-        b->spill = reinterpret_cast<unsigned long long *>(c + o_spill);
-    }
-    return end;
+    if (base && b) b->order = static_cast<int32_t *>(base);
+    return range_carve(base, range_up16((size_t)nq * nprobe * sizeof(int32_t)), nq, p.grid.parts(), p.spill, b);
 }
 
 static int ivf_range_args(IvfRangeArgs &a, size_t &lds, const OpqModelDev &m, const float *q_rot, int64_t nq, int nprobe, const int64_t *list_off,
@@ -282,8 +251,7 @@ int launch_ivf_range_count(const OpqModelDev &m, const float *q_rot, int64_t nq,
     const int parts = p.grid.parts();
     CVTMI_TRY(launch("ivf_range_order_kernel", ivf_range_order_kernel, nq, 128, 0, st, probe, nprobe, b.order));
     CVTMI_TRY(launch("ivf_range_scan_kernel", ivf_range_scan_kernel, nq * parts, kBlock, lds, st, a));
-    CVTMI_TRY(launch("ivf_range_part_offsets_kernel", ivf_range_part_offsets_kernel, nq, kBlock, 0, st, b.part_cnt, parts, b.part_off, lims));
-    return launch("ivf_range_lims_kernel", ivf_range_lims_kernel, 1, kBlock, 0, st, lims, nq);
+    return launch_range_offsets(b, parts, nq, lims, st);
 }
 
 int launch_ivf_range_fill(const OpqModelDev &m, const float *q_rot, int64_t nq, int nprobe, const int64_t *list_off, const uint8_t *codes,

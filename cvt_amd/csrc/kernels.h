@@ -227,6 +227,14 @@ int launch_ivf_search(const OpqModelDev &m, const float *q_rot, int64_t nq, int 
 size_t ivf_mask_bytes(int64_t n_csr);
 int launch_ivf_mask_order(const uint64_t *mask, const uint32_t *entry, int64_t n_csr, uint64_t *lmask, hipStream_t st);
 
+// ---- range_common.h ----  the areas both range searches count in; a cell is a (query, part)
+struct RangeBufs {
+    uint32_t *part_cnt = nullptr, *part_off = nullptr;   // [nq][parts] hits of a part, and where they start inside the query's
+    unsigned long long *spill = nullptr;                  // [nq][parts][plan.spill] (distance or score bits << 32 | row or position)
+};
+// part_off = exclusive scan of part_cnt per query, lims[0 .. nq] = exclusive scan of the queries' hit counts (ivf_range.hip)
+int launch_range_offsets(const RangeBufs &b, int parts, int64_t nq, int64_t *lims, hipStream_t st);
+
 // ---- ivf_range.hip ----  every entry of the probed lists with score < radius (cvtmi_opq_range_search_ivf)
 struct IvfRangePlan {
     IvfPlan grid;        // one workgroup per part; grid.rule 4 = the spill area had to shrink
@@ -234,10 +242,8 @@ struct IvfRangePlan {
 };
 // pure host logic; spill = records per part wanted ("ivf_range_spill"; 0 = a count-only call), cap_bytes = room for the spill area
 IvfRangePlan plan_ivf_range(int64_t nq, int nprobe, int64_t longest, int64_t spill, size_t cap_bytes, int cus = 0);
-struct IvfRangeBufs {
+struct IvfRangeBufs : RangeBufs {               // spill: score bits << 32 | position in the list-ordered copy
     int32_t *order = nullptr;                     // [nq][nprobe] probed lists by list id
-    uint32_t *part_cnt = nullptr, *part_off = nullptr;   // [nq][parts] hits of a part, and where they start inside the query's
-    unsigned long long *spill = nullptr;          // [nq][parts][plan.spill] (score bits << 32 | position in the list-ordered copy)
 };
 // bytes of scratch the plan needs; with base != null the four areas are laid out in it
 size_t ivf_range_carve(void *base, const IvfRangePlan &p, int64_t nq, int nprobe, IvfRangeBufs *b);
@@ -262,10 +268,7 @@ struct FlatRangePlan {
 };
 // pure host logic; part_rows = 0: the default parts; spill < 0: the default records, 0 = a count-only call / every part walks twice
 FlatRangePlan plan_flat_range(int metric, int D, bool has_norms, int64_t n, int64_t nq, int64_t part_rows, int64_t spill);
-struct FlatRangeBufs {
-    uint32_t *part_cnt = nullptr, *part_off = nullptr;   // [nq][parts] hits of a part, and where they start inside the query's
-    unsigned long long *spill = nullptr;                  // [nq][parts][plan.spill] (distance bits << 32 | row)
-};
+struct FlatRangeBufs : RangeBufs {};   // spill: distance bits << 32 | row
 // bytes of scratch the plan needs; with base != null the three areas are laid out in it
 size_t flat_range_carve(void *base, const FlatRangePlan &p, int64_t nq, FlatRangeBufs *b);
 // the rows of the handle as the kernels read them (labels null: id_base + row)

@@ -35,7 +35,7 @@ I64_MIN, I64_MAX = -2 ** 63, 2 ** 63 - 1
 PAD = 0x7f800000
 CVTMI_EINVAL = -1
 FORM = {(IP, 4): 1, (IP, 32): 1, (IP, 128): 1, (IP, 37): 0, (L2F, 4): 1, (L2F, 32): 1, (L2F, 128): 1, (L2F, 37): 0,
-        (L2U8, 32): 3, (L2U8, 48): 3, (L2U8, 5): 2}
+        (L2U8, 32): 3, (L2U8, 48): 3, (L2U8, 5): 2, (L2U8, 80): 3, (L2U8, 160): 3}
 ONES = np.uint64(2 ** 64 - 1)
 
 
@@ -261,7 +261,7 @@ def test_allowed_equal_to_k_one_fewer_and_none(amd, orc, metric, D):
 
 
 # ---- 3. the parts divide the list: the same result from 1, 2, 5 and 1024 of them, and a clustered mask still splits ----
-@pytest.mark.parametrize("metric,D", [(IP, 32), (L2F, 128), (L2F, 37), (L2U8, 48), (L2U8, 5)])
+@pytest.mark.parametrize("metric,D", [(IP, 32), (L2F, 128), (L2F, 37), (L2U8, 48), (L2U8, 5), (L2U8, 80), (L2U8, 160)])
 def test_parts_do_not_change_the_result(amd, orc, metric, D):
     n, nq = 1025, 9
     rows = make_rows(metric, n, D, seed=D + 4)

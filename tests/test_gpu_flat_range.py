@@ -30,7 +30,7 @@ I64_MIN, I64_MAX = -2 ** 63, 2 ** 63 - 1
 INF = float("inf")
 CVTMI_OK, CVTMI_ESPACE = 0, -7
 FORM = {(IP, 4): 1, (IP, 32): 1, (IP, 128): 1, (IP, 37): 0, (L2F, 4): 1, (L2F, 32): 1, (L2F, 128): 1, (L2F, 37): 0,
-        (L2U8, 32): 4, (L2U8, 48): 3, (L2U8, 5): 2}
+        (L2U8, 32): 4, (L2U8, 48): 3, (L2U8, 5): 2, (L2U8, 80): 3, (L2U8, 160): 4}
 
 
 def want_qt(metric, nq):
@@ -255,7 +255,8 @@ def test_non_finite(amd, orc, metric, D):
 HUGE = 2 ** 40
 
 
-@pytest.mark.parametrize("metric,D", [(IP, 32), (L2F, 128), (L2F, 37), (L2U8, 32), (L2U8, 48), (L2U8, 5)])
+# (uint8 80 and 160: rows longer than one step of the scan's read-ahead, four 16-byte pieces -- 5 pieces without norms, 10 with them)
+@pytest.mark.parametrize("metric,D", [(IP, 32), (L2F, 128), (L2F, 37), (L2U8, 32), (L2U8, 48), (L2U8, 5), (L2U8, 80), (L2U8, 160)])
 def test_part_and_spill_seams(amd, orc, metric, D):
     n, nq = 1025, 9
     rows = make_rows(metric, n, D, seed=3 * D)
