@@ -373,8 +373,10 @@ def _same_min(a, b):
 def test_sq8_train_sign_of_a_zero_minimum(amd, orc, d, n, l2):
     """A column whose minimum is zero and that holds zeros of both signs: the loop this restates (faiss train_NonUniform, RS_minmax:
     strict '<' in row order behind sq_train.cpp:100) keeps the FIRST zero it meets; the device reduction orders -0.0 below +0.0.  The
-    training call therefore looks such columns up again (sq8_zero_first_kernel).  Every kernel family (wave-per-row with sample pass,
-    tile, two-pass) and both first-zero signs, zeros that only appear through an infinite norm, and columns without any zero."""
+    training call therefore looks such columns up again (sq8_zero_first_kernel).  The wave-per-row kernels without and with the sample
+    pass (512-d, 256-d) and the tile kernel (64-d at 500 rows, 300-d and 12-d: all multiples of 4 up to 512; the two-pass kernels'
+    turn is in test_gpu_sq8_routes.py), both first-zero signs, zeros that only appear through an infinite norm, and columns without
+    any zero."""
     import torch
     rng = np.random.default_rng(d + n + int(l2))
     x = np.abs(rng.normal(size=(n, d))).astype(np.float32)          # non-negative: the minimum of a column with a zero IS zero
