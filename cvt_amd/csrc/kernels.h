@@ -28,7 +28,8 @@ int launch_rotate_gemm(const float *R, int D, const float *x, int64_t n, float *
 // ---- opq_encode.hip ----
 int launch_coarse_assign(const OpqModelDev &m, const float *x_rot, int64_t n, int32_t *list_id, hipStream_t st);
 // list_id may be null (=> list 0 for every row)
-// variant: 0 = choose, 1 = VALU kernel, 2 = matrix-core filter + exact resolution
+// variant: 0 = choose, 1 = VALU kernel, 2 = matrix-core filter + exact resolution (K = 256, step 8 or 16, M <= 16, 16-byte aligned
+// rows, and an LDS footprint (M 256 step + M 256 + M) floats of at most 160 KB: M <= 9 at step 16; EUNSUPPORTED otherwise)
 // single_list_out (coarseK == 1 only, and only when pq_encode_fuses_lists() says so): the encode kernel writes the list
 // assignment (0, or -1 for rows no centroid can claim) itself, sparing the separate pass over the rows
 int launch_pq_encode(const OpqModelDev &m, const float *x_rot, int64_t n, const int32_t *list_id, uint8_t *codes,

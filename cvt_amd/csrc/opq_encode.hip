@@ -14,7 +14,8 @@
 //                          codebook slice (8 KB at step 8) is staged in LDS and every lane walks all K centroids for
 //                          its V rows (LDS broadcast reads, row sub-vectors in registers)
 //   pq_encode_mfma_kernel  the GEMM form on the bf16 matrix cores as a FILTER with a proven error bound; pairs it
-//                          cannot separate go through the reference's chain (K = 256, step 8 / 16, D <= 128)
+//                          cannot separate go through the reference's chain (K = 256, step 8 / 16, M <= 16 and an LDS
+//                          footprint encm_lds() of at most 160 KB: every M at step 8, M <= 9 -- D <= 144 -- at step 16)
 // Codes are packed in registers and leave as one 16-byte (M=16) store per row.
 #include <algorithm>
 
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(kBlock) void pq_encode_kernel(const float *__restri
 }
 
 // ------------------------------------------------------------------------------------------
-// PQ encode, matrix-core filter + exact resolution (K = 256, D <= 128, step 8 or 16)
+// PQ encode, matrix-core filter + exact resolution (K = 256, step 8 or 16, LDS footprint <= 160 KB: see encm_ok)
 //
 // The code byte is an argmin: only WHICH centroid wins has to equal the reference, not the distances.  For
 // row sub-vector r and centroid c_j, |r - c_j|^2 = |r|^2 - 2 T_j with T_j = r.c_j - |c_j|^2 / 2, so the winner
@@ -510,12 +511,16 @@ __global__ __launch_bounds__(ENCM_THREADS) void pq_encode_mfma_kernel(const floa
         if (list_out && lk == 0 && row < n) {
             // coarseK == 1 (IVFOPQ.cpp:110-129 with one centroid): list 0 when the sequential fp32 sum of (x - c0)^2 stays
             // below the start value float(UINT_MAX), else -1.  norm2 is that sum up to ~1e-5 relative: far from 2^32 it
-            // decides; otherwise (huge or non-finite rows) the lane walks the reference's chain.
+            // decides; otherwise (huge or non-finite rows) the lane walks the reference's chain.  PERM: the reference sums over the
+            // reordered row, y[kk] = x[perm[kk]] against coarse[kk] in ascending kk -- the order decides within a few ulps of the start
+            // value, and the pairing of row and centroid entries decides everything.
             int lst = 0;
             if (!(norm2 * 1.01f < 0x1p31f)) {
                 float acc = 0.0f;
                 for (int kk = 0; kk < D; ++kk) {
-                    const float t = __fsub_rn(x[row * D + kk], coarse[kk]);
+                    int src = kk;
+                    if constexpr (PERM) src = perm[kk];
+                    const float t = __fsub_rn(x[row * D + src], coarse[kk]);
                     acc = __fadd_rn(acc, __fmul_rn(t, t));
                 }
                 lst = acc < kStartDist ? 0 : -1;
@@ -595,7 +600,7 @@ int launch_pq_encode(const OpqModelDev &m, const float *x_rot, int64_t n, const 
     if (m.K > 256) return fail(CVTMI_EUNSUPPORTED, "pq_encode: K=%d > 256", m.K);
     const size_t lds_mfma = encm_lds(m);
     const bool mfma_ok = encm_ok(m, x_rot);
-    if (variant == 2 && !mfma_ok) return fail(CVTMI_EUNSUPPORTED, "pq_encode: the matrix-core encode needs K = 256, step 8 or 16, M <= 16, D <= 128");
+    if (variant == 2 && !mfma_ok) return fail(CVTMI_EUNSUPPORTED, "pq_encode: the matrix-core encode needs K = 256, step 8 or 16, M <= 16, an LDS footprint of at most 160 KB (M <= 9 at step 16) and 16-byte aligned rows");
     if (single_list_out && !pq_encode_fuses_lists(m, x_rot, n, variant)) return fail(CVTMI_EINVAL, "pq_encode: list output without the fused kernel");
     if (mfma_ok && (variant == 2 || (variant == 0 && n >= ENCM_MIN_ROWS))) {
         constexpr int waves = ENCM_THREADS / 64;

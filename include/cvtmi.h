@@ -442,7 +442,8 @@ int cvtmi_opq_remove_ids_dev(cvtmi_opq_t h, const int64_t *ids, int64_t n_ids, i
  *   "profile"  1 = bracket the scan kernel with HIP events on its stream
  *   "encode_variant"  PQ encode kernel: 0 = choose (default); 1 = every centroid through the reference's sub / mul / add
  *                 chain on the VALU; 2 = fp32 matrix-core filter, exact chain only for pairs it cannot separate
- *                 (K = 256, step 8 or 16, D <= 128; chosen automatically from 8192 rows up).  Same codes either way.
+ *                 (K = 256, step 8 or 16, M <= 9 at step 16, 16-byte aligned rows; chosen automatically at every row count).
+ *                 Same codes either way.
  *   "scan_variant"  M = 16 kernel choice: 0 row-per-lane; 1 / 2 skewed fp32 tables (512 / 1024 threads);
  *                   3 / 4 skewed 15-bit lower-bound tables, 8 queries per pass (1024 / 512 threads; 3 = default);
  *                   5 = variant 3 without checkpoints: one wave of the workgroup compacts beside the 15 that scan

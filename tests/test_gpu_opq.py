@@ -116,7 +116,7 @@ def test_encode_parity_seeded(amd, orc, D, M, K, coarseK):
     assert np.array_equal(lists, ol)
     assert np.array_equal(codes, oc)
     assert lists[5] == -1 and np.all(codes[5] == 255)
-    if K == 256 and D // M in (8, 16) and M <= 16:   # the matrix-core filter kernel is chosen from 8192 rows up: force it
+    if K == 256 and D // M in (8, 16) and M <= 16:   # the matrix-core filter kernel (the dispatch takes it at every row count): forced as well
         idx.set_param("encode_variant", 2)
         l2, c2 = idx.encode(x)
         assert np.array_equal(l2, ol) and np.array_equal(c2, oc)
