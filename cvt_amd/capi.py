@@ -487,6 +487,12 @@ class OpqIndex:
     def set_param(self, name, value):
         _check(lib().cvtmi_opq_set_param(self.h, name.encode(), C.c_int64(value)))
 
+    def last_mfma(self):
+        """(queries, queries the exact scan had to answer) of the last profiled search that took the "scan_mfma" route (cvtmi_opq_last_mfma)"""
+        o = (C.c_int64 * 2)()
+        _check(lib().cvtmi_opq_last_mfma(self.h, o))
+        return int(o[0]), int(o[1])
+
     def last_scan(self):
         ms = C.c_float(0); b = C.c_int64(0); qt = C.c_int(0); sp = C.c_int(0)
         _check(lib().cvtmi_opq_last_scan(self.h, C.byref(ms), C.byref(b), C.byref(qt), C.byref(sp)))

@@ -621,6 +621,12 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16q_kernel(const ScanArg
             group = g0 + b / my_splits;
         }
     }
+    if (a.only) {   // workgroup-uniform: a group none of whose queries is flagged has its answers already (adc_mfma.hip's fall-back)
+        uint32_t any = 0u;
+        for (int q = 0; q < QT; ++q)
+            if (group * QT + q < a.nq) any |= a.only[group * QT + q];
+        if (!any) return;
+    }
     const int tid = threadIdx.x, lane = tid & 63;
     topk_init(tk);
     scan16q_build_tables<NT>(a, group, lut, qp, reinterpret_cast<uint32_t(*)[16]>(&tk.buf[0][0]), ck.nonfinite, ck.lazy);  // scratch on the (still unused) buffers
@@ -1387,7 +1393,7 @@ int launch_rotate_codes(const uint8_t *codes, uint8_t *codes_rot, int64_t row0, 
 
 int launch_adc_scan(const OpqModelDev &m, const uint8_t *codes, int64_t n_rows, int64_t id_base, const float *q_rot,
                     int64_t nq, int k, const ScanPlan &plan, float *part_d, int64_t *part_id, float *lut_scratch,
-                    const uint8_t *codes_rot, hipStream_t st, uint32_t *gthr, int lazy, float *final_d, int64_t *final_id, const uint32_t *only)
+                    const uint8_t *codes_rot, hipStream_t st, uint32_t *gthr, int lazy, float *final_d, int64_t *final_id, const uint32_t *only, bool lut_ready)
 {
     if (nq <= 0) return CVTMI_OK;
     if (k < 1 || k > kBigK) return fail(CVTMI_EUNSUPPORTED, "adc_scan: k=%d outside 1..%d", k, kBigK);
@@ -1418,7 +1424,7 @@ int launch_adc_scan(const OpqModelDev &m, const uint8_t *codes, int64_t n_rows, 
             OpqModelDev mr = m;
             mr.M = plan.real_M;
             CVTMI_TRY(launch_lut(mr, q_rot, nq, nullptr, lut_scratch, st, 256, 16));
-        } else
+        } else if (!lut_ready)
         CVTMI_TRY(launch_lut(m, q_rot, nq, nullptr, lut_scratch, st, 256));  // [nq][16][256] fp32 (+inf past K), once per query
         int64_t blocks = (int64_t)a.groups * a.splits;
         if (plan.splits_b > plan.splits && plan.groups_a > 0 && plan.groups_a < a.groups) {

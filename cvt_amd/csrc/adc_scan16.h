@@ -113,6 +113,24 @@ struct ExactFromLut {
     }
 };
 
+// ascending bitonic sort of n (a power of two) 64-bit keys in LDS by the whole workgroup of NT threads
+template <int NT>
+__device__ __forceinline__ void block_bitonic_u64(unsigned long long *e, int n)
+{
+    for (int size = 2; size <= n; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            for (int i = threadIdx.x; i < n / 2; i += NT) {
+                const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;   // lo = (i / stride) * 2 stride + i % stride
+                const bool up = (lo & size) == 0;
+                const unsigned long long a0 = e[lo], a1 = e[hi];
+                if ((a0 > a1) == up) { e[lo] = a1; e[hi] = a0; }
+            }
+        }
+    }
+    __syncthreads();
+}
+
 // batched form for the register compaction: up to 4 entries per lane, all row loads first, then all
 // 64 table gathers, then the in-order sums -- two dependent memory round trips per batch instead of 2 x 4
 struct ExactFromLutBatch {

@@ -1368,24 +1368,6 @@ __global__ __launch_bounds__(1024, 8) void scan16k_collect_kernel(const ScanSArg
     if (tid < QT) a.wcnt[((size_t)grp * a.G + blockIdx.x) * QT + tid] = cnt[tid];
 }
 
-// ascending bitonic sort of n (a power of two, <= SK_NSEL) 64-bit keys in LDS by the whole workgroup
-template <int NT>
-__device__ __forceinline__ void block_bitonic_u64(unsigned long long *e, int n)
-{
-    for (int size = 2; size <= n; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            for (int i = threadIdx.x; i < n / 2; i += NT) {
-                const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;   // lo = (i / stride) * 2 stride + i % stride
-                const bool up = (lo & size) == 0;
-                const unsigned long long a0 = e[lo], a1 = e[hi];
-                if ((a0 > a1) == up) { e[lo] = a1; e[hi] = a0; }
-            }
-        }
-    }
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(1024) void scan16k_select_kernel(const ScanSArgs a, int wcap, uint32_t *__restrict__ flags)
 {
     constexpr int NT = 1024, QT = SQ_QT;

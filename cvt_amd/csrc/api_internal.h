@@ -268,6 +268,17 @@ struct cvtmi_opq_s {
     DevBuf codes16;       // M < 16: the rows padded to 16 bytes with zeros, what the M = 16 scan kernels read (opq_pads; built lazily like codes_rot, which is then its rotation)
     int64_t pad_n = 0;    // rows of codes16 that are up to date
     int rot_kind = 0;     // what codes_rot holds: 0 = 16-byte rows (M = 16, or the padded copy) rotated by row & 15; 1 = the packed rotation of an M = 8 / 4 index (adc_scan_p.hip)
+    // adc_mfma.hip: the int8 matrix-core bound filter of large M = 16 batches.  The model's part (books_h: the codebooks on the host, what
+    // it is computed from on first use) and the decoded operand copy of the rows, built lazily like codes_rot (132 bytes per row at 128-d)
+    std::vector<float> books_h;
+    int mf_state = 0;           // 0 = not looked at yet, 1 = usable, -1 = off for this index (a non-finite codebook entry, K != 256, no memory)
+    DevBuf mf_model;            // xb | nrm | c | s
+    AdcMfmaModel mf{};
+    DevBuf mf_pack, mf_norm;
+    DevBuf mf_stat;             // profiled searches: queries and flagged queries of the last search on this route (cvtmi_opq_last_mfma)
+    int64_t mf_n = 0;           // rows of mf_pack / mf_norm that are up to date
+    int p_mfma = 1, p_mfma_cap = 4096, p_mfma_sample = 2;   // "scan_mfma", "scan_mfma_cap", "scan_mfma_sample"
+    int64_t p_mfma_min_nq = 512, p_mfma_min_rows = 1000000, p_mfma_max_rows = -1;   // "scan_mfma_min_nq" / "_min_rows" / "_max_rows" (-1: the copy stays within 1 GB)
     int64_t n = 0;
     bool has_lists = false, has_videos = false;
     int64_t id_base = 0;

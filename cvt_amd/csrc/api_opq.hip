@@ -104,6 +104,9 @@ int cvtmi_opq_create(int D, int coarseK, int M, int K, const float *coarse, cons
     if (rc != CVTMI_OK) { cvtmi_opq_destroy(h); return rc; }
     h->m.D = D; h->m.coarseK = coarseK; h->m.M = M; h->m.K = K; h->m.step = D / M;
     h->m.coarse = h->d_coarse; h->m.books = h->d_books; h->m.R = h->d_R; h->m.perm = h->d_perm;
+    if (M == 16 && K == 256 && coarseK == 1) {   // (what the matrix-core bound filter's operands are made from on first use, adc_mfma.hip)
+        try { h->books_h.assign(books, books + (size_t)D * K); } catch (...) { h->mf_state = -1; }
+    }
     *out = h;
     return CVTMI_OK;
 }
@@ -117,6 +120,7 @@ int cvtmi_opq_destroy(cvtmi_opq_t h)
     if (h->d_R) (void)hipFree(h->d_R);
     if (h->d_perm) (void)hipFree(h->d_perm);
     h->codes.release(); h->lists.release(); h->videos.release(); h->codes_rot.release(); h->codes16.release();
+    h->mf_model.release(); h->mf_pack.release(); h->mf_norm.release(); h->mf_stat.release();
     h->csr_codes.release(); h->csr_videos.release(); h->csr_off.release(); h->csr_scratch.release(); h->csr_stats.release(); h->csr_entry.release();
     h->s_qrot.release(); h->s_probe.release(); h->s_rot.release(); h->rm_scratch.release();
     h->pool.destroy();
@@ -319,7 +323,7 @@ int cvtmi_opq_ntotal(cvtmi_opq_t h, int64_t *n)
 int cvtmi_opq_reset(cvtmi_opq_t h)
 {
     CHECK_H_SERIAL(h, nullptr);
-    h->n = 0; h->has_lists = false; h->has_videos = false; h->csr_valid = false; h->csr_entry_valid = false; h->rot_n = 0; h->pad_n = 0;
+    h->n = 0; h->has_lists = false; h->has_videos = false; h->csr_valid = false; h->csr_entry_valid = false; h->rot_n = 0; h->pad_n = 0; h->mf_n = 0;
     return CVTMI_OK;
 }
 
@@ -498,9 +502,82 @@ static ScanPlan opq_plan(cvtmi_opq_t h, int64_t nq, int k)
     return plan;
 }
 
+// Does a search of this shape ask for the matrix-core bound filter (adc_mfma.hip)?  Everything but the state of the operand
+// copy: forced scan forms (scan_variant, qtile, splits) bypass it, the bounds are the handle's "scan_mfma*" parameters.
+static bool mfma_wanted(const cvtmi_opq_s *h, int64_t nq, int k)
+{
+    const int64_t max_rows = h->p_mfma_max_rows >= 0 ? h->p_mfma_max_rows : ((int64_t)1 << 30) / (h->m.D + 4);   // the copy: D + 4 bytes per row
+    return h->p_mfma && h->mf_state >= 0 && !h->books_h.empty() && h->m.M == 16 && h->m.K == 256 && h->m.D % 32 == 0 && h->m.D <= 256 && h->m.coarseK == 1 &&
+           k >= 1 && k <= 128 && h->p_variant == 7 && h->p_qtile == 0 && h->p_splits == 0 && nq >= h->p_mfma_min_nq && nq <= 0x7fffffff &&
+           h->n >= h->p_mfma_min_rows && h->n <= max_rows && h->n < 0x7fffffe0LL;
+}
+
+// the model's part of that filter (once per handle) and the decoded operand copy of the rows, built and extended like codes_rot.  Whatever
+// does not fit in memory, or a codebook the bound cannot be stated for, turns the route off for the handle: the scan answers.
+static int opq_prepare_mfma(cvtmi_opq_t h, int64_t nq, int k, hipStream_t st)
+{
+    {
+        std::shared_lock<std::shared_timed_mutex> rd(h->rw);
+        if (h->n == 0 || !mfma_wanted(h, nq, k)) return CVTMI_OK;
+        if (h->mf_state == 1 && h->mf_n == h->n) return CVTMI_OK;
+    }
+    Serial serial(h->sync, st);
+    OpqExclusive excl(h, st);
+    const auto soft = [&](int rc) {   // out of memory: off, and not an error
+        if (rc != CVTMI_ENOMEM) return rc;
+        (void)hipGetLastError(); g_err.clear();
+        h->mf_state = -1; h->mf_n = 0; h->mf_pack.release(); h->mf_norm.release();
+        return (int)CVTMI_OK;
+    };
+    const int D = h->m.D;
+    if (h->mf_state == 0) {
+        const size_t o_xb = 4096 * sizeof(double), o_c = o_xb + (size_t)256 * D, o_s = o_c + (size_t)D * sizeof(float), bytes = o_s + (size_t)D * sizeof(float);
+        std::vector<double> blob((bytes + 7) / 8);   // nrm | xb | c | s
+        char *b = reinterpret_cast<char *>(blob.data());
+        double x_max = 0.0, eps_max = 0.0, xhat_max = 0.0;
+        if (!adc_mfma_model(h->books_h.data(), D, h->m.K, reinterpret_cast<int8_t *>(b + o_xb), blob.data(), reinterpret_cast<float *>(b + o_c),
+                            reinterpret_cast<float *>(b + o_s), &x_max, &eps_max, &xhat_max)) {
+            h->mf_state = -1;
+            return CVTMI_OK;
+        }
+        int rc = h->mf_model.reserve(bytes);
+        if (rc == CVTMI_OK) rc = h->mf_stat.reserve(2 * sizeof(unsigned long long));
+        if (rc != CVTMI_OK) return soft(rc);
+        CVTMI_HIP(hipMemsetAsync(h->mf_stat.p, 0, 2 * sizeof(unsigned long long), st));
+        CVTMI_HIP(hipMemcpyAsync(h->mf_model.p, b, bytes, hipMemcpyHostToDevice, st));
+        CVTMI_HIP(stream_wait(st));   // (the blob goes out of scope)
+        const char *d = h->mf_model.as<char>();
+        h->mf.nrm = reinterpret_cast<const double *>(d); h->mf.xb = reinterpret_cast<const int8_t *>(d + o_xb);
+        h->mf.c = reinterpret_cast<const float *>(d + o_c); h->mf.s = reinterpret_cast<const float *>(d + o_s);
+        h->mf.x_max = x_max; h->mf.eps_max = eps_max; h->mf.xhat_max = xhat_max;
+        h->mf_state = 1;
+    }
+    if (h->mf_state != 1) return CVTMI_OK;
+    if (h->mf_n > h->n) h->mf_n = 0;
+    const size_t need = adc_mfma_pack_bytes(D, h->n);
+    if (h->mf_pack.cap < need || h->mf_norm.cap < (size_t)h->n * sizeof(float)) {
+        const int64_t room = std::max<int64_t>(h->n, (int64_t)(h->codes.cap / 16));   // as many rows as the code buffer holds: appended rows extend the copy
+        int rc = h->mf_pack.reserve(adc_mfma_pack_bytes(D, room));
+        if (rc == CVTMI_ENOMEM) rc = h->mf_pack.reserve(need);
+        h->mf_n = 0;   // reserve() does not keep the old contents
+        if (rc != CVTMI_OK) return soft(rc);
+        rc = h->mf_norm.reserve((size_t)room * sizeof(float));
+        if (rc != CVTMI_OK) return soft(rc);
+    }
+    CVTMI_TRY(launch_adc_mfma_pack(h->mf, D, h->codes.as<uint8_t>(), h->mf_n, h->n, h->mf_pack.p, h->mf_norm.as<float>(), st));
+    h->mf_n = h->n;
+    return CVTMI_OK;
+}
+
 // what a search needs of the index beyond the rows: the pre-rotated copy the M = 16 scans stream, extended under the EXCLUSIVE lock
 // (once per index state; the searches that follow on other streams wait for the event the exclusive call leaves)
+static int opq_prepare_rot(cvtmi_opq_t h, int64_t nq, int k, hipStream_t st);
 static int opq_prepare(cvtmi_opq_t h, int64_t nq, int k, hipStream_t st)
+{
+    CVTMI_TRY(opq_prepare_rot(h, nq, k, st));
+    return opq_prepare_mfma(h, nq, k, st);
+}
+static int opq_prepare_rot(cvtmi_opq_t h, int64_t nq, int k, hipStream_t st)
 {
     bool padded = false, packed = false;
     {
@@ -592,6 +669,63 @@ static int opq_search_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64
 {
     if (h->n == 0)  // an empty index (e.g. a rank whose row block is empty): all padding, (+inf, -1)
         return launch_topk_select(nullptr, nullptr, nq, 0, k, dist, ids, st);
+    bool mfma = mfma_wanted(h, nq, k) && h->mf_state == 1 && h->mf_n == h->n && h->mf_pack.p;
+    // what the flagged queries beyond the short redo batch go through: the planned 8-query scan, a group scanned when one of its queries is
+    // flagged -- a call whose every query is flagged then costs the filter plus the scan it would have been without the route
+    ScanPlan redo_plan = plan_scan(h->m, h->n, nq, k, 8, 0, 3);
+    redo_plan.groups_a = 0; redo_plan.splits_b = 0;
+    const bool redo_fast = redo_plan.variant == 3 && redo_plan.qtile == 8;
+    if (mfma) {   // the route's scratch (about 1 GB at most) is its own need: without the memory the scan answers, as without the operand copy
+        int rc = S.s_lut.reserve((size_t)nq * 16 * 256 * sizeof(float));
+        if (rc == CVTMI_OK) rc = S.s_spill.reserve(adc_mfma_scratch_bytes(h->m.D, h->n, nq, k, h->p_mfma_cap, h->p_mfma_sample, nullptr));
+        if (rc == CVTMI_OK && redo_fast && redo_plan.stride() > 1) {
+            rc = S.s_part_d.reserve((size_t)nq * redo_plan.stride() * k * sizeof(float));
+            if (rc == CVTMI_OK) rc = S.s_part_id.reserve((size_t)nq * redo_plan.stride() * k * sizeof(int64_t));
+        }
+        if (rc == CVTMI_ENOMEM) { (void)hipGetLastError(); g_err.clear(); mfma = false; }
+        else CVTMI_TRY(rc);
+    }
+    if (!mfma && h->p_profile && h->mf_stat.p)   // (cvtmi_opq_last_mfma speaks of the last profiled search: this one did not take the route)
+        CVTMI_HIP(hipMemsetAsync(h->mf_stat.p, 0, 2 * sizeof(unsigned long long), st));
+    if (mfma) {
+        // large batches, k <= 128: the int8 matrix-core bound filter over the decoded rows, exact sums of the survivors (adc_mfma.hip);
+        // the queries it could not answer are flagged and go through the scan kernels behind it under a predicate
+        const float *q_rot = nullptr;
+        CVTMI_TRY(opq_rotate_probe(h, S, q, nq, rotate, 0, st, &q_rot));
+        int slot = 0;
+        if (h->p_profile) {
+            CVTMI_TRY(opq_profile_slot(h, &slot));
+            CVTMI_HIP(hipEventRecord(h->ev0[slot], st));
+        }
+        AdcMfmaRedo redo{};
+        CVTMI_TRY(launch_adc_mfma(h->m, h->mf, h->codes.as<uint8_t>(), h->mf_pack.p, h->mf_norm.as<float>(), h->n, h->id_base, q_rot, nq, k, h->p_mfma_cap,
+                                  h->p_mfma_sample, S.s_lut.as<float>(), S.s_spill.p, dist, ids, &redo, h->p_profile ? h->mf_stat.as<unsigned long long>() : nullptr, st));
+        // The exact kernel under a predicate, as after the big-k pipeline below -- over the flagged queries as a short batch with row splits
+        // (one workgroup per query of the call and row split costs more in empty workgroups than the filter saves, and without splits a
+        // lone flagged query holds the call for a whole pass of one workgroup over the rows), then over whoever found no slot there.
+        ScanPlan exact;
+        exact.qtile = 1; exact.splits = redo.splits; exact.variant = 0;
+        CVTMI_TRY(launch_adc_scan(h->m, h->codes.as<uint8_t>(), h->n, h->id_base, redo.q, redo.cap, k, exact, redo.splits > 1 ? redo.part_d : redo.d,
+                                  redo.splits > 1 ? redo.part_i : redo.i, nullptr, nullptr, st, nullptr, h->p_lazy, nullptr, nullptr, redo.only));
+        if (redo.splits > 1) CVTMI_TRY(launch_topk_merge(redo.part_d, redo.part_i, redo.cap, redo.splits, k, redo.d, redo.i, st, redo.only));
+        CVTMI_TRY(launch_adc_mfma_scatter(redo, k, dist, ids, st));
+        if (redo_fast) {
+            const uint8_t *crot = (h->p_prerot && h->rot_kind == 0 && h->rot_n == h->n && h->codes_rot.p) ? h->codes_rot.as<uint8_t>() : nullptr;
+            const bool split = redo_plan.stride() > 1;
+            CVTMI_TRY(launch_adc_scan(h->m, h->codes.as<uint8_t>(), h->n, h->id_base, q_rot, nq, k, redo_plan, split ? S.s_part_d.as<float>() : dist,
+                                      split ? S.s_part_id.as<int64_t>() : ids, S.s_lut.as<float>(), crot, st, nullptr, h->p_lazy, nullptr, nullptr, redo.rest, true));
+            if (split) CVTMI_TRY(launch_topk_merge(S.s_part_d.as<float>(), S.s_part_id.as<int64_t>(), nq, redo_plan.stride(), k, dist, ids, st, redo.rest));
+        } else {   // (shapes the 8-query kernel is not planned for: one workgroup per flagged query)
+            exact.splits = 1;
+            CVTMI_TRY(launch_adc_scan(h->m, h->codes.as<uint8_t>(), h->n, h->id_base, q_rot, nq, k, exact, dist, ids, nullptr, nullptr, st, nullptr, h->p_lazy, nullptr,
+                                      nullptr, redo.rest));
+        }
+        if (h->p_profile) {
+            CVTMI_HIP(hipEventRecord(h->ev1[slot], st));
+            opq_note_scan(h, ((nq + 7) / 8) * h->n * h->m.M, 8, 1);   // the scan's passes x rows x M code bytes: an EQUIVALENT look-up rate
+        }
+        return CVTMI_OK;
+    }
     if (scans_chosen(h, nq, k)) {
         // 1 .. 128 queries (up to sixteen query groups): global bounds first, candidate lists, one selection workgroup per query
         // (adc_scan_h.hip) -- four launches, the rotation folded into the first
@@ -1439,7 +1573,7 @@ static int opq_remove_common(cvtmi_opq_t h, const int32_t *table, int64_t T, con
     CVTMI_TRY(launch_rm_move(p, S, h->codes.as<uint8_t>(), h->has_lists ? h->lists.as<int32_t>() : nullptr, h->videos.as<int32_t>(), shift ? 1 : 0,
                              remap_dev, st));
     h->n = kept;
-    h->rot_n = 0; h->pad_n = 0; h->csr_valid = false; h->csr_entry_valid = false;
+    h->rot_n = 0; h->pad_n = 0; h->mf_n = 0; h->csr_valid = false; h->csr_entry_valid = false;
     if (removed) *removed = dropped;
     return CVTMI_OK;
 }
@@ -1526,12 +1660,51 @@ int cvtmi_opq_set_param(cvtmi_opq_t h, const char *name, int64_t value)
         h->p_encode = (int)value;
         return CVTMI_OK;
     }
+    if (!strcmp(name, "scan_mfma")) { h->p_mfma = value != 0; return CVTMI_OK; }
+    if (!strcmp(name, "scan_mfma_min_nq") || !strcmp(name, "scan_mfma_min_rows")) {
+        if (value < 1) return fail(CVTMI_EINVAL, "cvtmi_opq_set_param: %s must be at least 1", name);
+        (strcmp(name, "scan_mfma_min_nq") == 0 ? h->p_mfma_min_nq : h->p_mfma_min_rows) = value;
+        return CVTMI_OK;
+    }
+    if (!strcmp(name, "scan_mfma_max_rows")) { h->p_mfma_max_rows = value; return CVTMI_OK; }   // negative: the default
+    if (!strcmp(name, "scan_mfma_cap")) {
+        if (value < 1 || value > 4096) return fail(CVTMI_EINVAL, "cvtmi_opq_set_param: scan_mfma_cap must be 1 .. 4096");
+        h->p_mfma_cap = (int)value;
+        return CVTMI_OK;
+    }
+    if (!strcmp(name, "scan_mfma_sample")) {
+        if (value < 1 || value > 3) return fail(CVTMI_EINVAL, "cvtmi_opq_set_param: scan_mfma_sample must be 1 .. 3");
+        h->p_mfma_sample = (int)value;
+        return CVTMI_OK;
+    }
     if (!strcmp(name, "scan_variant")) {
         if (value < 0 || value > 7) return fail(CVTMI_EINVAL, "cvtmi_opq_set_param: scan_variant must be 0..7");
         h->p_variant = (int)value;
         return CVTMI_OK;
     }
     return fail(CVTMI_EINVAL, "cvtmi_opq_set_param: unknown parameter '%s'", name);
+}
+
+// the pieces a batch would go through on the "scan_mfma" route, for inspection and for the CPU tests of that arithmetic (include/cvtmi.h)
+int cvtmi_opq_mfma_plan(int D, int64_t n_rows, int64_t nq, int k, int list_cap, int sample, int64_t out[3])
+{
+    if (!out || D < 32 || D > 256 || D % 32 != 0 || n_rows < 1 || nq < 1 || k < 1 || k > 128 || list_cap < 1 || list_cap > 4096)
+        return fail(CVTMI_EINVAL, "cvtmi_opq_mfma_plan: bad arguments");
+    int64_t per = 0;
+    out[2] = (int64_t)adc_mfma_scratch_bytes(D, n_rows, nq, k, list_cap, sample, &per);
+    out[0] = per; out[1] = (nq + per - 1) / per;
+    return CVTMI_OK;
+}
+
+int cvtmi_opq_last_mfma(cvtmi_opq_t h, int64_t out[2])
+{
+    CHECK_H_SERIAL(h, nullptr);
+    if (!out) return fail(CVTMI_EINVAL, "cvtmi_opq_last_mfma: null out");
+    out[0] = out[1] = 0;
+    if (!h->mf_stat.p) return CVTMI_OK;
+    CVTMI_HIP(hipDeviceSynchronize());
+    CVTMI_HIP(hipMemcpy(out, h->mf_stat.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return CVTMI_OK;
 }
 
 int cvtmi_opq_last_scan(cvtmi_opq_t h, float *ms, int64_t *code_bytes, int *qtile, int *splits)

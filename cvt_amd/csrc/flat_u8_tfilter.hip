@@ -45,6 +45,9 @@ struct UtArgs {
     uint32_t *smax;          // MAX mode: [nq][UT_SLOTS] (a ^ 0x80000000), zeroed by the caller
     const int32_t *thr;      // FILTER mode: [nq] (INT_MAX: nothing passes)
     uint4 *rec; uint32_t *wcnt; uint32_t cap;
+    uint32_t qxor;           // 0x80808080: Q holds uint8 values (q - 128 is made here); 0: int8 values as they are (adc_mfma.hip)
+    int bias_direct;         // 0: a row starts at -(norms[row] >> 1); 1: at -norms[row] (the caller's own row term)
+    int smax_stride;         // slots per query of smax (UT_SLOTS; fewer when the grid has fewer row slices)
     int dbg;   // CVTMI_UT_DBG: timing experiments (results wrong) 1 = no epilogue, 2 = rows loaded once; test hook (results right) 4 = record regions of two records
 };
 
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(64 * UT_WAVES) __attribute__((amdgpu_waves_per_eu(2
         const int hl = i & 1, ss = (i >> 1) % KS, qq = i / (2 * KS);
         const int qi = q0 + (qq < nqc ? qq : nqc - 1);
         uint4 v = *reinterpret_cast<const uint4 *>(a.Q + (int64_t)qi * a.D + 32 * ss + 16 * hl);
-        v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
+        v.x ^= a.qxor; v.y ^= a.qxor; v.z ^= a.qxor; v.w ^= a.qxor;
         *reinterpret_cast<uint4 *>(ut_q + ((size_t)((qq >> 5) * KS + ss) * 1024) + (size_t)(hl * 32 + (qq & 31)) * 16) = v;
     }
     if constexpr (!MAXMODE)
@@ -123,7 +126,7 @@ __global__ __launch_bounds__(64 * UT_WAVES) __attribute__((amdgpu_waves_per_eu(2
 #pragma unroll
         for (int i = lane; i < RT * 32; i += 64) {
             const int64_t row = g_rows * RT * 32 + i;
-            bias_w[i] = row < a.n ? -(a.norms[row] >> 1) : UT_NEG;
+            bias_w[i] = row < a.n ? (a.bias_direct ? -a.norms[row] : -(a.norms[row] >> 1)) : UT_NEG;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -197,7 +200,7 @@ __global__ __launch_bounds__(64 * UT_WAVES) __attribute__((amdgpu_waves_per_eu(2
 #pragma unroll
         for (int b = 0; b < UT_NBQ; ++b) {   // (a slot nobody's rows reached stays 0 = empty: the caller zeroed the array)
             const int qq = 32 * b + lj;
-            if (b < nb && qq < nqc && mreg[b] > UT_NEG / 2) a.smax[(size_t)(q0 + qq) * UT_SLOTS + slot] = (uint32_t)mreg[b] ^ 0x80000000u;
+            if (b < nb && qq < nqc && mreg[b] > UT_NEG / 2) a.smax[(size_t)(q0 + qq) * a.smax_stride + slot] = (uint32_t)mreg[b] ^ 0x80000000u;
         }
     } else {
         if (lane == 0) a.wcnt[wave_g] = wcnt + (none == 0x12345678 ? 1u : 0u);
@@ -242,7 +245,7 @@ __global__ __launch_bounds__(256) void ut_theta_kernel(const uint32_t *__restric
 // records -> per-query (distance, row) lists: as ft_bucket_kernel (flat_f32_tfilter.hip), the distance made exact on the way
 __global__ __launch_bounds__(1024) void ut_bucket_kernel(const uint4 *__restrict__ rec, const uint32_t *__restrict__ wcnt, uint32_t cap,
                                                          const int32_t *__restrict__ thr, const int32_t *__restrict__ qqv, const int32_t *__restrict__ norms,
-                                                         uint32_t *__restrict__ cnt, uint2 *__restrict__ cand, int chunks, int qper, int nq, uint32_t *__restrict__ flag)
+                                                         uint32_t *__restrict__ cnt, uint2 *__restrict__ cand, int chunks, int qper, int nq, uint32_t *__restrict__ flag, uint32_t lcap, int flag_per_chunk)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t ut_stage[];
     __shared__ uint32_t hist[32 * UT_NBMAX], base_s[32 * UT_NBMAX];
@@ -257,13 +260,14 @@ __global__ __launch_bounds__(1024) void ut_bucket_kernel(const uint4 *__restrict
     if (tid == 0) nstage_s = 0u;
     const int per = 1024 / UT_WAVES, r = tid / per, t = tid % per;
     uint32_t n = wcnt[j * UT_WAVES + r];
-    if (n > cap) { if (t == 0) atomicOr(flag, 2u); n = cap; }   // (the call's word: whose records were lost is not known)
+    // (the call's word: whose records were lost is not known -- beyond that a region holds records of its chunk's queries only: flag_per_chunk)
+    if (n > cap) { if (t == 0) atomicOr(flag + (flag_per_chunk ? chunk : 0), 2u); n = cap; }
     const uint4 *rp = rec + (size_t)(j * UT_WAVES + r) * cap * 5;
     __syncthreads();
     auto each_hit = [&](auto &&f) {
         for (uint32_t i = t; i < n; i += per) {
             const uint4 h = rp[(size_t)i * 5 + 4];
-            const int tb = thr[h.x], qq = qqv[h.x];
+            const int tb = thr[h.x], qq = qqv ? qqv[h.x] : 0;
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
                 const uint4 s4 = rp[(size_t)i * 5 + jj];
@@ -272,7 +276,7 @@ __global__ __launch_bounds__(1024) void ut_bucket_kernel(const uint4 *__restrict
                 for (int e = 0; e < 4; ++e)
                     if (sv[e] >= tb) {
                         const uint32_t row = h.y + (uint32_t)(e + 8 * jj);
-                        f(h.x, h.z, (uint32_t)(qq - 2 * sv[e] + (norms[row] & 1)), row);
+                        f(h.x, h.z, norms ? (uint32_t)(qq - 2 * sv[e] + (norms[row] & 1)) : (uint32_t)sv[e], row);   // (no norms: the score itself, the caller ranks the rows its own way)
                     }
             }
         }
@@ -294,13 +298,13 @@ __global__ __launch_bounds__(1024) void ut_bucket_kernel(const uint4 *__restrict
         for (uint32_t i = tid; i < nstage; i += 1024) {
             const uint32_t ql = st_q[i];
             const uint32_t pos = base_s[ql] + atomicAdd(&hist[ql], 1u);
-            if (pos < (uint32_t)UT_CAP) cand[(size_t)(q0 + ql) * UT_CAP + pos] = st_dr[i];
+            if (pos < lcap) cand[(size_t)(q0 + ql) * lcap + pos] = st_dr[i];
         }
         return;
     }
     each_hit([&](uint32_t q, uint32_t ql, uint32_t d, uint32_t row) {   // more hits than the stage holds: the records once more
         const uint32_t pos = base_s[ql] + atomicAdd(&hist[ql], 1u);
-        if (pos < (uint32_t)UT_CAP) cand[(size_t)q * UT_CAP + pos] = make_uint2(d, row);
+        if (pos < lcap) cand[(size_t)q * lcap + pos] = make_uint2(d, row);
     });
 }
 
@@ -430,33 +434,33 @@ __global__ __launch_bounds__(1024) void ut_finish_kernel(int64_t n, int k, const
 }
 
 template <int KS, int RT>
-static int ut_launch(bool maxmode, const UtArgs &a, size_t lds, hipStream_t st)
+static int ut_launch(bool maxmode, const UtArgs &a, size_t lds, hipStream_t st, int grid)
 {
     static LdsOnce attr_a = {}, attr_b = {};
-    if (maxmode) return launch_lds_once("flat_u8_tfilter_kernel", flat_u8_tfilter_kernel<KS, RT, true>, attr_a, 163840, UT_GRID, 64 * UT_WAVES, lds, st, a);
-    return launch_lds_once("flat_u8_tfilter_kernel", flat_u8_tfilter_kernel<KS, RT, false>, attr_b, 163840, UT_GRID, 64 * UT_WAVES, lds, st, a);
+    if (maxmode) return launch_lds_once("flat_u8_tfilter_kernel", flat_u8_tfilter_kernel<KS, RT, true>, attr_a, 163840, grid, 64 * UT_WAVES, lds, st, a);
+    return launch_lds_once("flat_u8_tfilter_kernel", flat_u8_tfilter_kernel<KS, RT, false>, attr_b, 163840, grid, 64 * UT_WAVES, lds, st, a);
 }
 
 // by the K steps of a row (D / 32) and the row tiles a wave holds
-static int ut_launch_any(int ks, bool maxmode, const UtArgs &a, size_t lds, hipStream_t st)
+static int ut_launch_any(int ks, bool maxmode, const UtArgs &a, size_t lds, hipStream_t st, int grid = UT_GRID)
 {
     switch (ks) {
-        case 16: return ut_launch<16, 2>(maxmode, a, lds, st);
-        case 15: return ut_launch<15, 2>(maxmode, a, lds, st);
-        case 14: return ut_launch<14, 2>(maxmode, a, lds, st);
-        case 13: return ut_launch<13, 2>(maxmode, a, lds, st);
-        case 12: return ut_launch<12, 2>(maxmode, a, lds, st);
-        case 11: return ut_launch<11, 3>(maxmode, a, lds, st);
-        case 10: return ut_launch<10, 3>(maxmode, a, lds, st);
-        case 9: return ut_launch<9, 3>(maxmode, a, lds, st);
-        case 8: return ut_launch<8, 3>(maxmode, a, lds, st);
-        case 7: return ut_launch<7, 3>(maxmode, a, lds, st);
-        case 6: return ut_launch<6, 3>(maxmode, a, lds, st);
-        case 5: return ut_launch<5, 3>(maxmode, a, lds, st);
-        case 4: return ut_launch<4, 3>(maxmode, a, lds, st);
-        case 3: return ut_launch<3, 4>(maxmode, a, lds, st);
-        case 2: return ut_launch<2, 4>(maxmode, a, lds, st);
-        default: return ut_launch<1, 4>(maxmode, a, lds, st);
+        case 16: return ut_launch<16, 2>(maxmode, a, lds, st, grid);
+        case 15: return ut_launch<15, 2>(maxmode, a, lds, st, grid);
+        case 14: return ut_launch<14, 2>(maxmode, a, lds, st, grid);
+        case 13: return ut_launch<13, 2>(maxmode, a, lds, st, grid);
+        case 12: return ut_launch<12, 2>(maxmode, a, lds, st, grid);
+        case 11: return ut_launch<11, 3>(maxmode, a, lds, st, grid);
+        case 10: return ut_launch<10, 3>(maxmode, a, lds, st, grid);
+        case 9: return ut_launch<9, 3>(maxmode, a, lds, st, grid);
+        case 8: return ut_launch<8, 3>(maxmode, a, lds, st, grid);
+        case 7: return ut_launch<7, 3>(maxmode, a, lds, st, grid);
+        case 6: return ut_launch<6, 3>(maxmode, a, lds, st, grid);
+        case 5: return ut_launch<5, 3>(maxmode, a, lds, st, grid);
+        case 4: return ut_launch<4, 3>(maxmode, a, lds, st, grid);
+        case 3: return ut_launch<3, 4>(maxmode, a, lds, st, grid);
+        case 2: return ut_launch<2, 4>(maxmode, a, lds, st, grid);
+        default: return ut_launch<1, 4>(maxmode, a, lds, st, grid);
     }
 }
 
@@ -559,6 +563,7 @@ int launch_flat_u8_tfilter(int D, const void *pack, const int32_t *norms, int64_
         UtArgs a;
         a.pack = reinterpret_cast<const uint4 *>(pack); a.norms = norms; a.n = n; a.n_tiles = n_tiles; a.Q = q + a0 * D; a.D = D; a.nq = (int)m;
         { const char *e = getenv("CVTMI_UT_DBG"); a.dbg = e ? atoi(e) : 0; }
+        a.qxor = 0x80808080u; a.bias_direct = 0; a.smax_stride = UT_SLOTS;
         a.chunks = chunks; a.qper = qper; a.smax = smax; a.thr = thr; a.rec = rec; a.wcnt = wcnt; a.cap = cap;
         {   // the sample: a whole number of tile groups per wave of a chunk
             const int64_t all_groups = (n_tiles + rt - 1) / rt, streams = (int64_t)(UT_GRID / chunks) * UT_WAVES;
@@ -574,11 +579,51 @@ int launch_flat_u8_tfilter(int D, const void *pack, const int32_t *norms, int64_
         const size_t bucket_lds = (size_t)UT_STAGE * (sizeof(uint2) + sizeof(uint16_t)), fin_lds = (size_t)UT_CAP * sizeof(uint32_t);
         static LdsOnce attr_k = {}, attr_f = {};
         CVTMI_TRY(launch_lds_once("ut_bucket_kernel", ut_bucket_kernel, attr_k, bucket_lds, UT_GRID, 1024, bucket_lds, st, rec, wcnt, cap, thr, qqv, norms, cnt, cand, chunks, qper,
-                                  (int)m, flags));
+                                  (int)m, flags, (uint32_t)UT_CAP, 0));
         CVTMI_TRY(launch_lds_once("ut_finish_kernel", ut_finish_kernel, attr_f, fin_lds, m, 1024, fin_lds, st, n, k, cnt, cand, out_d + a0 * k, out_i + a0 * k, flags + 1 + a0,
                                   flags));
     }
     return CVTMI_OK;
+}
+
+// The same kernels for a caller with operands of its own (adc_mfma.hip): int8 queries, the rows' starting values as they are, one launch
+// over all of the batch's query chunks -- 8 j.spx row slices per chunk, 16 slots of the sample each.
+int u8_filter_rt(int D) { return ut_rt(D / 32); }
+size_t u8_filter_rec_bytes() { return 80; }
+static int u8_filter_args(const U8FilterJob &j, UtArgs &a, size_t &lds)
+{
+    const int ks = j.D / 32;
+    if (!flat_u8_tfilter_width(j.D) || j.qper % 32 != 0 || j.qper < 32 || j.qper > UT_QPER || j.chunks < 1 || j.spx < 1 || 8 * j.spx > UT_GRID ||
+        j.nq < 1 || j.nq > j.chunks * j.qper || j.n < 1 || j.n >= 0x7fffffe0LL || j.smax_stride < 8 * j.spx * UT_WAVES * 2)
+        return fail(CVTMI_EINVAL, "u8_filter: bad job (D=%d nq=%d chunks=%d qper=%d spx=%d)", j.D, j.nq, j.chunks, j.qper, j.spx);
+    a.pack = reinterpret_cast<const uint4 *>(j.pack); a.norms = j.bias; a.n = j.n; a.n_tiles = (j.n + 31) / 32; a.n_sample = j.n_sample;
+    a.Q = reinterpret_cast<const uint8_t *>(j.W); a.D = j.D; a.nq = j.nq; a.chunks = j.chunks; a.qper = j.qper;
+    a.smax = j.smax; a.thr = j.thr; a.rec = reinterpret_cast<uint4 *>(j.rec); a.wcnt = j.wcnt; a.cap = j.rec_cap;
+    a.qxor = 0u; a.bias_direct = 1; a.smax_stride = j.smax_stride; a.dbg = 0;
+    lds = (size_t)(j.qper / 32) * ks * 1024 + (size_t)j.qper * sizeof(int) + (size_t)UT_WAVES * ut_rt(ks) * 32 * sizeof(int) + 3072;
+    return CVTMI_OK;
+}
+int launch_u8_filter_sample(const U8FilterJob &j, hipStream_t st)
+{
+    UtArgs a; size_t lds = 0;
+    CVTMI_TRY(u8_filter_args(j, a, lds));
+    const int64_t all_groups = (a.n_tiles + ut_rt(j.D / 32) - 1) / ut_rt(j.D / 32);
+    if (j.n_sample < 1 || j.n_sample > all_groups) return fail(CVTMI_EINVAL, "u8_filter: sample of %lld tile groups", (long long)j.n_sample);
+    return ut_launch_any(j.D / 32, true, a, lds, st, 8 * j.spx * j.chunks);
+}
+int launch_u8_filter_pass(const U8FilterJob &j, hipStream_t st)
+{
+    UtArgs a; size_t lds = 0;
+    CVTMI_TRY(u8_filter_args(j, a, lds));
+    return ut_launch_any(j.D / 32, false, a, lds, st, 8 * j.spx * j.chunks);
+}
+int launch_u8_filter_bucket(const U8FilterJob &j, hipStream_t st)
+{
+    const size_t bucket_lds = (size_t)UT_STAGE * (sizeof(uint2) + sizeof(uint16_t));
+    static LdsOnce attr_k = {};
+    return launch_lds_once("ut_bucket_kernel", ut_bucket_kernel, attr_k, bucket_lds, 8 * j.spx * j.chunks, 1024, bucket_lds, st, reinterpret_cast<const uint4 *>(j.rec),
+                           j.wcnt, j.rec_cap, j.thr, (const int32_t *)nullptr, (const int32_t *)nullptr, j.cnt, j.cand, j.chunks, j.qper, j.nq, j.pass_flag,
+                           j.list_cap, 1);
 }
 
 }  // namespace cvtmi

@@ -80,7 +80,9 @@ inline int64_t scan_in_place_queries(const ScanPlan &plan, int M, int64_t nq)
 int launch_adc_scan(const OpqModelDev &m, const uint8_t *codes, int64_t n_rows, int64_t id_base, const float *q_rot,
                     int64_t nq, int k, const ScanPlan &plan, float *part_d, int64_t *part_id, float *lut_scratch,
                     const uint8_t *codes_rot, hipStream_t st, uint32_t *gthr = nullptr, int lazy = 1, float *final_d = nullptr,
-                    int64_t *final_id = nullptr, const uint32_t *only = nullptr);
+                    int64_t *final_id = nullptr, const uint32_t *only = nullptr, bool lut_ready = false);
+// adc_scan16q (variant 3 / 4) with only: a query group is scanned when only[] is up for any of its queries (every query of such a group gets its
+// list: the same list whoever computes it); lut_ready: lut_scratch already holds the tables of launch_lut(..., 256)
 // only ([nq] words or null; k > 128 with one query per workgroup and ONE row split): answer query g only when only[g] != 0
 // final_d / final_id ([nq][k], or null): where the first scan_in_place_queries() queries' lists go instead of part_* (with stride 1
 // part_* ARE the final arrays: pass them again)
@@ -373,6 +375,47 @@ bool flat_u8_tfilter_applies(int D, int64_t n, int64_t nq, int k);
 size_t flat_u8_tfilter_scratch(int D, int64_t n, int64_t nq, int k);
 int launch_flat_u8_tfilter(int D, const void *pack, const int32_t *norms, int64_t n, const uint8_t *q, int64_t nq, int k, void *scratch, float *out_d,
                            int64_t *out_i, uint32_t *flags, hipStream_t st);
+// the same sample, filter and bucket kernels over a caller's own operands (adc_mfma.hip): int8 queries W[nq][D], pack in launch_flat_u8_pack's
+// layout, a row's accumulator starts at -bias[row].  One launch covers `chunks` chunks of `qper` queries (a multiple of 32, <= 256), each over
+// 8 spx row slices; the sample leaves 16 slots per slice and query in smax (zeroed by the caller; key = value ^ 0x80000000, 0 = empty);
+// the bucket leaves (value, row) pairs, list_cap per query, counted in cnt (zeroed by the caller), and ORs 2 into pass_flag[chunk] when a
+// wave's record region (rec_cap records of u8_filter_rec_bytes(), 8 spx chunks x 8 regions) ran over
+struct U8FilterJob {
+    const void *pack; const int32_t *bias; int64_t n; int D;
+    const int8_t *W; int nq, chunks, qper, spx;
+    uint32_t *smax; int smax_stride; int64_t n_sample;
+    const int32_t *thr; void *rec; uint32_t *wcnt; uint32_t rec_cap;
+    uint32_t *cnt; uint2 *cand; uint32_t list_cap; uint32_t *pass_flag;
+};
+int u8_filter_rt(int D);   // row tiles of 32 per tile group
+size_t u8_filter_rec_bytes();
+int launch_u8_filter_sample(const U8FilterJob &j, hipStream_t st);
+int launch_u8_filter_pass(const U8FilterJob &j, hipStream_t st);
+int launch_u8_filter_bucket(const U8FilterJob &j, hipStream_t st);
+// adc_mfma.hip: large M = 16 ADC batches through that filter over the decoded rows
+struct AdcMfmaModel {   // per index, from the codebooks alone
+    const int8_t *xb;      // [16][256][step] the codewords as int8, X = round((v - c) / s)
+    const double *nrm;     // [16][256] |codeword|^2
+    const float *c, *s;    // [D] centre and scale per dimension (s = 0: every codeword holds c there)
+    double x_max, eps_max, xhat_max;   // >= max |X(row)|, max |(x^ - c) / s - X|, max |x^(row)|
+};
+// host side: xb / nrm / c / s into caller-sized arrays; false when an entry is not finite or a range cannot be scaled (the route stays off)
+bool adc_mfma_model(const float *books, int D, int K, int8_t *xb, double *nrm, float *c, float *s, double *x_max, double *eps_max, double *xhat_max);
+size_t adc_mfma_pack_bytes(int D, int64_t n);
+int launch_adc_mfma_pack(const AdcMfmaModel &mm, int D, const uint8_t *codes, int64_t row0, int64_t n, void *pack, float *norms, hipStream_t st);
+size_t adc_mfma_scratch_bytes(int D, int64_t n, int64_t nq, int k, int list_cap, int sample_div, int64_t *per);
+// The queries the filter could not answer, for the caller to run the exact kernel on: up to `cap` of them as a short batch of their own (q:
+// their rotated queries, only: the slots in use, d / i: where that batch's answers go, part_*: its partial lists under `splits` row splits;
+// launch_adc_mfma_scatter then copies the answers to the queries' places) and rest[nq]: != 0 for flagged queries that found no slot.
+// stat (device, two words, or null): the call's queries and how many of them were flagged
+struct AdcMfmaRedo {
+    int cap, splits;
+    int32_t *slot_q; uint32_t *only; float *q; float *d; int64_t *i; float *part_d; int64_t *part_i; uint32_t *rest;
+};
+int launch_adc_mfma_scatter(const AdcMfmaRedo &redo, int k, float *dist, int64_t *ids, hipStream_t st);
+int launch_adc_mfma(const OpqModelDev &m, const AdcMfmaModel &mm, const uint8_t *codes, const void *pack, const float *norms, int64_t n, int64_t id_base,
+                    const float *q_rot, int64_t nq, int k, int list_cap, int sample_div, float *lut_g, void *scratch, float *dist, int64_t *ids,
+                    AdcMfmaRedo *redo, unsigned long long *stat, hipStream_t st);
 // bias[r] (and zeroed padding rows) for rows [row0, row1); stats[0] = max |x|^2 bits, stats[1] = non-finite rows (both accumulate)
 int launch_flat_f32_bias(float *X, int D, int metric, int64_t row0, int64_t row1, float *bias, uint32_t *stats, hipStream_t st);
 // redo[nq], cnt[nq] (zeroed inside): redo is set to 1 for queries the exact kernels must answer

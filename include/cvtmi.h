@@ -361,6 +361,12 @@ int cvtmi_opq_mask_videos_dev(cvtmi_opq_t h, const int32_t *video_ids, int64_t n
 /* The handle's last masked IVF search: out = the six numbers of cvtmi_opq_ivf_plan, then out[6] = bytes of its partial lists and
  * out[7] = bytes of the mask in list order (both in the leased scratch set). */
 int cvtmi_opq_last_ivf_masked(cvtmi_opq_t h, int64_t out[8]);
+/* The handle's last PROFILED search ("profile" 1) that took the "scan_mfma" route: out[0] = its queries, out[1] = how many of them the
+ * filter could not answer and the exact scan answered instead.  Zeros while there has been none, and after a profiled search that did not take the route.  Waits for the device. */
+int cvtmi_opq_last_mfma(cvtmi_opq_t h, int64_t out[2]);
+/* How a batch of nq queries would go through that route (nothing touches a device): out[0] = queries per piece, out[1] = pieces (any
+ * number: they follow each other on the stream), out[2] = bytes of scratch.  A piece's lists and record regions stay within 1 GB. */
+int cvtmi_opq_mfma_plan(int D, int64_t n_rows, int64_t nq, int k, int list_cap, int sample, int64_t out[3]);
 
 /* Range search over the probed lists: for every query, EVERY entry of its nprobe nearest coarse lists whose score is under
  * `radius` -- the threshold test IVFOPQ::Query / QueryThrehold make (their cells start at 1.0 and fold with min(score, cell):
@@ -470,7 +476,15 @@ int cvtmi_opq_remove_ids_dev(cvtmi_opq_t h, const int64_t *ids, int64_t n_ids, i
  *   "groups_a", "splits_b"  force that two-region shape: the first groups_a query groups use "splits" row
  *                 splits, the others splits_b (> splits); 0 = planner's choice
  *   "remove_chunk"  rows cvtmi_opq_remove_* moves at a time (0 = default, 4 194 304): the scratch of a removal holds one chunk.
- *                 Rounded UP to whole tiles of 256 rows (1 .. 256 give one tile); negative values fail with CVTMI_EINVAL */
+ *                 Rounded UP to whole tiles of 256 rows (1 .. 256 give one tile); negative values fail with CVTMI_EINVAL
+ *   "scan_mfma"   1 (default) = large batches (M = 16, K = 256, D a multiple of 32 up to 256, coarseK = 1, k <= 128, "scan_variant" 7, no forced
+ *                 "qtile" / "splits") take the int8 matrix-core bound filter over a decoded copy of the rows (D + 4 bytes per row, built by
+ *                 the first such search and extended after appends) and re-sum the survivors exactly; queries it cannot answer go through the
+ *                 exact scan in the same call, so the results are the scan's, bit for bit; 0 = the scan
+ *   "scan_mfma_min_nq", "scan_mfma_min_rows"  the smallest batch (default 512) and index (default 1 000 000 rows) that take it (>= 1)
+ *   "scan_mfma_max_rows"  the largest index that takes it; negative (default) = while the copy stays within 1 GB
+ *   "scan_mfma_cap"  candidate rows per query the selection accepts, 1 .. 4096 (default 4096); a query with more goes to the exact scan
+ *   "scan_mfma_sample"  the threshold comes from a sample of one tile group in this many, 1 .. 3 (default 2) */
 int cvtmi_opq_set_param(cvtmi_opq_t h, const char *name, int64_t value);
 /* With "profile" on: MEAN duration of the scan-kernel launches recorded since the previous call
  * (the 64 most recent are kept) and the algorithmic code bytes ONE launch reads
