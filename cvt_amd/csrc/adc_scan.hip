@@ -490,107 +490,6 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16_kernel(const ScanArgs
 // Measured on the bare loop (tools/ubench/scan_loop_u16.hip): 36-45 T look-ups/s vs 21-25 for fp32.
 // ==========================================================================================
 
-// The QT queries' tables of `group`, quantised into LDS: lut[code j][m][q] u16, with the per-query scale / bias /
-// lazy-selection parameters in qp.  mx_bits = QT x 16 words of scratch; nonfinite / lazy = QT flags each.
-// Called by the whole workgroup; ends with a barrier.
-template <int NT>
-__device__ __forceinline__ void scan16q_build_tables(const ScanArgs &a, int group, uint32_t *lut, QuantParams &qp, uint32_t (*mx_bits)[16],
-                                                     int *nonfinite, int *lazy)
-{
-    constexpr int M = 16, QT = SQ_QT;
-    const int tid = threadIdx.x, lane = tid & 63;
-    if (tid < QT * 16) {
-        qp.mn_bits[tid >> 4][tid & 15] = 0x7f7fffffu;  // FLT_MAX
-        mx_bits[tid >> 4][tid & 15] = 0u;
-    }
-    if (tid < QT) nonfinite[tid] = 0;
-    __syncthreads();
-    // fp32 table entries of (m, j) for the QT queries, from the per-query tables a.lut_g
-    // (lut_kernel: IVFOPQ.cpp:279-291); lanes walk consecutive j -> coalesced
-    int qis[QT];
-#pragma unroll
-    for (int q = 0; q < QT; ++q) {
-        const int qi = group * QT + q;
-        qis[q] = qi < a.nq ? qi : a.nq - 1;
-    }
-    auto entry = [&](int m, int j, float (&acc)[QT]) {
-#pragma unroll
-        for (int q = 0; q < QT; ++q)
-            acc[q] = a.lut_g[((int64_t)qis[q] * M + m) * 256 + j];  // padded with +inf past K
-    };
-    // pass A: per (query, m) range of the finite entries (a wave covers 64 consecutive j of one m)
-    for (int e = tid; e < M * 256; e += NT) {
-        const int m = e >> 8, j = e & 255;
-        float acc[QT];
-        entry(m, j, acc);
-#pragma unroll
-        for (int q = 0; q < QT; ++q) {
-            const uint32_t bits = __float_as_uint(acc[q]);
-            uint32_t lo = bits < 0x7f800000u ? bits : 0x7f7fffffu;  // non-finite: ignored
-            uint32_t hi = bits < 0x7f800000u ? bits : 0u;
-            if (__ballot(bits >= 0x7f800000u) != 0 && lane == 0) nonfinite[q] = 1;  // (the +inf padding past K counts: a code >= K reaches it)
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                const uint32_t l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
-                lo = l2 < lo ? l2 : lo;
-                hi = h2 > hi ? h2 : hi;
-            }
-            if (lane == 0) {
-                atomicMin(&qp.mn_bits[q][m], lo);
-                atomicMax(&mx_bits[q][m], hi);
-            }
-        }
-    }
-    __syncthreads();
-    if (tid < QT) {
-        const int q = tid;
-        float range = 0.0f;
-        double bias = 0.0;
-        for (int m = 0; m < M; ++m) {
-            uint32_t lo = qp.mn_bits[q][m], hi = mx_bits[q][m];
-            if (lo > hi) { lo = 0u; hi = 0u; }  // no finite entry at all
-            const float fl = __uint_as_float(lo), fh = __uint_as_float(hi);
-            qp.mn[q][m] = fl;
-            range += fh - fl;
-            bias += (double)fl;
-        }
-        float scale = range > 0.0f ? range / (float)SQ_MAXSUM * 1.001f : 1.0f;
-        if (!(scale > 1e-37f)) scale = 1e-37f;
-        const float inv = 1.0f / scale;
-        qp.inv_scale[q] = inv;
-        qp.scale_eff[q] = 1.0 / (double)inv;
-        qp.bias[q] = bias;
-        // lazy selection (scan_compact_lazy_q): usable when every table entry is finite and the band stays narrow
-        const double sl = 34.0 + ceil(4e-6 * (32767.0 + bias * (double)inv));
-        const bool lazy_ok = a.lazy && !nonfinite[q] && sl < 1024.0 && bias >= 0.0;
-        qp.slack[q] = lazy_ok ? (uint32_t)sl : 0u;
-        lazy[q] = lazy_ok ? 1 : 0;
-    }
-    __syncthreads();
-    // pass B: quantise  qv = max(0, floor((v - min_m) * inv) - 1), non-finite entries -> 0 (a lower bound of anything)
-    for (int e = tid; e < M * 256; e += NT) {
-        const int m = e >> 8, j = e & 255;
-        float acc[QT];
-        entry(m, j, acc);
-        uint32_t qv[QT];
-#pragma unroll
-        for (int q = 0; q < QT; ++q) {
-            const float v = acc[q];
-            int iv = 0;
-            if (__float_as_uint(v) < 0x7f800000u) {
-                const float f = __fmul_rn(__fsub_rn(v, qp.mn[q][m]), qp.inv_scale[q]);
-                iv = (int)floorf(f) - 1;
-                iv = iv < 0 ? 0 : (iv > SQ_MAXSUM ? SQ_MAXSUM : iv);
-            }
-            qv[q] = (uint32_t)iv;
-        }
-        *reinterpret_cast<uint4 *>(&lut[(j * 16 + m) * (QT / 2)]) =
-            make_uint4(qv[0] | (qv[1] << 16), qv[2] | (qv[3] << 16), qv[4] | (qv[5] << 16), qv[6] | (qv[7] << 16));
-    }
-    __syncthreads();  // tables ready; the scratch words on tk.buf are dead from here on
-}
-
-
 template <int NT, int R, bool PREROT>
 __global__ __launch_bounds__(NT, NT / 128) void adc_scan16q_kernel(const ScanArgs a)
 {
@@ -601,55 +500,19 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16q_kernel(const ScanArg
     __shared__ struct { int stop, done_waves; uint32_t next_chunk; uint32_t thr_pk[QT / 2]; int lazy[QT]; int nonfinite[QT]; } ck;
 
     SQ_T0();
-    int group, split, my_splits = a.splits;
-    int64_t my_rps = a.rows_per_split;
-    {
-        int b = blockIdx.x, g0 = 0;
-        if (b >= a.groups_a * a.splits) {  // region B: the tail groups, split finer (dispatched last)
-            b -= a.groups_a * a.splits;
-            g0 = a.groups_a;
-            my_splits = a.splits_b;
-            my_rps = a.rows_per_split_b;
-        }
-        if ((my_splits & 7) == 0) {
-            const int s8 = my_splits >> 3;
-            const int xcd = b & 7, i = b >> 3;
-            split = xcd + 8 * (i % s8);
-            group = g0 + i / s8;
-        } else {
-            split = b % my_splits;
-            group = g0 + b / my_splits;
-        }
-    }
-    if (a.only) {   // workgroup-uniform: a group none of whose queries is flagged has its answers already (adc_mfma.hip's fall-back)
-        uint32_t any = 0u;
-        for (int q = 0; q < QT; ++q)
-            if (group * QT + q < a.nq) any |= a.only[group * QT + q];
-        if (!any) return;
-    }
+    const ScanBlock blk = scan16_block(a);
+    const int group = blk.group, split = blk.split;
+    const int64_t my_rps = blk.my_rps;
+    if (a.only && !scan16_group_wanted(a, group)) return;   // a group none of whose queries is flagged has its answers already
     const int tid = threadIdx.x, lane = tid & 63;
     topk_init(tk);
     scan16q_build_tables<NT>(a, group, lut, qp, reinterpret_cast<uint32_t(*)[16]>(&tk.buf[0][0]), ck.nonfinite, ck.lazy);  // scratch on the (still unused) buffers
     SQ_T(0);  // prologue
 
     const uint4 *rows = reinterpret_cast<const uint4 *>(a.codes);
-    const ExactFromLutBatch fixb{ rows, a.lut_g, a.K, a.nq, group };
+    const ExactFromLutBatch<> fixb{ rows, a.lut_g, a.K, a.nq, group };
     const QuantThr thrx{ &qp };
-    if (tid < QT / 2) {  // pass-all until k rows are known -- or what the other row splits of these queries have already established
-        uint32_t t2[2] = { 32767u, 32767u };
-        if (a.gthr) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int qi = group * QT + 2 * tid + h;
-                if (qi < a.nq) {  // a stale value is an older, looser, still valid bound
-                    const uint32_t g = __hip_atomic_load(&a.gthr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    t2[h] = g < t2[h] ? g : t2[h];
-                }
-            }
-        }
-        tk.thr_x[2 * tid] = t2[0]; tk.thr_x[2 * tid + 1] = t2[1];
-        ck.thr_pk[tid] = t2[0] | (t2[1] << 16);
-    }
+    scan16_init_thresholds(a, group, tid, tk, ck.thr_pk);
     if (tid == 0) { ck.stop = 0; ck.done_waves = 0; ck.next_chunk = 0; }
     __syncthreads();
 
@@ -697,21 +560,11 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16q_kernel(const ScanArg
     // compacted when one is full or past TRIG.  Row order across waves is arbitrary: legal here because
     // the filter is a superset test and the exact (distance, id) sort decides (block_topk.h).
     constexpr int NW = NT / 64;
-    // chunks are handed out dynamically (one LDS atomic per 64*R rows): waves that run faster take more,
-    // so nobody waits long at the final checkpoint.  `it` = chunk in hand, `it_next` = already reserved
+    // chunks are handed out dynamically (scan16_grab_pair: one LDS atomic per two chunks of 64*R rows): waves that run faster
+    // take more, so nobody waits long at the final checkpoint.  `it` = chunk in hand, `it_next` = already reserved
     // and being prefetched.
-    // (the atomic is spelled out: for `if (lane == 0) atomicAdd(...)` hipcc emits its wave-aggregation sequence -- two mbcnt, a
-    //  compare, a population count and two moves -- around the one-lane atomic: 6 of the loop's 66 vector instructions per row)
     const uint32_t next_chunk_addr = (uint32_t)(uintptr_t)&ck.next_chunk;
-    // Chunks go out in PAIRS (2 p, 2 p + 1): one atomic per two chunks, the odd one follows without asking.
-    auto grab_pair = [&]() -> uint32_t {
-        uint32_t v;
-        asm volatile("" : "=v"(v));  // (only lane 0's value is read: no instruction to define the others)
-        if (lane == 0) asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(next_chunk_addr), "v"(1u) : "memory");
-        return 2u * (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-    };
-    auto after = [&](uint32_t chunk) -> uint32_t { return (chunk & 1u) ? grab_pair() : chunk + 1u; };  // wave-uniform branch
-    uint32_t it = grab_pair(), it_next = it + 1u, done = 0, done_for = 0xffffffffu;
+    uint32_t it = scan16_grab_pair(next_chunk_addr, lane), it_next = it + 1u, done = 0, done_for = 0xffffffffu;
     bool counted = false;
     uint4 cur[R], nxt[R];
     if (n_local) {
@@ -745,17 +598,7 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16q_kernel(const ScanArg
                     asm volatile("" : "+v"(lrow));  // (keeps the tail test in here: hipcc otherwise folds it into the common path's branch)
                     if (sg != 0 && lrow < n_local) {
                         const uint32_t sums[4] = { s0, s1, s2, s3 };
-#pragma unroll
-                        for (int q = 0; q < QT; ++q) {
-                            const uint32_t bit = 1u << (r * QT + q);
-                            const uint32_t sq = (sums[q >> 1] >> (16 * (q & 1))) & 0xffffu;
-                            const uint32_t tq = (tpk[q >> 1] >> (16 * (q & 1))) & 0xffffu;
-                            if (sq < tq && !(done & bit)) {
-                                bool dummy = false;
-                                if (topk_push<QT, SQ_CAP, SQ_TRIG>(tk, q, sq, (uint32_t)(row_begin + lrow), dummy)) done |= bit;
-                                else failed = true;
-                            }
-                        }
+                        failed = scan16_push_candidates(tk, sums, tpk, row_begin, lrow, r * QT, done);
                     }
                     failed_any |= __ballot(failed) != 0;
                 }
@@ -767,7 +610,7 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16q_kernel(const ScanArg
 #pragma unroll
             for (int r = 0; r < R; ++r) cur[r] = nxt[r];
             it = it_next;
-            it_next = after(it);
+            it_next = scan16_after(it, next_chunk_addr, lane);
             if (__builtin_amdgcn_readfirstlane(stop_seen)) break;
         }
         SQ_T(1);  // look-ups + pushes
@@ -781,30 +624,7 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16q_kernel(const ScanArg
 #pragma unroll
         for (int q = 0; q < QT; ++q) need |= tk.cnt[q] >= SQ_TRIG;
         const bool all_done = ck.done_waves == NW;
-        if (need) {  // workgroup-uniform
-            {
-                const int wv = tid >> 6;
-                const int keep_max = a.k + 48 < SQ_TRIG - 24 ? a.k + 48 : SQ_TRIG - 24;
-                for (int q = wv; q < QT; q += NW) {  // wave-uniform: one wave per query, in registers
-                    const int keep = ck.lazy[q] ? scan_compact_lazy_q<QT, SQ_CAP>(tk, q, a.k, fixb, thrx, qp.slack[q], keep_max, &ck.lazy[q])
-                                                : topk_compact_wave_q<QT, SQ_CAP, false>(tk, q, a.k, fixb, thrx);
-                    if (lane == 0) {
-                        tk.cnt[q] = keep;
-                        if (a.gthr) {  // the row splits of a query tighten each other's filter (same tables -> same units)
-                            const int qi = group * QT + q;
-                            if (qi < a.nq) {
-                                const uint32_t mine = tk.thr_x[q];
-                                const uint32_t seen = atomicMin(&a.gthr[qi], mine);
-                                tk.thr_x[q] = seen < mine ? seen : mine;
-                            }
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-            if (tid < QT / 2) ck.thr_pk[tid] = tk.thr_x[2 * tid] | (tk.thr_x[2 * tid + 1] << 16);
-            if (tid == 0) ck.stop = 0;
-        }
+        if (need) scan16_checkpoint_compact<NT>(a, group, tk, qp, ck.lazy, ck.thr_pk, ck.stop, fixb, thrx);  // workgroup-uniform
         __syncthreads();  // checkpoint (B)
         SQ_T(3);  // checkpoint protocol + compactions
         if (all_done && !need) break;
@@ -814,35 +634,7 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16q_kernel(const ScanArg
     topk_compact_wave<QT, SQ_CAP, NT, true>(tk, a.k, fixb, thrx);
     SQ_T(4);  // final compaction
     SQ_TEND();
-#pragma unroll
-    for (int q = 0; q < QT; ++q) {
-        const int qi = group * QT + q;
-        if (qi >= a.nq) break;
-        const int cnt = tk.cnt[q];
-        // a group of the first region that was scanned in one piece holds its queries' final lists: they go where the caller wants them
-        const bool in_place = a.out_d != nullptr && group < a.groups_a;   // (out_d is only set when that region has one split)
-        float *const pd = in_place ? a.out_d : a.part_d;
-        int64_t *const pi = in_place ? a.out_id : a.part_id;
-        const int64_t o = in_place ? (int64_t)qi * a.k : ((int64_t)qi * a.stride + split) * a.k;
-        for (int i = tid; i < a.k; i += NT) {
-            if (i < cnt) {
-                const unsigned long long e = tk.buf[q][i];
-                pd[o + i] = __uint_as_float((uint32_t)(e >> 32));
-                pi[o + i] = a.id_base + (int64_t)(uint32_t)e;
-            } else {
-                pd[o + i] = __uint_as_float(0x7f800000u);
-                pi[o + i] = -1;
-            }
-        }
-        // a region with fewer splits than the partial stride leaves the other slots empty for the merge
-        if (!in_place && split == 0 && my_splits < a.stride) {
-            const int64_t o2 = ((int64_t)qi * a.stride + my_splits) * a.k;
-            for (int i = tid; i < (a.stride - my_splits) * a.k; i += NT) {
-                a.part_d[o2 + i] = __uint_as_float(0x7f800000u);
-                a.part_id[o2 + i] = -1;
-            }
-        }
-    }
+    scan16_write_lists<NT, true>(a, tk, group, split, blk.my_splits);
 }
 
 // ==========================================================================================
@@ -945,7 +737,7 @@ __device__ __forceinline__ void scan16a_compact(ScanAsyncTopK &tk, ScanAsyncCtl 
     const int lane = threadIdx.x & 63;
     const bool l0 = lane == 0;
     const int k = ck.k, group = ck.group;
-    const ExactFromLutBatch fixb{ ck.rows, ck.lut_g, ck.K, ck.nq, group };
+    const ExactFromLutBatch<> fixb{ ck.rows, ck.lut_g, ck.K, ck.nq, group };
     const QuantThr thrx{ &qp };
     const int keep_max = k + 48 < SQ_TRIG - 24 ? k + 48 : SQ_TRIG - 24;
     [[maybe_unused]] const long long t_c0 = SQA_NOW();
@@ -1024,49 +816,18 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16a_kernel(const ScanArg
     __shared__ ScanAsyncCtl ck;
 
     SQ_T0();
-    int group, split, my_splits = a.splits;
-    int64_t my_rps = a.rows_per_split;
-    {
-        int b = blockIdx.x, g0 = 0;
-        if (b >= a.groups_a * a.splits) {  // region B: the tail groups, split finer (dispatched last)
-            b -= a.groups_a * a.splits;
-            g0 = a.groups_a;
-            my_splits = a.splits_b;
-            my_rps = a.rows_per_split_b;
-        }
-        if ((my_splits & 7) == 0) {
-            const int s8 = my_splits >> 3;
-            const int xcd = b & 7, i = b >> 3;
-            split = xcd + 8 * (i % s8);
-            group = g0 + i / s8;
-        } else {
-            split = b % my_splits;
-            group = g0 + b / my_splits;
-        }
-    }
+    const ScanBlock blk = scan16_block(a);
+    const int group = blk.group, split = blk.split;
+    const int64_t my_rps = blk.my_rps;
     const int tid = threadIdx.x, lane = tid & 63;
     topk_init(tk);
     scan16q_build_tables<NT>(a, group, lut, qp, reinterpret_cast<uint32_t(*)[16]>(&tk.buf[0][0]), ck.nonfinite, ck.lazy);
     SQ_T(0);  // prologue
 
     const uint4 *rows = reinterpret_cast<const uint4 *>(a.codes);
-    const ExactFromLutBatch fixb{ rows, a.lut_g, a.K, a.nq, group };
+    const ExactFromLutBatch<> fixb{ rows, a.lut_g, a.K, a.nq, group };
     const QuantThr thrx{ &qp };
-    if (tid < QT / 2) {  // pass-all until k rows are known -- or what the other row splits of these queries have already established
-        uint32_t t2[2] = { 32767u, 32767u };
-        if (a.gthr) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int qi = group * QT + 2 * tid + h;
-                if (qi < a.nq) {  // a stale value is an older, looser, still valid bound
-                    const uint32_t g = __hip_atomic_load(&a.gthr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    t2[h] = g < t2[h] ? g : t2[h];
-                }
-            }
-        }
-        tk.thr_x[2 * tid] = t2[0]; tk.thr_x[2 * tid + 1] = t2[1];
-        ck.thr_pk[tid] = t2[0] | (t2[1] << 16);
-    }
+    scan16_init_thresholds(a, group, tid, tk, ck.thr_pk);
 #ifdef CVTMI_SCAN_TIMING
     if (tid < 8) ck.dbg[tid] = 0;
 #endif
@@ -1194,30 +955,7 @@ __global__ __launch_bounds__(NT, NT / 128) void adc_scan16a_kernel(const ScanArg
 #ifdef CVTMI_SCAN_TIMING
     if (tid < 8) atomicAdd(&g_scan_dbg2[tid], ck.dbg[tid]);
 #endif
-#pragma unroll
-    for (int q = 0; q < QT; ++q) {
-        const int qi = group * QT + q;
-        if (qi >= a.nq) break;
-        const int cnt = tk.cnt[q];
-        const int64_t o = ((int64_t)qi * a.stride + split) * a.k;
-        for (int i = tid; i < a.k; i += NT) {
-            if (i < cnt) {
-                const unsigned long long e = tk.buf[q][i];
-                a.part_d[o + i] = __uint_as_float((uint32_t)(e >> 32));
-                a.part_id[o + i] = a.id_base + (int64_t)(uint32_t)e;
-            } else {
-                a.part_d[o + i] = __uint_as_float(0x7f800000u);
-                a.part_id[o + i] = -1;
-            }
-        }
-        if (split == 0 && my_splits < a.stride) {  // a region with fewer splits than the partial stride: the other slots stay empty
-            const int64_t o2 = ((int64_t)qi * a.stride + my_splits) * a.k;
-            for (int i = tid; i < (a.stride - my_splits) * a.k; i += NT) {
-                a.part_d[o2 + i] = __uint_as_float(0x7f800000u);
-                a.part_id[o2 + i] = -1;
-            }
-        }
-    }
+    scan16_write_lists<NT, false>(a, tk, group, split, blk.my_splits);   // (never in place: scan_in_place_queries, kernels.h)
 }
 
 int scan_seed_enabled() { return tune_scan_seed.geti(); }
@@ -1443,6 +1181,9 @@ int launch_adc_scan(const OpqModelDev &m, const uint8_t *codes, int64_t n_rows, 
         }
         if (plan.packed) return launch_adc_scan16p(a, plan.real_M, blocks, st);   // (codes = the model's own rows, codes_rot = their packed rotation)
         const int v = plan.variant;   // 3, 4: adc_scan16q with 1024 / 512 threads; else adc_scan16a
+        // `only` comes from the matrix-core route's fall-back (adc_mfma.hip) alone, which plans variant 3 / 4 (or k > 128: adc_scan_kernel):
+        // adc_scan16q_kernel is the one filter scan that reads it
+        if (only && v != 3 && v != 4) return fail(CVTMI_EINVAL, "adc_scan16a: no group predicate (only)");
         decltype(&adc_scan16q_kernel<1024, 1, true>) kern;
         if (codes_rot) {
             if (v == 3) kern = adc_scan16q_kernel<1024, 1, true>;

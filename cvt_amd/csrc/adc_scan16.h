@@ -1,7 +1,13 @@
-// adc_scan16.h -- pieces shared by the M = 16 skewed scan kernels (adc_scan.hip: adc_scan16q / adc_scan16a,
-// adc_scan_h.hip: adc_scan16h): kernel arguments, the 15-bit lower-bound tables' parameters, the conflict-free look-up
-// loop of one row, the exact re-sum of candidates and the lazy (integer-key) selection.  See adc_scan.hip for the
-// reference arithmetic (opq/src/IVFOPQ.cpp:273-306) and the derivations.
+// adc_scan16.h -- pieces shared by the M = 16 skewed scan kernels (adc_scan.hip: adc_scan16q / adc_scan16a, adc_scan_p.hip:
+// adc_scan16p, adc_scan_h.hip: adc_scan16h and its table kernel): kernel arguments, the rule of the 15-bit lower-bound tables
+// (scan16_query_params, scan16_quantise: stated here ONCE, every form calls them) and their build in LDS, the conflict-free
+// look-up loop of one row, the exact re-sum of candidates, the lazy (integer-key) selection, the seed, and the workgroup frame
+// of the checkpointed forms (block decoding, first thresholds, chunk hand-out, candidate push, checkpoint compaction, list
+// epilogue).  A kernel keeps what is its own: its shared-memory layout, its look-up loop and its control words.  See
+// adc_scan.hip for the reference arithmetic (opq/src/IVFOPQ.cpp:273-306) and the derivations.
+// Shape of the helpers: they take structures by reference and read them where the value is used, and keep what they update in
+// locals; a helper that takes a value the caller has loaded already, or updates a caller's variable through a reference inside a
+// loop, moves loads and branches and with them the kernel's schedule (check a change with tools/device_asm_diff.sh).
 #pragma once
 #include "block_topk.h"
 #include "kernels.h"
@@ -31,8 +37,9 @@ struct ScanArgs {
     uint32_t *gthr;            // adc_scan16q: [nq] filter thresholds (table units) shared by the row splits of a query, or null
     int lazy;                  // adc_scan16q: 1 = intermediate compactions select on the integer lower bounds (exact sums only at the end)
     int seed;                  // adc_scan16q / 16a: 1 = first thresholds from a histogram of the split's first rows (scan16q_seed)
-    const uint32_t *only = nullptr;  // adc_scan_kernel with one query per workgroup (k > 128): answer query g only when only[g] != 0 (the
-                                     // big-k filter pipeline's fall-back, adc_scan_h.hip); null: every query
+    const uint32_t *only = nullptr;  // answer query g only when only[g] != 0; null: every query.  Read by adc_scan_kernel with one query per
+                                     // workgroup (the big-k filter pipeline's fall-back, adc_scan_h.hip) and by adc_scan16q_kernel (the
+                                     // matrix-core route's, adc_mfma.hip); the launches of adc_scan16a / adc_scan16p refuse it
 };
 
 #ifdef CVTMI_SCAN_TIMING
@@ -85,6 +92,119 @@ struct QuantThr {
     }
 };
 
+// ---- the table rule: every later stage trusts this arithmetic (why the sums are lower bounds: adc_scan.hip ahead of adc_scan16q_kernel;
+// the band of the lazy selection: scan_compact_lazy_q below) -----------------------------------------------------------------------
+// Query q's parameters from the collected ranges of its MP real tables (qp.mn_bits / mx_bits hold the minimum / maximum finite entry of
+// each table as float bits): per-table minimum, one scale over the sum of the ranges such that sum_m max_j qv <= SQ_MAXSUM, the bias,
+// and the band of the lazy selection (scan_compact_lazy_q; derived for sixteen entries of two units each, MP entries need less) --
+// usable when every entry is finite and the band stays narrow.  One thread per query; returns whether the query may select lazily
+// (the same as qp.slack != 0).
+template <int MP>
+__device__ __forceinline__ bool scan16_query_params(QuantParams &qp, const uint32_t (*mx_bits)[16], int q, int lazy_on, const int *nonfinite)
+{
+    float range = 0.0f;
+    double bias = 0.0;
+    for (int m = 0; m < MP; ++m) {
+        uint32_t lo = qp.mn_bits[q][m], hi = mx_bits[q][m];
+        if (lo > hi) { lo = 0u; hi = 0u; }  // no finite entry at all
+        const float fl = __uint_as_float(lo), fh = __uint_as_float(hi);
+        qp.mn[q][m] = fl;
+        range += fh - fl;
+        bias += (double)fl;
+    }
+    float scale = range > 0.0f ? range / (float)SQ_MAXSUM * 1.001f : 1.0f;
+    if (!(scale > 1e-37f)) scale = 1e-37f;
+    const float inv = 1.0f / scale;
+    qp.inv_scale[q] = inv;
+    qp.scale_eff[q] = 1.0 / (double)inv;
+    qp.bias[q] = bias;
+    const double sl = 34.0 + ceil(4e-6 * (32767.0 + bias * (double)inv));
+    const bool lazy_ok = lazy_on && !nonfinite[q] && sl < 1024.0 && bias >= 0.0;
+    qp.slack[q] = lazy_ok ? (uint32_t)sl : 0u;
+    return lazy_ok;
+}
+// One entry: qv = clamp(floor((v - min_m) * inv) - 1, 0, SQ_MAXSUM), a lower bound of (v - min_m) in table units; a non-finite
+// entry -> 0 (a lower bound of anything).  (qp by reference: its two LDS reads stay inside the finite-entry branch.)
+__device__ __forceinline__ uint32_t scan16_quantise(float v, const QuantParams &qp, int q, int m)
+{
+    int iv = 0;
+    if (__float_as_uint(v) < 0x7f800000u) {
+        const float f = __fmul_rn(__fsub_rn(v, qp.mn[q][m]), qp.inv_scale[q]);
+        iv = (int)floorf(f) - 1;
+        iv = iv < 0 ? 0 : (iv > SQ_MAXSUM ? SQ_MAXSUM : iv);
+    }
+    return (uint32_t)iv;
+}
+
+// The QT queries' tables of `group`, quantised into LDS: lut[code j][slot][q] u16, with the per-query scale / bias /
+// lazy-selection parameters in qp.  MP = the model's real tables (range and bias run over these only); the sixteen 16-byte slots of a
+// code value hold 16 / MP copies of them, copy c of sub-space m at slot m + MP c (adc_scan16p's packed rows; MP = 16: slot = m).
+// mx_bits = QT x 16 words of scratch; nonfinite / lazy = QT flags each.  Called by the whole workgroup; ends with a barrier.
+template <int NT, int MP = 16>
+__device__ __forceinline__ void scan16q_build_tables(const ScanArgs &a, int group, uint32_t *lut, QuantParams &qp, uint32_t (*mx_bits)[16],
+                                                     int *nonfinite, int *lazy)
+{
+    constexpr int QT = SQ_QT;
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < QT * 16) {
+        qp.mn_bits[tid >> 4][tid & 15] = 0x7f7fffffu;  // FLT_MAX
+        mx_bits[tid >> 4][tid & 15] = 0u;
+    }
+    if (tid < QT) nonfinite[tid] = 0;
+    __syncthreads();
+    // fp32 table entries of (m, j) for the QT queries, from the per-query tables a.lut_g
+    // (lut_kernel: IVFOPQ.cpp:279-291); lanes walk consecutive j -> coalesced
+    int qis[QT];
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+        const int qi = group * QT + q;
+        qis[q] = qi < a.nq ? qi : a.nq - 1;
+    }
+    auto entry = [&](int m, int j, float (&acc)[QT]) {
+#pragma unroll
+        for (int q = 0; q < QT; ++q)
+            acc[q] = a.lut_g[((int64_t)qis[q] * 16 + m) * 256 + j];  // padded with +inf past K
+    };
+    // pass A: per (query, m) range of the finite entries (a wave covers 64 consecutive j of one m)
+    for (int e = tid; e < MP * 256; e += NT) {
+        const int m = e >> 8, j = e & 255;
+        float acc[QT];
+        entry(m, j, acc);
+#pragma unroll
+        for (int q = 0; q < QT; ++q) {
+            const uint32_t bits = __float_as_uint(acc[q]);
+            uint32_t lo = bits < 0x7f800000u ? bits : 0x7f7fffffu;  // non-finite: ignored
+            uint32_t hi = bits < 0x7f800000u ? bits : 0u;
+            if (__ballot(bits >= 0x7f800000u) != 0 && lane == 0) nonfinite[q] = 1;  // (the +inf padding past K counts: a code >= K reaches it)
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const uint32_t l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+                lo = l2 < lo ? l2 : lo;
+                hi = h2 > hi ? h2 : hi;
+            }
+            if (lane == 0) {
+                atomicMin(&qp.mn_bits[q][m], lo);
+                atomicMax(&mx_bits[q][m], hi);
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < QT) lazy[tid] = scan16_query_params<MP>(qp, mx_bits, tid, a.lazy, nonfinite) ? 1 : 0;
+    __syncthreads();
+    // pass B: quantise every slot
+    for (int e = tid; e < 16 * 256; e += NT) {
+        const int slot = e >> 8, j = e & 255, m = slot & (MP - 1);
+        float acc[QT];
+        entry(m, j, acc);
+        uint32_t qv[QT];
+#pragma unroll
+        for (int q = 0; q < QT; ++q) qv[q] = scan16_quantise(acc[q], qp, q, m);
+        *reinterpret_cast<uint4 *>(&lut[(j * 16 + slot) * (QT / 2)]) =
+            make_uint4(qv[0] | (qv[1] << 16), qv[2] | (qv[3] << 16), qv[4] | (qv[5] << 16), qv[6] | (qv[7] << 16));
+    }
+    __syncthreads();  // tables ready; the scratch words are dead from here on
+}
+
 // exact reference-order distance of (row, query): sum over m ascending of the fp32 table entries
 // (IVFOPQ.cpp:302-306) gathered from the per-query tables in HBM -- 16 independent loads.
 struct ExactFromLut {
@@ -132,9 +252,11 @@ __device__ __forceinline__ void block_bitonic_u64(unsigned long long *e, int n)
 }
 
 // batched form for the register compaction: up to 4 entries per lane, all row loads first, then all
-// 64 table gathers, then the in-order sums -- two dependent memory round trips per batch instead of 2 x 4
+// 4 MP table gathers, then the in-order sums -- two dependent memory round trips per batch instead of 2 x 4.
+// Rows of MP code bytes (16: one 16-byte load); tables [nq][16][256] fp32 of which the first MP belong to the model.
+template <int MP = 16>
 struct ExactFromLutBatch {
-    const uint4 *rows;
+    const void *rows;
     const float *lut_g;
     int K, nq, group;
     __device__ __forceinline__ void operator()(int q, unsigned long long (&e)[4], const bool (&need)[4]) const
@@ -142,19 +264,28 @@ struct ExactFromLutBatch {
         int qi = group * SQ_QT + q;
         qi = qi < nq ? qi : nq - 1;
         const float *t = lut_g + (int64_t)qi * 16 * 256;
-        uint4 c[4];
+        uint32_t c[4][MP / 4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) c[r] = rows[need[r] ? (uint32_t)e[r] : 0u];
+        for (int r = 0; r < 4; ++r) {
+            const uint32_t row = need[r] ? (uint32_t)e[r] : 0u;
+            if constexpr (MP == 16) {
+                const uint4 c4 = static_cast<const uint4 *>(rows)[row];
+                c[r][0] = c4.x; c[r][1] = c4.y; c[r][2] = c4.z; c[r][3] = c4.w;
+            } else {
+                const uint32_t *p = reinterpret_cast<const uint32_t *>(static_cast<const uint8_t *>(rows) + (size_t)row * MP);
 #pragma unroll
-        for (int h = 0; h < 4; h += 2) {  // two entries at a time: 32 gathers in flight, 32 registers
+                for (int w = 0; w < MP / 4; ++w) c[r][w] = p[w];
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < 4; h += 2) {  // two entries at a time: 2 MP gathers in flight
             if (__ballot(need[h] || need[h + 1]) == 0) continue;  // wave-uniform: nothing to fix in this pair
-            float v[2][16];
+            float v[2][MP];
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                const uint32_t w[4] = { c[h + r].x, c[h + r].y, c[h + r].z, c[h + r].w };
 #pragma unroll
-                for (int m = 0; m < 16; ++m) {
-                    const int j = (int)((w[m >> 2] >> (8 * (m & 3))) & 0xffu);
+                for (int m = 0; m < MP; ++m) {
+                    const int j = (int)((c[h + r][m >> 2] >> (8 * (m & 3))) & 0xffu);
                     // (a predicated gather made hipcc wait vmcnt(0) after every one of the 64 loads:
                     //  64 serialized memory round trips, 14 us per compaction)
                     v[r][m] = t[m * 256 + j];  // scratch tables are padded to 256 entries (+inf past K): no predicate
@@ -164,7 +295,7 @@ struct ExactFromLutBatch {
             for (int r = 0; r < 2; ++r) {
                 float s = 0.0f;
 #pragma unroll
-                for (int m = 0; m < 16; ++m) s = __fadd_rn(s, v[r][m]);
+                for (int m = 0; m < MP; ++m) s = __fadd_rn(s, v[r][m]);
                 if (need[h + r]) e[h + r] = ((unsigned long long)__float_as_uint(s) << 32) | (uint32_t)e[h + r];
             }
         }
@@ -301,32 +432,12 @@ __device__ __forceinline__ void scan16q_row_sums(const uint4 &row, const uint32_
     }
 }
 
-// Seed: a first filter threshold per query from a histogram of the split's first SQ_SEED_CHUNKS x 64 rows.
-// Without it a scan starts with "every row passes": a thousand rows in flight against SQ_CAP slots, and four to five rounds of
-// the whole workgroup waiting for compactions before the pass rate has fallen.  bin = sum >> 7; the first bin b at which the
-// cumulative count reaches k proves k rows with sum < (b + 1) << 7 =: S, hence S_k <= S, and T = S + slack is a valid (looser)
-// lazy-selection threshold (scan_compact_lazy_q).  Queries that cannot select lazily keep "pass all".  The seed rows are
-// scanned again by the main loop.  hist = SQ_QT x 256 words (the still unused selection buffers).  Whole workgroup; ends with a barrier.
-constexpr uint32_t SQ_SEED_CHUNKS = 32;
-template <int NT, bool PREROT, class LoadRow>
-__device__ __forceinline__ void scan16q_seed(int k, const LoadRow &load64, const uint32_t (&moffp)[4], uint32_t cr8, uint32_t cq, const char *lut_b,
-                                             uint32_t *hist, const QuantParams &qp, const int *lazy, uint32_t *thr_x, uint32_t *thr_pk)
+// The threshold half of a seed: wave q turns query q's histogram (256 bins of 128 table units) into a first threshold.  The first bin b
+// at which the cumulative count reaches k proves k rows with sum < (b + 1) << 7; queries that cannot select lazily keep what they have.
+__device__ __forceinline__ void scan16_seed_threshold(int k, const uint32_t *hist, const QuantParams &qp, const int *lazy, uint32_t *thr_x, uint32_t *thr_pk)
 {
-    constexpr int QT = SQ_QT, NW = NT / 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < QT * 256; i += NT) hist[i] = 0;
-    __syncthreads();
-    for (uint32_t ch = wave; ch < SQ_SEED_CHUNKS; ch += NW) {
-        const uint4 row = load64(ch);
-        uint32_t sm[4];
-        scan16q_row_sums<PREROT>(row, moffp, cr8, cq, lut_b, sm[0], sm[1], sm[2], sm[3]);
-#pragma unroll
-        for (int q = 0; q < QT; ++q) {
-            const uint32_t sq = (sm[q >> 1] >> (16 * (q & 1))) & 0xffffu;
-            atomicAdd(&hist[q * 256 + (sq >> 7)], 1u);
-        }
-    }
-    __syncthreads();
+    constexpr int QT = SQ_QT;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (wave < QT && lazy[wave]) {
         const int q = wave;
         uint32_t c4[4], mine = 0;
@@ -358,7 +469,205 @@ __device__ __forceinline__ void scan16q_seed(int k, const LoadRow &load64, const
             }
         }
     }
+}
+
+// Seed: a first filter threshold per query from a histogram of the split's first SQ_SEED_CHUNKS x 64 rows.
+// Without it a scan starts with "every row passes": a thousand rows in flight against SQ_CAP slots, and four to five rounds of
+// the whole workgroup waiting for compactions before the pass rate has fallen.  bin = sum >> 7; the first bin b at which the
+// cumulative count reaches k proves k rows with sum < (b + 1) << 7 =: S, hence S_k <= S, and T = S + slack is a valid (looser)
+// lazy-selection threshold (scan_compact_lazy_q).  Queries that cannot select lazily keep "pass all".  The seed rows are
+// scanned again by the main loop.  hist = SQ_QT x 256 words (the still unused selection buffers).  Whole workgroup; ends with a barrier.
+constexpr uint32_t SQ_SEED_CHUNKS = 32;
+template <int NT, bool PREROT, class LoadRow>
+__device__ __forceinline__ void scan16q_seed(int k, const LoadRow &load64, const uint32_t (&moffp)[4], uint32_t cr8, uint32_t cq, const char *lut_b,
+                                             uint32_t *hist, const QuantParams &qp, const int *lazy, uint32_t *thr_x, uint32_t *thr_pk)
+{
+    constexpr int QT = SQ_QT, NW = NT / 64;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    for (int i = tid; i < QT * 256; i += NT) hist[i] = 0;
     __syncthreads();
+    for (uint32_t ch = wave; ch < SQ_SEED_CHUNKS; ch += NW) {
+        const uint4 row = load64(ch);
+        uint32_t sm[4];
+        scan16q_row_sums<PREROT>(row, moffp, cr8, cq, lut_b, sm[0], sm[1], sm[2], sm[3]);
+#pragma unroll
+        for (int q = 0; q < QT; ++q) {
+            const uint32_t sq = (sm[q >> 1] >> (16 * (q & 1))) & 0xffffu;
+            atomicAdd(&hist[q * 256 + (sq >> 7)], 1u);
+        }
+    }
+    __syncthreads();
+    scan16_seed_threshold(k, hist, qp, lazy, thr_x, thr_pk);
+    __syncthreads();
+}
+
+// ---- the workgroup frame of adc_scan16q / adc_scan16p / adc_scan16a: everything around their look-up loops ------------------------------
+using ScanTopK = TopKShared<SQ_QT, SQ_CAP>;
+
+// block -> (query group, row split) of the two-region plan (kernels.h).  A region whose split count is a multiple of 8 keeps a row
+// split on one XCD (block b runs on XCD b % 8), so each XCD's L2 only ever caches 1/8 of the code matrix.
+struct ScanBlock {
+    int group, split, my_splits;
+    int64_t my_rps;  // rows per split of this block's region
+};
+__device__ __forceinline__ ScanBlock scan16_block(const ScanArgs &a)
+{
+    int group, split, my_splits = a.splits;
+    int64_t my_rps = a.rows_per_split;
+    int b = blockIdx.x, g0 = 0;
+    if (b >= a.groups_a * a.splits) {  // region B: the tail groups, split finer (dispatched last)
+        b -= a.groups_a * a.splits;
+        g0 = a.groups_a;
+        my_splits = a.splits_b;
+        my_rps = a.rows_per_split_b;
+    }
+    if ((my_splits & 7) == 0) {
+        const int s8 = my_splits >> 3;
+        const int xcd = b & 7, i = b >> 3;
+        split = xcd + 8 * (i % s8);
+        group = g0 + i / s8;
+    } else {
+        split = b % my_splits;
+        group = g0 + b / my_splits;
+    }
+    return { group, split, my_splits, my_rps };
+}
+
+// a.only (the matrix-core route's fall-back, adc_mfma.hip): does any query of `group` still want its answer?  Workgroup-uniform.
+// adc_scan16q_kernel alone honours the predicate; the launches of the other forms refuse it.
+__device__ __forceinline__ bool scan16_group_wanted(const ScanArgs &a, int group)
+{
+    uint32_t any = 0u;
+    for (int q = 0; q < SQ_QT; ++q)
+        if (group * SQ_QT + q < a.nq) any |= a.only[group * SQ_QT + q];
+    return any != 0u;
+}
+
+// first thresholds: pass-all until k rows are known -- or what the other row splits of these queries have already established
+__device__ __forceinline__ void scan16_init_thresholds(const ScanArgs &a, int group, int tid, ScanTopK &tk, uint32_t (&thr_pk)[SQ_QT / 2])
+{
+    if (tid < SQ_QT / 2) {
+        uint32_t t2[2] = { 32767u, 32767u };
+        if (a.gthr) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int qi = group * SQ_QT + 2 * tid + h;
+                if (qi < a.nq) {  // a stale value is an older, looser, still valid bound
+                    const uint32_t g = __hip_atomic_load(&a.gthr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    t2[h] = g < t2[h] ? g : t2[h];
+                }
+            }
+        }
+        tk.thr_x[2 * tid] = t2[0]; tk.thr_x[2 * tid + 1] = t2[1];
+        thr_pk[tid] = t2[0] | (t2[1] << 16);
+    }
+}
+
+// Chunks are handed out dynamically, in PAIRS (2 p, 2 p + 1): one LDS atomic per two chunks, the odd one follows without asking.
+// next_chunk_addr = the LDS address of the workgroup's counter.  Wave-uniform result.
+// (the atomic is spelled out: for `if (lane == 0) atomicAdd(...)` hipcc emits its wave-aggregation sequence -- two mbcnt, a
+//  compare, a population count and two moves -- around the one-lane atomic: 6 of the loop's 66 vector instructions per row)
+__device__ __forceinline__ uint32_t scan16_grab_pair(uint32_t next_chunk_addr, int lane)
+{
+    uint32_t v;
+    asm volatile("" : "=v"(v));  // (only lane 0's value is read: no instruction to define the others)
+    if (lane == 0) asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(next_chunk_addr), "v"(1u) : "memory");
+    return 2u * (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+// the chunk after `chunk`: its pair's second half, or a new pair (wave-uniform branch)
+__device__ __forceinline__ uint32_t scan16_after(uint32_t chunk, uint32_t next_chunk_addr, int lane)
+{
+    return (chunk & 1u) ? scan16_grab_pair(next_chunk_addr, lane) : chunk + 1u;
+}
+
+// the rare path of a row: this lane's row (lrow within the split) goes to the buffer of every query whose plain sum lies under its
+// threshold.  Bit done_bit0 + q of `done` remembers what was stored already (a chunk is walked again after a full buffer).
+// Returns true when a buffer was full.  (`done` is worked on in a local copy: written through the reference inside the loop, hipcc
+// keeps the bits in a branch and the failure in a select -- the other way round than before, and with it another look-up loop.)
+__device__ __forceinline__ bool scan16_push_candidates(ScanTopK &tk, const uint32_t (&sums)[4], const uint32_t (&tpk)[SQ_QT / 2], int64_t row_begin,
+                                                       uint32_t lrow, int done_bit0, uint32_t &done_io)
+{
+    uint32_t done = done_io;
+    bool failed = false;
+#pragma unroll
+    for (int q = 0; q < SQ_QT; ++q) {
+        const uint32_t bit = 1u << (done_bit0 + q);
+        const uint32_t sq = (sums[q >> 1] >> (16 * (q & 1))) & 0xffffu;
+        const uint32_t tq = (tpk[q >> 1] >> (16 * (q & 1))) & 0xffffu;
+        if (sq < tq && !(done & bit)) {
+            bool dummy = false;
+            if (topk_push<SQ_QT, SQ_CAP, SQ_TRIG>(tk, q, sq, (uint32_t)(row_begin + lrow), dummy)) done |= bit;
+            else failed = true;
+        }
+    }
+    done_io = done;
+    return failed;
+}
+
+// The compactions of a checkpoint, between its two barriers: one wave per query, in registers; the row splits of a query tighten each
+// other's filter through a.gthr (same tables -> same units); then the packed thresholds of the loop are renewed and `stop` is cleared.
+// Whole workgroup.
+template <int NT, class FixB>
+__device__ __forceinline__ void scan16_checkpoint_compact(const ScanArgs &a, int group, ScanTopK &tk, const QuantParams &qp, int (&lazy)[SQ_QT],
+                                                          uint32_t (&thr_pk)[SQ_QT / 2], int &stop, const FixB &fixb, const QuantThr &thrx)
+{
+    constexpr int QT = SQ_QT, NW = NT / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int keep_max = a.k + 48 < SQ_TRIG - 24 ? a.k + 48 : SQ_TRIG - 24;
+    for (int q = wv; q < QT; q += NW) {  // wave-uniform
+        const int keep = lazy[q] ? scan_compact_lazy_q<QT, SQ_CAP>(tk, q, a.k, fixb, thrx, qp.slack[q], keep_max, &lazy[q])
+                                 : topk_compact_wave_q<QT, SQ_CAP, false>(tk, q, a.k, fixb, thrx);
+        if (lane == 0) {
+            tk.cnt[q] = keep;
+            if (a.gthr) {
+                const int qi = group * QT + q;
+                if (qi < a.nq) {
+                    const uint32_t mine = tk.thr_x[q];
+                    const uint32_t seen = atomicMin(&a.gthr[qi], mine);
+                    tk.thr_x[q] = seen < mine ? seen : mine;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < QT / 2) thr_pk[tid] = tk.thr_x[2 * tid] | (tk.thr_x[2 * tid + 1] << 16);
+    if (tid == 0) stop = 0;
+}
+
+// Epilogue: the workgroup's lists to its partial slot [qi][split] -- or, IN_PLACE (adc_scan16q / 16p), a group of the first region
+// that was scanned in one piece holds its queries' final lists: they go where the caller wants them (a.out_d is only set when that
+// region has one split).  A region with fewer splits than the partial stride leaves the other slots empty for the merge.
+template <int NT, bool IN_PLACE>
+__device__ __forceinline__ void scan16_write_lists(const ScanArgs &a, const ScanTopK &tk, int group, int split, int my_splits)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < SQ_QT; ++q) {
+        const int qi = group * SQ_QT + q;
+        if (qi >= a.nq) break;
+        const int cnt = tk.cnt[q];
+        const bool in_place = IN_PLACE ? a.out_d != nullptr && group < a.groups_a : false;
+        float *const pd = in_place ? a.out_d : a.part_d;
+        int64_t *const pi = in_place ? a.out_id : a.part_id;
+        const int64_t o = in_place ? (int64_t)qi * a.k : ((int64_t)qi * a.stride + split) * a.k;
+        for (int i = tid; i < a.k; i += NT) {
+            if (i < cnt) {
+                const unsigned long long e = tk.buf[q][i];
+                pd[o + i] = __uint_as_float((uint32_t)(e >> 32));
+                pi[o + i] = a.id_base + (int64_t)(uint32_t)e;
+            } else {
+                pd[o + i] = __uint_as_float(0x7f800000u);
+                pi[o + i] = -1;
+            }
+        }
+        if (!in_place && split == 0 && my_splits < a.stride) {
+            const int64_t o2 = ((int64_t)qi * a.stride + my_splits) * a.k;
+            for (int i = tid; i < (a.stride - my_splits) * a.k; i += NT) {
+                a.part_d[o2 + i] = __uint_as_float(0x7f800000u);
+                a.part_id[o2 + i] = -1;
+            }
+        }
+    }
 }
 
 }  // namespace cvtmi

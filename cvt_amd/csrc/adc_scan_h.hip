@@ -223,44 +223,14 @@ __global__ __launch_bounds__(1024) void scan16h_prep_kernel(const float *__restr
     PREP_T(1);  // table entries, fp32 tables out, ranges
     __syncthreads();
     PREP_T(2);
-    if (tid < QT) {  // scale, bias, lazy-selection band: as scan16q_build_tables (adc_scan.hip)
-        const int q = tid;
-        float range = 0.0f;
-        double bias = 0.0;
-        for (int m = 0; m < M; ++m) {
-            uint32_t lo = qp.mn_bits[q][m], hi = mx_bits[q][m];
-            if (lo > hi) { lo = 0u; hi = 0u; }  // no finite entry at all
-            const float fl = __uint_as_float(lo), fh = __uint_as_float(hi);
-            qp.mn[q][m] = fl;
-            range += fh - fl;
-            bias += (double)fl;
-        }
-        float scale = range > 0.0f ? range / (float)SQ_MAXSUM * 1.001f : 1.0f;
-        if (!(scale > 1e-37f)) scale = 1e-37f;
-        const float inv = 1.0f / scale;
-        qp.inv_scale[q] = inv;
-        qp.scale_eff[q] = 1.0 / (double)inv;
-        qp.bias[q] = bias;
-        const double sl = 34.0 + ceil(4e-6 * (32767.0 + bias * (double)inv));
-        const bool lazy_ok = lazy_on && !nonfinite[q] && sl < 1024.0 && bias >= 0.0;
-        qp.slack[q] = lazy_ok ? (uint32_t)sl : 0u;
-    }
+    if (tid < QT) (void)scan16_query_params<M>(qp, mx_bits, tid, lazy_on, nonfinite);  // (the scan reads the lazy flag off qp.slack)
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int e = tid + i * NT, m = e >> 8, j = e & 255;
         uint32_t qv[QT];
 #pragma unroll
-        for (int q = 0; q < QT; ++q) {
-            const float v = acc[i][q];
-            int iv = 0;
-            if (__float_as_uint(v) < 0x7f800000u) {
-                const float f = __fmul_rn(__fsub_rn(v, qp.mn[q][m]), qp.inv_scale[q]);
-                iv = (int)floorf(f) - 1;
-                iv = iv < 0 ? 0 : (iv > SQ_MAXSUM ? SQ_MAXSUM : iv);
-            }
-            qv[q] = (uint32_t)iv;
-        }
+        for (int q = 0; q < QT; ++q) qv[q] = scan16_quantise(acc[i][q], qp, q, m);
         stage[j * 16 + m] = make_uint4(qv[0] | (qv[1] << 16), qv[2] | (qv[3] << 16), qv[4] | (qv[5] << 16), qv[6] | (qv[7] << 16));
     }
     PREP_T(3);  // scales + quantisation into the stage
@@ -372,7 +342,7 @@ __device__ __forceinline__ bool scanh_publish(ScanHCtl &ck, int q, uint32_t t)
 // when more survive T, what is there is reduced to its k best exact entries first, whose k-th distance tightens T.
 template <bool SORTED>
 __device__ __attribute__((noinline)) int scanh_select_q(TopKShared<SQ_QT, SQ_CAP> &tk, int q, int k, const unsigned long long *sp, int n,
-                                                       int ex, uint32_t T, const ExactFromLutBatch &fixb, const QuantThr &thrx)
+                                                       int ex, uint32_t T, const ExactFromLutBatch<> &fixb, const QuantThr &thrx)
 {
     const int lane = threadIdx.x & 63;
     unsigned long long *b = tk.buf[q];
@@ -470,7 +440,7 @@ __global__ __launch_bounds__(1024, 8) void adc_scan16h_kernel(const ScanHArgs a)
         const int group = item.group;
         const int64_t row_begin = (int64_t)item.row0_64 * 64;
         const uint32_t n_local = item.rows;
-        const ExactFromLutBatch fixb{ rows, a.lut_g, a.K, a.nq, group };
+        const ExactFromLutBatch<> fixb{ rows, a.lut_g, a.K, a.nq, group };
         // bounds shared by the segments of a group: read when a segment starts, written when it ends (a global atomic per published bound
         // sat in the scan loop's vmcnt queue: the row prefetch waited for its acknowledgement)
         uint32_t *const gthr = item.nseg > 1 ? a.gthr : nullptr;
@@ -554,14 +524,7 @@ __global__ __launch_bounds__(1024, 8) void adc_scan16h_kernel(const ScanHArgs a)
         __syncthreads();
         SQ_T(1);  // seed
 
-        auto grab_pair = [&]() -> uint32_t {  // chunks go out in pairs: one LDS atomic per 128 rows (adc_scan16q_kernel)
-            uint32_t v;
-            asm volatile("" : "=v"(v));
-            if (lane == 0) asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(next_chunk_addr), "v"(1u) : "memory");
-            return 2u * (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-        };
-        auto after = [&](uint32_t chunk) -> uint32_t { return (chunk & 1u) ? grab_pair() : chunk + 1u; };
-        uint32_t it = grab_pair(), it_next = it + 1u;
+        uint32_t it = scan16_grab_pair(next_chunk_addr, lane), it_next = it + 1u;  // chunks go out in pairs: one LDS atomic per 128 rows
         bool counted = false;
         int wn = 0;  // candidates in this wave's staging area (wave-uniform)
         unsigned long long *stage_w = sh.stage[wave];
@@ -711,7 +674,7 @@ __global__ __launch_bounds__(1024, 8) void adc_scan16h_kernel(const ScanHArgs a)
                     if (raised) break;  // a spill area is full: everybody stops, this wave comes back to this chunk after the reduction
                     cur = nxt;
                     it = it_next;
-                    it_next = after(it);
+                    it_next = scan16_after(it, next_chunk_addr, lane);
                     SH_CNT(7, 1);
                     // scalar compare: somebody (this wave included) published a bound or asked for a stop -> next round
                     if ((uint32_t)__builtin_amdgcn_readfirstlane((int)ep_now) != ep_seen || moved) break;
@@ -1116,7 +1079,7 @@ __global__ __launch_bounds__(1024, 8) void scan16s_select_kernel(const ScanSArgs
         }
     }
     const QuantThr thrx{ &qp };
-    const ExactFromLutBatch fixb{ reinterpret_cast<const uint4 *>(a.codes), a.lut_g, a.K, a.nq, grp };
+    const ExactFromLutBatch<> fixb{ reinterpret_cast<const uint4 *>(a.codes), a.lut_g, a.K, a.nq, grp };
     const int keep = scanh_select_q<true>(tk, ql, a.k, cand, (int)n, 0, Tsel, fixb, thrx);
     for (int i = lane; i < a.k; i += 64) {
         if (i < keep) {

@@ -1,8 +1,8 @@
 """Inputs at the edges of the ADC scans' 15-bit lower-bound tables, shared by test_scan_table_regimes.py (which pins
 each case to the regime its name claims, on the CPU) and test_gpu_opq_scan_tables.py (which runs the kernels on them).
 
-Every fast scan quantises each query's fp32 distance tables with the query's own scale / bias / slack (adc_scan.hip
-scan16q_build_tables, adc_scan_p.hip scan16p_build_tables, adc_scan_h.hip scan16h_prep_kernel).  `classify` derives the
+Every fast scan quantises each query's fp32 distance tables with the query's own scale / bias / slack (adc_scan16.h
+scan16_query_params / scan16_quantise, called by scan16q_build_tables and adc_scan_h.hip scan16h_prep_kernel).  `classify` derives the
 same quantities from the oracle's tables, one fp32 operation at a time, so the predicates are conditions on the INPUTS:
 nothing of the library is loaded here.
 

@@ -1,8 +1,9 @@
 """The ADC scan kernels at the edges of their 15-bit lower-bound tables, against the oracle, bit for bit.
 
 Every fast scan is a filter over integer lower bounds of the fp32 distance tables; each query's tables are quantised
-with their own scale / bias / slack (adc_scan.hip scan16q_build_tables, adc_scan_p.hip scan16p_build_tables,
-adc_scan_h.hip scan16h_prep_kernel) and every later stage trusts those numbers: the filter threshold, the lazy
+with their own scale / bias / slack (adc_scan16.h scan16_query_params / scan16_quantise: one rule, called by
+scan16q_build_tables<NT, M> for adc_scan16q / 16a / 16p and by adc_scan_h.hip scan16h_prep_kernel; each form still builds
+and reads its tables its own way, so each is run here) and every later stage trusts those numbers: the filter threshold, the lazy
 selection, the seed and 16h histograms, the packed sums.  The cases of scan_table_cases.py (pinned to their regimes by
 test_scan_table_regimes.py) reach the branches ordinary data never does: range == 0, the 1e-37 clamp, a range that
 overflows fp32 (inv_scale 0, scale_eff +inf), a slack past 1024 on finite tables, denormal entries, row sums at +inf
@@ -152,7 +153,7 @@ def test_other_sub_vector_lengths(amd, orc, name, D):
 @pytest.mark.parametrize("D,M", NATIVE_SHAPES)
 @pytest.mark.parametrize("name", NATIVE_CASES)
 def test_native_m8_m4(amd, orc, name, D, M, form):
-    """M = 8 / M = 4: the native packed scan (adc_scan_p.hip, scan16p_build_tables) and the rows padded to 16 bytes with all-zero
+    """M = 8 / M = 4: the native packed scan (adc_scan_p.hip, scan16q_build_tables<NT, M>) and the rows padded to 16 bytes with all-zero
     tables behind the model's own (adc_scan16q: the range comes from the real tables only)"""
     c = Case(amd, orc, name, D=D, M=M)
     try:
