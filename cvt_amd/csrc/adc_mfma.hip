@@ -476,7 +476,7 @@ int launch_adc_mfma(const OpqModelDev &m, const AdcMfmaModel &mm, const uint8_t 
         uint32_t *wcnt = reinterpret_cast<uint32_t *>(p); p += mf_align((size_t)s.regions * 4, 256);
         uint2 *cand = reinterpret_cast<uint2 *>(p); p += mf_align((size_t)mq * list_cap * sizeof(uint2), 256);
         void *rec = p;
-        CVTMI_HIP(hipMemsetAsync(smax, 0, (size_t)mq * s.stride * 4, st));
+        // (no memset of smax: s.stride is 8 spx x 16, one slot per half wave of a chunk's workgroups, and the sample pass writes every one of them)
         U8FilterJob j;
         j.pack = pack; j.bias = bias; j.n = n; j.D = D; j.W = W + q0 * D; j.nq = (int)mq; j.chunks = s.chunks; j.qper = s.qper; j.spx = s.spx;
         j.smax = smax; j.smax_stride = s.stride;

@@ -39,16 +39,22 @@ constexpr int UT_WAVES = 8, UT_GRID = 256, UT_SLOTS = 4096, UT_CAP = 32768, UT_K
 constexpr int UT_NBQ = UT_QPER / 32;   // query blocks of a workgroup
 constexpr int UT_NEG = -(1 << 30);   // start value of a padding row's accumulator: never reaches a threshold
 
+// the filter kernel's forms by K steps and row tiles (see the kernel), and its LDS: the queries, their thresholds, the waves' row terms and 3 KB
+// the query ring may read into
+constexpr int ut_ring(int ks) { return ks % 4 == 0 ? 4 : (ks % 3 == 0 ? 3 : (ks % 2 == 0 ? 2 : 1)); }
+constexpr bool ut_narrow(int ks, int rt) { return ks <= 4 && 8 * rt * ks + 32 * rt + 4 * ut_ring(ks) <= 208; }
+constexpr size_t ut_lds_bytes(int ks, int rt, int qper) { return (size_t)(qper / 32) * ks * 1024 + (size_t)qper * sizeof(int) + (size_t)UT_WAVES * rt * 32 * sizeof(int) + 3072; }
+
 struct UtArgs {
     const uint4 *pack; const int32_t *norms; int64_t n, n_tiles, n_sample;
     const uint8_t *Q; int D, nq, chunks, qper;
-    uint32_t *smax;          // MAX mode: [nq][UT_SLOTS] (a ^ 0x80000000), zeroed by the caller
+    uint32_t *smax;          // MAX mode: [nq][smax_stride] (a ^ 0x80000000, 0 = empty); every half wave of the grid writes its own slot, the caller zeroes the others
     const int32_t *thr;      // FILTER mode: [nq] (INT_MAX: nothing passes)
     uint4 *rec; uint32_t *wcnt; uint32_t cap;
     uint32_t qxor;           // 0x80808080: Q holds uint8 values (q - 128 is made here); 0: int8 values as they are (adc_mfma.hip)
     int bias_direct;         // 0: a row starts at -(norms[row] >> 1); 1: at -norms[row] (the caller's own row term)
     int smax_stride;         // slots per query of smax (UT_SLOTS; fewer when the grid has fewer row slices)
-    int dbg;   // CVTMI_UT_DBG: timing experiments (results wrong) 1 = no epilogue, 2 = rows loaded once; test hook (results right) 4 = record regions of two records
+    int dbg;   // CVTMI_UT_DBG: timing experiments (results wrong) 1 = no epilogue, 2 = rows loaded once, 8 = hits counted but no record written; test hook (results right) 4 = record regions of two records
 };
 
 __device__ __forceinline__ int ut_max3(int a, int b, int c)
@@ -72,7 +78,7 @@ template <int KS, int RT, bool MAXMODE>
 __global__ __launch_bounds__(64 * UT_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) void flat_u8_tfilter_kernel(const UtArgs a)
 {
     constexpr int NW = UT_WAVES;
-    extern __shared__ __attribute__((aligned(16))) uint8_t ut_q[];   // [block][K step] x 1 KB, the blocks' thresholds, the waves' row terms, 3 KB of padding
+    extern __shared__ __attribute__((aligned(16))) uint8_t ut_q[];   // [block][K step] x 1 KB, the blocks' thresholds, the waves' row terms, 3 KB of padding (ut_lds_bytes)
     const int tid = threadIdx.x, lane = tid & 63, lj = lane & 31, lk = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
@@ -104,106 +110,224 @@ __global__ __launch_bounds__(64 * UT_WAVES) __attribute__((amdgpu_waves_per_eu(2
     uint32_t wcnt = 0;
     int none = 0;   // (the timing experiments' sink)
     uint8_t *rec_w = reinterpret_cast<uint8_t *>(a.rec) + (size_t)wave_g * a.cap * 80;
+    const uint32_t rec_room = (a.dbg & 8) ? 0u : a.cap;   // (the timing experiment without records: a region that holds none, nothing more in the hit path)
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-    i32x4 xa[RT][KS];
-    // the rows' starting values -(|x'|^2 >> 1) reach the accumulators through the wave's own LDS words (no registers held for them);
-    // the queries' operands through a ring of R registers, R - 1 K steps ahead across the blocks of a group
-    int *bias_w = thr_s + nb * 32 + wave * (RT * 32);
-    constexpr int R = KS % 4 == 0 ? 4 : (KS % 3 == 0 ? 3 : (KS % 2 == 0 ? 2 : 1));   // (the ring runs on across the blocks: R divides KS; 1 = read, then use)
+    int *bias_w = thr_s + nb * 32 + wave * (RT * 32);   // the wave's own LDS words: a group's row terms on their way into accumulator layout
+    constexpr int R = ut_ring(KS);   // (the ring runs on across the blocks: R divides KS; 1 = read, then use)
     const uint8_t *qp = ut_q + lane * 16;
-    for (int64_t g = slice + (int64_t)slices * wave; g < n_groups; g += stride) {
-        const int64_t g_rows = MAXMODE ? g * all_groups / a.n_sample : g;
-        if (!(a.dbg & 2) || g < stride) {
+    // the narrow-row form of the wave's loop, see below (two row sets, the terms, the accumulators and the query ring within 208 registers: KS = 4 with
+    // RT = 3, KS = 1 and 2 with RT = 4; KS = 3 with RT = 4 would spill and keeps the other form)
+    constexpr bool NARROW = ut_narrow(KS, RT);
+    // what a block of 32 queries does with its finished accumulators: the sample's maxima, or the test against the thresholds and the records
+    auto epilogue = [&](i32x16 (&acc)[RT], const int b, int &mx, const uint32_t tile_row) __attribute__((always_inline)) {
+        // (inline-assembly readers of matrix results: the wait states are spelled out, see flat_f32_tfilter.hip)
+        static_assert(RT >= 2 && RT <= 4, "operand lists below");
+        if constexpr (RT == 2) asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0]), "+v"(acc[1]));
+        if constexpr (RT == 3) asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]));
+        if constexpr (RT == 4) asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
+        const int qq = 32 * b + lj;
+        if (a.dbg & 1) { mx = acc[0][0] + acc[RT - 1][3] > mx ? acc[0][0] : mx; return; }
+        if constexpr (MAXMODE) {
+            int m = ut_max16(acc[0]);
 #pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const int64_t t = g_rows * RT + r;
-            const int64_t tc = t < a.n_tiles ? t : a.n_tiles - 1;
-            const uint4 *tp = a.pack + (tc * KS) * 64 + lane;
+            for (int r = 1; r < RT; ++r) { const int m2 = ut_max16(acc[r]); m = m2 > m ? m2 : m; }
+            mx = m > mx ? m : mx;
+        } else {
+            const int tb = thr_s[qq];
+            int tmax[RT];   // (all of the block's tiles first: their chains interleave; the tests and the rare hit path after)
 #pragma unroll
-            for (int s_ = 0; s_ < KS; ++s_) xa[r][s_] = __builtin_bit_cast(i32x4, tp[s_ * 64]);
+            for (int r = 0; r < RT; ++r) tmax[r] = ut_max16(acc[r]);
+#pragma unroll
+            for (int r = 0; r < RT; ++r) {
+                const bool hit = tmax[r] >= tb;
+                const unsigned long long hm = __ballot(hit);
+                if (hm) {
+                    const uint32_t pos = wcnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
+                    wcnt += (uint32_t)__popcll(hm);
+                    if (hit && pos < rec_room) {
+                        // (these five stores of one or two lanes are 29 % of the 128-d filter pass, CVTMI_UT_DBG 8; records collected in an LDS stage of
+                        //  the wave and written 64 at a time with whole-wave stores made the pass 10 % slower still: profiles/adc_mfma_narrow_attrib.txt)
+                        uint8_t *dst = rec_w + pos * 80u;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            *reinterpret_cast<uint4 *>(dst + 16 * j) = make_uint4((uint32_t)acc[r][4 * j], (uint32_t)acc[r][4 * j + 1], (uint32_t)acc[r][4 * j + 2], (uint32_t)acc[r][4 * j + 3]);
+                        *reinterpret_cast<uint4 *>(dst + 64) = make_uint4((uint32_t)(q0 + qq), tile_row + (uint32_t)(32 * r), (uint32_t)qq, 0u);
+                    }
+                }
+            }
         }
-        }
+    };
+    if constexpr (NARROW) {
+        // Narrow rows: a group is only RT x KS x 8 matrix instructions per wave, too few to hide what stands between two groups.  The
+        // wave's loop is a software pipeline instead: two register sets of row tiles -- the next group's rows are fetched while this
+        // group's query blocks run -- and the row terms held in registers, in accumulator layout, where every block's first K step takes
+        // them as its C operand.  The next group's terms are fetched with its rows, pass through the wave's LDS words once (lane i holds
+        // rows i and i + 64 of the group; the accumulators want rows 8 j + 4 lk .. + 3 of every tile) and replace the current ones
+        // behind the group's last block.
+        constexpr int NT = (RT * 32 + 63) / 64;
+        i32x4 xa[2][RT][KS];
+        i32x16 bt[RT];
+        int nv[NT];
+        auto g_rows_of = [&](const int64_t g) -> int64_t { return MAXMODE ? g * all_groups / a.n_sample : g; };
+        auto rows_fetch = [&](i32x4 (&x)[RT][KS], const int64_t gr) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = lane; i < RT * 32; i += 64) {
-            const int64_t row = g_rows * RT * 32 + i;
-            bias_w[i] = row < a.n ? (a.bias_direct ? -a.norms[row] : -(a.norms[row] >> 1)) : UT_NEG;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const uint32_t tile_row = (uint32_t)(g_rows * RT * 32 + 4 * lk);
-        i32x4 qr[R];
+            for (int r = 0; r < RT; ++r) {
+                const int64_t t = gr * RT + r;
+                const int64_t tc = t < a.n_tiles ? t : a.n_tiles - 1;   // (a tile past the last: that one again, its rows start at UT_NEG)
+                const uint4 *tp = a.pack + (tc * KS) * 64 + lane;
 #pragma unroll
-        for (int j = 0; j < R - 1; ++j) qr[j] = *reinterpret_cast<const i32x4 *>(qp + j * 1024);
-        auto block = [&](const int b, int &mx) {
-            i32x16 acc[RT];
+                for (int s_ = 0; s_ < KS; ++s_) x[r][s_] = __builtin_bit_cast(i32x4, tp[s_ * 64]);
+            }
+        };
+        auto terms_fetch = [&](const int64_t gr) __attribute__((always_inline)) {
+#pragma unroll
+            for (int c = 0; c < NT; ++c) {
+                const int i = lane + 64 * c;
+                const int64_t row = gr * RT * 32 + i;
+                nv[c] = (i < RT * 32 && row < a.n) ? a.norms[row] : 0;
+            }
+        };
+        auto terms_stage = [&](const int64_t gr) __attribute__((always_inline)) {
+#pragma unroll
+            for (int c = 0; c < NT; ++c) {
+                asm volatile("" : "+v"(nv[c]));   // (the fetched words are first touched here: arithmetic hoisted ahead of the blocks would wait for the fetches there)
+                const int i = lane + 64 * c;
+                const int64_t row = gr * RT * 32 + i;
+                if (i < RT * 32) bias_w[i] = row < a.n ? (a.bias_direct ? -nv[c] : -(nv[c] >> 1)) : UT_NEG;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int r = 0; r < RT; ++r)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {   // element 4 j + i: row i + 8 j + 4 lk of the tile
                     const int4 v = *reinterpret_cast<const int4 *>(bias_w + r * 32 + 8 * j + 4 * lk);
-                    acc[r][4 * j] = v.x; acc[r][4 * j + 1] = v.y; acc[r][4 * j + 2] = v.z; acc[r][4 * j + 3] = v.w;
+                    bt[r][4 * j] = v.x; bt[r][4 * j + 1] = v.y; bt[r][4 * j + 2] = v.z; bt[r][4 * j + 3] = v.w;
                 }
-            const uint8_t *qb = qp + (size_t)b * (KS * 1024);
-#pragma unroll
-            for (int s_ = 0; s_ < KS; ++s_) {
-                // (the last R - 1 steps of the last block read past the queries, into the thresholds and the padding behind them: never used)
-                qr[(s_ + R - 1) % R] = *reinterpret_cast<const i32x4 *>(qb + (s_ + R - 1) * 1024);
-#pragma unroll
-                for (int r = 0; r < RT; ++r) acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[r][s_], qr[s_ % R], acc[r], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (the words are written again only after these reads)
+            __builtin_amdgcn_wave_barrier();
+        };
+        // one group out of the set xc, the next into xn; false after the wave's last
+        auto group = [&](i32x4 (&xc)[RT][KS], i32x4 (&xn)[RT][KS], int64_t &g, int64_t &gr) __attribute__((always_inline)) -> bool {
+            const int64_t gn = g + stride;
+            const bool more = gn < n_groups;
+            const int64_t grn = more ? g_rows_of(gn) : 0;
+            // (this group's rows, fetched a group ago, are waited for here, ahead of the next fetches: a wait placed in front of the block
+            //  loop, where the compiler puts one for operands still in flight, would take the new fetches with it)
+            __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
+            if (more) {
+                terms_fetch(grn);
+                if (!(a.dbg & 2)) rows_fetch(xn, grn);
             }
-            // (inline-assembly readers of matrix results: the wait states are spelled out, see flat_f32_tfilter.hip)
-            static_assert(RT >= 2 && RT <= 4, "operand lists below");
-            if constexpr (RT == 2) asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0]), "+v"(acc[1]));
-            if constexpr (RT == 3) asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]));
-            if constexpr (RT == 4) asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
-            const int qq = 32 * b + lj;
-            if (a.dbg & 1) { mx = acc[0][0] + acc[RT - 1][3] > mx ? acc[0][0] : mx; return; }
+            const uint32_t tile_row = (uint32_t)(gr * RT * 32 + 4 * lk);
+            i32x4 qr[R];
+#pragma unroll
+            for (int j = 0; j < R - 1; ++j) qr[j] = *reinterpret_cast<const i32x4 *>(qp + j * 1024);
+            auto block = [&](const int b, int &mx) __attribute__((always_inline)) {
+                i32x16 acc[RT];
+                const uint8_t *qb = qp + (size_t)b * (KS * 1024);
+#pragma unroll
+                for (int s_ = 0; s_ < KS; ++s_) {
+                    // (the last R - 1 steps of the last block read past the queries, into the thresholds and the padding behind them: never used)
+                    qr[(s_ + R - 1) % R] = *reinterpret_cast<const i32x4 *>(qb + (s_ + R - 1) * 1024);
+#pragma unroll
+                    for (int r = 0; r < RT; ++r) {
+                        if (s_ == 0) acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xc[r][0], qr[0], bt[r], 0, 0, 0);
+                        else acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xc[r][s_], qr[s_ % R], acc[r], 0, 0, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                epilogue(acc, b, mx, tile_row);
+            };
             if constexpr (MAXMODE) {
-                int m = ut_max16(acc[0]);
 #pragma unroll
-                for (int r = 1; r < RT; ++r) { const int m2 = ut_max16(acc[r]); m = m2 > m ? m2 : m; }
-                mx = m > mx ? m : mx;
+                for (int b = 0; b < UT_NBQ; ++b)
+                    if (b < nb) block(b, mreg[b]);
             } else {
-                const int tb = thr_s[qq];
-                int tmax[RT];   // (all of the block's tiles first: their chains interleave; the tests and the rare hit path after)
-#pragma unroll
-                for (int r = 0; r < RT; ++r) tmax[r] = ut_max16(acc[r]);
+#pragma unroll 1
+                for (int b = 0; b < nb; ++b) block(b, none);
+            }
+            // (behind the blocks, not inside the last one: the fetched words must not be touched inside the block loop -- see the wait above -- and a
+            //  last block peeled out of the loop for it made the filter instances spill)
+            if (more) terms_stage(grn);
+            g = gn; gr = grn;
+            return more;
+        };
+        int64_t g = slice + (int64_t)slices * wave;
+        if (g < n_groups) {
+            int64_t gr = g_rows_of(g);
+            rows_fetch(xa[0], gr);
+            if (a.dbg & 2) rows_fetch(xa[1], gr);   // (the timing experiment: both sets hold the first group's rows, nothing is fetched again)
+            terms_fetch(gr);
+            terms_stage(gr);
+            while (group(xa[0], xa[1], g, gr) && group(xa[1], xa[0], g, gr)) {}
+        }
+    } else {
+        // wider rows: one register set of row tiles; the rows' starting values -(|x'|^2 >> 1) reach the accumulators through the wave's own
+        // LDS words (no registers held for them), the queries' operands through a ring of R registers, R - 1 K steps ahead across the
+        // blocks of a group
+        i32x4 xa[RT][KS];
+        for (int64_t g = slice + (int64_t)slices * wave; g < n_groups; g += stride) {
+            const int64_t g_rows = MAXMODE ? g * all_groups / a.n_sample : g;
+            if (!(a.dbg & 2) || g < stride) {
 #pragma unroll
                 for (int r = 0; r < RT; ++r) {
-                    const bool hit = tmax[r] >= tb;
-                    const unsigned long long hm = __ballot(hit);
-                    if (hm) {
-                        const uint32_t pos = wcnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
-                        wcnt += (uint32_t)__popcll(hm);
-                        if (hit && pos < a.cap) {
-                            uint8_t *dst = rec_w + pos * 80u;
+                    const int64_t t = g_rows * RT + r;
+                    const int64_t tc = t < a.n_tiles ? t : a.n_tiles - 1;
+                    const uint4 *tp = a.pack + (tc * KS) * 64 + lane;
 #pragma unroll
-                            for (int j = 0; j < 4; ++j)
-                                *reinterpret_cast<uint4 *>(dst + 16 * j) = make_uint4((uint32_t)acc[r][4 * j], (uint32_t)acc[r][4 * j + 1], (uint32_t)acc[r][4 * j + 2], (uint32_t)acc[r][4 * j + 3]);
-                            *reinterpret_cast<uint4 *>(dst + 64) = make_uint4((uint32_t)(q0 + qq), tile_row + (uint32_t)(32 * r), (uint32_t)qq, 0u);
-                        }
-                    }
+                    for (int s_ = 0; s_ < KS; ++s_) xa[r][s_] = __builtin_bit_cast(i32x4, tp[s_ * 64]);
                 }
             }
-        };
-        if constexpr (MAXMODE) {
 #pragma unroll
-            for (int b = 0; b < UT_NBQ; ++b)
-                if (b < nb) block(b, mreg[b]);
-        } else {
+            for (int i = lane; i < RT * 32; i += 64) {
+                const int64_t row = g_rows * RT * 32 + i;
+                bias_w[i] = row < a.n ? (a.bias_direct ? -a.norms[row] : -(a.norms[row] >> 1)) : UT_NEG;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const uint32_t tile_row = (uint32_t)(g_rows * RT * 32 + 4 * lk);
+            i32x4 qr[R];
+#pragma unroll
+            for (int j = 0; j < R - 1; ++j) qr[j] = *reinterpret_cast<const i32x4 *>(qp + j * 1024);
+            auto block = [&](const int b, int &mx) {
+                i32x16 acc[RT];
+#pragma unroll
+                for (int r = 0; r < RT; ++r)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {   // element 4 j + i: row i + 8 j + 4 lk of the tile
+                        const int4 v = *reinterpret_cast<const int4 *>(bias_w + r * 32 + 8 * j + 4 * lk);
+                        acc[r][4 * j] = v.x; acc[r][4 * j + 1] = v.y; acc[r][4 * j + 2] = v.z; acc[r][4 * j + 3] = v.w;
+                    }
+                const uint8_t *qb = qp + (size_t)b * (KS * 1024);
+#pragma unroll
+                for (int s_ = 0; s_ < KS; ++s_) {
+                    // (the last R - 1 steps of the last block read past the queries, into the thresholds and the padding behind them: never used)
+                    qr[(s_ + R - 1) % R] = *reinterpret_cast<const i32x4 *>(qb + (s_ + R - 1) * 1024);
+#pragma unroll
+                    for (int r = 0; r < RT; ++r) acc[r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[r][s_], qr[s_ % R], acc[r], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                epilogue(acc, b, mx, tile_row);
+            };
+            if constexpr (MAXMODE) {
+#pragma unroll
+                for (int b = 0; b < UT_NBQ; ++b)
+                    if (b < nb) block(b, mreg[b]);
+            } else {
 #pragma unroll 1
-            for (int b = 0; b < nb; ++b) block(b, none);
+                for (int b = 0; b < nb; ++b) block(b, none);
+            }
         }
     }
     if constexpr (MAXMODE) {
 #pragma unroll
-        for (int b = 0; b < UT_NBQ; ++b) {   // (a slot nobody's rows reached stays 0 = empty: the caller zeroed the array)
+        for (int b = 0; b < UT_NBQ; ++b) {   // (a half wave whose rows never came writes 0 = empty into its slot itself; slots without an owner are the caller's to zero)
             const int qq = 32 * b + lj;
-            if (b < nb && qq < nqc && mreg[b] > UT_NEG / 2) a.smax[(size_t)(q0 + qq) * a.smax_stride + slot] = (uint32_t)mreg[b] ^ 0x80000000u;
+            if (b < nb && qq < nqc) a.smax[(size_t)(q0 + qq) * a.smax_stride + slot] = mreg[b] > UT_NEG / 2 ? (uint32_t)mreg[b] ^ 0x80000000u : 0u;
         }
     } else {
-        if (lane == 0) a.wcnt[wave_g] = wcnt + (none == 0x12345678 ? 1u : 0u);
+        if (lane == 0) a.wcnt[wave_g] = (a.dbg & 8) ? 0u : wcnt + (none == 0x12345678 ? 1u : 0u);   // (no records were written: the bucket pass must read none)
     }
 }
 
@@ -570,7 +694,7 @@ int launch_flat_u8_tfilter(int D, const void *pack, const int32_t *norms, int64_
             const int64_t want = std::max<int64_t>(all_groups / div, std::min<int64_t>(all_groups, 2048 / rt));
             a.n_sample = std::min<int64_t>(all_groups, std::max<int64_t>(1, (want + streams - 1) / streams) * streams);   // (never a smaller sample than asked for)
         }
-        const size_t lds = (size_t)(qper / 32) * ks * 1024 + (size_t)qper * sizeof(int) + (size_t)UT_WAVES * rt * 32 * sizeof(int) + 3072;
+        const size_t lds = ut_lds_bytes(ks, rt, qper);
         CVTMI_TRY(ut_launch_any(ks, true, a, lds, st));
         // (merged keys while that leaves eight per neighbour wanted)
         CVTMI_TRY(launch("ut_theta_kernel", k * 8 <= UT_SLOTS / 4 / chunks ? ut_theta_kernel<UT_SLOTS / 256> : ut_theta_kernel<UT_SLOTS / 64>, blocks_for(m, 4), 256, 0, st, smax,
@@ -594,13 +718,14 @@ static int u8_filter_args(const U8FilterJob &j, UtArgs &a, size_t &lds)
 {
     const int ks = j.D / 32;
     if (!flat_u8_tfilter_width(j.D) || j.qper % 32 != 0 || j.qper < 32 || j.qper > UT_QPER || j.chunks < 1 || j.spx < 1 || 8 * j.spx > UT_GRID ||
-        j.nq < 1 || j.nq > j.chunks * j.qper || j.n < 1 || j.n >= 0x7fffffe0LL || j.smax_stride < 8 * j.spx * UT_WAVES * 2)
+        j.nq < 1 || j.nq > j.chunks * j.qper || j.n < 1 || j.n >= 0x7fffffe0LL || j.smax_stride != 8 * j.spx * UT_WAVES * 2)   // (a wider stride would leave slots no half wave writes)
         return fail(CVTMI_EINVAL, "u8_filter: bad job (D=%d nq=%d chunks=%d qper=%d spx=%d)", j.D, j.nq, j.chunks, j.qper, j.spx);
     a.pack = reinterpret_cast<const uint4 *>(j.pack); a.norms = j.bias; a.n = j.n; a.n_tiles = (j.n + 31) / 32; a.n_sample = j.n_sample;
     a.Q = reinterpret_cast<const uint8_t *>(j.W); a.D = j.D; a.nq = j.nq; a.chunks = j.chunks; a.qper = j.qper;
     a.smax = j.smax; a.thr = j.thr; a.rec = reinterpret_cast<uint4 *>(j.rec); a.wcnt = j.wcnt; a.cap = j.rec_cap;
-    a.qxor = 0u; a.bias_direct = 1; a.smax_stride = j.smax_stride; a.dbg = 0;
-    lds = (size_t)(j.qper / 32) * ks * 1024 + (size_t)j.qper * sizeof(int) + (size_t)UT_WAVES * ut_rt(ks) * 32 * sizeof(int) + 3072;
+    a.qxor = 0u; a.bias_direct = 1; a.smax_stride = j.smax_stride;
+    { const char *e = getenv("CVTMI_UT_DBG"); a.dbg = e ? atoi(e) & 11 : 0; }   // (the timing experiments only: the record regions are this caller's own)
+    lds = ut_lds_bytes(ks, ut_rt(ks), j.qper);
     return CVTMI_OK;
 }
 int launch_u8_filter_sample(const U8FilterJob &j, hipStream_t st)

@@ -377,7 +377,8 @@ int launch_flat_u8_tfilter(int D, const void *pack, const int32_t *norms, int64_
                            int64_t *out_i, uint32_t *flags, hipStream_t st);
 // the same sample, filter and bucket kernels over a caller's own operands (adc_mfma.hip): int8 queries W[nq][D], pack in launch_flat_u8_pack's
 // layout, a row's accumulator starts at -bias[row].  One launch covers `chunks` chunks of `qper` queries (a multiple of 32, <= 256), each over
-// 8 spx row slices; the sample leaves 16 slots per slice and query in smax (zeroed by the caller; key = value ^ 0x80000000, 0 = empty);
+// 8 spx row slices; the sample leaves 16 slots per slice and query in smax (smax_stride = 8 spx x 16 exactly: the pass writes every slot, an
+// empty one as 0, so the caller does not zero the array; key = value ^ 0x80000000, 0 = empty);
 // the bucket leaves (value, row) pairs, list_cap per query, counted in cnt (zeroed by the caller), and ORs 2 into pass_flag[chunk] when a
 // wave's record region (rec_cap records of u8_filter_rec_bytes(), 8 spx chunks x 8 regions) ran over
 struct U8FilterJob {
