@@ -30,6 +30,7 @@ namespace {
 constexpr double MF_UP = 1.0 + 1e-9;        // every bound is rounded up by this much: the double arithmetic that evaluates it
 constexpr double MF_BMAX = 4194304.0;       // floor(n^ / 2t) stays below 2^22: the accumulators stay far inside int32 and n^ - |x^|^2 <= t
 constexpr int MF_NSEL = 4096;               // the largest list cap: 64 entries per lane of the selecting wave
+constexpr int MF_NSHORT = 1024;             // lists of up to so many entries take the short form of the selection (16 entries per lane), longer ones the long form's launch
 constexpr int MF_KEEP = 512;                // rows at or below the k-th distance the selection sorts (k + its ties; more: the exact scan)
 constexpr int MF_CALL_WORDS = 64;           // [0] bits of max |w|, [63] the count of flagged queries
 
@@ -194,30 +195,76 @@ __global__ __launch_bounds__(256) void mf_theta_kernel(const uint32_t *__restric
 // score A2 of the list is reached by k rows, so by the sample's argument only rows with a >= A2 - margin can be in the answer: those (about
 // k + a band) get their exact sums in the reference's order; the ones at or below the k-th smallest sum are sorted by (distance, row),
 // and the first k are written out.
-template <int NK>   // NK x 64 list entries at most
-__device__ __forceinline__ void mf_select_body(const uint8_t *__restrict__ codes, const float *__restrict__ lut_g, int K, int nq_lut, int64_t q_base, int64_t n, int k,
+// How the wave reaches memory: the list is read once, whole entries at a clamped index with no predicate (all loads in flight; entries
+// past the count are masked afterwards); the rows inside the band are compacted into LDS, and lane l sums entries l, l + 64, ... of them,
+// four at a time through ExactFromLutBatch (code rows and table gathers without a predicate, lanes past the end sum row 0 and drop it) --
+// three dependent round trips per 256 band rows.  Both selections count keys and do not care where a key sits.
+template <int NK>   // NK x 64 list entries at most: 16 = lists of up to 1024 entries, the usual case; MF_NSEL / 64 = the longer ones, a launch of their own
+__global__ __launch_bounds__(64) void mf_select_kernel(const uint8_t *__restrict__ codes, const float *__restrict__ lut_g, int K, int nq_lut, int64_t q_base, int64_t n, int k,
                                                        const uint32_t *__restrict__ cnt, const uint2 *__restrict__ cand, uint32_t lcap, const int32_t *__restrict__ margin,
-                                                       const uint32_t *__restrict__ pass_flag, int64_t id_base, float *__restrict__ out_d,
-                                                       int64_t *__restrict__ out_id, uint32_t *__restrict__ flags, unsigned long long *sel, uint32_t nc)
+                                                       const uint32_t *__restrict__ pass_flag, int qper, int64_t id_base, float *__restrict__ out_d,
+                                                       int64_t *__restrict__ out_id, uint32_t *__restrict__ flags)
 {
+    __shared__ __attribute__((aligned(16))) unsigned long long sel[NK * 32 > MF_KEEP ? NK * 32 : MF_KEEP];   // the band's rows (NK x 64 words) first, the kept pairs after
+    uint32_t *band = reinterpret_cast<uint32_t *>(sel);
     const int lane = threadIdx.x, ql = blockIdx.x;         // the query inside its piece ...
     const int64_t q = q_base + ql;                          // ... and inside the call (tables, margins, flags and results)
     const int64_t want = k < n ? k : n;
+    const uint32_t nc = cnt[ql];
+    static_assert(NK == MF_NSHORT / 64 || NK == MF_NSEL / 64, "the two forms");
+    if constexpr (NK == MF_NSHORT / 64) {
+        if (flags[q] != 0u || pass_flag[ql / qper] != 0u || nc > lcap || (int64_t)nc < want) {   // wave-uniform: the exact scan answers this query
+            if (lane == 0) flags[q] = 1u;
+            return;
+        }
+        if (nc > (uint32_t)MF_NSHORT) return;   // (the long form's launch, behind this one)
+    } else {
+        if (flags[q] != 0u || nc <= (uint32_t)MF_NSHORT) return;   // (the short form, ahead of this launch, has raised the flag of every query the scan answers)
+    }
     const uint2 *cq = cand + (size_t)ql * lcap;
-    uint32_t key[NK];   // score ^ 0x80000000 (never 0: scores stay far above INT_MIN), 0 = no entry
+    uint32_t key[NK], row[NK];   // key: score ^ 0x80000000 (never 0: scores stay far above INT_MIN), 0 = no entry
 #pragma unroll
-    for (int j = 0; j < NK; ++j) key[j] = (uint32_t)(j * 64 + lane) < nc ? (cq[j * 64 + lane].x ^ 0x80000000u) : 0u;
+    for (int j = 0; j < NK; ++j) {
+        const uint32_t i = (uint32_t)(j * 64 + lane);
+        const uint2 e = cq[i < nc ? i : nc - 1u];   // (nc >= want >= 1)
+        key[j] = i < nc ? (e.x ^ 0x80000000u) : 0u;
+        row[j] = e.y;
+    }
     const uint32_t a2 = fs_wave_select(key, (int)want, (int)want);
     const uint32_t cut = (uint32_t)((int32_t)(a2 ^ 0x80000000u) - margin[q]) ^ 0x80000000u;
-    // the exact sums of the rows inside the band, where they sit: key[j] becomes ~(distance bits), larger = nearer (0 = out)
-    const ExactFromLut fix{ reinterpret_cast<const uint4 *>(codes), lut_g, K, nq_lut, (int)(q / SQ_QT) };
+    uint32_t nb = 0;   // the rows inside the band, side by side
 #pragma unroll
     for (int j = 0; j < NK; ++j) {
         const bool in = key[j] != 0u && key[j] >= cut;
+        const unsigned long long m = __ballot(in);
+        const uint32_t pos = nb + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (in) band[pos] = row[j];
+        nb += (uint32_t)__popcll(m);
         key[j] = 0u;
-        if (__ballot(in) == 0ull) continue;
-        if (in) key[j] = ~(uint32_t)(fix((int)(q % SQ_QT), (unsigned long long)cq[j * 64 + lane].y) >> 32);   // (non-negative sums or +inf: never 0)
     }
+    __syncthreads();
+    // their exact sums: key[j] becomes ~(distance bits), larger = nearer (0 = no entry), row[j] its row
+    const ExactFromLutBatch<> fixb{ codes, lut_g, K, nq_lut, (int)(q / SQ_QT) };
+#pragma unroll
+    for (int b = 0; b < NK / 4; ++b) {
+        if ((uint32_t)(b * 256) < nb) {   // wave-uniform
+            unsigned long long e[4];
+            bool need[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const uint32_t i = (uint32_t)((4 * b + r) * 64 + lane);
+                need[r] = i < nb;
+                e[r] = band[need[r] ? i : 0u];
+            }
+            fixb((int)(q % SQ_QT), e, need);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                key[4 * b + r] = need[r] ? ~(uint32_t)(e[r] >> 32) : 0u;   // (non-negative sums or +inf: never 0)
+                row[4 * b + r] = (uint32_t)e[r];
+            }
+        }
+    }
+    __syncthreads();   // (the band's words have been read: their space takes the kept pairs)
     const uint32_t kd = fs_wave_select(key, (int)want, (int)want);   // the k-th smallest distance: everything at or below it is sorted
     uint32_t ns = 0;
 #pragma unroll
@@ -226,7 +273,7 @@ __device__ __forceinline__ void mf_select_body(const uint8_t *__restrict__ codes
         const unsigned long long m = __ballot(in);
         if (m == 0ull) continue;
         const uint32_t pos = ns + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        if (in && pos < (uint32_t)MF_KEEP) sel[pos] = ((unsigned long long)(~key[j]) << 32) | cq[j * 64 + lane].y;
+        if (in && pos < (uint32_t)MF_KEEP) sel[pos] = ((unsigned long long)(~key[j]) << 32) | row[j];
         ns += (uint32_t)__popcll(m);
     }
     if (ns > (uint32_t)MF_KEEP) {   // masses of rows at the k-th distance (equal rows): the exact scan
@@ -247,23 +294,6 @@ __device__ __forceinline__ void mf_select_body(const uint8_t *__restrict__ codes
             out_id[q * k + i] = -1;
         }
     }
-}
-
-__global__ __launch_bounds__(64) void mf_select_kernel(const uint8_t *__restrict__ codes, const float *__restrict__ lut_g, int K, int nq_lut, int64_t q_base, int64_t n, int k,
-                                                       const uint32_t *__restrict__ cnt, const uint2 *__restrict__ cand, uint32_t lcap, const int32_t *__restrict__ margin,
-                                                       const uint32_t *__restrict__ pass_flag, int qper, int64_t id_base, float *__restrict__ out_d,
-                                                       int64_t *__restrict__ out_id, uint32_t *__restrict__ flags)
-{
-    __shared__ __attribute__((aligned(16))) unsigned long long sel[MF_KEEP];
-    const int64_t q = q_base + blockIdx.x;
-    const uint32_t nc = cnt[blockIdx.x];
-    if (flags[q] != 0u || pass_flag[blockIdx.x / qper] != 0u || nc > lcap || (int64_t)nc < (k < n ? k : n)) {   // wave-uniform: the exact scan answers this query
-        if (threadIdx.x == 0) flags[q] = 1u;
-        return;
-    }
-    // (the wave's two selections walk every slot of the list's capacity: a short list, the usual case, takes the short form)
-    if (nc <= 1024u) mf_select_body<16>(codes, lut_g, K, nq_lut, q_base, n, k, cnt, cand, lcap, margin, pass_flag, id_base, out_d, out_id, flags, sel, nc);
-    else mf_select_body<MF_NSEL / 64>(codes, lut_g, K, nq_lut, q_base, n, k, cnt, cand, lcap, margin, pass_flag, id_base, out_d, out_id, flags, sel, nc);
 }
 
 // The flagged queries of a call side by side, so that the exact scan runs over a short batch with row splits instead of one workgroup per
@@ -493,8 +523,13 @@ int launch_adc_mfma(const OpqModelDev &m, const AdcMfmaModel &mm, const uint8_t 
         CVTMI_TRY(launch("mf_theta_kernel", theta, blocks_for(mq, 4), 256, 0, st, smax, (int)mq, k, margin + q0, thr, cnt, flags + q0));
         CVTMI_TRY(launch_u8_filter_pass(j, st));
         CVTMI_TRY(launch_u8_filter_bucket(j, st));
-        CVTMI_TRY(launch("mf_select_kernel", mf_select_kernel, mq, 64, 0, st, codes, lut_g, m.K, (int)nq, q0, n, k, cnt, cand, (uint32_t)list_cap, margin, cflag, s.qper,
+        CVTMI_TRY(launch("mf_select_kernel", mf_select_kernel<MF_NSHORT / 64>, mq, 64, 0, st, codes, lut_g, m.K, (int)nq, q0, n, k, cnt, cand, (uint32_t)list_cap, margin, cflag, s.qper,
                          id_base, dist, ids, flags));
+        // lists of more than 1024 entries: the same body over MF_NSEL slots, with the registers and the LDS that takes (every workgroup looks at
+        // its query's count; the ones whose list the short form took leave at once)
+        if (list_cap > MF_NSHORT)
+            CVTMI_TRY(launch("mf_select_long_kernel", mf_select_kernel<MF_NSEL / 64>, mq, 64, 0, st, codes, lut_g, m.K, (int)nq, q0, n, k, cnt, cand, (uint32_t)list_cap, margin,
+                             cflag, s.qper, id_base, dist, ids, flags));
     }
     if (stat) {
         CVTMI_HIP(hipMemsetAsync(stat, 0, 2 * sizeof(unsigned long long), st));
