@@ -12,7 +12,10 @@
 //   filter pass + bucket: the rows at or above it, per query; selection: their exact sums in the reference's order from the fp32 tables
 //     (ExactFromLut), sorted by (distance, id) -- the answer is the reference's, bit for bit.
 // A query that is not finite, whose sample filled fewer than 1.25 k slots, whose margin cannot be held or whose list ran over raises ITS
-// flag; a record region that ran over flags the queries of its chunk (the 256 or fewer whose records it holds).  The caller answers flagged queries with the exact scan.
+// flag; a record region that ran over flags the queries of its chunk (the 256 or fewer whose records it holds).
+// Flagged queries: up to MF_REDO of them take a slot and are answered here by the same scheme in exact fp32 over ALL rows (mf_redo_*: the
+// k-th smallest of the exact minima over disjoint row sets is a bound tau on the k-th distance, the rows at or below tau are listed, the
+// list is ranked); the others, and a slot whose list ran over or met a NaN, are left to the caller's exact scan through rest[q].
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -33,6 +36,9 @@ constexpr int MF_NSEL = 4096;               // the largest list cap: 64 entries 
 constexpr int MF_NSHORT = 1024;             // lists of up to so many entries take the short form of the selection (16 entries per lane), longer ones the long form's launch
 constexpr int MF_KEEP = 512;                // rows at or below the k-th distance the selection sorts (k + its ties; more: the exact scan)
 constexpr int MF_CALL_WORDS = 64;           // [0] bits of max |w|, [63] the count of flagged queries
+constexpr int MF_REDO = 64;                 // flagged queries that get a slot of the exact redo (its list: MF_NSHORT entries)
+constexpr int MF_REDO_SLICES = 256;         // row slices of the redo's passes at most, one workgroup per slice and slot ...
+constexpr int MF_REDO_SETS = 16 * MF_REDO_SLICES;   // ... each with one row set per 16 lanes: set minima per slot
 
 // [tile][s][lane] 16 bytes: row 32 t + (lane & 31), dimensions 32 s + 16 (lane >> 5) .. + 16 of its decoded int8 row
 __global__ __launch_bounds__(kBlock) void mf_pack_kernel(const uint4 *__restrict__ codes, int64_t n, int ks, int step, const int8_t *__restrict__ xb,
@@ -191,6 +197,43 @@ __global__ __launch_bounds__(256) void mf_theta_kernel(const uint32_t *__restric
     }
 }
 
+// One wave ranks its exact sums (key: ~(distance bits), larger = nearer, 0 = no entry; at least `want` present): everything at or below
+// the k-th smallest distance goes into sel (MF_KEEP pairs of LDS), is sorted by (distance, row), and the first k are query q's answer,
+// padded with (+inf, -1).  False, and nothing written, when more than MF_KEEP rows stand at or below the k-th distance.
+template <int NK>
+__device__ __forceinline__ bool mf_rank_write(const uint32_t (&key)[NK], const uint32_t (&row)[NK], unsigned long long *sel, int want, int k, int64_t q, int64_t id_base,
+                                              float *__restrict__ out_d, int64_t *__restrict__ out_id)
+{
+    const int lane = threadIdx.x;
+    const uint32_t kd = fs_wave_select(key, want, want);   // the k-th smallest distance: everything at or below it is sorted
+    uint32_t ns = 0;
+#pragma unroll
+    for (int j = 0; j < NK; ++j) {
+        const bool in = key[j] != 0u && key[j] >= kd;
+        const unsigned long long m = __ballot(in);
+        if (m == 0ull) continue;
+        const uint32_t pos = ns + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (in && pos < (uint32_t)MF_KEEP) sel[pos] = ((unsigned long long)(~key[j]) << 32) | row[j];
+        ns += (uint32_t)__popcll(m);
+    }
+    if (ns > (uint32_t)MF_KEEP) return false;
+    int np = 64;
+    while (np < (int)ns) np <<= 1;
+    for (int i = (int)ns + lane; i < np; i += 64) sel[i] = ~0ull;   // padding sorts last
+    block_bitonic_u64<64>(sel, np);
+    for (int i = lane; i < k; i += 64) {
+        if ((uint32_t)i < ns) {
+            const unsigned long long e = sel[i];
+            out_d[q * k + i] = __uint_as_float((uint32_t)(e >> 32));
+            out_id[q * k + i] = id_base + (int64_t)(uint32_t)e;
+        } else {
+            out_d[q * k + i] = __uint_as_float(0x7f800000u);
+            out_id[q * k + i] = -1;
+        }
+    }
+    return true;
+}
+
 // One wave per query.  Its list holds every row at or above the SAMPLED threshold; now that all rows have been seen, the k-th largest
 // score A2 of the list is reached by k rows, so by the sample's argument only rows with a >= A2 - margin can be in the answer: those (about
 // k + a band) get their exact sums in the reference's order; the ones at or below the k-th smallest sum are sorted by (distance, row),
@@ -265,71 +308,153 @@ __global__ __launch_bounds__(64) void mf_select_kernel(const uint8_t *__restrict
         }
     }
     __syncthreads();   // (the band's words have been read: their space takes the kept pairs)
-    const uint32_t kd = fs_wave_select(key, (int)want, (int)want);   // the k-th smallest distance: everything at or below it is sorted
-    uint32_t ns = 0;
+    if (!mf_rank_write(key, row, sel, (int)want, k, q, id_base, out_d, out_id) && lane == 0) flags[q] = 1u;   // masses of rows at the k-th distance (equal rows): the exact scan
+}
+
+// The flagged queries of a call: the first MF_REDO of them take a slot of the exact redo below (slot_q[slot] = q; *count, zeroed by the
+// launcher, ends as the number of flagged queries, so slots [0, min(*count, MF_REDO)) are the taken ones); rest[q] is raised for those that
+// found none.  One lane per query, one atomic per wave.  Also clears the slots' list counters and fail words, and -- profiled searches --
+// leaves stat[0] = queries of the call, stat[1] = how many of them were flagged (stat[1] zeroed by the launcher).
+__global__ __launch_bounds__(256) void mf_compact_kernel(const uint32_t *__restrict__ flags, int nq, uint32_t *__restrict__ count, int32_t *__restrict__ slot_q,
+                                                         uint32_t *__restrict__ lcnt, uint32_t *__restrict__ fail, uint32_t *__restrict__ rest,
+                                                         unsigned long long *__restrict__ stat)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    if (blockIdx.x == 0 && threadIdx.x < MF_REDO) { lcnt[threadIdx.x] = 0u; fail[threadIdx.x] = 0u; }
+    if (stat && q == 0) stat[0] = (unsigned long long)nq;
+    const bool flagged = q < nq && flags[q] != 0u;
+    const unsigned long long m = __ballot(flagged);
+    uint32_t base = 0;
+    if (lane == 0 && m) {
+        base = atomicAdd(count, (uint32_t)__popcll(m));
+        if (stat) atomicAdd(stat + 1, (unsigned long long)__popcll(m));
+    }
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    if (q >= nq) return;
+    const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const bool taken = flagged && slot < (uint32_t)MF_REDO;
+    if (taken) slot_q[slot] = q;
+    rest[q] = flagged && !taken ? 1u : 0u;
+}
+
+// The exact redo of the queries that took a slot: the route's scheme (bound, collect, finish) over ALL rows in fp32.
+// A distance is the reference's sum, m ascending with __fadd_rn over the query's fp32 table (as ExactFromLut; the 16 KB table in LDS);
+// its key is the uint bits of that non-negative float.
+__device__ __forceinline__ uint32_t mf_redo_sum(const float *t, const uint4 c)
+{
+    const uint32_t w[4] = { c.x, c.y, c.z, c.w };
+    float v[16];
 #pragma unroll
-    for (int j = 0; j < NK; ++j) {
-        const bool in = key[j] != 0u && key[j] >= kd;
-        const unsigned long long m = __ballot(in);
-        if (m == 0ull) continue;
-        const uint32_t pos = ns + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        if (in && pos < (uint32_t)MF_KEEP) sel[pos] = ((unsigned long long)(~key[j]) << 32) | row[j];
-        ns += (uint32_t)__popcll(m);
-    }
-    if (ns > (uint32_t)MF_KEEP) {   // masses of rows at the k-th distance (equal rows): the exact scan
-        if (lane == 0) flags[q] = 1u;
-        return;
-    }
-    int np = 64;
-    while (np < (int)ns) np <<= 1;
-    for (int i = (int)ns + lane; i < np; i += 64) sel[i] = ~0ull;   // padding sorts last
-    block_bitonic_u64<64>(sel, np);
-    for (int i = lane; i < k; i += 64) {
-        if ((uint32_t)i < ns) {
-            const unsigned long long e = sel[i];
-            out_d[q * k + i] = __uint_as_float((uint32_t)(e >> 32));
-            out_id[q * k + i] = id_base + (int64_t)(uint32_t)e;
-        } else {
-            out_d[q * k + i] = __uint_as_float(0x7f800000u);
-            out_id[q * k + i] = -1;
+    for (int m = 0; m < 16; ++m) v[m] = t[m * 256 + (int)((w[m >> 2] >> (8 * (m & 3))) & 0xffu)];
+    float s = 0.0f;
+#pragma unroll
+    for (int m = 0; m < 16; ++m) s = __fadd_rn(s, v[m]);
+    return __float_as_uint(s);
+}
+// Both passes over the rows.  Grid (row slices of `per` rows, slot lanes): a workgroup takes slots blockIdx.y, + gridDim.y, ... below the
+// taken count (none: it leaves at once); lane t of it sums rows t, t + 256, ... of its slice, four loads in flight.
+//   bound (COLLECT false): the minimum over the rows of every 16 lanes -- a row set of its own -- into smin[slot][16 slice + .] (~0: the set
+//     holds no row).  mf_redo_tau_kernel takes the k-th smallest of them: k distinct rows reach it, so it bounds the k-th distance.
+//     A sum that is NaN (or negative: no key) raises fail[slot]: the exact scan answers that query.
+//   collect: every row at or below tau[slot] is appended to list[slot] as (distance bits, row) under lcnt[slot]; entries past MF_NSHORT are
+//     dropped, the count shows it.
+template <bool COLLECT>
+__global__ __launch_bounds__(256) void mf_redo_pass_kernel(const uint4 *__restrict__ codes, int64_t n, int64_t per, const float *__restrict__ lut_g,
+                                                           const uint32_t *__restrict__ call, const int32_t *__restrict__ slot_q, uint32_t *__restrict__ smin,
+                                                           const uint32_t *__restrict__ tau, uint32_t *__restrict__ lcnt, uint2 *__restrict__ list,
+                                                           uint32_t *__restrict__ fail)
+{
+    __shared__ float4 tab[16 * 256 / 4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const uint32_t taken = call[MF_CALL_WORDS - 1] < (uint32_t)MF_REDO ? call[MF_CALL_WORDS - 1] : (uint32_t)MF_REDO;
+    const int64_t row0 = (int64_t)blockIdx.x * per, row1 = row0 + per < n ? row0 + per : n;   // (row0 < n: the grid is blocks_for(n, per))
+    for (uint32_t slot = blockIdx.y; slot < taken; slot += gridDim.y) {   // workgroup-uniform
+        const float4 *src = reinterpret_cast<const float4 *>(lut_g + (int64_t)slot_q[slot] * 16 * 256);
+        __syncthreads();   // (the last slot's table has been read)
+        for (int i = tid; i < 16 * 256 / 4; i += 256) tab[i] = src[i];
+        __syncthreads();
+        const float *t = reinterpret_cast<const float *>(tab);
+        const uint32_t cut = COLLECT ? tau[slot] : 0u;
+        uint32_t best = ~0u;
+        bool bad = false;
+        for (int64_t b = row0; b < row1; b += 1024) {
+            uint4 c[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t r = b + j * 256 + tid;
+                c[j] = codes[r < row1 ? r : row1 - 1];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t r = b + j * 256 + tid;
+                const uint32_t bits = mf_redo_sum(t, c[j]);
+                if constexpr (COLLECT) {
+                    const bool in = r < row1 && bits <= cut;
+                    const unsigned long long m = __ballot(in);
+                    if (m == 0ull) continue;   // wave-uniform
+                    uint32_t base = 0;
+                    if (lane == 0) base = atomicAdd(lcnt + slot, (uint32_t)__popcll(m));
+                    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                    const uint32_t pos = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    if (in && pos < (uint32_t)MF_NSHORT) list[(size_t)slot * MF_NSHORT + pos] = make_uint2(bits, (uint32_t)r);
+                } else if (r < row1) {
+                    if (bits > 0x7f800000u) bad = true;
+                    else best = bits < best ? bits : best;
+                }
+            }
+        }
+        if constexpr (!COLLECT) {
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) {
+                const uint32_t other = (uint32_t)__shfl_xor((int)best, o, 64);
+                best = other < best ? other : best;
+            }
+            if ((tid & 15) == 0) smin[(size_t)slot * MF_REDO_SETS + blockIdx.x * 16 + (tid >> 4)] = best;
+            if (bad) fail[slot] = 1u;
         }
     }
 }
-
-// The flagged queries of a call side by side, so that the exact scan runs over a short batch with row splits instead of one workgroup per
-// query of the call: up to `cap` of them get a slot (their rotated query copied, the slot's predicate word raised); rest[q] stays up for
-// those that found none.
-__global__ __launch_bounds__(256) void mf_compact_kernel(const uint32_t *__restrict__ flags, int nq, int D, const float *__restrict__ q_rot, uint32_t *__restrict__ count,
-                                                         int cap, int32_t *__restrict__ slot_q, float *__restrict__ q_c, uint32_t *__restrict__ only_c,
-                                                         uint32_t *__restrict__ rest)
+// one wave per slot: tau = the k-th smallest set minimum (distance bits); fewer than `want` sets with a row: no bound, every row passes
+__global__ __launch_bounds__(64) void mf_redo_tau_kernel(const uint32_t *__restrict__ smin, int nsets, int want, const uint32_t *__restrict__ call, uint32_t *__restrict__ tau)
 {
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (q >= nq) return;
-    if (flags[q] == 0u) { if (lane == 0) rest[q] = 0u; return; }
-    uint32_t slot = 0;
-    if (lane == 0) slot = atomicAdd(count, 1u);
-    slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot);
-    if (slot >= (uint32_t)cap) { if (lane == 0) rest[q] = 1u; return; }
-    for (int d = lane; d < D; d += 64) q_c[(size_t)slot * D + d] = q_rot[(int64_t)q * D + d];
-    if (lane == 0) { slot_q[slot] = q; only_c[slot] = 1u; rest[q] = 0u; }
+    const int slot = blockIdx.x, lane = threadIdx.x;
+    if ((uint32_t)slot >= call[MF_CALL_WORDS - 1]) return;
+    uint32_t key[MF_REDO_SETS / 64];   // ~bits: larger = nearer, 0 = no set or a set without a row
+#pragma unroll
+    for (int j = 0; j < MF_REDO_SETS / 64; ++j) {
+        const int i = j * 64 + lane;
+        const uint32_t v = smin[(size_t)slot * MF_REDO_SETS + (i < nsets ? i : 0)];
+        key[j] = i < nsets ? ~v : 0u;
+    }
+    const uint32_t sel = fs_wave_select(key, want, want);
+    if (lane == 0) tau[slot] = sel != 0u ? ~sel : ~0u;
 }
-// ... and their answers back to the queries' own places
-__global__ __launch_bounds__(128) void mf_scatter_kernel(const int32_t *__restrict__ slot_q, const uint32_t *__restrict__ only_c, int k, const float *__restrict__ d_c,
-                                                         const int64_t *__restrict__ i_c, float *__restrict__ dist, int64_t *__restrict__ ids)
+// One wave per slot ranks the slot's list -- every row at or below tau, so every row of the answer -- and writes the answer to the query's
+// own place.  A list over its cap, more than MF_KEEP rows at or below the k-th distance or a NaN met by the bound pass: rest[q].
+__global__ __launch_bounds__(64) void mf_redo_finish_kernel(const uint32_t *__restrict__ call, const int32_t *__restrict__ slot_q, const uint32_t *__restrict__ lcnt,
+                                                            const uint2 *__restrict__ list, const uint32_t *__restrict__ fail, int64_t n, int k, int64_t id_base,
+                                                            float *__restrict__ out_d, int64_t *__restrict__ out_id, uint32_t *__restrict__ rest)
 {
-    const int slot = blockIdx.x;
-    if (only_c[slot] == 0u) return;
-    const int64_t q = slot_q[slot];
-    for (int i = threadIdx.x; i < k; i += 128) { dist[q * k + i] = d_c[(int64_t)slot * k + i]; ids[q * k + i] = i_c[(int64_t)slot * k + i]; }
-}
-
-// profiled searches: stat[0] = queries of the call, stat[1] = how many of them were flagged (zeroed by the launcher)
-__global__ __launch_bounds__(256) void mf_count_kernel(const uint32_t *__restrict__ flags, int nq, unsigned long long *__restrict__ stat)
-{
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long m = __ballot(q < nq && flags[q] != 0u);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(stat + 1, (unsigned long long)__popcll(m));
-    if (q == 0) stat[0] = (unsigned long long)nq;
+    __shared__ __attribute__((aligned(16))) unsigned long long sel[MF_KEEP];
+    constexpr int NK = MF_NSHORT / 64;
+    const int slot = blockIdx.x, lane = threadIdx.x;
+    if ((uint32_t)slot >= call[MF_CALL_WORDS - 1]) return;
+    const int64_t q = slot_q[slot], want = k < n ? k : n;
+    const uint32_t nc = lcnt[slot];
+    if (fail[slot] != 0u || nc > (uint32_t)MF_NSHORT || (int64_t)nc < want) {   // wave-uniform
+        if (lane == 0) rest[q] = 1u;
+        return;
+    }
+    const uint2 *lq = list + (size_t)slot * MF_NSHORT;
+    uint32_t key[NK], row[NK];
+#pragma unroll
+    for (int j = 0; j < NK; ++j) {
+        const uint32_t i = (uint32_t)(j * 64 + lane);
+        const uint2 e = lq[i < nc ? i : nc - 1u];   // (nc >= want >= 1)
+        key[j] = i < nc ? ~e.x : 0u;   // (bits of non-negative sums or +inf: never 0)
+        row[j] = e.y;
+    }
+    if (!mf_rank_write(key, row, sel, (int)want, k, q, id_base, out_d, out_id) && lane == 0) rest[q] = 1u;
 }
 
 size_t mf_align(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -372,15 +497,14 @@ MfShape mf_shape(int D, int64_t n, int64_t m, int k, int list_cap, int div, bool
               mf_align((size_t)m * list_cap * sizeof(uint2), 256) + mf_align((size_t)s.regions * s.rec_cap * u8_filter_rec_bytes(), 256);
     return s;
 }
-constexpr int MF_REDO = 64, MF_REDO_SPLITS = 32;   // flagged queries that get a slot of the short batch, and its row splits
-size_t mf_redo_bytes(int D, int k)
+// the exact redo's scratch: slot_q, list counters, fail words and tau per slot, the set minima (1 MB) and the lists (0.5 MB)
+size_t mf_redo_bytes()
 {
-    return mf_align(MF_REDO * 4, 256) * 2 + mf_align((size_t)MF_REDO * D * 4, 256) + mf_align((size_t)MF_REDO * k * 4, 256) + mf_align((size_t)MF_REDO * k * 8, 256) +
-           mf_align((size_t)MF_REDO * MF_REDO_SPLITS * k * 4, 256) + mf_align((size_t)MF_REDO * MF_REDO_SPLITS * k * 8, 256);
+    return mf_align(MF_REDO * 4, 256) * 4 + mf_align((size_t)MF_REDO * MF_REDO_SETS * 4, 256) + mf_align((size_t)MF_REDO * MF_NSHORT * sizeof(uint2), 256);
 }
 size_t mf_call_bytes(int D, int64_t n, int64_t nq)
 {
-    return mf_redo_bytes(D, 128) + mf_align((size_t)nq * 4, 256) + mf_align(MF_CALL_WORDS * 4, 256) + mf_align((size_t)nq * 4, 256) * 2 + mf_align((size_t)nq * D, 256) + mf_align((size_t)n * 4, 256);
+    return mf_redo_bytes() + mf_align((size_t)nq * 4, 256) + mf_align(MF_CALL_WORDS * 4, 256) + mf_align((size_t)nq * 4, 256) * 2 + mf_align((size_t)nq * D, 256) + mf_align((size_t)n * 4, 256);
 }
 
 }  // namespace
@@ -475,13 +599,12 @@ int launch_adc_mfma(const OpqModelDev &m, const AdcMfmaModel &mm, const uint8_t 
     int32_t *margin = reinterpret_cast<int32_t *>(sc); sc += mf_align((size_t)nq * 4, 256);
     int8_t *W = reinterpret_cast<int8_t *>(sc); sc += mf_align((size_t)nq * D, 256);
     int32_t *bias = reinterpret_cast<int32_t *>(sc); sc += mf_align((size_t)n * 4, 256);
-    redo->slot_q = reinterpret_cast<int32_t *>(sc); sc += mf_align(MF_REDO * 4, 256);
-    redo->only = reinterpret_cast<uint32_t *>(sc); sc += mf_align(MF_REDO * 4, 256);
-    redo->q = reinterpret_cast<float *>(sc); sc += mf_align((size_t)MF_REDO * D * 4, 256);
-    redo->d = reinterpret_cast<float *>(sc); sc += mf_align((size_t)MF_REDO * 128 * 4, 256);
-    redo->i = reinterpret_cast<int64_t *>(sc); sc += mf_align((size_t)MF_REDO * 128 * 8, 256);
-    redo->part_d = reinterpret_cast<float *>(sc); sc += mf_align((size_t)MF_REDO * MF_REDO_SPLITS * 128 * 4, 256);
-    redo->part_i = reinterpret_cast<int64_t *>(sc); sc += mf_align((size_t)MF_REDO * MF_REDO_SPLITS * 128 * 8, 256);
+    int32_t *slot_q = reinterpret_cast<int32_t *>(sc); sc += mf_align(MF_REDO * 4, 256);
+    uint32_t *lcnt = reinterpret_cast<uint32_t *>(sc); sc += mf_align(MF_REDO * 4, 256);
+    uint32_t *rfail = reinterpret_cast<uint32_t *>(sc); sc += mf_align(MF_REDO * 4, 256);
+    uint32_t *tau = reinterpret_cast<uint32_t *>(sc); sc += mf_align(MF_REDO * 4, 256);
+    uint32_t *smin = reinterpret_cast<uint32_t *>(sc); sc += mf_align((size_t)MF_REDO * MF_REDO_SETS * 4, 256);
+    uint2 *rlist = reinterpret_cast<uint2 *>(sc); sc += mf_align((size_t)MF_REDO * MF_NSHORT * sizeof(uint2), 256);
     redo->rest = reinterpret_cast<uint32_t *>(sc); sc += mf_align((size_t)nq * 4, 256);
     CVTMI_HIP(hipMemsetAsync(call, 0, MF_CALL_WORDS * 4, st));
     // (step + 19) roundings of non-negative partial sums in the reference's evaluation of one distance: five to spare
@@ -531,22 +654,18 @@ int launch_adc_mfma(const OpqModelDev &m, const AdcMfmaModel &mm, const uint8_t 
             CVTMI_TRY(launch("mf_select_long_kernel", mf_select_kernel<MF_NSEL / 64>, mq, 64, 0, st, codes, lut_g, m.K, (int)nq, q0, n, k, cnt, cand, (uint32_t)list_cap, margin,
                              cflag, s.qper, id_base, dist, ids, flags));
     }
-    if (stat) {
-        CVTMI_HIP(hipMemsetAsync(stat, 0, 2 * sizeof(unsigned long long), st));
-        CVTMI_TRY(launch("mf_count_kernel", mf_count_kernel, blocks_for(nq, 256), 256, 0, st, flags, (int)nq, stat));
-    }
-    // the flagged queries as a short batch of their own
-    redo->cap = MF_REDO; redo->splits = n >= (1 << 18) ? MF_REDO_SPLITS : 1;
-    CVTMI_HIP(hipMemsetAsync(redo->only, 0, MF_REDO * 4, st));
-    CVTMI_HIP(hipMemsetAsync(redo->q, 0, (size_t)MF_REDO * D * 4, st));   // (slots nobody took: the predicate skips them, their queries are still read by nobody)
-    CVTMI_TRY(launch("mf_compact_kernel", mf_compact_kernel, blocks_for(nq, 4), 256, 0, st, flags, (int)nq, D, q_rot, call + MF_CALL_WORDS - 1, MF_REDO, redo->slot_q, redo->q,
-                     redo->only, redo->rest));
-    return CVTMI_OK;
-}
-
-int launch_adc_mfma_scatter(const AdcMfmaRedo &redo, int k, float *dist, int64_t *ids, hipStream_t st)
-{
-    return launch("mf_scatter_kernel", mf_scatter_kernel, redo.cap, 128, 0, st, redo.slot_q, redo.only, k, redo.d, redo.i, dist, ids);
+    // The flagged queries: up to MF_REDO take a slot and are answered here, exactly, over all rows (bound, tau, collect, finish); no
+    // memset and no copy of a query: the slots' words are cleared by the compaction, the tables are the selection's.
+    if (stat) CVTMI_HIP(hipMemsetAsync(stat, 0, 2 * sizeof(unsigned long long), st));
+    CVTMI_TRY(launch("mf_compact_kernel", mf_compact_kernel, blocks_for(nq, 256), 256, 0, st, flags, (int)nq, call + MF_CALL_WORDS - 1, slot_q, lcnt, rfail, redo->rest, stat));
+    // row slices: 256 at 1 M rows, never under 256 rows each -- a row per lane, so that a small index still has many more sets than k
+    const int64_t rper = std::max<int64_t>(256, blocks_for(n, MF_REDO_SLICES)), slices = blocks_for(n, rper);
+    const Grid rgrid{ slices, 8 };   // eight slot lanes: one or two flagged queries leave few workgroups without work, 64 share the rows' reads
+    const uint4 *rows = reinterpret_cast<const uint4 *>(codes);
+    CVTMI_TRY(launch("mf_redo_bound_kernel", mf_redo_pass_kernel<false>, rgrid, 256, 0, st, rows, n, rper, lut_g, call, slot_q, smin, tau, lcnt, rlist, rfail));
+    CVTMI_TRY(launch("mf_redo_tau_kernel", mf_redo_tau_kernel, MF_REDO, 64, 0, st, smin, (int)slices * 16, (int)std::min<int64_t>(k, n), call, tau));
+    CVTMI_TRY(launch("mf_redo_collect_kernel", mf_redo_pass_kernel<true>, rgrid, 256, 0, st, rows, n, rper, lut_g, call, slot_q, smin, tau, lcnt, rlist, rfail));
+    return launch("mf_redo_finish_kernel", mf_redo_finish_kernel, MF_REDO, 64, 0, st, call, slot_q, lcnt, rlist, rfail, n, k, id_base, dist, ids, redo->rest);
 }
 
 }  // namespace cvtmi

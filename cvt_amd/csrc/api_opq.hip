@@ -670,7 +670,7 @@ static int opq_search_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64
     if (h->n == 0)  // an empty index (e.g. a rank whose row block is empty): all padding, (+inf, -1)
         return launch_topk_select(nullptr, nullptr, nq, 0, k, dist, ids, st);
     bool mfma = mfma_wanted(h, nq, k) && h->mf_state == 1 && h->mf_n == h->n && h->mf_pack.p;
-    // what the flagged queries beyond the short redo batch go through: the planned 8-query scan, a group scanned when one of its queries is
+    // what the flagged queries the route's own exact redo leaves over (rest) go through: the planned 8-query scan, a group scanned when one of its queries is
     // flagged -- a call whose every query is flagged then costs the filter plus the scan it would have been without the route
     ScanPlan redo_plan = plan_scan(h->m, h->n, nq, k, 8, 0, 3);
     redo_plan.groups_a = 0; redo_plan.splits_b = 0;
@@ -700,15 +700,8 @@ static int opq_search_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64
         AdcMfmaRedo redo{};
         CVTMI_TRY(launch_adc_mfma(h->m, h->mf, h->codes.as<uint8_t>(), h->mf_pack.p, h->mf_norm.as<float>(), h->n, h->id_base, q_rot, nq, k, h->p_mfma_cap,
                                   h->p_mfma_sample, S.s_lut.as<float>(), S.s_spill.p, dist, ids, &redo, h->p_profile ? h->mf_stat.as<unsigned long long>() : nullptr, st));
-        // The exact kernel under a predicate, as after the big-k pipeline below -- over the flagged queries as a short batch with row splits
-        // (one workgroup per query of the call and row split costs more in empty workgroups than the filter saves, and without splits a
-        // lone flagged query holds the call for a whole pass of one workgroup over the rows), then over whoever found no slot there.
-        ScanPlan exact;
-        exact.qtile = 1; exact.splits = redo.splits; exact.variant = 0;
-        CVTMI_TRY(launch_adc_scan(h->m, h->codes.as<uint8_t>(), h->n, h->id_base, redo.q, redo.cap, k, exact, redo.splits > 1 ? redo.part_d : redo.d,
-                                  redo.splits > 1 ? redo.part_i : redo.i, nullptr, nullptr, st, nullptr, h->p_lazy, nullptr, nullptr, redo.only));
-        if (redo.splits > 1) CVTMI_TRY(launch_topk_merge(redo.part_d, redo.part_i, redo.cap, redo.splits, k, redo.d, redo.i, st, redo.only));
-        CVTMI_TRY(launch_adc_mfma_scatter(redo, k, dist, ids, st));
+        // The route has answered up to 64 flagged queries itself, exactly and over all rows (mf_redo_*, adc_mfma.hip).  The scan kernels run
+        // under redo.rest for whoever is left: flagged queries beyond those 64, and the few a slot could not answer.
         if (redo_fast) {
             const uint8_t *crot = (h->p_prerot && h->rot_kind == 0 && h->rot_n == h->n && h->codes_rot.p) ? h->codes_rot.as<uint8_t>() : nullptr;
             const bool split = redo_plan.stride() > 1;
@@ -716,7 +709,8 @@ static int opq_search_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, int64
                                       split ? S.s_part_id.as<int64_t>() : ids, S.s_lut.as<float>(), crot, st, nullptr, h->p_lazy, nullptr, nullptr, redo.rest, true));
             if (split) CVTMI_TRY(launch_topk_merge(S.s_part_d.as<float>(), S.s_part_id.as<int64_t>(), nq, redo_plan.stride(), k, dist, ids, st, redo.rest));
         } else {   // (shapes the 8-query kernel is not planned for: one workgroup per flagged query)
-            exact.splits = 1;
+            ScanPlan exact;
+            exact.qtile = 1; exact.splits = 1; exact.variant = 0;
             CVTMI_TRY(launch_adc_scan(h->m, h->codes.as<uint8_t>(), h->n, h->id_base, q_rot, nq, k, exact, dist, ids, nullptr, nullptr, st, nullptr, h->p_lazy, nullptr,
                                       nullptr, redo.rest));
         }

@@ -405,15 +405,13 @@ bool adc_mfma_model(const float *books, int D, int K, int8_t *xb, double *nrm, f
 size_t adc_mfma_pack_bytes(int D, int64_t n);
 int launch_adc_mfma_pack(const AdcMfmaModel &mm, int D, const uint8_t *codes, int64_t row0, int64_t n, void *pack, float *norms, hipStream_t st);
 size_t adc_mfma_scratch_bytes(int D, int64_t n, int64_t nq, int k, int list_cap, int sample_div, int64_t *per);
-// The queries the filter could not answer, for the caller to run the exact kernel on: up to `cap` of them as a short batch of their own (q:
-// their rotated queries, only: the slots in use, d / i: where that batch's answers go, part_*: its partial lists under `splits` row splits;
-// launch_adc_mfma_scatter then copies the answers to the queries' places) and rest[nq]: != 0 for flagged queries that found no slot.
+// The queries the filter could not answer: the route answers up to 64 of them itself, exactly, over all rows (mf_redo_*); what is left to
+// the caller's exact scan is rest[nq] (inside the call's scratch): != 0 for a flagged query that found no slot there or whose slot could
+// not answer it (a list over its cap, masses of rows at the k-th distance, a NaN sum).
 // stat (device, two words, or null): the call's queries and how many of them were flagged
 struct AdcMfmaRedo {
-    int cap, splits;
-    int32_t *slot_q; uint32_t *only; float *q; float *d; int64_t *i; float *part_d; int64_t *part_i; uint32_t *rest;
+    uint32_t *rest;
 };
-int launch_adc_mfma_scatter(const AdcMfmaRedo &redo, int k, float *dist, int64_t *ids, hipStream_t st);
 int launch_adc_mfma(const OpqModelDev &m, const AdcMfmaModel &mm, const uint8_t *codes, const void *pack, const float *norms, int64_t n, int64_t id_base,
                     const float *q_rot, int64_t nq, int k, int list_cap, int sample_div, float *lut_g, void *scratch, float *dist, int64_t *ids,
                     AdcMfmaRedo *redo, unsigned long long *stat, hipStream_t st);
