@@ -313,6 +313,34 @@ class OpqIndex:
                                            C.c_int(nprobe), C.c_int(img_num), _ptr(ms)))
         return ms
 
+    def rank_videos(self, q, seg_off, nprobe, img_num, k, rotate=True, want_total=False):
+        """The reference's whole query for several query videos at once (cvtmi_opq_rank_videos): segment s is frames seg_off[s] ..
+        seg_off[s + 1] - 1 of q; per segment the rows of query_video are added up in frame order and the k smallest (total, video)
+        pairs are returned: (score [nseg][k] float32, video [nseg][k] int64), padded with (+inf, -1), and with want_total the totals
+        [nseg][img_num] as well.  seg_off is read on the host (a list, numpy or a CPU tensor) whatever q is."""
+        seg = np.ascontiguousarray(np.asarray(seg_off.cpu() if _is_torch(seg_off) else seg_off), dtype=np.int64).reshape(-1)
+        assert seg.shape[0] >= 1, "seg_off holds nseg + 1 offsets"
+        nseg = seg.shape[0] - 1
+        args = (C.c_int64(nseg), C.c_int(1 if rotate else 0), C.c_int(nprobe), C.c_int(img_num), C.c_int(k))
+        if _is_torch(q):
+            import torch
+            s = torch.empty((nseg, k), dtype=torch.float32, device=q.device)
+            v = torch.empty((nseg, k), dtype=torch.int64, device=q.device)
+            t = torch.empty((nseg, img_num), dtype=torch.float32, device=q.device) if want_total else None
+            _check(lib().cvtmi_opq_rank_videos_dev(self.h, _ptr(q), _ptr(seg), *args, _ptr(s), _ptr(v), _ptr(t), _stream()))
+        else:
+            q = _np(q, np.float32)
+            s = np.empty((nseg, k), dtype=np.float32); v = np.empty((nseg, k), dtype=np.int64)
+            t = np.empty((nseg, img_num), dtype=np.float32) if want_total else None
+            _check(lib().cvtmi_opq_rank_videos(self.h, _ptr(q), _ptr(seg), *args, _ptr(s), _ptr(v), _ptr(t)))
+        return (s, v, t) if want_total else (s, v)
+
+    def last_rank(self):
+        """chunks and scratch areas of the last rank_videos on this handle (cvtmi_opq_last_rank)"""
+        o = (C.c_int64 * 4)()
+        _check(lib().cvtmi_opq_last_rank(self.h, o))
+        return dict(chunks=o[0], frames_per_chunk=o[1], score_bytes=o[2], total_bytes=o[3])
+
     def search_ivf(self, q, nprobe, k, rotate=True, out=None):
         """Row-level IVF search (cvtmi_opq_search_ivf): the k nearest entries among the nprobe nearest coarse lists of every query:
         (distances [nq][k] float32, ids [nq][k] int64), padded with (+inf, -1)."""

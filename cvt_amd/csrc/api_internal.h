@@ -242,6 +242,8 @@ struct OpqScratch : ScratchBase {
     DevBuf s_masked;           // masked IVF search: the mask in list order; cvtmi_opq_mask_videos: the marked bitmap and its table
     DevBuf s_range;            // range search (ivf_range.hip): probe order, part counts and offsets, spill area; host entry: lims behind them
     DevBuf s_ref_d, s_ref_i;   // cvtmi_opq_search_refine: the [nq][R] candidate lists between the scan and the rerank
+    DevBuf s_rank_ms, s_rank_tot, s_rank_seg;   // cvtmi_opq_rank_videos: the score rows of a frame chunk, the totals of a segment group, the segment offsets
+    DevBuf io_t;               // ... its host-pointer entry: the totals the caller asked for
     ScanHPlan hplan;                       // the item table s_items holds ...
     int64_t hplan_n = -1, hplan_nq = -1;   // ... and the (rows, queries, forced splits, planner settings) it was built for
     int hplan_splits = 0, hplan_key = 0;
@@ -249,7 +251,7 @@ struct OpqScratch : ScratchBase {
     PinBuf io_pin;             // the pinned staging area of the host-pointer search (cvtmi_opq_search)
     void release_all()
     {
-        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &s_masked, &s_range, &s_ref_d, &s_ref_i, &io_v }) b->release();
+        for (DevBuf *b : { &s_qrot, &s_part_d, &s_part_id, &s_lut, &s_gthr, &s_qlut, &s_qp, &s_spill, &s_items, &s_probe, &s_ivf, &s_masked, &s_range, &s_ref_d, &s_ref_i, &s_rank_ms, &s_rank_tot, &s_rank_seg, &io_t, &io_v }) b->release();
         io_pin.release();
         release_lease_state();
     }
@@ -294,6 +296,7 @@ struct cvtmi_opq_s {
     int64_t ivf_last[8] = {};               // grid of the last IVF search (cvtmi_opq_last_ivf_plan), written under pool.mu
     int64_t ivf_masked_last[8] = {};        // ... of the last masked IVF search (cvtmi_opq_last_ivf_masked)
     int64_t range_last[8] = {};             // ... and of the last range search (cvtmi_opq_last_range_plan)
+    int64_t rank_last[4] = {};              // chunks and areas of the last ranking (cvtmi_opq_last_rank)
     // scratch of the calls that run one at a time (query_video: probe lists, rotated queries)
     DevBuf s_qrot, s_probe, s_rot;
     DevBuf rm_scratch;         // removal (opq_remove.hip): bitmap, tile offsets, the table of removal ids, the chunk-sized row scratch

@@ -1170,6 +1170,141 @@ int cvtmi_opq_query_video(cvtmi_opq_t h, const float *q, int64_t nq, int rotate,
     return opq_query_video_common(h, q, nq, rotate, nprobe, img_num, match_score, nullptr, true);
 }
 
+// ---- cvtmi_opq_rank_videos: the whole query of multi_frame_index_test.cpp:51-84 for several query videos (video_rank.hip) ----
+// The frames are rotated and probed once, as cvtmi_opq_query_video over all of them would; the dense score rows exist a chunk of whole
+// frames at a time (s_rank_ms), each chunk is folded into the totals of its segments in frame order, and launch_topk_select reads the
+// totals.  Without a `total` of the caller's the totals of a group of segments live in s_rank_tot and the group is selected before the
+// next begins.  Both areas are bounded by "ivf_part_cap_mb" (at least one frame / one segment).  A search: shared lock, leased set.
+struct RankPlan {
+    int64_t frames_per_chunk = 1, segs_per_group = 1, chunks = 0;
+    size_t ms_bytes = 0, tot_bytes = 0;
+};
+static RankPlan plan_rank(const int64_t *seg_off, int64_t nseg, int img_num, bool own_totals, size_t cap_bytes)
+{
+    RankPlan p;
+    const size_t row = (size_t)img_num * sizeof(float);
+    const int64_t fit = std::max<int64_t>(1, (int64_t)(cap_bytes / row));
+    const int64_t frames = seg_off[nseg];
+    p.frames_per_chunk = std::min(fit, std::max<int64_t>(frames, 1));
+    p.segs_per_group = own_totals ? std::min(fit, nseg) : nseg;
+    for (int64_t g0 = 0; g0 < nseg; g0 += p.segs_per_group) {
+        const int64_t g1 = std::min(nseg, g0 + p.segs_per_group);
+        p.chunks += blocks_for(seg_off[g1] - seg_off[g0], p.frames_per_chunk);
+    }
+    p.ms_bytes = frames > 0 ? (size_t)p.frames_per_chunk * row : 0;
+    p.tot_bytes = own_totals ? (size_t)p.segs_per_group * row : 0;
+    return p;
+}
+
+static int opq_rank_videos_leased(cvtmi_opq_t h, OpqScratch &S, const float *q, const int64_t *seg_off, int64_t nseg, int rotate, int nprobe, int img_num,
+                                  int k, float *score, int64_t *video, float *total, hipStream_t st)
+{
+    if (!h->csr_valid) return fail(CVTMI_EINVAL, "cvtmi_opq_rank_videos: the index changed while the query was being prepared");
+    if (h->csr_kept > 0 && (h->csr_vmin < 0 || h->csr_vmax >= img_num))
+        return fail(CVTMI_EINVAL, "cvtmi_opq_rank_videos: video id %d outside img_num=%d", h->csr_vmin < 0 ? h->csr_vmin : h->csr_vmax, img_num);
+    const int64_t frames = seg_off[nseg];
+    const RankPlan plan = plan_rank(seg_off, nseg, img_num, !total, (size_t)tune_ivf_part_cap_mb.geti() << 20);
+    {
+        std::lock_guard<std::mutex> g(h->pool.mu);
+        const int64_t v[4] = { plan.chunks, plan.frames_per_chunk, (int64_t)plan.ms_bytes, (int64_t)plan.tot_bytes };
+        for (int i = 0; i < 4; ++i) h->rank_last[i] = v[i];
+    }
+    if (plan.ms_bytes) CVTMI_TRY(S.s_rank_ms.reserve(plan.ms_bytes));
+    if (plan.tot_bytes) CVTMI_TRY(S.s_rank_tot.reserve(plan.tot_bytes));
+    CVTMI_TRY(S.s_rank_seg.reserve(((size_t)nseg + 1) * sizeof(int64_t)));
+    int64_t *seg_dev = S.s_rank_seg.as<int64_t>();
+    CVTMI_TRY(launch_video_seg_table(seg_off, nseg + 1, seg_dev, st));
+    const float *q_rot = nullptr;
+    if (frames > 0) CVTMI_TRY(opq_rotate_probe(h, S, q, frames, rotate, nprobe, st, &q_rot));
+    float *ms = S.s_rank_ms.as<float>();
+    for (int64_t g0 = 0; g0 < nseg; g0 += plan.segs_per_group) {
+        const int64_t g1 = std::min(nseg, g0 + plan.segs_per_group);
+        float *tot = total ? total : S.s_rank_tot.as<float>();   // row of segment s: tot + (s - tot_s0) * img_num
+        const int64_t tot_s0 = total ? 0 : g0;
+        bool empty = false;
+        for (int64_t s = g0; s < g1 && !empty; ++s) empty = seg_off[s] == seg_off[s + 1];
+        if (empty) CVTMI_TRY(launch_video_total_zero(seg_dev, g0, g1, img_num, tot, tot_s0, st));
+        int64_t s_lo = g0;
+        for (int64_t c0 = seg_off[g0]; c0 < seg_off[g1]; c0 += plan.frames_per_chunk) {
+            const int64_t c1 = std::min(seg_off[g1], c0 + plan.frames_per_chunk);
+            CVTMI_TRY(launch_query_video(h->m, q_rot + c0 * h->m.D, c1 - c0, nprobe, S.s_probe.as<int32_t>() + c0 * nprobe, h->csr_off.as<int64_t>(),
+                                         h->csr_codes.as<uint8_t>(), h->csr_videos.as<int32_t>(), img_num, ms, h->csr_longest, st));
+            while (seg_off[s_lo + 1] <= c0) ++s_lo;           // the segment of frame c0 ...
+            int64_t s_hi = s_lo + 1;
+            while (s_hi < g1 && seg_off[s_hi] < c1) ++s_hi;   // ... up to the segment of frame c1 - 1
+            CVTMI_TRY(launch_video_frame_sum(ms, c0, c1, seg_dev, s_lo, s_hi, img_num, tot, tot_s0, st));
+        }
+        CVTMI_TRY(launch_topk_select(tot + (g0 - tot_s0) * img_num, nullptr, g1 - g0, img_num, k, score + g0 * k, video + g0 * k, st));
+    }
+    return CVTMI_OK;
+}
+
+// arguments first, before anything touches the device
+static int opq_rank_videos_check(cvtmi_opq_t h, const float *q, const int64_t *seg_off, int64_t nseg, int *nprobe, int img_num, int k, const float *score,
+                                 const int64_t *video)
+{
+    if (!h) return fail(CVTMI_EINVAL, "cvtmi_opq_rank_videos: null handle");
+    if (!seg_off || !score || !video || nseg < 0) return fail(CVTMI_EINVAL, "cvtmi_opq_rank_videos: bad arguments");
+    if (seg_off[0] != 0) return fail(CVTMI_EINVAL, "cvtmi_opq_rank_videos: seg_off[0]=%lld, not 0", (long long)seg_off[0]);
+    for (int64_t s = 0; s < nseg; ++s)
+        if (seg_off[s + 1] < seg_off[s]) return fail(CVTMI_EINVAL, "cvtmi_opq_rank_videos: seg_off decreases at segment %lld", (long long)s);
+    if (!q && seg_off[nseg] > 0) return fail(CVTMI_EINVAL, "cvtmi_opq_rank_videos: null frames");
+    if (*nprobe < 1) return fail(CVTMI_EINVAL, "cvtmi_opq_rank_videos: nprobe=%d", *nprobe);
+    if (img_num < 1) return fail(CVTMI_EINVAL, "cvtmi_opq_rank_videos: img_num=%d", img_num);
+    if (k < 1 || k > CVTMI_K_MAX) return fail(CVTMI_EINVAL, "cvtmi_opq_rank_videos: k=%d outside 1..%d", k, CVTMI_K_MAX);
+    if (h->m.K > 256) return fail(CVTMI_EUNSUPPORTED, "cvtmi_opq_rank_videos: K=%d > 256", h->m.K);
+    if (*nprobe > h->m.coarseK) *nprobe = h->m.coarseK;
+    if (*nprobe > 128) return fail(CVTMI_EUNSUPPORTED, "cvtmi_opq_rank_videos: nprobe=%d outside 1..128", *nprobe);
+    return CVTMI_OK;
+}
+
+// host = true: frames up and the lists (and the totals, where the caller wants them) down through the leased set's staging buffers
+static int opq_rank_videos_common(cvtmi_opq_t h, const float *q, const int64_t *seg_off, int64_t nseg, int rotate, int nprobe, int img_num, int k, float *score,
+                                  int64_t *video, float *total, hipStream_t stream, bool host)
+{
+    CVTMI_TRY(opq_rank_videos_check(h, q, seg_off, nseg, &nprobe, img_num, k, score, video));
+    CVTMI_TRY(use_device(h->device));
+    if (nseg == 0) return CVTMI_OK;
+    return opq_ivf_enter(h, false, stream, host, -1, [&](OpqLease &lease) -> int {
+        OpqScratch &S = *lease.s;
+        hipStream_t st = lease.st;
+        if (!host) return opq_rank_videos_leased(h, S, q, seg_off, nseg, rotate, nprobe, img_num, k, score, video, total, st);
+        const size_t qb = (size_t)seg_off[nseg] * h->m.D * sizeof(float), sb = (size_t)nseg * k * sizeof(float), vb = (size_t)nseg * k * sizeof(int64_t);
+        const size_t tb = total ? (size_t)nseg * img_num * sizeof(float) : 0;
+        if (qb) CVTMI_TRY(S.io_q.reserve(qb));
+        CVTMI_TRY(S.io_d.reserve(sb));
+        CVTMI_TRY(S.io_i.reserve(vb));
+        if (tb) CVTMI_TRY(S.io_t.reserve(tb));
+        if (qb) CVTMI_HIP(hipMemcpyAsync(S.io_q.p, q, qb, hipMemcpyHostToDevice, st));
+        CVTMI_TRY(opq_rank_videos_leased(h, S, S.io_q.as<float>(), seg_off, nseg, rotate, nprobe, img_num, k, S.io_d.as<float>(), S.io_i.as<int64_t>(),
+                                         tb ? S.io_t.as<float>() : nullptr, st));
+        CVTMI_HIP(hipMemcpyAsync(score, S.io_d.p, sb, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(hipMemcpyAsync(video, S.io_i.p, vb, hipMemcpyDeviceToHost, st));
+        if (tb) CVTMI_HIP(hipMemcpyAsync(total, S.io_t.p, tb, hipMemcpyDeviceToHost, st));
+        CVTMI_HIP(stream_wait(st));
+        return CVTMI_OK;
+    });
+}
+
+int cvtmi_opq_rank_videos_dev(cvtmi_opq_t h, const float *q, const int64_t *seg_off, int64_t nseg, int rotate, int nprobe, int img_num, int k, float *score,
+                              int64_t *video, float *total, void *stream)
+{
+    return opq_rank_videos_common(h, q, seg_off, nseg, rotate, nprobe, img_num, k, score, video, total, (hipStream_t)stream, false);
+}
+
+int cvtmi_opq_rank_videos(cvtmi_opq_t h, const float *q, const int64_t *seg_off, int64_t nseg, int rotate, int nprobe, int img_num, int k, float *score,
+                          int64_t *video, float *total)
+{
+    return opq_rank_videos_common(h, q, seg_off, nseg, rotate, nprobe, img_num, k, score, video, total, nullptr, true);
+}
+
+int cvtmi_opq_last_rank(cvtmi_opq_t h, int64_t out[4])
+{
+    if (!h || !out) return fail(CVTMI_EINVAL, "cvtmi_opq_last_rank: null");
+    copy_last(h->pool, h->rank_last, out);
+    return CVTMI_OK;
+}
+
 // ---- IVF search: the k nearest ENTRIES of the nprobe nearest lists (ivf_search.hip) ----
 // Concurrency as for query_video: shared lock + leased scratch set; the first search after an append (or the first IVF search of
 // a handle whose list-ordered copy has no insertion indices yet) rebuilds the copy under the exclusive lock (opq_ivf_enter).

@@ -168,6 +168,16 @@ int launch_csr_build(const int32_t *lists, const int32_t *videos, const uint8_t 
                      int64_t *list_off, uint8_t *out_codes, int32_t *out_videos, void *stats_out, hipStream_t st,
                      uint32_t *out_entry = nullptr);   // out_entry: [n] insertion index per entry of the copy, or null
 
+// ---- video_rank.hip ----  frame sums of cvtmi_opq_rank_videos: total[segment][img_num] = the in-order fp32 sum of the segment's score rows
+// the host's count offsets into seg_off_dev, carried in kernel arguments (nothing the stream would have to wait for)
+int launch_video_seg_table(const int64_t *seg_off_host, int64_t count, int64_t *seg_off_dev, hipStream_t st);
+// +0.0 into the total rows of the segments of [s_lo, s_hi) that have no frames; the row of segment s is total + (s - total_s0) * img_num
+int launch_video_total_zero(const int64_t *seg_off_dev, int64_t s_lo, int64_t s_hi, int img_num, float *total, int64_t total_s0, hipStream_t st);
+// ms: the score rows of frames [c0, c1); segments [s_lo, s_hi) are those with frames in the chunk (others in between are skipped).  A
+// segment that begins inside the chunk starts from +0.0 and does not read its total row, one that began earlier continues from it
+int launch_video_frame_sum(const float *ms, int64_t c0, int64_t c1, const int64_t *seg_off_dev, int64_t s_lo, int64_t s_hi, int img_num, float *total,
+                           int64_t total_s0, hipStream_t st);
+
 // ---- opq_remove.hip ----  stable compaction of the insertion-ordered entry arrays (cvtmi_opq_remove_videos / _ids)
 constexpr int kRmTile = 256;                    // rows of a tile: the unit of the kept counts, of a workgroup of the move, of "remove_chunk"
 constexpr int64_t kRmChunkDefault = 1 << 22;    // rows the move works on at a time (96 MB of scratch at M = 16)

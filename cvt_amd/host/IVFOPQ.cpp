@@ -2,6 +2,7 @@
 #include "IVFOPQ.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -203,6 +204,76 @@ void IVFOPQ::queryImpl(const std::string &featFile, vector<vector<float> > &matc
 }
 void IVFOPQ::Query(string featFile, vector<vector<float> > &matchScore, int nk) { queryImpl(featFile, matchScore, nk); }
 void IVFOPQ::QueryThrehold(string featFile, vector<vector<float> > &matchScore, int nk) { queryImpl(featFile, matchScore, nk); }
+
+// Query -> frame sum -> get_sort_results of one file, as the reference's main does it (multi_frame_index_test.cpp:51-84)
+void IVFOPQ::rankOneFile(const std::string &featFile, int nk, int show, std::vector<std::pair<float, unsigned> > &result, int &frameNum)
+{
+    vector<vector<float> > score;
+    Query(featFile, score, nk);
+    frameNum = (int)score.size();
+    result.clear();
+    if (frameNum == 0) return;
+    const int img_num = (int)score.at(0).size();
+    vector<float> score_total(img_num, 0.0f);
+    for (int j = 0; j < frameNum; j++)
+        for (int v = 0; v < img_num; v++) score_total.at(v) += score.at(j).at(v);
+    result = get_sort_results(score_total, show);
+}
+
+int IVFOPQ::QueryRank(const std::vector<std::string> &featFiles, int nk, int show, std::vector<std::vector<std::pair<float, unsigned> > > &results,
+                      std::vector<int> &frameNums)
+{
+    m_err.clear();
+    const size_t n = featFiles.size();
+    results.assign(n, std::vector<std::pair<float, unsigned> >());
+    frameNums.assign(n, 0);
+    if (!ensureHandle()) return 0;
+    // what the device ranking does not take goes file by file: the sharded modes, an empty index, a `show` the selection does not
+    // take, and files with a non-finite value (std::partial_sort_copy's order of NaN totals is not the device's)
+    const bool batch = m_hs.size() <= 1 && !m_comm && m_imgNum > 0 && show >= 1 && show <= CVTMI_K_MAX;
+    std::vector<float> frames;
+    std::vector<int64_t> seg_off(1, 0);
+    std::vector<size_t> batched;
+    std::vector<char> single(n, batch ? 0 : 1);
+    for (size_t i = 0; batch && i < n; ++i) {
+        float **feat = NULL;
+        int frameNum = 0;
+        LoadSingleFeatFile(featFiles[i], feat, frameNum);
+        frameNums[i] = frameNum;
+        if (frameNum == 0) continue;
+        const float *x = feat[0];
+        const size_t count = (size_t)frameNum * m_featDim;
+        bool finite = true;
+        for (size_t j = 0; j < count && finite; ++j) finite = std::isfinite(x[j]);
+        if (finite) {
+            frames.insert(frames.end(), x, x + count);
+            seg_off.push_back(seg_off.back() + frameNum);
+            batched.push_back(i);
+        } else {
+            single[i] = 1;
+        }
+        Delete2DArray(feat);
+    }
+    if (!batched.empty()) {
+        const int64_t nseg = (int64_t)batched.size();
+        std::vector<float> score((size_t)nseg * show);
+        std::vector<int64_t> video((size_t)nseg * show);
+        if (cvtmi_opq_rank_videos(m_h, frames.data(), seg_off.data(), nseg, /*rotate=*/0, nk, m_imgNum, show, score.data(), video.data(), NULL) != CVTMI_OK) {
+            m_err = cvtmi_last_error();
+            for (size_t b = 0; b < batched.size(); ++b) single[batched[b]] = 1;   // the file-by-file path reports what Query reports
+        } else {
+            for (size_t b = 0; b < batched.size(); ++b) {
+                // all `show` entries: those past img_num are (0, 0), as get_sort_results leaves them
+                std::vector<std::pair<float, unsigned> > &r = results[batched[b]];
+                r.assign(show, std::pair<float, unsigned>(0.0f, 0u));
+                for (int j = 0; j < show && j < m_imgNum; ++j) r[j] = std::make_pair(score[b * show + j], (unsigned)video[b * show + j]);
+            }
+        }
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (single[i]) rankOneFile(featFiles[i], nk, show, results[i], frameNums[i]);
+    return m_err.empty() ? 1 : 0;
+}
 
 int IVFOPQ::SearchTopK(const float *q, int nq, int k, float *dist, long long *ids)
 {

@@ -64,6 +64,13 @@ public:
     // then writes exactly the file IndexDatabase writes over the kept feature files alone.  Ids outside [0, numImages()) and
     // duplicates are ignored.  Returns the number of entries removed, or -1 (lastError()); single-GPU only, like SearchTopKProbe.
     int RemoveVideos(const std::vector<int> &videoIds);
+    // The reference's whole query (Query, the sum of its rows in frame order, get_sort_results(total, show)) for several query files
+    // in ONE cvtmi_opq_rank_videos call: results[i] is what that sequence gives for featFiles[i] -- always `show` entries, those past
+    // numImages() (0, 0); a file without frames gives an empty results[i] -- and frameNums[i] its number of frames.  Only the lists
+    // leave the device.  Files holding a non-finite value, show > CVTMI_K_MAX and the sharded modes go through Query file by file.
+    // 1 ok / 0 failure (lastError(); the files then went through Query as well).
+    int QueryRank(const std::vector<std::string> &featFiles, int nk, int show, std::vector<std::vector<std::pair<float, unsigned> > > &results,
+                  std::vector<int> &frameNums);
     std::string lastError() const;
     // row-sharded operation (one process per GPU): this object holds the row block that starts at global
     // row id_base; with a communicator set (cvtmi_comm_t, include/cvtmi.h) SearchTopK returns the GLOBAL top k on every
@@ -89,6 +96,7 @@ private:
     void init();
     bool ensureHandle();
     void queryImpl(const std::string &featFile, std::vector<std::vector<float> > &matchScore, int nk);
+    void rankOneFile(const std::string &featFile, int nk, int show, std::vector<std::pair<float, unsigned> > &result, int &frameNum);
 
     cvtmi_opq_s *m_h;                     // single-GPU handle (= device 0's in multi-device mode)
     cvtmi_comm_s *m_comm;

@@ -102,7 +102,9 @@ int cvtmi_set_device(int device);
  *                     splits while that still leaves at most one workgroup per CU (a last round is only expensive while it leaves CUs
  *                     empty: 4256 queries over 1 M rows 2.11 -> 2.79 M queries/s, 10 000 queries unchanged); -1 = never; S > 0 = S splits
  *   "ivf_part_cap_mb" cvtmi_opq_search_ivf: megabytes the partial lists of one search may take in the leased scratch set (default 256,
- *                     0 = none: one workgroup per query); a grid that needs more is cut coarser (rule 4 of cvtmi_opq_ivf_plan)
+ *                     0 = none: one workgroup per query); a grid that needs more is cut coarser (rule 4 of cvtmi_opq_ivf_plan).
+ *                     cvtmi_opq_rank_videos: the same bound on each of the ranking's two areas, the score rows of a frame chunk and
+ *                     the totals of a segment group (0 = one frame per chunk, one segment per group)
  *   "scan_pad_m"      1 (default) = an OPQ index with M < 16 is searched by the M = 16 scan kernels over rows padded to 16 code bytes
  *                     with zeros (derived copies: 32 bytes per row) and per-query tables padded with all-zero tables -- M = 8 at
  *                     10 000 queries x 1 M rows: 9.8 -> 3.2 ms, and every M from 1 to 15 is searchable; 0 = the row-per-lane
@@ -282,6 +284,38 @@ int cvtmi_opq_query_video(cvtmi_opq_t h, const float *q, int64_t nq, int rotate,
                           int img_num, float *match_score);
 int cvtmi_opq_query_video_dev(cvtmi_opq_t h, const float *q, int64_t nq, int rotate, int nprobe,
                               int img_num, float *match_score, void *stream);
+
+/* The whole query of the reference's main (opq/src/multi_frame_index_test.cpp:51-84) for nseg query videos at once: Query, the sum
+ * of its rows in frame order, get_sort_results -- and only the lists leave the device.
+ *   Input    q holds seg_off[nseg] frames of D floats; segment s (one query video) is frames seg_off[s] .. seg_off[s + 1] - 1.
+ *            seg_off is a HOST array of nseg + 1 int64 in BOTH entries, seg_off[0] == 0, never decreasing; it is read before the
+ *            call returns (the host plans the chunks from it).  The _dev entry never waits for the device: q, score, video and
+ *            total are device pointers there.
+ *   Scores   ms[f][v] is exactly what cvtmi_opq_query_video(h, q, seg_off[nseg], rotate, nprobe, img_num, ms) writes: rotation,
+ *            probing, the clamp of nprobe and its limit of 128, NaN frames and the 1.0 start value are that function's, and a
+ *            video id outside [0, img_num) fails with CVTMI_EINVAL (nothing is written).
+ *   Totals   total[s][v] = the fold t = +0.0f; for f ascending: t = t + ms[f][v], every step one fp32 round-to-nearest add (no
+ *            fma, no reassociation).  A segment without frames has +0.0 everywhere.  total may be NULL; otherwise it is
+ *            [nseg][img_num], written in full and never read.
+ *   Result   score[nseg][k] / video[nseg][k]: what cvtmi_topk_select(total, nseg, img_num, k, ...) returns on those totals, bit
+ *            for bit -- the k smallest (total, video) pairs ascending, ties to the smaller video id, NaN totals in that function's
+ *            key order, (+inf, -1) behind the img_num-th entry.
+ *   Checks   before any device work: CVTMI_EINVAL for a NULL h, seg_off, score or video, nseg < 0, seg_off[0] != 0, a decreasing
+ *            seg_off, a NULL q with frames, nprobe < 1, img_num < 1, k outside 1 .. CVTMI_K_MAX; CVTMI_EUNSUPPORTED for K > 256 or
+ *            more than 128 probes after the clamp.  nseg == 0 does nothing.
+ *   Memory   the dense score rows exist a chunk of whole frames at a time, and with total == NULL so do the totals, a group of
+ *            whole segments at a time (each group is selected before the next begins); both areas live in the leased scratch set
+ *            and are bounded by "ivf_part_cap_mb" (at least one frame, one segment).  A chunk may end inside a segment: the running
+ *            totals carry over and the order of the adds does not change.  The host-pointer entry stages a `total` the caller
+ *            asked for in full.
+ * A search like cvtmi_opq_query_video: calls on one handle run side by side.
+ * cvtmi_opq_last_rank: out = { frame chunks, frames per full chunk (at most the frames there were), bytes of the score area, bytes
+ * of the totals area (0 when the caller gave total) } of the handle's last ranking. */
+int cvtmi_opq_rank_videos(cvtmi_opq_t h, const float *q, const int64_t *seg_off, int64_t nseg, int rotate, int nprobe, int img_num, int k,
+                          float *score, int64_t *video, float *total);
+int cvtmi_opq_rank_videos_dev(cvtmi_opq_t h, const float *q, const int64_t *seg_off, int64_t nseg, int rotate, int nprobe, int img_num, int k,
+                              float *score, int64_t *video, float *total, void *stream);
+int cvtmi_opq_last_rank(cvtmi_opq_t h, int64_t out[4]);
 
 /* Row-level IVF search: the k nearest ENTRIES among the nprobe nearest coarse lists -- the query an index with coarseK > 1 is
  * built for, where cvtmi_opq_query_video only returns per-video minima.  Rotation and probing are cvtmi_opq_query_video's
